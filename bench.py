@@ -30,6 +30,9 @@ One JSON line on rank 0.  Besides the contract keys it carries
                 1024x1024x128 LockExchange hierarchy ((2,2,1) refinements, 128^3 boxes, 940 M cells), every level's boxes
                 sharded in y-slabs over the N GPUs, ms per AMR V-cycle (MappedAMRMultiGrid::AMRVCycle, 4/4/2), measured in
                 the same run at every N
+--dump-outputs DIR writes what the headline's last timed V-cycle handed its caller, the correction on the n^3 cells, as
+DIR/c2_correction.npy (float64; above DUMP_SAMPLE cells a fixed seeded sample of them), so that two builds run with the
+same arguments -- hence the same inputs -- can be compared output for output.
 The run FAILS (non-zero exit) when a timed operator does not contract, when the one-GPU contraction departs from the
 recorded value, or when an N > 1 run does not reproduce (to 1e-6) the contraction of the SAME N-box layout held by one
 process, which rank 0 computes next to its shard: a broken exchange must not produce a plausible throughput line.
@@ -55,6 +58,7 @@ SINGLE_RANK_CONTRACTION = {("stretched", 512): 0.49259591046055523}
 # one AMR V-cycle of the full-size C4 / C5 hierarchies on their compatible composite residual (profiles/r03_*): the box layout
 # -- hence the hierarchy and the arithmetic -- is the same at every N, only owners change
 AMR_CONTRACTION = {"c4": 0.0244679, "c5": 0.0033342}
+DUMP_SAMPLE = 4 << 20          # --dump-outputs: at most this many float64 values (32 MB)
 
 
 def host_cores():
@@ -108,13 +112,33 @@ def upload_c2_residual(gpu, F, field):
     gpu.removeMean(F.F_RES)
 
 
+def cpu_vcycle_module(cv, tmp):
+    """cv = oracle.cpu_vcycle, whose timing library (-march=native, one per host CPU) is made on first use next to its
+    sources.  A checkout the benchmark may not write to gets that library from a copy of the module, its C sources and
+    Makefile in the directory `tmp`, built and loaded there."""
+    src = os.path.dirname(os.path.abspath(cv.__file__))
+    if os.access(src, os.W_OK):
+        return cv
+    import importlib.util
+    import shutil
+    for f in ("cpu_vcycle.py", "cpu_vcycle.c", "kernels.c", "Makefile"):
+        shutil.copy2(os.path.join(src, f), tmp)
+    spec = importlib.util.spec_from_file_location("cpu_vcycle_copy", os.path.join(tmp, "cpu_vcycle.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
 def cpu_baseline(n=N_FINE, field=None):
     """The reference's V-cycle on the host: C orchestration + restated Fortran kernels + OpenMP (oracle/cpu_vcycle.c),
     the real n^3 problem on the SAME random residual as the GPU run.  Bounded: 1 timed cycle on one core, 3 on all cores
     (~20-40 s of CPU work at 512^3)."""
+    import tempfile
     import numpy as np
-    from oracle import cpu_vcycle as cv
+    from oracle import cpu_vcycle
     from somar_amd import synthetic
+    tmp = tempfile.TemporaryDirectory(prefix="somar_cpu_baseline_")
+    cv = cpu_vcycle_module(cpu_vcycle, tmp.name)
     cores = host_cores()
     dx = (1.0 / n,) * 3
     jg, jinv = synthetic.stretched_diagonal_metric((0, 0, 0), (n - 1,) * 3, dx, (1.0, 1.0, 1.0))
@@ -144,6 +168,7 @@ def cpu_baseline(n=N_FINE, field=None):
     h.close()
     triad_all = cv.triad_gbs(cores)
     triad_one = cv.triad_gbs(1)
+    tmp.cleanup()
     return {"value": 1.0 / t_all, "unit": "V-cycles/s", "cores": cores, "kind": "port",
             "one_core_value": 1.0 / t_one, "cpu_model": cpu_model(),
             "stream_triad_GBs": {"all_cores": triad_all, "one_core": triad_one},
@@ -229,6 +254,22 @@ def time_c2(gpu, F, torch, dist, steps, warmup):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t[0])
     return dt
+
+
+def dump_c2_outputs(gpu, F, n, out_dir):
+    """F_CORR on the n^3 cells after the timed loop -> out_dir/c2_correction.npy: all of them in Fortran order, or above
+    DUMP_SAMPLE cells the same seeded sample of them (ascending Fortran-order index) at every run with the same n"""
+    import numpy as np
+    corr = np.empty((n, n, n), order="F")
+    for q in range(gpu.num_local_patches):
+        lo, hi, _ = gpu.patch_box(q)
+        corr[lo[0]:hi[0] + 1, lo[1]:hi[1] + 1, lo[2]:hi[2] + 1] = gpu.download(F.F_CORR, q, (0, 0, 0))
+    corr = corr.ravel(order="F")
+    if corr.size > DUMP_SAMPLE:
+        idx = np.random.default_rng(12345).choice(corr.size, DUMP_SAMPLE, replace=False, shuffle=False)
+        corr = corr[np.sort(idx)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "c2_correction.npy"), corr)
 
 
 def contraction_c2(gpu, F):
@@ -326,7 +367,12 @@ def main():
     ap.add_argument("--c4-steps", type=int, default=5)
     ap.add_argument("--c4-warmup", type=int, default=1)
     ap.add_argument("--c4-scale", type=int, default=1, help="divide every C4 extent (rehearsals on small boxes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the headline's last timed V-cycle output as DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
 
     import torch
     from somar_amd import api, synthetic   # the measured path never touches oracle/ (only cpu_baseline() above does)
@@ -377,6 +423,8 @@ def main():
     dt = time_c2(gpu, F, torch, dist, args.steps, args.warmup)
     ms_per_step = 1e3 * dt / args.steps
     value = args.steps / dt
+    if args.dump_outputs:
+        dump_c2_outputs(gpu, F, n, args.dump_outputs)
 
     # per-kernel HIP events: a separate profiled pass (launch by launch, events around the depth-0 kernels), NOT timed above
     gpu.profileEnable(True)

@@ -48,7 +48,8 @@ extern "C" {
  * 5: + somar_amr_solve_host (multi-level host boundary), somar_k_gsrbiter3dortho (box-by-box kernel hook); additions only
  * 6: + somar_amr_tga_step (composite MappedAMRTGA::oneStep); composite operations with heat coefficients installed no
  *    longer fail (the flux-register scales follow beta); somar_solver_set_vel_bc (inflow / outflow sides); somar_solver_set_metric_map (cylindrical and bathymetric
- *    metric producers on the device); somar_k_fillmappedlapdiag3d, somar_k_mappedaverage2 (kernel-level hooks); additions only */
+ *    metric producers on the device); somar_k_fillmappedlapdiag3d, somar_k_mappedaverage2 (kernel-level hooks); additions only
+ * 11: ... + somar_solver_set_bc_face_values (position-dependent Dirichlet values); additions only, so the number stays 11 */
 #define SOMAR_AMD_ABI_VERSION 11
 
 /* BCType codes, calculus/BCInterface/BCDescriptor.H:34-39 */
@@ -134,6 +135,31 @@ int somar_solver_set_metric_ortho(somar_solver_t* s, int patch, const double* jg
  * the two-pass GSRB and direct-load operator kernels (line relaxation included: Dirichlet vertical ends are folded into
  * the column systems); with a non-diagonal metric the Dirichlet ghosts are steps of the ghost programs. */
 int somar_solver_set_bc_values(somar_solver_t* s, const double* values6);
+/* Position-dependent values of one Dirichlet side: EllipticDiriBCGhostClass (BCInterface/EllipticBCUtils.H:257-308,
+ * EllipticBCUtils.cpp:548-646), whose functor f(pos, dir, side, value, dx, time) gives one value per boundary face.
+ *   values: one double per boundary face of side (dir, side) over the level's WHOLE domain box (not only local patches),
+ *           Fortran order over the two transverse directions in increasing order: (nx, ny) for a z side, (ny, nz) for an
+ *           x side, (nx, nz) for a y side (space_dim 2: a line).  Entry (fc[t0] - domain_lo[t0]) + n_t0 * (fc[t1] -
+ *           domain_lo[t1]) is what the reference functor returns at the face centre
+ *               pos[d] = (fc[d] + offset[d]) * dx[d],  offset[d] = 0.5 for d != dir, offset[dir] = 0,
+ *           fc = the boundary face: fc[dir] = domain_lo[dir] (low side) or domain_hi[dir] + 1 (high side), fc[t] the
+ *           cell index along the transverse directions t (EllipticBCUtils.cpp:595-626).
+ *   ghost:  (-first valid) + 2.0 * value, order 1 (EllipticBCUtils.cpp:612-636), for every value (no zero shortcut);
+ *           homogeneous: -first valid.  A constant plane gives the bits of somar_solver_set_bc_values with that value.
+ *   NULL:   the side returns to its constant from somar_solver_set_bc_values.
+ * Refused (non-zero return, somar_last_error): a side that is not SOMAR_BC_DIRI, a periodic or inactive direction, dir not
+ * in 0..2, side not 0 / 1.  May be called before or after somar_solver_finalize; after it the call only copies into the
+ * existing device buffers (no rebuild, no reallocation, addresses unchanged).  Each rank keeps the slices its own patches
+ * touch.  On AMR level handles (somar_amr_level) each level takes its own plane at its own resolution.
+ * The values enter where the constants of somar_solver_set_bc_values do: the outer residuals of somar_solver_solve[_host] /
+ * somar_amr_solve[_host] unless force_homogeneous is set, somar_level_apply_op_bc / somar_level_residual_bc with
+ * homogeneous = 0, the heat integrators (and the fluxes somar_heat_flux_download returns) and the projections' solves;
+ * corrections and relaxation see zero.
+ * Limits: the values do not depend on time -- the reference evaluates the functor at a_time, so a Crank-Nicolson / TGA
+ * step there sees old- and new-time values, while here one set serves every stage of a step (exact for time-independent
+ * functors such as HorizConvBCUtil's topBCValueFunc); change them between steps.  somar_leptic_solve and
+ * somar_amr_solve_leptic refuse a level with a face-valued side. */
+int somar_solver_set_bc_face_values(somar_solver_t* s, int dir, int side, const double* values);
 /* Non-diagonal metric (LevelGeometry::isDiagonal() == false): jgD holds J g^{Db}, b = 0..2, over faces(valid, D),
  * component slowest (the FluxBox layout of LevelGeometry::getFCJgupPtr).  Selects the 19-point kernels
  * (GSRBITER3D, GSRBBOUNDARYITER3D, MAPPEDGETFLUX, fillExtrap / ExtrapolateFaceAndCopy, the cross-term Neumann

@@ -73,6 +73,7 @@ _SIGS = {
     "somar_solver_set_metric_ortho": [_H, C.c_int, _PD, _PD, _PD, _PD],
     "somar_solver_set_metric_full": [_H, C.c_int, _PD, _PD, _PD, _PD],
     "somar_solver_set_bc_values": [_H, _PD],
+    "somar_solver_set_bc_face_values": [_H, C.c_int, C.c_int, _PD],
     "somar_solver_finalize": [_H],
     "somar_solver_depth": [_H, _PI],
     "somar_solver_mg_ref_ratio": [_H, C.c_int, _PI],
@@ -449,6 +450,16 @@ class AMRPressureSolver:
     def setBCValues(self, values6):
         """values of the Dirichlet sides {loX,hiX,loY,hiY,loZ,hiZ} (before finalize)"""
         _ck(lib().somar_solver_set_bc_values(self._h, _da(values6)))
+
+    def setBCFaceValues(self, dir, side, values):
+        """position-dependent values of the Dirichlet side (dir, side) (EllipticDiriBCGhostClass): a plane over the whole
+        domain's faces of that side, indexed [t0, t1] by the two transverse directions in increasing order; None restores
+        the constant of setBCValues.  Before or after finalize."""
+        if values is None:
+            _ck(lib().somar_solver_set_bc_face_values(self._h, int(dir), int(side), None))
+            return
+        a = np.asfortranarray(np.asarray(values, dtype=np.float64))
+        _ck(lib().somar_solver_set_bc_face_values(self._h, int(dir), int(side), _dp(a)))
 
     def heatFlux(self, dir, patch):
         """a_flux of the last heat step(s) on faces(valid, dir) of one local patch"""

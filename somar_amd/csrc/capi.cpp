@@ -392,6 +392,15 @@ int somar_solver_set_bc_values(somar_solver_t* s, const double* values6)
     API_END
 }
 
+int somar_solver_set_bc_face_values(somar_solver_t* s, int dir, int side, const double* values)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps, "null argument");
+    SOMAR_CHECK(dir >= 0 && dir < 3 && (side == 0 || side == 1), "somar_solver_set_bc_face_values: dir must be 0..2 and side 0 (low) or 1 (high)");
+    s->ps->set_bc_face_values(dir, side, values);
+    API_END
+}
+
 int somar_solver_set_metric_full(somar_solver_t* s, int patch, const double* jg0, const double* jg1, const double* jg2,
                                  const double* jinv)
 {
@@ -1667,6 +1676,10 @@ int somar_amr_enable_leptic(somar_amr_t* a, const somar_leptic_params_t* lp, int
 int somar_amr_solve_leptic(somar_amr_t* a, int l_max, int l_base, int zero_phi, int force_homogeneous, somar_stats_t* stats)
 {
     API_BEGIN
+    SOMAR_CHECK(a, "null argument");
+    for (size_t l = 0; l < a->levels.size(); ++l)
+        SOMAR_CHECK(!a->levels[l]->ps->has_face_values(), "somar_amr_solve_leptic: level " + std::to_string(l) +
+                    " has position-dependent Dirichlet values (somar_solver_set_bc_face_values); the leptic path does not read them");
     SolveStats st;
     a->amr->solve_leptic(l_max, l_base, zero_phi != 0, force_homogeneous != 0, st);
     fill_stats(st, stats);
@@ -1779,6 +1792,9 @@ int somar_leptic_solve(somar_leptic_t* h, int homogeneous, somar_leptic_stats_t*
 {
     API_BEGIN
     SOMAR_CHECK(h, "null argument");
+    for (somar_solver* q : {h->level, h->parts[0], h->parts[1]})
+        SOMAR_CHECK(!(q && q->ps && q->ps->has_face_values()), "somar_leptic_solve: position-dependent Dirichlet values "
+                    "(somar_solver_set_bc_face_values) are set; the leptic path does not read them");
     LepticStats S;
     h->lep->solve(homogeneous != 0, S);
     if (stats) fill_leptic_stats(S, stats);

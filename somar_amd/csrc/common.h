@@ -79,17 +79,25 @@ struct CFCell {
 };
 
 // One step of a ghost "program" of the non-diagonal (19-point) path (full19.hip): a region of one patch.
-enum { GHOST_COPY = 0, GHOST_EXTRAP = 1, GHOST_NEUM = 2, GHOST_DIRI = 3 };
+// GHOST_DIRI_FACE: a Dirichlet side with one value per boundary face (EllipticDiriBCGhostClass) instead of one per side
+enum { GHOST_COPY = 0, GHOST_EXTRAP = 1, GHOST_NEUM = 2, GHOST_DIRI = 3, GHOST_DIRI_FACE = 4 };
+__host__ __device__ inline bool ghost_is_diri(int type) { return type == GHOST_DIRI || type == GHOST_DIRI_FACE; }
 struct GhostOp {
     int patch, type;
     int lo[3];       // local start of the region
     int n[3];
-    int dir, sgn;    // EXTRAP / NEUM: direction and side sign (+1 high, -1 low)
+    int dir, sgn;    // EXTRAP / NEUM / DIRI: direction and side sign (+1 high, -1 low)
     int order;       // EXTRAP: 0, 1 or 2
     int dstf, srcf;  // 0 = phi, 1 = psi (the extrapolated copy)
     int pad_;
-    double val;      // DIRI: the boundary value of that side
+    union {
+        double val;      // DIRI: the boundary value of that side
+        long long voff;  // DIRI_FACE: start of this op's slice of the level's face-value buffer (LevelDev::bc_face), one
+                         // value per cell of the region in the op's own loop order (i fastest)
+    };
 };
+// k_ghost_program stages GP_MAX_OPS of these in LDS with 16-byte copies
+static_assert(sizeof(GhostOp) == 64 && sizeof(GhostOp) % 16 == 0, "GhostOp must stay 64 bytes (LDS staging, int4 copy)");
 
 // Per-level constants handed to the stencil kernels by value.
 struct StencilParams {

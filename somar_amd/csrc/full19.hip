@@ -34,9 +34,11 @@ struct JgFull { const double* c[3][3]; };  // c[faceDir][component]
 // REDIRECT: psi is kept in the boxes' frames only (its copy inside the valid region is never made): a read of psi at a
 // cell INSIDE the box's valid region returns phi there -- the value the full copy psi := phi would have put.
 // one op over the threads [t0, t0 + nt, ...) of the caller
+// bcf: the level's face-value buffer (GHOST_DIRI_FACE ops read bcf[op.voff + loop index]; null where no such op exists)
 template <bool REDIRECT>
 __device__ __forceinline__ void ghost_op_body(const GhostOp& op, const PatchDesc& p, double* phi, double* psi,   // may alias
-                                              const JgFull& J, const StencilParams& P, int t0, int nt)
+                                              const JgFull& J, const StencilParams& P, const double* __restrict__ bcf,
+                                              int t0, int nt)
 {
     const int n0 = op.n[0], n01 = op.n[0] * op.n[1];
     const int cells = n01 * op.n[2];   // a ghost region of one box: far below 2^31 (32-bit index arithmetic: no 64-bit divisions)
@@ -73,6 +75,12 @@ __device__ __forceinline__ void ghost_op_body(const GhostOp& op, const PatchDesc
             const double bcval = P.bc_homog ? 0.0 : op.val;
             if (bcval == 0.0) dst[c] = -src[c - s];
             else dst[c] = 2.0 * bcval - src[c - s];
+        } else if (op.type == GHOST_DIRI_FACE) {
+            // EllipticDiriBCGhostClass, cell-centred branch, order 1 (EllipticBCUtils.cpp:588-636): ghost = (-first valid) +
+            // 2 g(face); no shortcut for g == 0 (the reference has none).  Homogeneous: -first valid, as the constant form.
+            const long long s = op.sgn * st[op.dir];
+            if (P.bc_homog) dst[c] = -src[c - s];
+            else dst[c] = (-src[c - s]) + 2.0 * bcf[op.voff + idx];
         } else {  // GHOST_NEUM: phi ghost such that the boundary flux (cross terms from psi included) equals bcval = 0
             const int a = op.dir, b = (a + 1) % 3, cc = (a + 2) % 3;
             const long long sa = st[a], sb = st[b], sc = st[cc];
@@ -92,11 +100,11 @@ __device__ __forceinline__ void ghost_op_body(const GhostOp& op, const PatchDesc
 
 template <bool REDIRECT>
 __global__ void k_ghost_ops(const GhostOp* __restrict__ ops, const PatchDesc* __restrict__ patches,
-                            double* phi, double* psi, JgFull J, StencilParams P)
+                            double* phi, double* psi, JgFull J, StencilParams P, const double* __restrict__ bcf)
 {
     const GhostOp op = ops[blockIdx.x];
     const PatchDesc p = patches[op.patch];
-    ghost_op_body<REDIRECT>(op, p, phi, psi, J, P, (int)(blockIdx.y * blockDim.x + threadIdx.x), (int)(gridDim.y * blockDim.x));
+    ghost_op_body<REDIRECT>(op, p, phi, psi, J, P, bcf, (int)(blockIdx.y * blockDim.x + threadIdx.x), (int)(gridDim.y * blockDim.x));
 }
 
 // A whole ghost program in ONE launch, one workgroup per box.  Every op of a program reads and writes the storage of its own
@@ -109,9 +117,9 @@ constexpr int GP_MAX_OPS = 160;   // ops of one box staged in LDS (10 KB); a lon
 template <bool REDIRECT>
 __global__ __launch_bounds__(512) void k_ghost_program(const GhostOp* __restrict__ box_ops, const int* __restrict__ box_first,
                                                        const PatchDesc* __restrict__ patches, double* phi, double* psi,
-                                                       JgFull J, StencilParams P, int copy_all)
+                                                       JgFull J, StencilParams P, int copy_all, const double* __restrict__ bcf)
 {
-    __shared__ GhostOp sops[GP_MAX_OPS];
+    __shared__ alignas(16) GhostOp sops[GP_MAX_OPS];
     const int b = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
     const PatchDesc p = patches[b];
     const int first = box_first[b], nops = box_first[b + 1] - first;
@@ -143,7 +151,7 @@ __global__ __launch_bounds__(512) void k_ghost_program(const GhostOp* __restrict
         const int e = q + 1 + ((q < GP_MAX_OPS ? sops[q].pad_ : box_ops[first + q].pad_) >> 16);
         for (int o = q + wave; o < e; o += nwaves) {
             const GhostOp op = o < GP_MAX_OPS ? sops[o] : box_ops[first + o];
-            ghost_op_body<REDIRECT>(op, p, phi, psi, J, P, lane, 64);
+            ghost_op_body<REDIRECT>(op, p, phi, psi, J, P, bcf, lane, 64);
         }
         __threadfence_block();
         __syncthreads();
@@ -376,8 +384,8 @@ void launch_ghost_ops(hipStream_t st, const LevelDev& L, const GhostOp* ops, int
     if (nops == 0) return;
     StencilParams P = L.P;
     P.bc_homog = bc_homog ? 1 : 0;
-    if (redirect) hipLaunchKernelGGL(k_ghost_ops<true>, dim3(nops, L.ghost_gy), dim3(256), 0, st, ops, L.patches, phi, psi, jgfull(L), P);
-    else hipLaunchKernelGGL(k_ghost_ops<false>, dim3(nops, L.ghost_gy), dim3(256), 0, st, ops, L.patches, phi, psi, jgfull(L), P);
+    if (redirect) hipLaunchKernelGGL(k_ghost_ops<true>, dim3(nops, L.ghost_gy), dim3(256), 0, st, ops, L.patches, phi, psi, jgfull(L), P, L.bc_face);
+    else hipLaunchKernelGGL(k_ghost_ops<false>, dim3(nops, L.ghost_gy), dim3(256), 0, st, ops, L.patches, phi, psi, jgfull(L), P, L.bc_face);
 }
 
 void launch_ghost_program(hipStream_t st, const LevelDev& L, const GhostOp* box_ops, const int* box_first, double* phi,
@@ -386,8 +394,8 @@ void launch_ghost_program(hipStream_t st, const LevelDev& L, const GhostOp* box_
     if (L.npatches == 0) return;
     StencilParams P = L.P;
     P.bc_homog = bc_homog ? 1 : 0;
-    if (redirect) hipLaunchKernelGGL(k_ghost_program<true>, dim3(L.npatches), dim3(512), 0, st, box_ops, box_first, L.patches, phi, psi, jgfull(L), P, copy_all ? 1 : 0);
-    else hipLaunchKernelGGL(k_ghost_program<false>, dim3(L.npatches), dim3(512), 0, st, box_ops, box_first, L.patches, phi, psi, jgfull(L), P, copy_all ? 1 : 0);
+    if (redirect) hipLaunchKernelGGL(k_ghost_program<true>, dim3(L.npatches), dim3(512), 0, st, box_ops, box_first, L.patches, phi, psi, jgfull(L), P, copy_all ? 1 : 0, L.bc_face);
+    else hipLaunchKernelGGL(k_ghost_program<false>, dim3(L.npatches), dim3(512), 0, st, box_ops, box_first, L.patches, phi, psi, jgfull(L), P, copy_all ? 1 : 0, L.bc_face);
 }
 
 void launch_flux_full(hipStream_t st, const LevelDev& L, double* const out[3], const double* phi, const double* psi)

@@ -23,6 +23,9 @@ struct LevelDev {
     // non-diagonal metric: all components J g^{ab} on a-faces, jgf[a][b]; jgf[a][a] aliases jg[a]
     double* jgf[3][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     StencilParams P;
+    // position-dependent Dirichlet values of this level (depth 0 only): the slices GHOST_DIRI_FACE ops read at GhostOp::voff
+    // (PressureSolver::build_face_slices); the address never changes after finalize
+    const double* bc_face = nullptr;
     int narrow7 = 0;                    // the 7-point marching kernels' tile tables hold narrow lane classes (Level::build_march_tiles)
     int narrowq = 0;                    // the 19-point marching kernels' tile table does
 };

@@ -44,6 +44,7 @@ PressureSolver::~PressureSolver()
 {
     drop_graphs();
     for (GhostOp* q : d_diri_ops_) hipFree(q);
+    hipFree(d_bcface_);
     for (double* q : f_flux) Level::free_field(q);
     for (double* q : f_ccvel) Level::free_field(q);
     for (double* q : f_heat) Level::free_field(q);
@@ -560,6 +561,7 @@ void PressureSolver::finalize()
     f_corr.assign(D, nullptr);
     f_scratch.assign(D, nullptr);
     f_pp.assign(D, nullptr);
+    if (diri_) build_face_slices();   // before the op lists of depth 0, which take their slices from it
     if (full_) {
         SOMAR_CHECK(prm.relaxMode == RELAX_LEVEL_GSRB || prm.relaxMode == RELAX_JACOBI || prm.relaxMode == RELAX_LINE_GSRB,
                     "the non-diagonal metric path offers LevelGSRB, LineGSRB and Jacobi");
@@ -1592,10 +1594,12 @@ void PressureSolver::build_diri_ops(int d)
                 op.dir = a;
                 op.sgn = s ? 1 : -1;
                 op.val = bc_value_[a][s];
+                if (d == 0) set_diri_op(op);
                 ops.push_back(op);
             }
         }
     }
+    if (d == 0) h_diri_ops0_ = ops;
     n_diri_ops_[d] = (int)ops.size();
     if (!ops.empty()) {
         SOMAR_HIP(hipMalloc(&d_diri_ops_[d], ops.size() * sizeof(GhostOp)));
@@ -1606,6 +1610,127 @@ void PressureSolver::build_diri_ops(int d)
 void PressureSolver::apply_diri(int d, double* phi, bool homogeneous)
 {
     launch_ghost_ops(st_, lev[d]->dev, d_diri_ops_[d], n_diri_ops_[d], phi, phi, homogeneous);
+}
+
+void PressureSolver::set_bc_face_values(int dir, int side, const double* values)
+{
+    SOMAR_CHECK(!lev.empty(), "set_bc_face_values before define");
+    SOMAR_CHECK(dir >= 0 && dir < 3 && (side == 0 || side == 1), "set_bc_face_values: dir must be 0..2, side 0 (low) or 1 (high)");
+    const Level& L = *lev[0];
+    SOMAR_CHECK(L.active[dir], "set_bc_face_values: direction " + std::to_string(dir) + " is inactive (space_dim 2)");
+    SOMAR_CHECK(!L.periodic[dir], "set_bc_face_values: direction " + std::to_string(dir) + " is periodic");
+    SOMAR_CHECK(L.bc_type[dir][side] == BC_DIRI, "set_bc_face_values: side (" + std::to_string(dir) + ", " +
+                                                     std::to_string(side) + ") is not a Dirichlet side");
+    const bool was = face_[dir][side];
+    if (values) {
+        const int t0 = (dir + 1) % 3 < (dir + 2) % 3 ? (dir + 1) % 3 : (dir + 2) % 3, t1 = 3 - dir - t0;
+        const size_t n = (size_t)L.domain.size(t0) * L.domain.size(t1);
+        face_plane_[dir][side].assign(values, values + n);
+        face_[dir][side] = true;
+    } else {
+        face_plane_[dir][side].clear();
+        face_[dir][side] = false;
+    }
+    if (!finalized) return;   // finalize builds the ops and the buffer from these
+    sync();                   // nothing in flight reads the op lists or the values while they are rewritten
+    if (was != face_[dir][side]) refresh_diri_ops();
+    fill_face_values();
+}
+
+// One slice of d_bcface_ per (local patch of depth 0, Dirichlet side it touches), in patch order: the ghost layer over the
+// patch's transverse extent, as build_diri_ops and build_program cover it.  Allocated once, whether or not a side is
+// face-valued yet, so that a later set_bc_face_values only copies.
+void PressureSolver::build_face_slices()
+{
+    const Level& L = *lev[0];
+    face_off_.assign((size_t)6 * L.npatches(), -1);
+    long long total = 0;
+    for (int pi = 0; pi < L.npatches(); ++pi) {
+        const IBox valid = L.boxes[L.local[pi]];
+        for (int a = 0; a < 3; ++a) {
+            if (!L.active[a] || L.periodic[a]) continue;
+            for (int s = 0; s < 2; ++s) {
+                if (L.bc_type[a][s] != BC_DIRI) continue;
+                if ((s ? valid.hi[a] : valid.lo[a]) != (s ? L.domain.hi[a] : L.domain.lo[a])) continue;
+                face_off_[6 * pi + 2 * a + s] = total;
+                total += valid.numPts() / valid.size(a);
+            }
+        }
+    }
+    h_bcface_.assign((size_t)std::max(total, 1LL), 0.0);
+    SOMAR_HIP(hipMalloc(&d_bcface_, h_bcface_.size() * sizeof(double)));
+    lev[0]->dev.bc_face = d_bcface_;
+    fill_face_values();
+}
+
+// host mirror of every slice (face-valued sides from their planes, constant sides their constant, which no op reads), then
+// one copy into the device buffer
+void PressureSolver::fill_face_values()
+{
+    const Level& L = *lev[0];
+    for (int pi = 0; pi < L.npatches(); ++pi) {
+        const IBox valid = L.boxes[L.local[pi]];
+        for (int a = 0; a < 3; ++a)
+            for (int s = 0; s < 2; ++s) {
+                const long long off = face_off_[6 * pi + 2 * a + s];
+                if (off < 0) continue;
+                const int t0 = (a + 1) % 3 < (a + 2) % 3 ? (a + 1) % 3 : (a + 2) % 3, t1 = 3 - a - t0;
+                const long long nt0 = L.domain.size(t0);
+                // the op's loop order: i fastest over its region (extent 1 along a), i.e. t0 fastest, then t1
+                long long q = off;
+                for (int g1 = valid.lo[t1]; g1 <= valid.hi[t1]; ++g1)
+                    for (int g0 = valid.lo[t0]; g0 <= valid.hi[t0]; ++g0, ++q)
+                        h_bcface_[q] = face_[a][s] ? face_plane_[a][s][(g0 - L.domain.lo[t0]) + nt0 * (g1 - L.domain.lo[t1])]
+                                                   : bc_value_[a][s];
+            }
+    }
+    SOMAR_HIP(hipMemcpy(d_bcface_, h_bcface_.data(), h_bcface_.size() * sizeof(double), hipMemcpyHostToDevice));
+}
+
+// A Dirichlet op of depth 0 as its side now is: GHOST_DIRI with the side's constant, or GHOST_DIRI_FACE reading its slice.
+// The op must cover exactly the (patch, side) ghost layer its slice was laid out for, so that bcf[voff + loop index] stays
+// inside the buffer -- checked here, on the host, for every op before any upload.
+void PressureSolver::set_diri_op(GhostOp& op) const
+{
+    const Level& L = *lev[0];
+    SOMAR_CHECK(op.patch >= 0 && op.patch < L.npatches() && op.dir >= 0 && op.dir < 3 && (op.sgn == 1 || op.sgn == -1),
+                "Dirichlet ghost op: bad patch / direction / side");
+    const int a = op.dir, s = op.sgn > 0 ? 1 : 0;
+    const IBox valid = L.boxes[L.local[op.patch]];
+    for (int q = 0; q < 3; ++q) {
+        const int lo = q == a ? (s ? valid.size(a) : -1) : 0, n = q == a ? 1 : valid.size(q);
+        SOMAR_CHECK(op.lo[q] == lo && op.n[q] == n, "Dirichlet ghost op does not cover its patch's ghost layer");
+    }
+    const long long off = face_off_.at((size_t)6 * op.patch + 2 * a + s);
+    const long long cells = (long long)op.n[0] * op.n[1] * op.n[2];
+    SOMAR_CHECK(off >= 0 && off + cells <= (long long)h_bcface_.size(), "Dirichlet ghost op: face-value slice out of range");
+    if (face_[a][s]) {
+        op.type = GHOST_DIRI_FACE;
+        op.voff = off;
+    } else {
+        op.type = GHOST_DIRI;
+        op.val = bc_value_[a][s];
+    }
+}
+
+// after finalize: the Dirichlet ops of depth 0 rewritten in place (same lists, same lengths, same device addresses)
+void PressureSolver::refresh_diri_ops()
+{
+    auto fix = [&](std::vector<GhostOp>& v, GhostOp* dev) {
+        bool any = false;
+        for (GhostOp& op : v)
+            if (ghost_is_diri(op.type)) { set_diri_op(op); any = true; }
+        if (any) {
+            SOMAR_CHECK(dev != nullptr, "Dirichlet ghost ops without a device list");
+            SOMAR_HIP(hipMemcpy(dev, v.data(), v.size() * sizeof(GhostOp), hipMemcpyHostToDevice));
+        }
+    };
+    if (!d_diri_ops_.empty()) fix(h_diri_ops0_, d_diri_ops_[0]);
+    if (full_ && !full_prog_.empty())
+        for (FullProgram& P : full_prog_[0]) {
+            fix(P.h_ops, P.d_ops);
+            fix(P.h_box_ops, P.d_box_ops);
+        }
 }
 
 void PressureSolver::drop_graphs()
@@ -1805,7 +1930,7 @@ void PressureSolver::build_box_tables(int d)
                     const GhostOp& op = Pg.h_box_ops[o];
                     const int stage = op.pad_ & 0xffff;
                     if (stage != cur) { stg.push_back((int)ent.size() - efirst[b]); cur = stage; }
-                    SOMAR_CHECK(op.type != GHOST_DIRI, "k_box_bicgstab: Dirichlet ghosts are not compiled (levels with Dirichlet sides take the launch path)");
+                    SOMAR_CHECK(!ghost_is_diri(op.type), "k_box_bicgstab: Dirichlet ghosts are not compiled (levels with Dirichlet sides take the launch path)");
                     for (int k = 0; k < op.n[2]; ++k)
                         for (int j = 0; j < op.n[1]; ++j)
                             for (int i = 0; i < op.n[0]; ++i) {

@@ -125,6 +125,18 @@ public:
     // Dirichlet sides (EllipticConstDiriBCGhostClass, BCInterface/EllipticBCUtils.cpp:382-424): values per
     // {loX,hiX,loY,hiY,loZ,hiZ}, before finalize.  Such a solver runs the two-pass / direct-load kernels.
     void set_bc_values(const double v[6]);
+    // Position-dependent values of the Dirichlet side (dir, side) (EllipticDiriBCGhostClass, BCInterface/EllipticBCUtils.cpp:
+    // 548-646): one value per boundary face over the whole domain box of depth 0, Fortran order over the two transverse
+    // directions in increasing order.  nullptr: back to the constant of set_bc_values.  Before or after finalize; after it
+    // only copies into the existing device buffers (op lists and face values keep their addresses).
+    void set_bc_face_values(int dir, int side, const double* values);
+    bool has_face_values() const
+    {
+        for (int d = 0; d < 3; ++d)
+            for (int s = 0; s < 2; ++s)
+                if (face_[d][s]) return true;
+        return false;
+    }
     // Non-diagonal metric on a level with coarse-fine boundaries:
     //   cf_ev: ExtrapolateCFEV(phi, cfregion, 2) -- the edge / vertex ghosts next to the CF faces, after a CF fill
     //   (interpCFGhosts, MappedAMRPoissonOp.cpp:2193-2216);  flux_fields: getFlux (fillExtrap + MAPPEDGETFLUX, beta = 1)
@@ -141,7 +153,7 @@ public:
     {
         for (int d = 0; d < 3; ++d)
             for (int s = 0; s < 2; ++s)
-                if (bc_value_[d][s] != 0.0) return false;
+                if (bc_value_[d][s] != 0.0 || face_[d][s]) return false;
         return true;
     }
     // ConstInterpPS / ZeroAvgConstInterpPS of depth 0 from a coarse field living on layout C (AMRProlong)
@@ -297,7 +309,8 @@ private:
     // d_ops: the ops stage by stage (first / count per stage) for the staged form, one launch per stage; d_box_ops / d_box_first:
     // the same ops sorted by box, then stage (GhostOp::pad_), for the one-launch form (k_ghost_program, small levels)
     struct FullProgram { GhostOp* d_ops = nullptr; std::vector<int> first, count; GhostOp* d_box_ops = nullptr; int* d_box_first = nullptr; int max_box_ops = 0;
-                         std::vector<GhostOp> h_box_ops; std::vector<int> h_box_first; };   // host copy of the box-sorted list (k_box_bicgstab's tables)
+                         std::vector<GhostOp> h_box_ops; std::vector<int> h_box_first;   // host copy of the box-sorted list (k_box_bicgstab's tables)
+                         std::vector<GhostOp> h_ops; };                                   // ... and of d_ops (refresh_diri_ops)
     void upload_program(FullProgram& P, const std::vector<std::vector<GhostOp>>& stages, int npatches);
     static void free_program(FullProgram& P);
     // small levels run a ghost program as ONE launch, one workgroup per box (SOMAR_GHOST_STAGED=1: always stage by stage)
@@ -358,6 +371,20 @@ private:
     int n_extrapbc_ops_ = 0;
     void build_diri_ops(int d);
     void apply_diri(int d, double* phi, bool homogeneous);
+    // ---- position-dependent Dirichlet values (depth 0; every coarser depth and correction is homogeneous) ----
+    // face_[a][s]: side (a, s) takes face_plane_[a][s] instead of bc_value_[a][s].  Every Dirichlet op of depth 0 covers the
+    // ghost layer of one (local patch, side) and owns that pair's slice of d_bcface_ (face_off_[6 * patch + 2 * a + s], -1:
+    // the patch does not touch the side); slices hold the plane's values in the op's loop order.
+    bool face_[3][2] = {{false, false}, {false, false}, {false, false}};
+    std::vector<double> face_plane_[3][2];
+    std::vector<long long> face_off_;
+    std::vector<double> h_bcface_;
+    double* d_bcface_ = nullptr;
+    std::vector<GhostOp> h_diri_ops0_;   // host copy of d_diri_ops_[0]
+    void build_face_slices();
+    void fill_face_values();
+    void set_diri_op(GhostOp& op) const;   // depth-0 Dirichlet op: constant or face-valued, as its side is now
+    void refresh_diri_ops();
     int mini_depth_ = 0;  // > 0 while a mini V-cycle runs: the depth count it is limited to
     int cycle_override_ = 0;  // != 0 inside an F-cycle's inner V-cycles: the effective numMG ("m_cycle = 1" hack, MappedMultiGrid.H:603-605)
     void cycle_down(int d, double* corr, const double* res, bool corr_zero);  // pre-smoothing + restriction

@@ -97,9 +97,9 @@ static std::vector<std::vector<GhostOp>> schedule_stages(const std::vector<std::
         IBox r;
         for (int d = 0; d < 3; ++d) { r.lo[d] = op.lo[d]; r.hi[d] = op.lo[d] + op.n[d] - 1; }
         if (op.type == GHOST_COPY) rd.push_back({r, op.srcf});
-        else if (op.type == GHOST_EXTRAP || op.type == GHOST_DIRI) {
+        else if (op.type == GHOST_EXTRAP || ghost_is_diri(op.type)) {
             IBox b = r;   // 1 .. 3 steps back along dir
-            const int far = op.type == GHOST_DIRI ? 1 : (op.order == 2 ? 3 : (op.order == 1 ? 2 : 1));
+            const int far = ghost_is_diri(op.type) ? 1 : (op.order == 2 ? 3 : (op.order == 1 ? 2 : 1));
             if (op.sgn > 0) { b.lo[op.dir] = r.lo[op.dir] - far; b.hi[op.dir] = r.hi[op.dir] - 1; }
             else { b.lo[op.dir] = r.lo[op.dir] + 1; b.hi[op.dir] = r.hi[op.dir] + far; }
             rd.push_back({b, op.srcf});
@@ -130,7 +130,7 @@ static std::vector<std::vector<GhostOp>> schedule_stages(const std::vector<std::
             const GhostOp& op = ops[q];
             IBox w;
             for (int d = 0; d < 3; ++d) { w.lo[d] = op.lo[d]; w.hi[d] = op.lo[d] + op.n[d] - 1; }
-            wrs[q] = {w, (op.type == GHOST_NEUM || op.type == GHOST_DIRI) ? 0 : op.dstf};
+            wrs[q] = {w, (op.type == GHOST_NEUM || ghost_is_diri(op.type)) ? 0 : op.dstf};
             reads_of(op, rds[q]);
             int st = 0;
             for (size_t e = 0; e < q; ++e) {
@@ -162,8 +162,8 @@ void reads_offsets(const GhostOp& op, std::vector<ReadOff>& rd)
 {
     rd.clear();
     if (op.type == GHOST_COPY) rd.push_back({{0, 0, 0}, op.srcf});
-    else if (op.type == GHOST_EXTRAP || op.type == GHOST_DIRI) {
-        const int far = op.type == GHOST_DIRI ? 1 : (op.order == 2 ? 3 : (op.order == 1 ? 2 : 1));
+    else if (op.type == GHOST_EXTRAP || ghost_is_diri(op.type)) {
+        const int far = ghost_is_diri(op.type) ? 1 : (op.order == 2 ? 3 : (op.order == 1 ? 2 : 1));
         for (int k = 1; k <= far; ++k) {
             ReadOff r{{0, 0, 0}, op.srcf};
             r.o[op.dir] = -op.sgn * k;
@@ -215,7 +215,7 @@ static void drop_dead_ops(const Level& L, std::vector<std::vector<GhostOp>>& per
         std::vector<char> keep(ops.size(), 1);
         for (size_t q = ops.size(); q-- > 0;) {
             const GhostOp& op = ops[q];
-            const int wf = (op.type == GHOST_NEUM || op.type == GHOST_DIRI) ? 0 : op.dstf;
+            const int wf = (op.type == GHOST_NEUM || ghost_is_diri(op.type)) ? 0 : op.dstf;
             bool any = false;
             for (int k = op.lo[2]; k < op.lo[2] + op.n[2] && !any; ++k)
                 for (int j = op.lo[1]; j < op.lo[1] + op.n[1] && !any; ++j)
@@ -455,6 +455,7 @@ void PressureSolver::upload_program(FullProgram& P, const std::vector<std::vecto
     P.first.clear();
     P.count.clear();
     P.h_box_ops.clear();
+    P.h_ops.clear();
     P.h_box_first.assign(npatches + 1, 0);
     std::vector<std::vector<GhostOp>> byBox(npatches);
     for (size_t s = 0; s < stages.size(); ++s) {
@@ -502,6 +503,7 @@ void PressureSolver::upload_program(FullProgram& P, const std::vector<std::vecto
     SOMAR_HIP(hipMemcpy(P.d_box_ops, sorted.data(), sorted.size() * sizeof(GhostOp), hipMemcpyHostToDevice));
     P.h_box_ops = sorted;
     P.h_box_first = first;
+    P.h_ops = flat;
     SOMAR_HIP(hipMalloc(&P.d_box_first, first.size() * sizeof(int)));
     SOMAR_HIP(hipMemcpy(P.d_box_first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice));
 }
@@ -533,6 +535,10 @@ void PressureSolver::build_full_programs(int d)
         if (which >= 4 && !full_march(d)) continue;   // [4] / [5]: [0] / [1] for the marching kernels (psi in frames only)
         FullProgram& P = full_prog_[d][which];
         auto stages = build_program(L, which >= 4 ? which - 4 : which, bc_value_, which >= 4);
+        if (d == 0 && diri_)
+            for (auto& stage : stages)
+                for (GhostOp& op : stage)
+                    if (ghost_is_diri(op.type)) set_diri_op(op);
         upload_program(P, stages, L.npatches());
     }
     if (full_march(d)) upload_program(full_prog_[d][6], {frame_copy_stage(L)}, L.npatches());

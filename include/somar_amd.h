@@ -616,6 +616,36 @@ int somar_solver_set_metric_uniform(somar_solver_t* s, const double* c4);
 #define SOMAR_MAP_TWISTED1 4
 int somar_solver_set_metric_map(somar_solver_t* s, int kind, const double* L, const double* depth, const int* depth_lo,
                                 const int* depth_n);
+/* Metric refresh of a FINALIZED solver, without redefining it.  The reference redefines its projector with a new metric all the
+ * time: every implicit-gravity step installs an AlteredMetric that depends on dt and N^2 (AMRNavierStokesAdvancePPMIG.cpp:
+ * 331-342, 520-531), every sync projection builds its projector inside the time loop (AMRNavierStokesSync.cpp:280-281).  Here
+ * the layout, the BCs and the parameters stay; only the metric changes, in place:
+ *  - between begin and end the producers somar_solver_set_metric_ortho / _full / _uniform / _map are accepted on the finalized
+ *    handle and write into the depth-0 arrays that already exist (no address changes).  somar_altered_jgup followed by
+ *    somar_solver_set_metric_full is the implicit-gravity route.  Outside an open update they refuse after finalize as before.
+ *    _ortho / _uniform / a diagonal map refuse on a solver finalized with a non-diagonal metric, _full / a non-diagonal map on
+ *    a diagonal one: the kernel family and the ghost programs are fixed at finalize.
+ *  - end recomputes everything a fresh create + set_metric + finalize with the new metric computes, bit for bit, into the
+ *    existing buffers: metric ghosts and lapDiag of every depth, the coarse depths' face averages and harmonic J^{-1}
+ *    (fill_MGfields, MappedAMRPoissonOpFactory.cpp:1164-1234), the uniform-metric and zero-plane flags (and the marching tile
+ *    tables they select), the folded-prolongation volumes, the null-space probe of every depth (with the coefficients the
+ *    solver was created with, as at finalize), and on a sharded solver the agglomerated tail.  Captured graphs are dropped and
+ *    re-captured on the next cycle.  Kept: the coefficients of somar_solver_set_alpha_beta, the Dirichlet face values, the
+ *    velocity BCs.  Not touched: the velocity scale arrays of somar_solver_set_cc_j / _face_j, which are the caller's and can
+ *    be re-set after finalize on their own.
+ *  - while an update is open, solves, cycles, projections and heat steps refuse; a second begin and an end without begin refuse.
+ *  - the somar_solver_* pair takes a single-level handle or the level handle of a somar_leptic (somar_leptic_level, finalized
+ *    leptic handles only; the leptic solver's internal operators follow at end).  A level of a hierarchy goes through the
+ *    somar_amr_* pair: begin opens every level, each level's metric is written through its somar_amr_level handle, end
+ *    refreshes every level whose metric was written, and the leptic attachment of those levels (somar_amr_enable_leptic).
+ * somar_solver_metric_download (tests, diagnostics): one local patch at MG depth `depth` (the agglomerated tail included),
+ * valid region, Fortran order; which 0..2: J g^{aa} on faces(valid, a); 3: J^{-1}; 4: lapDiag; 16 + 3a + b: J g^{ab} of a
+ * non-diagonal metric on faces(valid, a). */
+int somar_solver_metric_update_begin(somar_solver_t* s);
+int somar_solver_metric_update_end(somar_solver_t* s);
+int somar_amr_metric_update_begin(somar_amr_t* a);
+int somar_amr_metric_update_end(somar_amr_t* a);
+int somar_solver_metric_download(somar_solver_t* s, int depth, int which, int patch, double* host);
 /* The nodal "depth" of the reference's analytic bathymetric maps, for SOMAR_MAP_BATHYMETRIC (host arithmetic, no GPU; x, y: the
  * Cartesian coordinates of the nodes, for these maps x = dXi0 * i, y = dXi1 * j):
  *   LedgeMap::fill_bathymetry            geometry/maps/LedgeMap.cpp:38-60, 98-164   order 1 / 3: h_l left of x_l, h_r right of x_r,

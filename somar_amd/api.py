@@ -3,6 +3,7 @@
 so the parity tests read like calls into the reference.  No computation happens here and there is no
 CPU fallback: a missing library or a missing GPU raises.
 """
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -184,6 +185,11 @@ _SIGS = {
     "somar_diag_stream_probe": [C.c_int, C.c_longlong, C.c_int, _PD],
     "somar_metric_jgup_from_dxdxi": [C.c_longlong, C.c_int, _PD, _PD, C.c_double, _PD],
     "somar_solver_set_metric_uniform": [_H, _PD],
+    "somar_solver_metric_update_begin": [_H],
+    "somar_solver_metric_update_end": [_H],
+    "somar_amr_metric_update_begin": [_H],
+    "somar_amr_metric_update_end": [_H],
+    "somar_solver_metric_download": [_H, C.c_int, C.c_int, C.c_int, _PD],
     "somar_comm_unique_id": [C.POINTER(C.c_ubyte)],
     "somar_comm_create": [C.POINTER(_H), C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int],
     "somar_comm_create_shm": [C.POINTER(_H), C.c_char_p, C.c_int, C.c_int, C.c_longlong],
@@ -526,6 +532,36 @@ class AMRPressureSolver:
         f, c = C.c_int(), (C.c_double * 4)()
         _ck(lib().somar_solver_metric_uniform(self._h, depth, C.byref(f), c))
         return tuple(c) if f.value else None
+
+    @contextlib.contextmanager
+    def metricUpdate(self):
+        """with s.metricUpdate(): s.setMetric...(...) -- refreshes the metric of a finalized solver (or hierarchy: write each
+        level through self.levels[l]) in place; the end recomputes everything finalize derived from it.  An exception inside
+        the block still closes the update (with the metric as far as it was written)."""
+        amr = getattr(self, "_amr", None)
+        if amr is not None:
+            _ck(lib().somar_amr_metric_update_begin(amr))
+        else:
+            _ck(lib().somar_solver_metric_update_begin(self._h))
+        try:
+            yield self
+        finally:
+            if amr is not None:
+                _ck(lib().somar_amr_metric_update_end(amr))
+            else:
+                _ck(lib().somar_solver_metric_update_end(self._h))
+
+    def metricDownload(self, depth, which, patch):
+        """one local patch's metric array at MG depth `depth` (valid region): which 0..2 J g^{aa} on faces(valid, a), 3 J^{-1},
+        4 lapDiag, 16 + 3a + b J g^{ab} of a non-diagonal metric"""
+        lo, hi, _ = self.patch_box(patch, depth)
+        shp = [h - l + 1 for l, h in zip(lo, hi)]
+        dir = which if which < 3 else ((which - 16) // 3 if which >= 16 else -1)
+        if dir >= 0:
+            shp[dir] += 1
+        out = np.zeros(shp, order="F")
+        _ck(lib().somar_solver_metric_download(self._h, int(depth), int(which), int(patch), _dp(out)))
+        return out
 
     def mgRefRatios(self):
         out = []

@@ -50,7 +50,7 @@ AMRLink::~AMRLink()
 // written by a fill kernel
 void PressureSolver::set_metric_uniform(const double c4[4])
 {
-    SOMAR_CHECK(!lev.empty() && !finalized, "set_metric before define / after finalize");
+    metric_written("uniform");
     SOMAR_CHECK(!full_, "set_metric_uniform is the diagonal-metric (Cartesian) producer");
     Level& L = *lev[0];
     for (int a = 0; a < 4; ++a) {
@@ -725,6 +725,7 @@ void AMRSolver::interp_cf(int l, double* phiFine, const double* phiCoarse, bool 
 void AMRSolver::level_project(int l, int centring, double dt, bool zeroPressure, bool forceHomogeneous, bool wall,
                               SolveStats& st)
 {
+    check_idle("level_project");
     SOMAR_CHECK(finalized_ && l >= 0 && l < nlevels(), "level_project: bad level / hierarchy not finalized");
     SOMAR_CHECK(centring == 0 || centring == 1, "centring: 0 MAC, 1 cell-centred");
     PressureSolver& P = *S[l];
@@ -898,6 +899,7 @@ void AMRSolver::average_down_ccvel(int l)
 void AMRSolver::cc_project(int l_min, int l_max, double dt, bool zeroPressure, bool forceHomogeneous, bool wall,
                            SolveStats& st)
 {
+    check_idle("cc_project");
     SOMAR_CHECK(finalized_ && 0 <= l_min && l_min <= l_max && l_max < nlevels(), "cc_project: bad level range");
     for (int l = l_min; l <= l_max; ++l) comp_divergence_cc(l, l_max, S[l]->field(0, 1), wall);
     if (dt != 0.0)
@@ -1082,6 +1084,7 @@ void AMRSolver::level_relax(int l, double* corr, const double* res, int iters, b
 
 void AMRSolver::vcycle(double* const* uberCorr, double* const* uberRes, int ilev, int l_max, int l_base)
 {
+    check_idle("vcycle");
     const bool lean = lean_ && !lepticCycle_ && l_max != l_base;
     if (ilev == l_max) {
         // m_residual := uberResidual, m_correction := 0 on every level (MappedAMRMultiGrid.H:1504-1510).  Lean: the copies of
@@ -1178,6 +1181,27 @@ void AMRSolver::vcycle(double* const* uberCorr, double* const* uberRes, int ilev
     }
 }
 
+void AMRSolver::check_idle(const char* what) const
+{
+    SOMAR_CHECK(!updating_, std::string(what) + " while a metric update is open (end it first: somar_amr_metric_update_end)");
+}
+
+void AMRSolver::metric_update_begin()
+{
+    SOMAR_CHECK(finalized_, "metric_update_begin: the hierarchy is not finalized (set the metrics before finalize instead)");
+    SOMAR_CHECK(!updating_, "metric_update_begin: an update is already open");
+    for (auto& s : S) s->metric_update_begin(true);
+    updating_ = true;
+}
+
+void AMRSolver::metric_update_end()
+{
+    SOMAR_CHECK(updating_, "metric_update_end without metric_update_begin");
+    updating_ = false;
+    for (int l = 0; l < nlevels(); ++l)
+        if (S[l]->metric_update_end(true) && l < (int)leptic_.size()) leptic_[l]->refresh_metric();
+}
+
 void AMRSolver::set_alpha_beta(double a, double b)
 {
     SOMAR_CHECK(finalized_, "set_alpha_beta before finalize");
@@ -1187,6 +1211,7 @@ void AMRSolver::set_alpha_beta(double a, double b)
 void AMRSolver::heat_step(int l, int scheme, double dt, bool zeroPhi, double oldTime, double crseOldTime, double crseNewTime,
                           SolveStats& st)
 {
+    check_idle("heat_step");
     SOMAR_CHECK(finalized_ && l >= 0 && l < nlevels(), "bad level / hierarchy not finalized");
     SOMAR_CHECK(scheme >= 0 && scheme <= 2, "heat scheme: 0 backward Euler, 1 Crank-Nicolson, 2 TGA");
     SOMAR_CHECK(dt >= 0.0 && crseNewTime >= crseOldTime, "negative time step");
@@ -1289,6 +1314,7 @@ void AMRSolver::heat_step(int l, int scheme, double dt, bool zeroPhi, double old
 // Per level: phiNew = phi(), rhst = rhs(), phiOld = heat_field(0), source = heat_field(1), srct = heat_field(2).
 void AMRSolver::tga_step(int l_max, int l_base, double dt, SolveStats& st)
 {
+    check_idle("tga_step");
     SOMAR_CHECK(finalized_ && l_base >= 0 && l_base <= l_max && l_max < nlevels(), "tga_step: bad level range");
     // createData allocates m_srct for l_base..l_max only (MappedAMRTGA.H:388-403); computeAMROperator on m_srct then reads
     // *m_srct[l_base - 1] for the coarse-fine values of level l_base (MappedAMRMultiGrid.H:907-909) -- a null pointer when
@@ -1372,6 +1398,7 @@ void AMRSolver::solve_leptic(int l_max, int l_base, bool zeroPhi, bool forceHomo
 
 void AMRSolver::solve_impl(int l_max, int l_base, bool zeroPhi, bool forceHomogeneous, SolveStats& s)
 {
+    check_idle("solve");
     SOMAR_CHECK(finalized_, "solve before finalize");
     SOMAR_CHECK(0 <= l_base && l_base <= l_max && l_max < nlevels(), "bad level range");
     const int n = nlevels();

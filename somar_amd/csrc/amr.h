@@ -167,6 +167,10 @@ public:
     // The flux-register scales follow: reflux() rewrites them when the coarse operator's beta differs from the one they hold
     // (sync_reflux_scales), as MappedAMRPoissonOp::reflux takes m_beta / m_dx when it runs.
     void set_alpha_beta(double a, double b);
+    // metric refresh of a finalized hierarchy: begin opens an update on every level (their set_metric_* producers then write
+    // in place); end refreshes every level whose metric was written, and the leptic attachment of such a level
+    void metric_update_begin();
+    void metric_update_end();
     // MappedAMRTGA<T>::oneStep (AMRElliptic/MappedAMRTGA.H:417-497): one composite TGA step over levels l_base..l_max;
     // phiNew = PHI, phiOld = HEAT_OLD, source = HEAT_SRC of every level; st = the LAST solve's
     void tga_step(int l_max, int l_base, double dt, SolveStats& st);
@@ -259,6 +263,8 @@ private:
     std::vector<int> visits_;
     bool lean_ = true;
     bool finalized_ = false;
+    bool updating_ = false;
+    void check_idle(const char* what) const;
 };
 
 }  // namespace somar

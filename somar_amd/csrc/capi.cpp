@@ -22,6 +22,7 @@ struct somar_solver {
     PressureSolver* ps = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool owned = true;  // false: a level of a somar_amr (somar_amr_level)
+    LepticSolver* lep = nullptr;  // the level handle of a somar_leptic: its internal solvers follow a metric refresh
 };
 
 struct somar_leptic {
@@ -1533,6 +1534,50 @@ int somar_solver_set_metric_map(somar_solver_t* s, int kind, const double* L, co
     API_END
 }
 
+// ---- metric refresh of a finalized solver / hierarchy (AMRNavierStokesAdvancePPMIG.cpp:331-342 redefines the projector with a
+// new AlteredMetric every implicit-gravity step; here only what the metric determines is recomputed) --------------------------
+int somar_solver_metric_update_begin(somar_solver_t* s)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps, "null argument");
+    s->ps->metric_update_begin();
+    API_END
+}
+
+int somar_solver_metric_update_end(somar_solver_t* s)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps, "null argument");
+    SOMAR_CHECK(s->ps->metric_updating(), "metric_update_end without metric_update_begin");
+    s->ps->metric_update_end();
+    if (s->lep) s->lep->refresh_metric();
+    API_END
+}
+
+int somar_amr_metric_update_begin(somar_amr_t* a)
+{
+    API_BEGIN
+    SOMAR_CHECK(a, "null argument");
+    a->amr->metric_update_begin();
+    API_END
+}
+
+int somar_amr_metric_update_end(somar_amr_t* a)
+{
+    API_BEGIN
+    SOMAR_CHECK(a, "null argument");
+    a->amr->metric_update_end();
+    API_END
+}
+
+int somar_solver_metric_download(somar_solver_t* s, int depth, int which, int patch, double* host)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps && host, "null argument");
+    s->ps->metric_download(depth, which, patch, host);
+    API_END
+}
+
 int somar_solver_set_metric_uniform(somar_solver_t* s, const double* c4)
 {
     API_BEGIN
@@ -1725,6 +1770,7 @@ int somar_leptic_create(somar_leptic_t** out, const int* domain_lo, const int* d
         h->level = new somar_solver;
         h->level->ps = &h->lep->orig();
         h->level->owned = false;
+        h->level->lep = h->lep;
         SOMAR_HIP(hipEventCreate(&h->level->ev0));
         SOMAR_HIP(hipEventCreate(&h->level->ev1));
         for (int q = 0; q < 2; ++q) {

@@ -191,6 +191,14 @@ void launch_stream_probe(hipStream_t st, int kind, int workgroups, double* const
 // (min, max) per (patch, k-chunk) of a over the valid cells (dir < 0) or valid dir-faces: out[2 * npatches * MM_CH] (device)
 constexpr int MM_CH = 64;
 void launch_minmax_valid(hipStream_t st, const LevelDev& L, const double* a, int dir, double* out);
+// metric refresh (metric_refresh.hip): every coarse metric array of one MG depth from the next finer one in one launch --
+// item dir 0..2: arithmetic average over faces(valid, dir) (k_avg_face), dir -1: harmonic cell average (k_avg_harmonic)
+struct CoarsenItem { const double* fine; double* crse; int patch; int dir; };
+void launch_coarsen_metric(hipStream_t st, const LevelDev& C, const LevelDev& F, const CoarsenItem* items, int nitems,
+                           int gy, const int r[3]);
+// k_minmax_valid over a table of arrays of any depth: out[2 * (item * MM_CH + chunk)] = (min, max)
+struct MinMaxItem { const double* a; const PatchDesc* patches; int patch; int dir; };
+void launch_minmax_all(hipStream_t st, const MinMaxItem* items, int nitems, double* out);
 // mode 0: sum a*b, 1: max|a|, 2: sum|a|, 3: signed max a  -> out[0] (device)
 // ordered: reference-ordered serial sum (modes 0 and 2; meant for small levels, see k_reduce_ordered)
 void launch_reduce(hipStream_t st, const LevelDev& L, const double* a, const double* b, int mode, double* partials,

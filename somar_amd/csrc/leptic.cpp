@@ -212,6 +212,29 @@ void LepticSolver::finalize()
     finalized_ = true;
 }
 
+void LepticSolver::refresh_metric()
+{
+    SOMAR_CHECK(finalized_, "leptic metric refresh before finalize");
+    Level& O = orig_->level(0);
+    Level& V = vert_->level(0);
+    if (full_) {
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) launch_copy(st_, V.dev.jgf[a][b], O.dev.jgf[a][b], V.field_elems);
+    } else {
+        for (int d = 0; d < 3; ++d) launch_copy(st_, V.dev.jg[d], O.dev.jg[d], V.field_elems);
+    }
+    launch_set(st_, V.dev.jinv, V.field_elems, 1.0);
+    if (doHorizSolve_) {
+        Level& F = horiz_->level(0);
+        if (full_) launch_lep_avg_metric_full(st_, V.d_ctiles, V.nctiles, V.ctile_j, V.dev, F.dev);
+        else launch_lep_avg_metric(st_, V.d_ctiles, V.nctiles, V.ctile_j, V.dev, F.dev);
+        launch_set(st_, F.dev.jinv, F.field_elems, 1.0);
+    }
+    sync();
+    vert_->refresh_metric();
+    if (doHorizSolve_) horiz_->refresh_metric();
+}
+
 // setZeroAvg, LevelLepticSolver.cpp:1668-1710: plain (unweighted) mean over the valid cells, removed from the whole FAB
 void LepticSolver::set_zero_avg(double* hphi)
 {
@@ -225,6 +248,7 @@ void LepticSolver::set_zero_avg(double* hphi)
 
 void LepticSolver::solve(bool homogeneous, LepticStats& S)
 {
+    orig_->check_idle("leptic solve");
     // Neumann walls are homogeneous either way; a Dirichlet wall's values enter the first residual unless homogeneous
     solve_fields(orig_->phi(), orig_->rhs(), S, homogeneous);
 }

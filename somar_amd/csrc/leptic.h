@@ -61,6 +61,8 @@ public:
     PressureSolver& horiz() { return *horiz_; }
     PressureSolver* horiz_ptr() { return horiz_.get(); }   // null: no column is Neumann-Neumann, there is no flat problem
     void finalize();  // after the metric of orig() is set: finalizes all three solvers
+    // after a metric refresh of orig(): the J-scaled operator's copy, the flat problem's vertical averages, then both solvers
+    void refresh_metric();
     // LevelLepticSolver::solve(phi, rhs) on orig()'s resident phi / rhs: phi += leptic correction
     void solve(bool homogeneous, LepticStats& S);
     // the same on any two fields of the level's layout: phi += leptic correction for rhs - L[phi] (homogeneous CF / BC values)

@@ -63,6 +63,9 @@ PressureSolver::~PressureSolver()
     for (double* f : f_psi) hipFree(f);
     for (double* f : f_W) hipFree(f);
     hipFree(d_fold);
+    for (CoarsenItem* q : d_coarsen_) hipFree(q);
+    hipFree(d_mm_items_);
+    hipFree(d_mm_out_);
     for (FullProgram& q : aux_prog_) free_program(q);
     for (double* f : f_heatflux) Level::free_field(f);
     for (auto& pr : full_prog_)
@@ -257,7 +260,7 @@ void PressureSolver::define(const IBox& domain, const bool periodic[3], const do
 void PressureSolver::set_metric_ortho(int patch, const double* jg0, const double* jg1, const double* jg2,
                                       const double* jinv)
 {
-    SOMAR_CHECK(!lev.empty() && !finalized, "set_metric before define / after finalize");
+    metric_written("ortho");
     Level& L = *lev[0];
     SOMAR_CHECK(patch >= 0 && patch < L.npatches(), "bad patch index");
     const IBox valid = L.boxes[L.local[patch]];
@@ -631,10 +634,9 @@ void PressureSolver::build_agglomerated_tail(int depth)
                     hasCF_ ? dxCrse_ : nullptr);
     Level& R = *coarse_->lev[0];
     // metric: faces of a box live at indices 0..n, so take one layer beyond the valid cells
-    Copier metric;
-    metric.define_allgather(T, R, 1, comm_);
-    for (int d = 0; d < prm.spaceDim; ++d) metric.run(T.dev.jg[d], R.dev.jg[d], st_);
-    metric.run(T.dev.jinv, R.dev.jinv, st_);
+    agglom_metric_.define_allgather(T, R, 1, comm_);   // kept: a metric refresh runs it again
+    for (int d = 0; d < prm.spaceDim; ++d) agglom_metric_.run(T.dev.jg[d], R.dev.jg[d], st_);
+    agglom_metric_.run(T.dev.jinv, R.dev.jinv, st_);
     sync();
     coarse_->finalize();
     agglom_depth_ = depth;
@@ -678,6 +680,266 @@ void PressureSolver::agglom_cycle(double* corr, const double* res, bool corr_zer
     bottom_exit = C.bottom_exit;
     launch_copy_items2(st_, C.lev[0]->dev.patches, T.dev.patches, d_agglom_back_, n_agglom_back_, cC, corr);
     if (profiling_) prof_end(3);
+}
+
+// ------------------------------------------------------------------------------------
+// metric refresh of a finalized solver (see solver.h).  The layout, the BCs and the coefficients stay; everything finalize
+// derived from the metric is recomputed, in finalize's order, into the buffers it allocated -- so the result is what a
+// fresh define + set_metric + finalize with the new metric computes, bit for bit.
+// ------------------------------------------------------------------------------------
+template <class T>
+static T* table_to_device(const std::vector<T>& v)
+{
+    T* d = nullptr;
+    SOMAR_HIP(hipMalloc(&d, v.size() * sizeof(T)));
+    SOMAR_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    SOMAR_HIP(hipDeviceSynchronize());   // null-stream copy vs the solver's non-blocking stream
+    return d;
+}
+
+void PressureSolver::check_idle(const char* what) const
+{
+    SOMAR_CHECK(!updating_, std::string(what) + " while a metric update is open (end it first: somar_solver_metric_update_end / "
+                                                "somar_amr_metric_update_end)");
+}
+
+void PressureSolver::metric_written(const char* producer)
+{
+    SOMAR_CHECK(!lev.empty() && (!finalized || updating_), "set_metric before define / after finalize");
+    if (!finalized) return;
+    const bool diag = !strcmp(producer, "ortho") || !strcmp(producer, "uniform") || !strcmp(producer, "cylindrical");
+    SOMAR_CHECK(!(diag && full_), std::string("set_metric_") + producer +
+                                      ": this solver was finalized with the non-diagonal metric (its kernels and ghost programs "
+                                      "are fixed at finalize); use set_metric_full / set_metric_map with a non-diagonal map");
+    SOMAR_CHECK(diag || full_, std::string("set_metric_") + producer +
+                                   ": this solver was finalized with a diagonal metric (its kernels and ghost programs are fixed "
+                                   "at finalize); use set_metric_ortho / set_metric_uniform");
+    metric_written_ = true;
+}
+
+void PressureSolver::metric_update_begin(bool amr_member_ok)
+{
+    SOMAR_CHECK(finalized, "metric_update_begin: the solver is not finalized (set the metric before finalize instead)");
+    SOMAR_CHECK(!amr_member_ || amr_member_ok,
+                "metric update on a level of an AMR hierarchy goes through the hierarchy (somar_amr_metric_update_begin / _end)");
+    SOMAR_CHECK(!updating_, "metric_update_begin: an update is already open");
+    updating_ = true;
+    metric_written_ = false;
+}
+
+bool PressureSolver::metric_update_end(bool only_if_written)
+{
+    SOMAR_CHECK(updating_, "metric_update_end without metric_update_begin");
+    const bool run = metric_written_ || !only_if_written;
+    updating_ = false;
+    metric_written_ = false;
+    if (run) refresh_metric();
+    return run;
+}
+
+void PressureSolver::detect_metric_flags()
+{
+    const int D = (int)lev.size();
+    const char* eu = getenv("SOMAR_NO_UNIFORM");
+    const char* ez = getenv("SOMAR_NO_ZERO_PLANES");
+    const bool uni_on = !(eu && atoi(eu) != 0) && !full_ && prm.spaceDim == 3;
+    const bool zero_on = !(ez && atoi(ez) != 0) && full_ && prm.spaceDim == 3;
+    for (auto& Lp : lev) { Lp->dev.P.uniform = 0; Lp->dev.P.zero_xy = 0; }
+    if (!uni_on && !zero_on) return;
+    const int na = uni_on ? 4 : 2;
+    auto array = [&](Level& L, int a, int* dir) -> const double* {
+        if (uni_on) { *dir = a < 3 ? a : -1; return a < 3 ? L.dev.jg[a] : L.dev.jinv; }
+        *dir = a;
+        return a == 0 ? L.dev.jgf[0][1] : L.dev.jgf[1][0];
+    };
+    if (!d_mm_items_) {
+        std::vector<MinMaxItem> items;
+        mm_first_.assign(D, 0);
+        for (int d = 0; d < D; ++d) {
+            Level& L = *lev[d];
+            mm_first_[d] = (int)items.size();
+            for (int a = 0; a < na; ++a)
+                for (int pi = 0; pi < L.npatches(); ++pi) {
+                    MinMaxItem it;
+                    it.a = array(L, a, &it.dir);
+                    it.patches = L.dev.patches;
+                    it.patch = pi;
+                    SOMAR_CHECK(it.a, "internal: metric plane missing");
+                    items.push_back(it);
+                }
+        }
+        n_mm_items_ = (int)items.size();
+        SOMAR_HIP(hipMalloc(&d_mm_out_, sizeof(double) * (2 * (size_t)std::max(n_mm_items_, 1) * MM_CH + 9 * (size_t)D)));
+        if (n_mm_items_) d_mm_items_ = table_to_device(items);
+        else SOMAR_HIP(hipMalloc(&d_mm_items_, sizeof(MinMaxItem)));
+    }
+    std::vector<double> mm(2 * (size_t)n_mm_items_ * MM_CH);
+    launch_minmax_all(st_, d_mm_items_, n_mm_items_, d_mm_out_);
+    if (n_mm_items_) SOMAR_HIP(hipMemcpyAsync(mm.data(), d_mm_out_, sizeof(double) * mm.size(), hipMemcpyDeviceToHost, st_));
+    SOMAR_HIP(hipStreamSynchronize(st_));
+    // per depth: uniform -- (max, -min) of the four arrays, -inf where a rank holds no box; zero planes -- max |value|
+    std::vector<double> h(9 * (size_t)D, -HUGE_VAL);
+    for (int d = 0; d < D; ++d) {
+        Level& L = *lev[d];
+        const int np = L.npatches();
+        double* hd = h.data() + 9 * d;
+        hd[8] = 0.0;
+        for (int a = 0; a < na && np; ++a) {
+            const size_t q0 = (size_t)(mm_first_[d] + a * np) * MM_CH, q1 = q0 + (size_t)np * MM_CH;
+            for (size_t q = q0; q < q1; ++q) {
+                if (uni_on) {
+                    hd[2 * a] = std::max(hd[2 * a], mm[2 * q + 1]);
+                    hd[2 * a + 1] = std::max(hd[2 * a + 1], -mm[2 * q]);
+                } else {
+                    if (std::isfinite(mm[2 * q])) hd[8] = std::max(hd[8], std::fabs(mm[2 * q]));
+                    if (std::isfinite(mm[2 * q + 1])) hd[8] = std::max(hd[8], std::fabs(mm[2 * q + 1]));
+                }
+            }
+        }
+    }
+    if (comm_->size > 1) {
+        double* dh = d_mm_out_ + 2 * (size_t)std::max(n_mm_items_, 1) * MM_CH;
+        SOMAR_HIP(hipMemcpyAsync(dh, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st_));
+        comm_->allreduce(dh, (int)h.size(), 1, st_);
+        SOMAR_HIP(hipMemcpyAsync(h.data(), dh, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st_));
+        SOMAR_HIP(hipStreamSynchronize(st_));
+    }
+    for (int d = 0; d < D; ++d) {
+        Level& L = *lev[d];
+        if (!(L.active[0] && L.active[1] && L.active[2])) continue;
+        const double* hd = h.data() + 9 * d;
+        if (zero_on) { L.dev.P.zero_xy = hd[8] == 0.0 ? 1 : 0; continue; }
+        bool uni = true;
+        for (int a = 0; a < 4; ++a) uni = uni && std::isfinite(hd[2 * a]) && hd[2 * a] == -hd[2 * a + 1];
+        if (!uni) continue;
+        L.dev.P.uniform = 1;
+        for (int a = 0; a < 4; ++a) L.dev.P.uc[a] = hd[2 * a];
+    }
+}
+
+void PressureSolver::refresh_metric()
+{
+    SOMAR_CHECK(finalized, "metric refresh before finalize");
+    static const bool timing = getenv("SOMAR_TIMING") && atoi(getenv("SOMAR_TIMING")) != 0;
+    auto now = [&]() { if (timing) SOMAR_HIP(hipStreamSynchronize(st_)); return std::chrono::steady_clock::now(); };
+    const auto t0 = now();
+    const int D = (int)lev.size();
+    const int nd = prm.spaceDim;
+    if (d_coarsen_.empty()) {
+        // k_coarsen_metric's work items per depth: the (face direction, component) arrays build_coarser averages, then J^{-1}
+        d_coarsen_.assign(D, nullptr);
+        n_coarsen_.assign(D, 0);
+        gy_coarsen_.assign(D, 1);
+        for (int d = 1; d < D; ++d) {
+            Level& F = *lev[d - 1];
+            Level& C = *lev[d];
+            std::vector<CoarsenItem> items;
+            long long maxGroups = 1;
+            for (int pi = 0; pi < C.npatches(); ++pi) {
+                auto add = [&](const double* f, double* c, int dir) {
+                    items.push_back(CoarsenItem{f, c, pi, dir});
+                    const int* n = C.hpatches[pi].n;
+                    const long long nj = n[1] + (dir == 1), nk = n[2] + (dir == 2);
+                    maxGroups = std::max(maxGroups, (nj + 3) / 4 * nk);
+                };
+                for (int a = 0; a < nd; ++a) add(F.dev.jg[a], C.dev.jg[a], a);
+                if (full_)
+                    for (int a = 0; a < nd; ++a)
+                        for (int c = 0; c < nd; ++c)
+                            if (c != a) add(F.dev.jgf[a][c], C.dev.jgf[a][c], a);
+                add(F.dev.jinv, C.dev.jinv, -1);
+            }
+            n_coarsen_[d] = (int)items.size();
+            // enough workgroups to fill the device a few times over, spread evenly over the items
+            gy_coarsen_[d] = (int)std::min<long long>(maxGroups, std::max<long long>(1, 8192 / std::max<int>(1, n_coarsen_[d])));
+            if (!items.empty()) d_coarsen_[d] = table_to_device(items);
+        }
+    }
+    launch_lapdiag(st_, lev[0]->dev);
+    fill_metric_ghosts(*lev[0]);
+    for (int d = 1; d < D; ++d) {
+        Level& F = *lev[d - 1];
+        Level& C = *lev[d];
+        launch_coarsen_metric(st_, C.dev, F.dev, d_coarsen_[d], n_coarsen_[d], gy_coarsen_[d], F.mgCrseRefRatio);
+        launch_lapdiag(st_, C.dev);
+        fill_metric_ghosts(C);
+    }
+    if (coarse_) {
+        Level& T = *lev[agglom_depth_];
+        Level& R = *coarse_->lev[0];
+        for (int a = 0; a < nd; ++a) agglom_metric_.run(T.dev.jg[a], R.dev.jg[a], st_);
+        agglom_metric_.run(T.dev.jinv, R.dev.jinv, st_);
+        sync();
+        coarse_->refresh_metric();
+    }
+    const auto t1 = now();
+    detect_metric_flags();
+    {
+        // finalize's choice of the 7-point marching tiles where the metric is uniform (SOMAR_NARROW_7PT forces it)
+        const char* e = getenv("SOMAR_NARROW_7PT");
+        bool rebuilt = false;
+        for (auto& Lp : lev) {
+            const bool want = e ? atoi(e) != 0 : Lp->dev.P.uniform != 0;
+            if (want != Lp->narrow7_) { Lp->build_march_tiles(want); rebuilt = true; }
+        }
+        if (rebuilt) {
+            int maxTiles = 1;
+            for (auto& L : lev) maxTiles = std::max(std::max(maxTiles, L->dev.ntiles), std::max(L->nrtiles, L->nftiles));
+            SOMAR_HIP(hipStreamSynchronize(st_));
+            hipFree(d_partials);
+            SOMAR_HIP(hipMalloc(&d_partials, (size_t)maxTiles * 2 * sizeof(double)));
+        }
+    }
+    const auto t2 = now();
+    for (int d = 0; d + 1 < D; ++d) {
+        Level& F = *lev[d];
+        Level& C = *lev[d + 1];
+        launch_child_volume(st_, C.dev, F.dev, f_W[d + 1], F.mgCrseRefRatio, F.dxProduct);
+        launch_reduce(st_, C.dev, f_W[d + 1], nullptr, 2, d_partials, d_fold + 8 * d + 2);
+        comm_->allreduce(d_fold + 8 * d + 2, 1, 0, st_);
+    }
+    // the probe runs with the factory's coefficients, as at finalize (set_alpha_beta keeps the probe's choice, and so does this)
+    const bool swap = coefs_saved_ && (lev[0]->alpha != aCoef_ || lev[0]->beta != bCoef_);
+    std::vector<std::pair<double, double>> ab;
+    if (swap)
+        for (auto& L : lev) {
+            ab.emplace_back(L->alpha, L->beta);
+            L->alpha = aCoef_;
+            L->beta = bCoef_;
+            L->refresh_params();
+        }
+    for (int d = 0; d < D; ++d) probe_null_space(d);
+    if (swap)
+        for (int d = 0; d < D; ++d) {
+            lev[d]->alpha = ab[d].first;
+            lev[d]->beta = ab[d].second;
+            lev[d]->refresh_params();
+        }
+    drop_graphs();   // captured launches carry the old StencilParams and tile tables in their arguments
+    sync();
+    if (timing)
+        fprintf(stderr, "[somar timing] metric refresh %lld cells: coarse depths %.3f s, flags + tiles %.3f s, volumes + probes %.3f s\n",
+                lev[0]->valid_cells_global, std::chrono::duration<double>(t1 - t0).count(),
+                std::chrono::duration<double>(t2 - t1).count(), std::chrono::duration<double>(now() - t2).count());
+}
+
+void PressureSolver::metric_download(int depth, int which, int patch, double* host)
+{
+    SOMAR_CHECK(finalized && depth >= 0 && depth < this->depth(), "metric_download: depth out of range / not finalized");
+    Level& L = level(depth);
+    SOMAR_CHECK(patch >= 0 && patch < L.npatches(), "metric_download: patch out of range");
+    const IBox valid = L.boxes[L.local[patch]];
+    const double* f = nullptr;
+    int dir = -1;
+    if (which >= 0 && which < 3) { f = L.dev.jg[which]; dir = which; }
+    else if (which == 3) f = L.dev.jinv;
+    else if (which == 4) f = L.dev.lapdiag;
+    else if (which >= 16 && which < 25) { dir = (which - 16) / 3; f = L.dev.jgf[dir][(which - 16) % 3]; }
+    SOMAR_CHECK(f && (dir < 0 || dir < prm.spaceDim), "metric_download: no such array (which 0..4, or 16 + 3a + b of a non-diagonal metric)");
+    IBox b = valid;
+    if (dir >= 0) b.hi[dir] += 1;
+    L.download(f, patch, host, b, b, st_);
+    sync();
 }
 
 // ------------------------------------------------------------------------------------
@@ -1251,6 +1513,7 @@ void PressureSolver::set_vel_bc(const int kind[6], const double value[6])
 
 void PressureSolver::mac_project(double dt, bool zeroPressure, bool forceHomogeneous, SolveStats& s)
 {
+    check_idle("mac_project");
     divergence_mac(f_rhs, dt);
     solve(zeroPressure, forceHomogeneous, s);
     mac_correct(f_phi, dt);
@@ -1327,6 +1590,7 @@ double* PressureSolver::heat_field(int which)
 //   TGA: (I - mu1 dt L)(I - mu2 dt L) phiNew = (I + mu3 dt L) phiOld + (I + mu4 dt L) dt src; stats are the last solve's
 void PressureSolver::heat_step(int scheme, double dt, bool zeroPhi, SolveStats& s)
 {
+    check_idle("heat_step");
     SOMAR_CHECK(scheme >= 0 && scheme <= 2, "heat scheme: 0 backward Euler, 1 Crank-Nicolson, 2 TGA");
     SOMAR_CHECK(dt >= 0.0, "negative time step");
     const long long n = lev[0]->field_elems;
@@ -1431,6 +1695,7 @@ void PressureSolver::cc_correct(double* phi, double dt)
 
 void PressureSolver::cc_project(double dt, bool zeroPressure, bool forceHomogeneous, bool wall, SolveStats& s)
 {
+    check_idle("cc_project");
     divergence_cc(f_rhs, dt, wall);
     solve(zeroPressure, forceHomogeneous, s);
     cc_correct(f_phi, dt);
@@ -1445,7 +1710,11 @@ void PressureSolver::fill_hash(int d, double* f, unsigned long long seed)
 // ------------------------------------------------------------------------------------
 // MappedMultiGrid::cycle, MappedMultiGrid.H:555-653 (V/W cycles; F-cycle not offered)
 // ------------------------------------------------------------------------------------
-void PressureSolver::vcycle(double* e, const double* res, bool e_zero) { cycle(0, e, res, e_zero); }
+void PressureSolver::vcycle(double* e, const double* res, bool e_zero)
+{
+    check_idle("vcycle");
+    cycle(0, e, res, e_zero);
+}
 
 // corr_zero: the correction is to be taken as zero whatever the array holds (the reference zeroes it with
 // setToZero right before: MappedMultiGrid.H:589, MappedAMRMultiGrid.H:1203); a smoother that knows this skips the
@@ -2172,6 +2441,7 @@ void PressureSolver::bottom_solve(double* phi, const double* rhs)
 void PressureSolver::solve(bool zeroPhi, bool forceHomogeneous, SolveStats& s)
 {
     SOMAR_CHECK(finalized, "solve before finalize");
+    check_idle("solve");
     Level& L = *lev[0];
     const long long n = L.field_elems;
     launch_set(st_, f_uberRes, n, 0.0);

@@ -69,6 +69,19 @@ public:
     void run_aux_program(int which, double* phi);
     void set_amr_member() { amr_member_ = true; }  // a level of an AMRSolver hierarchy (whose reflux tables carry beta)
     void finalize();  // builds the semicoarsened hierarchy, coarse metrics, lapDiag, null-space probes
+    // ---- metric refresh of a finalized solver (the implicit-gravity projector's per-step AlteredMetric, AMRNavierStokes-
+    // AdvancePPMIG.cpp:331-342): between begin and end the set_metric_* producers write the depth-0 arrays in place; end
+    // recomputes what finalize derived from the metric (ghosts, lapDiag, coarse depths, uniform / zero-plane flags, folded-
+    // prolongation volumes, null-space probes; the agglomerated tail) into the existing buffers and drops the graphs.
+    // amr_member_ok: the caller is the hierarchy (AMRSolver::metric_update_begin).  only_if_written: refresh only when a
+    // producer ran since begin; returns whether it refreshed.
+    void metric_update_begin(bool amr_member_ok = false);
+    bool metric_update_end(bool only_if_written = false);
+    bool metric_updating() const { return updating_; }
+    void refresh_metric();   // the recomputation alone (no begin / end bookkeeping): leptic internal solvers
+    // which 0..2: J g^{aa} on faces(valid, a); 3: J^{-1}; 4: lapDiag (valid); 16 + 3a + b: J g^{ab} of the non-diagonal metric
+    void metric_download(int depth, int which, int patch, double* host);
+    void check_idle(const char* what) const;   // refuses while a metric update is open
 
     // ---- data movement across the boundary (host FABs, caller-owned) ---------------------
     void upload_phi(int patch, const double* host, const int ghost[3]);
@@ -236,6 +249,16 @@ private:
     void fill_metric_ghosts(Level& L);
     void detect_zero_planes();     // sets StencilParams::zero_xy per depth (non-diagonal metric, 3-D)
     void detect_uniform_metric();  // sets StencilParams::uniform / uc per depth (diagonal metric, 3-D)
+    // both detections above for every depth in one k_minmax_all launch and one download (metric refresh); same truth table
+    void detect_metric_flags();
+    bool updating_ = false, metric_written_ = false;
+    void metric_written(const char* producer);   // a producer's check: before finalize, or inside an open update
+    std::vector<CoarsenItem*> d_coarsen_;        // per depth d >= 1: k_coarsen_metric's work items (built at the first refresh)
+    std::vector<int> n_coarsen_, gy_coarsen_;
+    MinMaxItem* d_mm_items_ = nullptr;
+    int n_mm_items_ = 0;
+    std::vector<int> mm_first_;                  // per depth: first item of (jg0, jg1, jg2, jinv) resp. (jgf01, jgf10), 4 / 2 arrays
+    double* d_mm_out_ = nullptr;
     void line_relax(int d, double* e, const double* res);
     double* f_vel[3] = {nullptr, nullptr, nullptr};
     double* f_ccvel[3] = {nullptr, nullptr, nullptr};
@@ -346,6 +369,7 @@ private:
     int agglom_depth_ = -1;
     long long agglom_cells_ = 2097152;  // 128^3: below this a level costs less to replicate (~0.2 ms of sweeps) than to exchange (~8 x 60 us)
     Copier agglom_gather_;                      // sharded depth agglom_depth_ -> replicated depth 0 of coarse_
+    Copier agglom_metric_;                      // the same for the metric (one layer of faces beyond the cells)
     CopyItem* d_agglom_back_ = nullptr;         // my boxes of the replicated correction -> sharded layout
     int n_agglom_back_ = 0;
     void build_agglomerated_tail(int depth);

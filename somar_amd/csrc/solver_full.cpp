@@ -687,7 +687,7 @@ void PressureSolver::mac_grad_full(double* phi)
 void PressureSolver::set_metric_full(int patch, const double* jg0, const double* jg1, const double* jg2,
                                      const double* jinv)
 {
-    SOMAR_CHECK(!lev.empty() && !finalized, "set_metric before define / after finalize");
+    metric_written("full");
     Level& L = *lev[0];
     SOMAR_CHECK(patch >= 0 && patch < L.npatches(), "bad patch index");
     full_ = true;
@@ -711,9 +711,10 @@ void PressureSolver::set_metric_full(int patch, const double* jg0, const double*
 // bathymetric map (O(N^2)) crosses PCIe.
 void PressureSolver::set_metric_map(int kind, const double Lc[3], const double* depth, const int dlo[2], const int dn[2])
 {
-    SOMAR_CHECK(!lev.empty() && !finalized, "set_metric before define / after finalize");
+    SOMAR_CHECK(!lev.empty() && (!finalized || updating_), "set_metric before define / after finalize");
     SOMAR_CHECK(prm.spaceDim == 3, "the map producers restate the CH_SPACEDIM = 3 algebra (GeoSourceInterface.cpp:236-291)");
     SOMAR_CHECK(kind >= 1 && kind <= 4, "map kind: 1 cylindrical, 2 bathymetric, 3 twisted (type 0), 4 twisted (type 1)");
+    metric_written(kind == 1 ? "cylindrical" : "map");
     Level& L = *lev[0];
     SOMAR_CHECK(L.npatches() < 65536, "too many local patches for one launch");
     double* d_depth = nullptr;

@@ -646,6 +646,22 @@ int somar_solver_metric_update_end(somar_solver_t* s);
 int somar_amr_metric_update_begin(somar_amr_t* a);
 int somar_amr_metric_update_end(somar_amr_t* a);
 int somar_solver_metric_download(somar_solver_t* s, int depth, int which, int patch, double* host);
+/* Opt-in mixed precision of the level solve.  NOT the reference's arithmetic: the reference is fp64 throughout.
+ *  mode 0: fp64, the default, bit for bit what the solver computes without this call.
+ *  mode 1: the leading multigrid depths run their V-cycle in fp32 -- depth d does when the fused red+black sweep runs there
+ *    and it has at least min_cells valid cells (min_cells <= 0: the fused sweep's own threshold, 262144); these depths form a
+ *    prefix 0 .. K-1.  Depth K and everything below it run the fp64 code unchanged.  The solve's outer loop (solve, the
+ *    projections, the heat steps) still computes and tests the fp64 residual and adds the fp32 correction to the fp64 phi,
+ *    so it reaches fp64 tolerances; each correction carries a relative error of about 1e-7, far below the cycle's own
+ *    contraction.  somar_vcycle / somar_vcycle_from_zero follow the mode; their fields stay fp64.  With K == 0, mode 1
+ *    computes exactly what mode 0 does.
+ *  Before or after finalize; after it, the fp32 buffers are allocated, the metric is converted and captured graphs are
+ *  dropped (a metric refresh regenerates the fp32 copies).  Refused while a metric update is open, and for mode 1 (here or at
+ *  finalize) on a level of an AMR hierarchy, a non-diagonal (19-point) metric, relax_mode other than LevelGSRB, num_mg != 1,
+ *  more than one rank, and the handles of a leptic solver.
+ * somar_solver_get_precision: the mode and K, the number of leading depths that run in fp32 (0 before finalize). */
+int somar_solver_set_precision(somar_solver_t* s, int mode, long long min_cells);
+int somar_solver_get_precision(const somar_solver_t* s, int* mode, int* fp32_depths);
 /* The nodal "depth" of the reference's analytic bathymetric maps, for SOMAR_MAP_BATHYMETRIC (host arithmetic, no GPU; x, y: the
  * Cartesian coordinates of the nodes, for these maps x = dXi0 * i, y = dXi1 * j):
  *   LedgeMap::fill_bathymetry            geometry/maps/LedgeMap.cpp:38-60, 98-164   order 1 / 3: h_l left of x_l, h_r right of x_r,

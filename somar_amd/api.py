@@ -190,6 +190,8 @@ _SIGS = {
     "somar_amr_metric_update_begin": [_H],
     "somar_amr_metric_update_end": [_H],
     "somar_solver_metric_download": [_H, C.c_int, C.c_int, C.c_int, _PD],
+    "somar_solver_set_precision": [_H, C.c_int, C.c_longlong],
+    "somar_solver_get_precision": [_H, _PI, _PI],
     "somar_comm_unique_id": [C.POINTER(C.c_ubyte)],
     "somar_comm_create": [C.POINTER(_H), C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int],
     "somar_comm_create_shm": [C.POINTER(_H), C.c_char_p, C.c_int, C.c_int, C.c_longlong],
@@ -550,6 +552,18 @@ class AMRPressureSolver:
                 _ck(lib().somar_amr_metric_update_end(amr))
             else:
                 _ck(lib().somar_solver_metric_update_end(self._h))
+
+    def setPrecision(self, mode, min_cells=0):
+        """Opt-in mixed precision (NOT the reference's arithmetic): mode 0 fp64 (the default), 1 an fp32 V-cycle on the
+        leading depths with at least min_cells cells (0: the fused sweep's threshold) inside the fp64 defect-correction loop.
+        Before or after finalize; see somar_solver_set_precision for what refuses it."""
+        _ck(lib().somar_solver_set_precision(self._h, int(mode), int(min_cells)))
+
+    def precision(self):
+        """(mode, number of leading MG depths that run in fp32)"""
+        m, k = C.c_int(), C.c_int()
+        _ck(lib().somar_solver_get_precision(self._h, C.byref(m), C.byref(k)))
+        return m.value, k.value
 
     def metricDownload(self, depth, which, patch):
         """one local patch's metric array at MG depth `depth` (valid region): which 0..2 J g^{aa} on faces(valid, a), 3 J^{-1},

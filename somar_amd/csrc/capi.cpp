@@ -1554,6 +1554,25 @@ int somar_solver_metric_update_end(somar_solver_t* s)
     API_END
 }
 
+int somar_solver_set_precision(somar_solver_t* s, int mode, long long min_cells)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps, "null argument");
+    SOMAR_CHECK(mode != 1 || (!s->lep && (s->owned || s->ps->amr_member())),
+                "set_precision: mixed precision is not available for the handles of a leptic solver");
+    s->ps->set_precision(mode, min_cells);
+    API_END
+}
+
+int somar_solver_get_precision(const somar_solver_t* s, int* mode, int* fp32_depths)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps, "null argument");
+    if (mode) *mode = s->ps->precision_mode();
+    if (fp32_depths) *fp32_depths = s->ps->fp32_depths();
+    API_END
+}
+
 int somar_amr_metric_update_begin(somar_amr_t* a)
 {
     API_BEGIN

@@ -58,6 +58,19 @@ struct Tile {
     int nk;
     int pad_[3];
 };
+// a pair of cells of one field (the marching kernels hold one per lane), for either element type of a field: fp64, or fp32 on the
+// depths of an opt-in mixed-precision cycle (PressureSolver::set_precision)
+template <class T> struct Vec2;
+template <> struct Vec2<double> { typedef double2 type; };
+template <> struct Vec2<float> { typedef float2 type; };
+template <class T>
+__host__ __device__ __forceinline__ typename Vec2<T>::type mk2(T a, T b)
+{
+    typename Vec2<T>::type v;
+    v.x = a;
+    v.y = b;
+    return v;
+}
 constexpr int TILE_I = 128;  // cells in i per block (64 lanes x double2)
 constexpr int TILE_J_MAX = 8;   // rows per block (blockDim.y), chosen per level
 constexpr int TILE_K_MAX = 32;  // planes marched by one block, chosen per level

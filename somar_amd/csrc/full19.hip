@@ -35,15 +35,16 @@ struct JgFull { const double* c[3][3]; };  // c[faceDir][component]
 // cell INSIDE the box's valid region returns phi there -- the value the full copy psi := phi would have put.
 // one op over the threads [t0, t0 + nt, ...) of the caller
 // bcf: the level's face-value buffer (GHOST_DIRI_FACE ops read bcf[op.voff + loop index]; null where no such op exists)
-template <bool REDIRECT>
-__device__ __forceinline__ void ghost_op_body(const GhostOp& op, const PatchDesc& p, double* phi, double* psi,   // may alias
+// T: the fields' element type (float: the homogeneous physical ghosts of a mixed-precision depth, arithmetic in float)
+template <bool REDIRECT, class T = double>
+__device__ __forceinline__ void ghost_op_body(const GhostOp& op, const PatchDesc& p, T* phi, T* psi,   // may alias
                                               const JgFull& J, const StencilParams& P, const double* __restrict__ bcf,
                                               int t0, int nt)
 {
     const int n0 = op.n[0], n01 = op.n[0] * op.n[1];
     const int cells = n01 * op.n[2];   // a ghost region of one box: far below 2^31 (32-bit index arithmetic: no 64-bit divisions)
-    double* dst = op.dstf ? psi : phi;
-    const double* src = op.srcf ? psi : phi;
+    T* dst = op.dstf ? psi : phi;
+    const T* src = op.srcf ? psi : phi;
     const long long st[3] = {1, (long long)p.pj, p.pk};
     for (int idx = t0; idx < cells; idx += nt) {
         const int k = idx / n01;
@@ -52,7 +53,7 @@ __device__ __forceinline__ void ghost_op_body(const GhostOp& op, const PatchDesc
         const int l0 = op.lo[0] + i, l1 = op.lo[1] + j, l2 = op.lo[2] + k;
         const long long c = fidx(p, l0, l1, l2);
         // value of field `f` (1 = psi) at this cell moved by m steps along direction dd (and mt steps along dt)
-        auto rd = [&](const double* f, bool is_psi, int dd, int m, int dt = 0, int mt = 0) {
+        auto rd = [&](const T* f, bool is_psi, int dd, int m, int dt = 0, int mt = 0) {
             int q[3] = {l0, l1, l2};
             q[dd] += m;
             q[dt] += mt;
@@ -67,44 +68,44 @@ __device__ __forceinline__ void ghost_op_body(const GhostOp& op, const PatchDesc
             const int s = -op.sgn;  // values come from 1, 2, 3 steps back along dir
             const bool ps = op.srcf != 0;
             if (op.order == 0) dst[c] = rd(src, ps, op.dir, s);
-            else if (op.order == 1) dst[c] = 2.0 * rd(src, ps, op.dir, s) - rd(src, ps, op.dir, 2 * s);
-            else dst[c] = 3.0 * (rd(src, ps, op.dir, s) - rd(src, ps, op.dir, 2 * s)) + rd(src, ps, op.dir, 3 * s);
+            else if (op.order == 1) dst[c] = T(2.0) * rd(src, ps, op.dir, s) - rd(src, ps, op.dir, 2 * s);
+            else dst[c] = T(3.0) * (rd(src, ps, op.dir, s) - rd(src, ps, op.dir, 2 * s)) + rd(src, ps, op.dir, 3 * s);
         } else if (op.type == GHOST_DIRI) {
             // ELLIPTICCONSTDIRIBCGHOST, order 1 (EllipticBCUtilsF.ChF:71-84): the value sits on the face
             const long long s = op.sgn * st[op.dir];
-            const double bcval = P.bc_homog ? 0.0 : op.val;
-            if (bcval == 0.0) dst[c] = -src[c - s];
-            else dst[c] = 2.0 * bcval - src[c - s];
+            const T bcval = P.bc_homog ? T(0) : T(op.val);
+            if (bcval == T(0)) dst[c] = -src[c - s];
+            else dst[c] = T(2.0) * bcval - src[c - s];
         } else if (op.type == GHOST_DIRI_FACE) {
             // EllipticDiriBCGhostClass, cell-centred branch, order 1 (EllipticBCUtils.cpp:588-636): ghost = (-first valid) +
             // 2 g(face); no shortcut for g == 0 (the reference has none).  Homogeneous: -first valid, as the constant form.
             const long long s = op.sgn * st[op.dir];
             if (P.bc_homog) dst[c] = -src[c - s];
-            else dst[c] = (-src[c - s]) + 2.0 * bcf[op.voff + idx];
+            else dst[c] = (-src[c - s]) + T(2.0) * T(bcf[op.voff + idx]);
         } else {  // GHOST_NEUM: phi ghost such that the boundary flux (cross terms from psi included) equals bcval = 0
             const int a = op.dir, b = (a + 1) % 3, cc = (a + 2) % 3;
             const long long sa = st[a], sb = st[b], sc = st[cc];
             const long long g = c;                                  // ghost cell
             const long long v = c - op.sgn * sa;                    // first valid cell
             const long long f = (op.sgn < 0) ? c + sa : c;          // boundary face (index of the cell it is the low face of)
-            const double idxb = -0.25 / P.dx[b], idxc = -0.25 / P.dx[cc];
+            const T idxb = T(-0.25) / T(P.dx[b]), idxc = T(-0.25) / T(P.dx[cc]);
             (void)sb; (void)sc;
             // g = this cell, v = this cell moved one step back along a
             const int bk = -op.sgn;
-            const double cross = (rd(psi, true, b, 1) - rd(psi, true, b, -1) + rd(psi, true, a, bk, b, 1) - rd(psi, true, a, bk, b, -1)) * J.c[a][b][f] * idxb +
-                                 (rd(psi, true, cc, 1) - rd(psi, true, cc, -1) + rd(psi, true, a, bk, cc, 1) - rd(psi, true, a, bk, cc, -1)) * J.c[a][cc][f] * idxc;
-            phi[g] = phi[v] + (0.0 - cross) * P.dx[a] / J.c[a][a][f];
+            const T cross = (rd(psi, true, b, 1) - rd(psi, true, b, -1) + rd(psi, true, a, bk, b, 1) - rd(psi, true, a, bk, b, -1)) * T(J.c[a][b][f]) * idxb +
+                            (rd(psi, true, cc, 1) - rd(psi, true, cc, -1) + rd(psi, true, a, bk, cc, 1) - rd(psi, true, a, bk, cc, -1)) * T(J.c[a][cc][f]) * idxc;
+            phi[g] = phi[v] + (T(0.0) - cross) * T(P.dx[a]) / T(J.c[a][a][f]);
         }
     }
 }
 
-template <bool REDIRECT>
+template <bool REDIRECT, class T = double>
 __global__ void k_ghost_ops(const GhostOp* __restrict__ ops, const PatchDesc* __restrict__ patches,
-                            double* phi, double* psi, JgFull J, StencilParams P, const double* __restrict__ bcf)
+                            T* phi, T* psi, JgFull J, StencilParams P, const double* __restrict__ bcf)
 {
     const GhostOp op = ops[blockIdx.x];
     const PatchDesc p = patches[op.patch];
-    ghost_op_body<REDIRECT>(op, p, phi, psi, J, P, bcf, (int)(blockIdx.y * blockDim.x + threadIdx.x), (int)(gridDim.y * blockDim.x));
+    ghost_op_body<REDIRECT, T>(op, p, phi, psi, J, P, bcf, (int)(blockIdx.y * blockDim.x + threadIdx.x), (int)(gridDim.y * blockDim.x));
 }
 
 // A whole ghost program in ONE launch, one workgroup per box.  Every op of a program reads and writes the storage of its own
@@ -386,6 +387,15 @@ void launch_ghost_ops(hipStream_t st, const LevelDev& L, const GhostOp* ops, int
     P.bc_homog = bc_homog ? 1 : 0;
     if (redirect) hipLaunchKernelGGL(k_ghost_ops<true>, dim3(nops, L.ghost_gy), dim3(256), 0, st, ops, L.patches, phi, psi, jgfull(L), P, L.bc_face);
     else hipLaunchKernelGGL(k_ghost_ops<false>, dim3(nops, L.ghost_gy), dim3(256), 0, st, ops, L.patches, phi, psi, jgfull(L), P, L.bc_face);
+}
+
+void launch_ghost_ops(hipStream_t st, const LevelDev& L, const GhostOp* ops, int nops, float* phi)
+{
+    if (nops == 0) return;
+    StencilParams P = L.P;
+    P.bc_homog = 1;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ghost_ops<false, float>), dim3(nops, L.ghost_gy), dim3(256), 0, st, ops, L.patches, phi, phi,
+                       jgfull(L), P, L.bc_face);
 }
 
 void launch_ghost_program(hipStream_t st, const LevelDev& L, const GhostOp* box_ops, const int* box_first, double* phi,

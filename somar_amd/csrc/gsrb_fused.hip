@@ -34,31 +34,36 @@
 namespace somar {
 
 
-__device__ __forceinline__ double pick(const double2& v, int s) { return s ? v.y : v.x; }
+// T: the element type of the fields and coefficient arrays -- double, or float on the depths of the opt-in mixed-precision
+// cycle (PressureSolver::set_precision), whose arithmetic then stays in float throughout
+template <class T>
+__device__ __forceinline__ T pick(const typename Vec2<T>::type& v, int s) { return s ? v.y : v.x; }
 
-// load a[idx], a[idx+1] with per-element predicates (idx is 16-byte aligned by construction)
-__device__ __forceinline__ double2 ld2(const double* __restrict__ a, long long idx, bool ok0, bool ok1,
-                                          long long safe)
+// load a[idx], a[idx+1] with per-element predicates (idx is pair-aligned by construction)
+template <class T>
+__device__ __forceinline__ typename Vec2<T>::type ld2(const T* __restrict__ a, long long idx, bool ok0, bool ok1,
+                                                      long long safe)
 {
     // branch-free: always one aligned 16-byte load (from `safe`, any valid aligned element of the patch, when
     // neither element may be touched), then selects.  Straight-line loads let the compiler count outstanding
     // loads exactly (s_waitcnt vmcnt(N)) instead of draining everything at every predicated branch.
 #ifdef SOMAR_NT_LOADS
     // streamed once per launch: keep the coefficient / right-hand-side lines out of the way of the phi halo reuse in L2
-    typedef double v2d_ __attribute__((ext_vector_type(2)));
+    typedef T v2d_ __attribute__((ext_vector_type(2)));
     const v2d_ w = __builtin_nontemporal_load(reinterpret_cast<const v2d_*>(a + ((ok0 || ok1) ? idx : safe)));
-    const double2 v = make_double2(w.x, w.y);
+    const typename Vec2<T>::type v = mk2<T>(w.x, w.y);
 #else
-    const double2 v = *reinterpret_cast<const double2*>(a + ((ok0 || ok1) ? idx : safe));
+    const typename Vec2<T>::type v = *reinterpret_cast<const typename Vec2<T>::type*>(a + ((ok0 || ok1) ? idx : safe));
 #endif
-    return make_double2(ok0 ? v.x : 0.0, ok1 ? v.y : 0.0);
+    return mk2<T>(ok0 ? v.x : T(0), ok1 ? v.y : T(0));
 }
 
 // the "load" of a uniform coefficient.  ld2 returns zeros where its predicate is off; those values only ever reach cells that
 // are not computed (a computed cell's coefficients lie inside the frame by construction), so the constant may stand in
 // unconditionally -- which makes every coefficient a wave-uniform loop invariant: the diagonal and the selects between the
 // pair's two members fold away.
-__device__ __forceinline__ double2 uni2(double c, bool, bool) { return make_double2(c, c); }
+template <class T>
+__device__ __forceinline__ typename Vec2<T>::type uni2(double c, bool, bool) { return mk2<T>(T(c), T(c)); }
 
 // One GSRB point update of cell (gi,gj,gk): interior form = GSRBITER3DORTHO, cells touching a domain
 // face = GSRBBOUNDARYITER3DORTHO (a Neumann face contributes neither flux nor diagonal; a Dirichlet face contributes
@@ -66,11 +71,11 @@ __device__ __forceinline__ double2 uni2(double c, bool, bool) { return make_doub
 // INT: the caller's tile (its red ring included) touches no domain face and no seam in x and y, so only the plane's position
 // in z -- the same for every lane -- decides between the two forms: the per-lane classification (periodic wrap, six
 // compares, a divergent branch) collapses into one scalar test per plane.
-template <bool DIRI, bool INT = false>
-__device__ __forceinline__ double gsrb_point(const StencilParams& P, double xxS, double yyS, double zzS, int gi,
-                                             int gj, int gk, double pxl, double pxh, double pyl, double pyh,
-                                             double pzl, double pzh, double gxl, double gxh, double gyl, double gyh,
-                                             double gzl, double gzh, double Ji, double rhs, double own)
+template <bool DIRI, bool INT, class T>
+__device__ __forceinline__ T gsrb_point(const StencilParams& P, T xxS, T yyS, T zzS, int gi,
+                                        int gj, int gk, T pxl, T pxh, T pyl, T pyh,
+                                        T pzl, T pzh, T gxl, T gxh, T gyl, T gyh,
+                                        T gzl, T gzh, T Ji, T rhs, T own)
 {
     // a ring cell may be the periodic image of a cell on the far side: classify the REAL cell
     if (!INT && P.periodic[0]) { const int n = P.dom_hi[0] - P.dom_lo[0] + 1; gi = gi < P.dom_lo[0] ? gi + n : (gi > P.dom_hi[0] ? gi - n : gi); }
@@ -79,13 +84,13 @@ __device__ __forceinline__ double gsrb_point(const StencilParams& P, double xxS,
     const bool onb = (!INT && ((gi == P.dom_lo[0]) || (gi == P.dom_hi[0]) || (gj == P.dom_lo[1]) || (gj == P.dom_hi[1]))) ||
                      (gk == P.dom_lo[2]) || (gk == P.dom_hi[2]);
     if (!onb) {
-        const double JDxx = xxS * (gxh * pxh + gxl * pxl);
-        const double JDyy = yyS * (gyh * pyh + gyl * pyl);
-        const double JDzz = zzS * (gzh * pzh + gzl * pzl);
-        const double lphi = P.beta * Ji * (JDxx + JDyy + JDzz);
+        const T JDxx = xxS * (gxh * pxh + gxl * pxl);
+        const T JDyy = yyS * (gyh * pyh + gyl * pyl);
+        const T JDzz = zzS * (gzh * pzh + gzl * pzl);
+        const T lphi = T(P.beta) * Ji * (JDxx + JDyy + JDzz);
         // lapDiag: FILLMAPPEDLAPDIAG3D's expression, bitwise the stored array's value
-        const double lapd = -Ji * ((gxh + gxl) * xxS + (gyh + gyl) * yyS + (gzh + gzl) * zzS);
-        return (rhs - lphi) / (P.alpha + P.beta * lapd);
+        const T lapd = -Ji * ((gxh + gxl) * xxS + (gyh + gyl) * yyS + (gzh + gzl) * zzS);
+        return (rhs - lphi) / (T(P.alpha) + T(P.beta) * lapd);
     }
     const bool nxl = !INT && (gi == P.dom_lo[0]) && P.neum[0][0];
     const bool nxh = !INT && (gi == P.dom_hi[0]) && P.neum[0][1];
@@ -105,7 +110,7 @@ __device__ __forceinline__ double gsrb_point(const StencilParams& P, double xxS,
         if ((gk == P.dom_lo[2]) && P.diri[2][0]) pzl = -own;
         if ((gk == P.dom_hi[2]) && P.diri[2][1]) pzh = -own;
     }
-    double JDloX = 0, JDhiX = 0, JDloY = 0, JDhiY = 0, JDloZ = 0, JDhiZ = 0, ld = 0.0;
+    T JDloX = 0, JDhiX = 0, JDloY = 0, JDhiY = 0, JDloZ = 0, JDhiZ = 0, ld = 0;
     if (!nxl) { JDloX = gxl * pxl; ld = ld - xxS * gxl; }
     if (!nyl) { JDloY = gyl * pyl; ld = ld - yyS * gyl; }
     if (!nzl) { JDloZ = gzl * pzl; ld = ld - zzS * gzl; }
@@ -113,8 +118,8 @@ __device__ __forceinline__ double gsrb_point(const StencilParams& P, double xxS,
     if (!nyh) { JDhiY = gyh * pyh; ld = ld - yyS * gyh; }
     if (!nzh) { JDhiZ = gzh * pzh; ld = ld - zzS * gzh; }
     ld = ld * Ji;
-    const double lphi = P.beta * Ji * ((JDloX + JDhiX) * xxS + (JDloY + JDhiY) * yyS + (JDloZ + JDhiZ) * zzS);
-    return (rhs - lphi) / (P.alpha + P.beta * ld);
+    const T lphi = T(P.beta) * Ji * ((JDloX + JDhiX) * xxS + (JDloY + JDhiY) * yyS + (JDloZ + JDhiZ) * zzS);
+    return (rhs - lphi) / (T(P.alpha) + T(P.beta) * ld);
 }
 
 // blockDim = (64, FR_J): lane = i-pair of the region, threadIdx.y = region row (one wavefront each).
@@ -132,20 +137,22 @@ __device__ __forceinline__ double gsrb_point(const StencilParams& P, double xxS,
 // the same values: same bits.
 // CLS: the tile's lane class (see full19_march.hip): a wavefront covers 2^CLS region rows of 128 >> CLS columns, all of the
 // same parity, so the colour column c stays wave-uniform.
-template <int FR_J, int INMODE, bool DIRI, bool UNI, bool INT, int CLS>
-__device__ __forceinline__ void gsrb_fused_body(double* __restrict__ S, const Tile& t, const PatchDesc& p,
-                                                double* __restrict__ phi_out,
-                                                const double* __restrict__ phi_in,
-                                                const double* __restrict__ rhs,
-                                                const double* __restrict__ jgx,
-                                                const double* __restrict__ jgy,
-                                                const double* __restrict__ jgz,
-                                                const double* __restrict__ jinv, const StencilParams& P,
+// sums (modes 2, 4) are fp64 whatever T is: the mean is formed in double, then taken to T
+template <int FR_J, int INMODE, bool DIRI, bool UNI, bool INT, int CLS, class T>
+__device__ __forceinline__ void gsrb_fused_body(T* __restrict__ S, const Tile& t, const PatchDesc& p,
+                                                T* __restrict__ phi_out,
+                                                const T* __restrict__ phi_in,
+                                                const T* __restrict__ rhs,
+                                                const T* __restrict__ jgx,
+                                                const T* __restrict__ jgy,
+                                                const T* __restrict__ jgz,
+                                                const T* __restrict__ jinv, const StencilParams& P,
                                                 const double* __restrict__ sums,
                                                 const PatchDesc* __restrict__ cpatches,
-                                                const double* __restrict__ crse, int r0, int r1, int r2)
+                                                const T* __restrict__ crse, int r0, int r1, int r2)
 {
-    const double avg = (INMODE == 2 || INMODE == 4) ? sums[0] / sums[1] : 0.0;
+    typedef typename Vec2<T>::type T2;
+    const T avg = (INMODE == 2 || INMODE == 4) ? T(sums[0] / sums[1]) : T(0);
     constexpr int LPR = 64 >> CLS;                 // lanes per region row
     constexpr int NR = FR_J << CLS;                // region rows of the workgroup
     constexpr int PITCH = 2 * LPR + (CLS >= 2 ? 2 : 0);
@@ -173,26 +180,26 @@ __device__ __forceinline__ void gsrb_fused_body(double* __restrict__ S, const Ti
         csh2 = r2 >> 1;                  // multigrid ratios are 1 or 2 per direction (checked by the launcher)
     }
     auto ldphi = [&](int kp, bool ok0, bool ok1) {
-        if (INMODE == 1) return make_double2(0.0, 0.0);
-        double2 v = ld2(phi_in, p.off + li + (long long)p.pj * lj + p.pk * kp, ok0, ok1, p.off);
+        if (INMODE == 1) return mk2<T>(T(0), T(0));
+        T2 v = ld2(phi_in, p.off + li + (long long)p.pj * lj + p.pk * kp, ok0, ok1, p.off);
         if (INMODE >= 3) {
             // floor(kp / r2) as an arithmetic shift; both coarse loads are unconditional loads from a safe address (no branch,
             // no load that waits for another: a branch here made the compiler drain vmcnt(0) in every plane)
             const bool any = ok0 || ok1;
             const long long c = any ? cbase + cpk * (long long)(kp >> csh2) : coff;
             const long long c2 = any ? c + cstep : coff;
-            const double c0 = crse[c];
-            const double c1 = crse[c2];
-            v.x = ok0 ? v.x + c0 : 0.0;
-            v.y = ok1 ? v.y + c1 : 0.0;
+            const T c0 = crse[c];
+            const T c1 = crse[c2];
+            v.x = ok0 ? v.x + c0 : T(0);
+            v.y = ok1 ? v.y + c1 : T(0);
         }
         if (INMODE == 2 || INMODE == 4) { v.x = v.x - avg; v.y = v.y - avg; }
         return v;
     };
     const int gj = p.lo[1] + lj;
-    const double xxS = 1.0 / (P.dx[0] * P.dx[0]);
-    const double yyS = 1.0 / (P.dx[1] * P.dx[1]);
-    const double zzS = 1.0 / (P.dx[2] * P.dx[2]);
+    const T xxS = T(1.0) / (T(P.dx[0]) * T(P.dx[0]));
+    const T yyS = T(1.0) / (T(P.dx[1]) * T(P.dx[1]));
+    const T zzS = T(1.0) / (T(P.dx[2]) * T(P.dx[2]));
 
     // memory predicates: a cell may be touched only inside the patch's 2-cell frame
     const bool fj = (lj >= -FRAME) && (lj < p.n[1] + FRAME);
@@ -233,18 +240,18 @@ __device__ __forceinline__ void gsrb_fused_body(double* __restrict__ S, const Ti
     // ---- prologue: planes k0-2 and k0-1 ------------------------------------------------------------
     int k = t.k0 - 1;  // first red plane (the ring below the tile)
     bool fk = (k - 1 >= -FRAME) && (k - 1 < p.n[2] + FRAME);
-    double2 Pm = ldphi(k - 1, f0 && fk, f1 && fk);
+    T2 Pm = ldphi(k - 1, f0 && fk, f1 && fk);
     fk = (k >= -FRAME) && (k < p.n[2] + FRAME);
-    double2 Pc = ldphi(k, f0 && fk, f1 && fk);
+    T2 Pc = ldphi(k, f0 && fk, f1 && fk);
     // Jg^zz on the LOW face of plane k
-    double2 Gzc = UNI ? uni2(P.uc[2], c0 && fk, c1 && fk) : ld2(jgz, base + sk * k, c0 && fk, c1 && fk, p.off);
+    T2 Gzc = UNI ? uni2<T>(P.uc[2], c0 && fk, c1 && fk) : ld2(jgz, base + sk * k, c0 && fk, c1 && fk, p.off);
     // coefficients of the black cell of plane k-1 (column c), captured one step earlier
-    double b_rhs = 0, b_ji = 1, b_gxl = 0, b_gxh = 0, b_gyl = 0, b_gyh = 0, b_gzl = 0;
-    double redPrev1 = 0.0, redPrev2 = 0.0;
+    T b_rhs = 0, b_ji = 1, b_gxl = 0, b_gxh = 0, b_gyl = 0, b_gyh = 0, b_gzl = 0;
+    T redPrev1 = 0, redPrev2 = 0;
     // UNI: with the coefficient streams gone a plane's loads are 2 x 16 bytes per lane, too little in flight to cover the memory
     // latency a lock-stepped (one barrier per plane) workgroup exposes: phi and rhs are fetched ONE PLANE FURTHER AHEAD
     // (phi of plane k+2 and rhs of plane k+1 are issued in step k and consumed in step k+1)
-    double2 Pn = make_double2(0.0, 0.0), Rn = make_double2(0.0, 0.0);
+    T2 Pn = mk2<T>(T(0), T(0)), Rn = mk2<T>(T(0), T(0));
     if (UNI) {
         const bool fkp0 = (k + 1 >= -FRAME) && (k + 1 < p.n[2] + FRAME);
         Pn = ldphi(k + 1, f0 && fkp0, f1 && fkp0);
@@ -262,7 +269,7 @@ __device__ __forceinline__ void gsrb_fused_body(double* __restrict__ S, const Ti
         fk = (k >= -FRAME) && (k < p.n[2] + FRAME);
         const bool fkp = (k + 1 >= -FRAME) && (k + 1 < p.n[2] + FRAME);
         // ---- this step's loads: phi and Jg^zz of plane k+1, cell coefficients of plane k --------
-        double2 Pp, Rh;
+        T2 Pp, Rh;
         if (UNI) {
             Pp = Pn;
             Rh = Rn;
@@ -273,26 +280,26 @@ __device__ __forceinline__ void gsrb_fused_body(double* __restrict__ S, const Ti
             Pp = ldphi(k + 1, f0 && fkp, f1 && fkp);
             Rh = ld2(rhs, base + sk * k, c0 && fk, c1 && fk, p.off);
         }
-        const double2 Gzp = UNI ? uni2(P.uc[2], c0 && fkp, c1 && fkp) : ld2(jgz, base + sk * (k + 1), c0 && fkp, c1 && fkp, p.off);
-        const double2 Ji = UNI ? uni2(P.uc[3], c0 && fk, c1 && fk) : ld2(jinv, base + sk * k, c0 && fk, c1 && fk, p.off);
-        const double2 Gx = UNI ? uni2(P.uc[0], c0 && fk, c1 && fk) : ld2(jgx, base + sk * k, c0 && fk, c1 && fk, p.off);
-        const double2 Gy = UNI ? uni2(P.uc[1], c0 && fk, c1 && fk) : ld2(jgy, base + sk * k, c0 && fk, c1 && fk, p.off);
-        const double2 Gyh = UNI ? uni2(P.uc[1], c0 && fk && fjh, c1 && fk && fjh)
-                                : ld2(jgy, base + sk * k + sj, c0 && fk && fjh, c1 && fk && fjh, p.off);
+        const T2 Gzp = UNI ? uni2<T>(P.uc[2], c0 && fkp, c1 && fkp) : ld2(jgz, base + sk * (k + 1), c0 && fkp, c1 && fkp, p.off);
+        const T2 Ji = UNI ? uni2<T>(P.uc[3], c0 && fk, c1 && fk) : ld2(jinv, base + sk * k, c0 && fk, c1 && fk, p.off);
+        const T2 Gx = UNI ? uni2<T>(P.uc[0], c0 && fk, c1 && fk) : ld2(jgx, base + sk * k, c0 && fk, c1 && fk, p.off);
+        const T2 Gy = UNI ? uni2<T>(P.uc[1], c0 && fk, c1 && fk) : ld2(jgy, base + sk * k, c0 && fk, c1 && fk, p.off);
+        const T2 Gyh = UNI ? uni2<T>(P.uc[1], c0 && fk && fjh, c1 && fk && fjh)
+                           : ld2(jgy, base + sk * k + sj, c0 && fk && fjh, c1 && fk && fjh, p.off);
         // Jg^xx on the face right of the pair = first component of the next lane's pair
-        const double gx_next = __shfl_down(Gx.x, 1, 64);
+        const T gx_next = __shfl_down(Gx.x, 1, 64);
 
         // ---- stage plane k (old values) in LDS; ONE barrier per plane -----------------------------
         //   slot k%3 was last read two steps ago (black of plane k-3); every wave has passed the
         //   previous barrier since, so overwriting it is safe.
         const int slot = ((k % 3) + 3) % 3;
-        *reinterpret_cast<double2*>(&Sx(slot, row, ri)) = Pc;
+        *reinterpret_cast<T2*>(&Sx(slot, row, ri)) = Pc;
         __syncthreads();
 
         // ---- red(k) at column c: reads only black cells of the plane, writes only red ones ---------
         // red = pass 0 = even i+j+k (GSRBF.ChF:381-387): c is this plane's red column of the pair
         const int rc = ri + c;
-        double red = pick(Pc, c);  // cells not computed here keep their old value
+        T red = pick<T>(Pc, c);  // cells not computed here keep their old value
         {
             bool comp = comp_ij[c] && (k >= -1) && (k <= p.n[2]);
             if ((gk < P.dom_lo[2] && (P.neum[2][0] || (DIRI && P.diri[2][0]))) ||
@@ -300,11 +307,11 @@ __device__ __forceinline__ void gsrb_fused_body(double* __restrict__ S, const Ti
                 comp = false;
             if ((k < 0 && (p.cf & 16)) || (k >= p.n[2] && (p.cf & 32))) comp = false;
             if (comp) {
-                const double pxl = Sx(slot, row, rc - 1), pxh = Sx(slot, row, rc + 1);
-                const double pyl = Sx(slot, row - 1, rc), pyh = Sx(slot, row + 1, rc);
-                red = gsrb_point<DIRI, INT>(P, xxS, yyS, zzS, p.lo[0] + li + c, gj, gk, pxl, pxh, pyl, pyh, pick(Pm, c),
-                                 pick(Pp, c), c ? Gx.y : Gx.x, c ? gx_next : Gx.y, pick(Gy, c), pick(Gyh, c),
-                                 pick(Gzc, c), pick(Gzp, c), pick(Ji, c), pick(Rh, c), red);
+                const T pxl = Sx(slot, row, rc - 1), pxh = Sx(slot, row, rc + 1);
+                const T pyl = Sx(slot, row - 1, rc), pyh = Sx(slot, row + 1, rc);
+                red = gsrb_point<DIRI, INT, T>(P, xxS, yyS, zzS, p.lo[0] + li + c, gj, gk, pxl, pxh, pyl, pyh, pick<T>(Pm, c),
+                                 pick<T>(Pp, c), c ? Gx.y : Gx.x, c ? gx_next : Gx.y, pick<T>(Gy, c), pick<T>(Gyh, c),
+                                 pick<T>(Gzc, c), pick<T>(Gzp, c), pick<T>(Ji, c), pick<T>(Rh, c), red);
                 Sx(slot, row, rc) = red;  // visible to the black phase of the NEXT step (after its barrier)
             }
         }
@@ -315,35 +322,35 @@ __device__ __forceinline__ void gsrb_fused_body(double* __restrict__ S, const Ti
             const int kb = k - 1;
             if ((kb >= t.k0) && (kb < t.k0 + t.nk) && (out_ij[0] || out_ij[1])) {
                 const int sb = ((kb % 3) + 3) % 3;
-                double black = 0.0;
+                T black = 0;
                 if (out_ij[c]) {
-                    double pxl = Sx(sb, row, rc - 1), pxh = Sx(sb, row, rc + 1);
-                    double pyl = Sx(sb, row - 1, rc), pyh = Sx(sb, row + 1, rc);
-                    double pzl = redPrev2, pzh = red;
+                    T pxl = Sx(sb, row, rc - 1), pxh = Sx(sb, row, rc + 1);
+                    T pyl = Sx(sb, row - 1, rc), pyh = Sx(sb, row + 1, rc);
+                    T pzl = redPrev2, pzh = red;
                     if (INT ? (p.cf & 48) != 0 : p.cf != 0) {
                         // homogeneousCFInterp between the colours (LevelGSRB refills the CF ghosts before the
                         // black pass): ghost = c1 * first valid cell (this black cell, old value) + c2 * second
                         // valid cell (its opposite neighbour, a NEW red value)
-                        const double own = Sx(sb, row, rc);
+                        const T own = Sx(sb, row, rc);
                         const int l = li + c;
-                        const double xl = pxl, xh = pxh, yl = pyl, yh = pyh, zl = pzl, zh = pzh;
+                        const T xl = pxl, xh = pxh, yl = pyl, yh = pyh, zl = pzl, zh = pzh;
                         if (!INT) {
-                            if ((p.cf & 1) && l == 0) pxl = P.cf_c1[0] * own + P.cf_c2[0] * xh;
-                            if ((p.cf & 2) && l == p.n[0] - 1) pxh = P.cf_c1[0] * own + P.cf_c2[0] * xl;
-                            if ((p.cf & 4) && lj == 0) pyl = P.cf_c1[1] * own + P.cf_c2[1] * yh;
-                            if ((p.cf & 8) && lj == p.n[1] - 1) pyh = P.cf_c1[1] * own + P.cf_c2[1] * yl;
+                            if ((p.cf & 1) && l == 0) pxl = T(P.cf_c1[0]) * own + T(P.cf_c2[0]) * xh;
+                            if ((p.cf & 2) && l == p.n[0] - 1) pxh = T(P.cf_c1[0]) * own + T(P.cf_c2[0]) * xl;
+                            if ((p.cf & 4) && lj == 0) pyl = T(P.cf_c1[1]) * own + T(P.cf_c2[1]) * yh;
+                            if ((p.cf & 8) && lj == p.n[1] - 1) pyh = T(P.cf_c1[1]) * own + T(P.cf_c2[1]) * yl;
                         }
-                        if ((p.cf & 16) && kb == 0) pzl = P.cf_c1[2] * own + P.cf_c2[2] * zh;
-                        if ((p.cf & 32) && kb == p.n[2] - 1) pzh = P.cf_c1[2] * own + P.cf_c2[2] * zl;
+                        if ((p.cf & 16) && kb == 0) pzl = T(P.cf_c1[2]) * own + T(P.cf_c2[2]) * zh;
+                        if ((p.cf & 32) && kb == p.n[2] - 1) pzh = T(P.cf_c1[2]) * own + T(P.cf_c2[2]) * zl;
                     }
-                    black = gsrb_point<DIRI, INT>(P, xxS, yyS, zzS, p.lo[0] + li + c, gj, p.lo[2] + kb, pxl, pxh, pyl, pyh,
-                                       pzl, pzh, b_gxl, b_gxh, b_gyl, b_gyh, b_gzl, pick(Gzc, c), b_ji, b_rhs,
+                    black = gsrb_point<DIRI, INT, T>(P, xxS, yyS, zzS, p.lo[0] + li + c, gj, p.lo[2] + kb, pxl, pxh, pyl, pyh,
+                                       pzl, pzh, b_gxl, b_gxh, b_gyl, b_gyh, b_gzl, pick<T>(Gzc, c), b_ji, b_rhs,
                                        Sx(sb, row, rc));
                 }
                 // plane k-1: column c is the new black, column c^1 is red(k-1) (= redPrev1)
-                double* dst = phi_out + base + sk * kb;
-                const double ox = c ? redPrev1 : black, oy = c ? black : redPrev1;
-                if (out_ij[0] && out_ij[1]) *reinterpret_cast<double2*>(dst) = make_double2(ox, oy);
+                T* dst = phi_out + base + sk * kb;
+                const T ox = c ? redPrev1 : black, oy = c ? black : redPrev1;
+                if (out_ij[0] && out_ij[1]) *reinterpret_cast<T2*>(dst) = mk2<T>(ox, oy);
                 else if (out_ij[0]) dst[0] = ox;
                 else dst[1] = oy;
             }
@@ -352,13 +359,13 @@ __device__ __forceinline__ void gsrb_fused_body(double* __restrict__ S, const Ti
         // ---- rotate: the next black cell is column c^1 of plane k ------------------------------------
         {
             const int cb = c ^ 1;
-            b_rhs = pick(Rh, cb);
-            b_ji = pick(Ji, cb);
+            b_rhs = pick<T>(Rh, cb);
+            b_ji = pick<T>(Ji, cb);
             b_gxl = cb ? Gx.y : Gx.x;
             b_gxh = cb ? gx_next : Gx.y;
-            b_gyl = pick(Gy, cb);
-            b_gyh = pick(Gyh, cb);
-            b_gzl = pick(Gzc, cb);
+            b_gyl = pick<T>(Gy, cb);
+            b_gyh = pick<T>(Gyh, cb);
+            b_gzl = pick<T>(Gzc, cb);
         }
         redPrev2 = redPrev1;
         redPrev1 = red;
@@ -391,22 +398,22 @@ __device__ __forceinline__ void gsrb_fused_body(double* __restrict__ S, const Ti
 
 // NARROW: the tile table holds narrow lane classes (uniform-metric depths, or SOMAR_NARROW_7PT=1); the instantiation without
 // them is the one-body kernel with 48 KB of LDS that the HBM-bound streaming sweep was tuned as.
-template <int FR_J, int INMODE, bool DIRI = false, bool UNI = false, bool NARROW = false>
+template <int FR_J, int INMODE, bool DIRI = false, bool UNI = false, bool NARROW = false, class T = double>
 __global__ __launch_bounds__(64 * FR_J) void k_gsrb_fused(const Tile* __restrict__ tiles,
                                                      const PatchDesc* __restrict__ patches,
-                                                     double* __restrict__ phi_out,
-                                                     const double* __restrict__ phi_in,
-                                                     const double* __restrict__ rhs,
-                                                     const double* __restrict__ jgx,
-                                                     const double* __restrict__ jgy,
-                                                     const double* __restrict__ jgz,
-                                                     const double* __restrict__ jinv, StencilParams P,
+                                                     T* __restrict__ phi_out,
+                                                     const T* __restrict__ phi_in,
+                                                     const T* __restrict__ rhs,
+                                                     const T* __restrict__ jgx,
+                                                     const T* __restrict__ jgy,
+                                                     const T* __restrict__ jgz,
+                                                     const T* __restrict__ jinv, StencilParams P,
                                                      const double* __restrict__ sums,
                                                      const PatchDesc* __restrict__ cpatches,
-                                                     const double* __restrict__ crse, int r0, int r1, int r2, int lean_ok)
+                                                     const T* __restrict__ crse, int r0, int r1, int r2, int lean_ok)
 {
     // one slot = the largest class's region: FR_J rows of 128, or 16 FR_J rows of 8 + 2
-    __shared__ __attribute__((aligned(16))) double S[3 * FR_J * (NARROW ? 160 : 128)];
+    __shared__ __attribute__((aligned(16))) T S[3 * FR_J * (NARROW ? 160 : 128)];
     const Tile t = tiles[blockIdx.x];
     const PatchDesc p = patches[t.patch];
     const int cls = NARROW ? t.pad_[1] : 0;
@@ -421,7 +428,7 @@ __global__ __launch_bounds__(64 * FR_J) void k_gsrb_fused(const Tile* __restrict
                !((p.cf & 4) && jlo < 0) && !((p.cf & 8) && jhi >= p.n[1]);
     }
 #define SOMAR_FUSED_BODY(INT_, CLS_)                                                                                          \
-    gsrb_fused_body<FR_J, INMODE, DIRI, UNI, INT_, CLS_>(S, t, p, phi_out, phi_in, rhs, jgx, jgy, jgz, jinv, P, sums, cpatches, \
+    gsrb_fused_body<FR_J, INMODE, DIRI, UNI, INT_, CLS_, T>(S, t, p, phi_out, phi_in, rhs, jgx, jgy, jgz, jinv, P, sums, cpatches, \
                                                         crse, r0, r1, r2)
     if (!NARROW || cls == 0) {
         if (lean) SOMAR_FUSED_BODY(UNI && !DIRI, 0);
@@ -435,9 +442,11 @@ __global__ __launch_bounds__(64 * FR_J) void k_gsrb_fused(const Tile* __restrict
 #undef SOMAR_FUSED_BODY
 }
 
-void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* phi_out,
-                       const double* phi_in, const double* rhs, int in_mode, const double* sums,
-                       const LevelDev* C, const double* crse, const int* r)
+// M: the level's coefficient arrays in T (L.jg / L.jinv, or their fp32 copies)
+template <class T>
+static void launch_gsrb_fused_t(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, const MetricPtrs<T>& M,
+                                T* phi_out, const T* phi_in, const T* rhs, int in_mode, const double* sums,
+                                const LevelDev* C, const T* crse, const int* r)
 {
     if (ntiles == 0) return;
     const PatchDesc* cpatches = C ? C->patches : nullptr;
@@ -446,17 +455,17 @@ void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const Leve
     SOMAR_CHECK(in_mode < 3 || ((r0 == 1 || r0 == 2) && (r1 == 1 || r1 == 2) && (r2 == 1 || r2 == 2)),
                 "internal: the prolongation folded into a sweep takes multigrid ratios of 1 or 2 per direction");
     auto go = [&](auto kern, int rows) {
-        hipLaunchKernelGGL(kern, dim3(ntiles), dim3(64, rows, 1), 0, st, tiles, L.patches, phi_out, phi_in, rhs, L.jg[0], L.jg[1],
-                           L.jg[2], L.jinv, L.P, sums, cpatches, crse, r0, r1, r2, lean_ok);
+        hipLaunchKernelGGL(kern, dim3(ntiles), dim3(64, rows, 1), 0, st, tiles, L.patches, phi_out, phi_in, rhs, M.jg[0], M.jg[1],
+                           M.jg[2], M.jinv, L.P, sums, cpatches, crse, r0, r1, r2, lean_ok);
     };
     // (rows, mode, Dirichlet sides, uniform metric, narrow lane classes in the tile table)
 #define SOMAR_FUSED_MODES(ROWS, D, U, N, M0, M1, M2, M3, M4)                    \
     switch (in_mode) {                                                          \
-        case 1: go(k_gsrb_fused<ROWS, M1, D, U, N>, ROWS); break;               \
-        case 2: go(k_gsrb_fused<ROWS, M2, D, U, N>, ROWS); break;               \
-        case 3: go(k_gsrb_fused<ROWS, M3, D, U, N>, ROWS); break;               \
-        case 4: go(k_gsrb_fused<ROWS, M4, D, U, N>, ROWS); break;               \
-        default: go(k_gsrb_fused<ROWS, M0, D, U, N>, ROWS);                     \
+        case 1: go(k_gsrb_fused<ROWS, M1, D, U, N, T>, ROWS); break;            \
+        case 2: go(k_gsrb_fused<ROWS, M2, D, U, N, T>, ROWS); break;            \
+        case 3: go(k_gsrb_fused<ROWS, M3, D, U, N, T>, ROWS); break;            \
+        case 4: go(k_gsrb_fused<ROWS, M4, D, U, N, T>, ROWS); break;            \
+        default: go(k_gsrb_fused<ROWS, M0, D, U, N, T>, ROWS);                  \
     }
     const bool rows16 = fused_rows() == 16;
     const bool narrow = L.narrow7 != 0 && rows16;   // Level::build_march_tiles hands the 8-row kernels class-0 tiles only
@@ -480,6 +489,32 @@ void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const Leve
     else if (narrow) { SOMAR_FUSED_MODES(16, false, false, true, 0, 1, 2, 3, 4) }
     else { SOMAR_FUSED_MODES(16, false, false, false, 0, 1, 2, 3, 4) }
 #undef SOMAR_FUSED_MODES
+}
+
+void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* phi_out,
+                       const double* phi_in, const double* rhs, int in_mode, const double* sums,
+                       const LevelDev* C, const double* crse, const int* r)
+{
+    launch_gsrb_fused_t<double>(st, tiles, ntiles, L, metric_ptrs(L), phi_out, phi_in, rhs, in_mode, sums, C, crse, r);
+}
+
+void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, const MetricPtrs<float>& M,
+                       float* phi_out, const float* phi_in, const float* rhs, int in_mode, const double* sums,
+                       const LevelDev* C, const float* crse, const int* r)
+{
+    // the fp32 copies of a uniform depth are not made (PressureSolver::mp_convert_metric): only the UNI kernels may run without them
+    SOMAR_CHECK(fused_uniform_kernel(L) || (M.jg[0] && M.jg[1] && M.jg[2] && M.jinv),
+                "internal: the fused sweep streams the metric of this depth, but its fp32 copies are missing");
+    launch_gsrb_fused_t<float>(st, tiles, ntiles, L, M, phi_out, phi_in, rhs, in_mode, sums, C, crse, r);
+}
+
+// the launcher's choice above: the uniform-metric kernels (coefficients from StencilParams::uc, no array read) run on a uniform
+// depth without Dirichlet sides in the 16-row form; the Dirichlet and 8-row tables stream the four arrays whatever the flag says
+bool fused_uniform_kernel(const LevelDev& L)
+{
+    bool diri = false;
+    for (int d = 0; d < 3; ++d) diri = diri || L.P.diri[d][0] || L.P.diri[d][1];
+    return L.P.uniform && fused_rows() == 16 && !diri;
 }
 
 // region rows per workgroup of the fused sweep (tile rows = rows - 4); SOMAR_FUSED_ROWS = 8 | 16

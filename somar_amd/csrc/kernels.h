@@ -30,6 +30,12 @@ struct LevelDev {
     int narrowq = 0;                    // the 19-point marching kernels' tile table does
 };
 
+// the coefficient arrays a marching kernel streams, in its element type: the level's own (fp64), or their fp32 copies on the
+// depths of the opt-in mixed-precision cycle (PressureSolver::set_precision; null where StencilParams::uniform stands in)
+template <class T>
+struct MetricPtrs { const T* jg[3]; const T* jinv; };
+inline MetricPtrs<double> metric_ptrs(const LevelDev& L) { return MetricPtrs<double>{{L.jg[0], L.jg[1], L.jg[2]}, L.jinv}; }
+
 // operands of MAPPEDGETFLUX with a non-diagonal metric, evaluated where a flux register needs it (amr_kernels.hip: reg_flux19)
 struct FullFlux { const double* psi = nullptr; const double* J[3][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}; double dxi[3] = {0, 0, 0}; };
 
@@ -38,6 +44,8 @@ struct FullFlux { const double* psi = nullptr; const double* J[3][3] = {{nullptr
 // boxes' frames only -- the frame-only programs of the marching 19-point kernels, full19_march.hip)
 void launch_ghost_ops(hipStream_t st, const LevelDev& L, const GhostOp* ops, int nops, double* phi, double* psi,
                       bool bc_homog = true, bool redirect = false);
+// homogeneous physical ghosts of an fp32 field (mixed-precision depths; ops without cross terms)
+void launch_ghost_ops(hipStream_t st, const LevelDev& L, const GhostOp* ops, int nops, float* phi);
 // a whole ghost program in one launch, one workgroup per box (ops sorted by box, then stage = GhostOp::pad_; box b owns
 // box_ops[box_first[b] .. box_first[b + 1])); copy_all: psi := phi on every box grown by one cell first
 void launch_ghost_program(hipStream_t st, const LevelDev& L, const GhostOp* box_ops, const int* box_first, double* phi,
@@ -72,13 +80,23 @@ void launch_gsrb_ortho(hipStream_t st, const LevelDev& L, double* phi, const dou
 void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* phi_out,
                        const double* phi_in, const double* rhs, int in_mode = 0, const double* sums = nullptr,
                        const LevelDev* C = nullptr, const double* crse = nullptr, const int* r = nullptr);
+// the same sweep on fp32 fields and coefficients (mixed-precision depths); sums stay fp64
+void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, const MetricPtrs<float>& M,
+                       float* phi_out, const float* phi_in, const float* rhs, int in_mode, const double* sums,
+                       const LevelDev* C, const float* crse, const int* r);
 int fused_rows();
+// whether launch_gsrb_fused takes a uniform-metric kernel on this level (it then reads none of the four coefficient arrays)
+bool fused_uniform_kernel(const LevelDev& L);
 // k-marching operator/residual of a large level (resid_march.hip); mode 0: out = rhs - L[phi], 1: out = L[phi]
 void launch_resid_march(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* out,
                         const double* phi, const double* rhs, int mode);
 void launch_resid_restrict(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const LevelDev& C,
                            double* crse, const double* phi, const double* rhs, const int r[3], double dxProduct = 0.0,
                            double* volsum = nullptr);
+// the same on fp32 fields and coefficients (mixed-precision depths); volsum is accumulated in fp64
+void launch_resid_restrict(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const MetricPtrs<float>& M,
+                           const LevelDev& C, float* crse, const float* phi, const float* rhs, const int r[3],
+                           double dxProduct, double* volsum);
 // crse(ic) = sum over the children of ic of dxProduct / fjinv(child): the volume a coarse value is spread over
 void launch_child_volume(hipStream_t st, const LevelDev& C, const LevelDev& F, double* crse, const int r[3],
                          double dxProduct);
@@ -106,14 +124,22 @@ void launch_avg_harmonic(hipStream_t st, const LevelDev& C, const LevelDev& F, d
 void launch_avg_face(hipStream_t st, const LevelDev& C, const LevelDev& F, int patch, const int cn[3], double* crse,
                      const double* fine, int dir, const int r[3]);
 void launch_copy_items(hipStream_t st, const LevelDev& L, const CopyItem* items, int nitems, double* f);
+void launch_copy_items(hipStream_t st, const LevelDev& L, const CopyItem* items, int nitems, float* f);
 void launch_pack(hipStream_t st, const LevelDev& L, const CopyItem* items, const long long* bufoff, int nitems,
                  double* f, double* buf, bool pack);
 void launch_set(hipStream_t st, double* a, long long n, double v);
+void launch_set(hipStream_t st, float* a, long long n, float v);
 // n device values -> coherent host memory, then the sequence number (system-scope release)
 void launch_publish(hipStream_t st, const double* src, int n, double* host_dst, unsigned long long* host_seq,
                     unsigned long long seq);
 void launch_copy(hipStream_t st, double* d, const double* s, long long n);
+void launch_copy(hipStream_t st, float* d, const float* s, long long n);
 void launch_incr(hipStream_t st, double* y, const double* x, double a, long long n);
+void launch_incr(hipStream_t st, double* y, const float* x, double a, long long n);   // y += a * (double)x
+// mixed-precision boundary: n values converted, one launch for up to four arrays (dst[q] = src[q]; null pairs are skipped)
+void launch_convert(hipStream_t st, float* const dst[4], const double* const src[4], long long n);
+void launch_convert(hipStream_t st, double* dst, const float* src, long long n);
+void launch_convert(hipStream_t st, float* dst, const double* src, long long n);
 void launch_incr2(hipStream_t st, double* y1, const double* x1, double a1, double* y2, const double* x2, double a2, long long n);
 void launch_bicg_p(hipStream_t st, double* p, const double* v, const double* r, double beta, double bw, long long n);  // p = (p*beta + bw*v) + r
 void launch_incr_copy(hipStream_t st, double* y, double* x, double a, long long n);  // y += a*x; x = y
@@ -203,6 +229,9 @@ void launch_minmax_all(hipStream_t st, const MinMaxItem* items, int nitems, doub
 // ordered: reference-ordered serial sum (modes 0 and 2; meant for small levels, see k_reduce_ordered)
 void launch_reduce(hipStream_t st, const LevelDev& L, const double* a, const double* b, int mode, double* partials,
                    double* out, bool ordered = false, const ScalarPublish* pub = nullptr);
+// mode 0 (sum a*b) with a in fp32: each term and the sum in fp64, in the tree order of the fp64 form
+void launch_reduce(hipStream_t st, const LevelDev& L, const float* a, const double* b, int mode, double* partials,
+                   double* out);
 // sharded small level: the rank's per-cell terms into their slot of the serial sequence (mode 0: a*b, 2: |a|, 6: X = dxProduct/b*a,
 // Y = dxProduct/b), then -- after a sum-allreduce of X (and Y) -- the walk in the reference's order (k_reduce_ordered_flat)
 void launch_ord_fill(hipStream_t st, const LevelDev& L, const long long* start, const double* a, const double* b,

@@ -565,8 +565,9 @@ __global__ void k_avg_face(const PatchDesc* __restrict__ cpatches, const PatchDe
 // ------------------------------------------------------------------------------------
 // one cell per thread, cells of an item numbered i-fastest: a 2-cell-wide x-face (n[0] = 2) keeps all 256 lanes
 // busy instead of 2 of 64 (halo copies at 128-wide boxes took longer than a sweep of the box otherwise)
+template <class T = double>
 __global__ void k_copy_items(const CopyItem* __restrict__ items, const PatchDesc* __restrict__ patches,
-                             double* __restrict__ f)
+                             T* __restrict__ f)
 {
     const CopyItem it = items[blockIdx.x];
     const PatchDesc sp = patches[it.src_patch];
@@ -608,18 +609,33 @@ __global__ void k_pack_items(const CopyItem* __restrict__ items, const PatchDesc
 // ------------------------------------------------------------------------------------
 // flat BLAS-1 over whole allocations (LevelDataOps semantics: whole FAB incl. ghosts)
 // ------------------------------------------------------------------------------------
-__global__ void k_set(double* __restrict__ a, long long n, double v)
+template <class T = double>
+__global__ void k_set(T* __restrict__ a, long long n, T v)
 {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         a[i] = v;
 }
-__global__ void k_copy(double* __restrict__ d, const double* __restrict__ s, long long n)
+template <class T = double>
+__global__ void k_copy(T* __restrict__ d, const T* __restrict__ s, long long n)
 {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         d[i] = s[i];
 }
-// y += a*x
-__global__ void k_incr(double* __restrict__ y, const double* __restrict__ x, double a, long long n)
+// mixed-precision boundary: dst[q] = src[q] converted, for the pairs q < blockIdx.y's range that are set (grid.y = 4)
+template <class TD, class TS>
+struct ConvertArgs { TD* dst[4]; const TS* src[4]; };
+template <class TD, class TS>
+__global__ void k_convert(ConvertArgs<TD, TS> A, long long n)
+{
+    TD* __restrict__ d = A.dst[blockIdx.y];
+    const TS* __restrict__ s = A.src[blockIdx.y];
+    if (!d) return;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        d[i] = (TD)s[i];
+}
+// y += a*x (x in fp64, or the fp32 correction of a mixed-precision cycle, taken to double first)
+template <class TX = double>
+__global__ void k_incr(double* __restrict__ y, const TX* __restrict__ x, double a, long long n)
 {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         y[i] = y[i] + a * x[i];
@@ -674,10 +690,11 @@ __global__ void k_axby(double* __restrict__ z, const double* __restrict__ x, con
 }
 
 // valid-cell reductions.  MODE 0: sum a*b   1: max |a|   2: sum |a|   3: signed max a
-template <int MODE>
+// TA: a's element type (float: an fp32 field of a mixed-precision cycle, each term formed and summed in double; MODE 0 only)
+template <int MODE, class TA = double>
 __global__ __launch_bounds__(512) void k_reduce_valid(const Tile* __restrict__ tiles,
                                                       const PatchDesc* __restrict__ patches,
-                                                      const double* __restrict__ a,
+                                                      const TA* __restrict__ a,
                                                       const double* __restrict__ b,
                                                       double* __restrict__ partials, unsigned int* __restrict__ counter,
                                                       double* __restrict__ out, ScalarPublish pub)
@@ -693,7 +710,7 @@ __global__ __launch_bounds__(512) void k_reduce_valid(const Tile* __restrict__ t
                 const int li = li0 + q;
                 if (li >= p.n[0]) continue;
                 const long long c = cidx(p, li, lj, t.k0 + kk);
-                if (MODE == 0) acc = acc + a[c] * b[c];
+                if (MODE == 0) acc = acc + (double)a[c] * b[c];
                 else if (MODE == 1) acc = fmax(acc, fabs(a[c]));
                 else if (MODE == 2) acc = acc + fabs(a[c]);
                 else if (MODE == 3) acc = fmax(acc, a[c]);
@@ -1097,7 +1114,12 @@ void launch_avg_face(hipStream_t st, const LevelDev& C, const LevelDev& F, int p
 void launch_copy_items(hipStream_t st, const LevelDev& L, const CopyItem* items, int nitems, double* f)
 {
     if (nitems == 0) return;
-    hipLaunchKernelGGL(k_copy_items, dim3(nitems, 16), dim3(256), 0, st, items, L.patches, f);
+    hipLaunchKernelGGL(k_copy_items<double>, dim3(nitems, 16), dim3(256), 0, st, items, L.patches, f);
+}
+void launch_copy_items(hipStream_t st, const LevelDev& L, const CopyItem* items, int nitems, float* f)
+{
+    if (nitems == 0) return;
+    hipLaunchKernelGGL(k_copy_items<float>, dim3(nitems, 16), dim3(256), 0, st, items, L.patches, f);
 }
 void launch_pack(hipStream_t st, const LevelDev& L, const CopyItem* items, const long long* bufoff, int nitems,
                  double* f, double* buf, bool pack)
@@ -1110,11 +1132,35 @@ void launch_pack(hipStream_t st, const LevelDev& L, const CopyItem* items, const
 }
 void launch_set(hipStream_t st, double* a, long long n, double v)
 {
-    hipLaunchKernelGGL(k_set, dim3(flat_grid(n)), dim3(256), 0, st, a, n, v);
+    hipLaunchKernelGGL(k_set<double>, dim3(flat_grid(n)), dim3(256), 0, st, a, n, v);
+}
+void launch_set(hipStream_t st, float* a, long long n, float v)
+{
+    hipLaunchKernelGGL(k_set<float>, dim3(flat_grid(n)), dim3(256), 0, st, a, n, v);
 }
 void launch_copy(hipStream_t st, double* d, const double* s, long long n)
 {
-    hipLaunchKernelGGL(k_copy, dim3(flat_grid(n)), dim3(256), 0, st, d, s, n);
+    hipLaunchKernelGGL(k_copy<double>, dim3(flat_grid(n)), dim3(256), 0, st, d, s, n);
+}
+void launch_copy(hipStream_t st, float* d, const float* s, long long n)
+{
+    hipLaunchKernelGGL(k_copy<float>, dim3(flat_grid(n)), dim3(256), 0, st, d, s, n);
+}
+void launch_convert(hipStream_t st, float* const dst[4], const double* const src[4], long long n)
+{
+    ConvertArgs<float, double> A;
+    for (int q = 0; q < 4; ++q) { A.dst[q] = dst[q]; A.src[q] = src[q]; }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_convert<float, double>), dim3(flat_grid(n), 4), dim3(256), 0, st, A, n);
+}
+void launch_convert(hipStream_t st, float* dst, const double* src, long long n)
+{
+    ConvertArgs<float, double> A = {{dst, nullptr, nullptr, nullptr}, {src, nullptr, nullptr, nullptr}};
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_convert<float, double>), dim3(flat_grid(n), 1), dim3(256), 0, st, A, n);
+}
+void launch_convert(hipStream_t st, double* dst, const float* src, long long n)
+{
+    ConvertArgs<double, float> A = {{dst, nullptr, nullptr, nullptr}, {src, nullptr, nullptr, nullptr}};
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_convert<double, float>), dim3(flat_grid(n), 1), dim3(256), 0, st, A, n);
 }
 __global__ void k_publish(const double* __restrict__ src, int n, double* host_dst, unsigned long long* host_seq,
                           unsigned long long seq)
@@ -1131,7 +1177,11 @@ void launch_publish(hipStream_t st, const double* src, int n, double* host_dst, 
 }
 void launch_incr(hipStream_t st, double* y, const double* x, double a, long long n)
 {
-    hipLaunchKernelGGL(k_incr, dim3(flat_grid(n)), dim3(256), 0, st, y, x, a, n);
+    hipLaunchKernelGGL(k_incr<double>, dim3(flat_grid(n)), dim3(256), 0, st, y, x, a, n);
+}
+void launch_incr(hipStream_t st, double* y, const float* x, double a, long long n)
+{
+    hipLaunchKernelGGL(k_incr<float>, dim3(flat_grid(n)), dim3(256), 0, st, y, x, a, n);
 }
 void launch_incr_copy(hipStream_t st, double* y, double* x, double a, long long n)
 {
@@ -1177,7 +1227,7 @@ void launch_reduce(hipStream_t st, const LevelDev& L, const double* a, const dou
         return;
     }
     if (L.ntiles == 0) {
-        hipLaunchKernelGGL(k_set, dim3(1), dim3(64), 0, st, out, 1, 0.0);
+        hipLaunchKernelGGL(k_set<double>, dim3(1), dim3(64), 0, st, out, 1, 0.0);
         if (pub) launch_publish(st, out, 1, pub->host_dst, pub->host_seq, pub->seq);
         return;
     }
@@ -1200,6 +1250,20 @@ void launch_reduce(hipStream_t st, const LevelDev& L, const double* a, const dou
     if (cnt) return;
     hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, st, partials, L.ntiles, 1,
                        mode == 1 ? 1 : (mode == 3 ? 2 : 0), out, P);
+}
+void launch_reduce(hipStream_t st, const LevelDev& L, const float* a, const double* b, int mode, double* partials,
+                   double* out)
+{
+    SOMAR_CHECK(mode == 0, "internal: fp32 reductions are sums of a * b");
+    if (L.ntiles == 0) {
+        hipLaunchKernelGGL(k_set<double>, dim3(1), dim3(64), 0, st, out, 1, 0.0);
+        return;
+    }
+    // the two-launch form of the fp64 reduction (same partition, same tree)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reduce_valid<0, float>), dim3(L.ntiles), tile_block(L), 0, st, L.tiles, L.patches, a, b,
+                       partials, nullptr, out, ScalarPublish{nullptr, nullptr, 0ull});
+    hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, st, partials, L.ntiles, 1, 0, out,
+                       ScalarPublish{nullptr, nullptr, 0ull});
 }
 void launch_ord_fill(hipStream_t st, const LevelDev& L, const long long* start, const double* a, const double* b,
                      int mode, double dxProduct, double* X, double* Y)

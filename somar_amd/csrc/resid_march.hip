@@ -18,37 +18,42 @@ namespace somar {
 
 constexpr int RM_J = 16;   // region rows = 14-row tile + 1 low + 1 high
 
-__device__ __forceinline__ double2 rm_ld2(const double* __restrict__ a, long long idx, bool ok0, bool ok1,
-                                          long long safe)
+// T: the element type of the fields and coefficient arrays -- double, or float on the depths of the opt-in mixed-precision
+// cycle (PressureSolver::set_precision), whose arithmetic then stays in float; only the volume sum is accumulated in double
+template <class T>
+__device__ __forceinline__ typename Vec2<T>::type rm_ld2(const T* __restrict__ a, long long idx, bool ok0, bool ok1,
+                                                         long long safe)
 {
     // branch-free: always one aligned 16-byte load (from `safe`, any valid aligned element of the patch, when
     // neither element may be touched), then selects.  Straight-line loads let the compiler count outstanding
     // loads exactly (s_waitcnt vmcnt(N)) instead of draining everything at every predicated branch.
 #ifdef SOMAR_NT_LOADS
     // streamed once per launch: keep the coefficient / right-hand-side lines out of the way of the phi halo reuse in L2
-    typedef double v2d_ __attribute__((ext_vector_type(2)));
+    typedef T v2d_ __attribute__((ext_vector_type(2)));
     const v2d_ w = __builtin_nontemporal_load(reinterpret_cast<const v2d_*>(a + ((ok0 || ok1) ? idx : safe)));
-    const double2 v = make_double2(w.x, w.y);
+    const typename Vec2<T>::type v = mk2<T>(w.x, w.y);
 #else
-    const double2 v = *reinterpret_cast<const double2*>(a + ((ok0 || ok1) ? idx : safe));
+    const typename Vec2<T>::type v = *reinterpret_cast<const typename Vec2<T>::type*>(a + ((ok0 || ok1) ? idx : safe));
 #endif
-    return make_double2(ok0 ? v.x : 0.0, ok1 ? v.y : 0.0);
+    return mk2<T>(ok0 ? v.x : T(0), ok1 ? v.y : T(0));
 }
 
 // unconditional: the zeros rm_ld2 returns under a false predicate only reach cells that are not written (see gsrb_fused.hip)
-__device__ __forceinline__ double2 rm_uni2(double c, bool, bool) { return make_double2(c, c); }
+template <class T>
+__device__ __forceinline__ typename Vec2<T>::type rm_uni2(double c, bool, bool) { return mk2<T>(T(c), T(c)); }
 
 // UNI: uniform metric, the four coefficient arrays are not read (StencilParams::uc)
 // CLS: the tile's lane class (see full19_march.hip): a wavefront covers 2^CLS region rows of 128 >> CLS columns
-template <int MODE, bool UNI, int CLS>
-__device__ __forceinline__ void resid_march_body(double* __restrict__ S, double* __restrict__ T, const Tile& t,
-                                                 const PatchDesc& p, double* __restrict__ out,
-                                                 const double* __restrict__ phi, const double* __restrict__ rhs,
-                                                 const double* __restrict__ jgx, const double* __restrict__ jgy,
-                                                 const double* __restrict__ jgz, const double* __restrict__ jinv,
+template <int MODE, bool UNI, int CLS, class E>
+__device__ __forceinline__ void resid_march_body(E* __restrict__ S, E* __restrict__ T, const Tile& t,
+                                                 const PatchDesc& p, E* __restrict__ out,
+                                                 const E* __restrict__ phi, const E* __restrict__ rhs,
+                                                 const E* __restrict__ jgx, const E* __restrict__ jgy,
+                                                 const E* __restrict__ jgz, const E* __restrict__ jinv,
                                                  const StencilParams& P, const PatchDesc* __restrict__ cpatches, int r0,
                                                  int r1, int r2, double dxProduct, double* __restrict__ volsum)
 {
+    typedef typename Vec2<E>::type E2;
     constexpr int LPR = 64 >> CLS;                 // lanes per region row
     constexpr int NR = RM_J << CLS;                // region rows of the workgroup
     constexpr int PITCH = 2 * LPR + (CLS >= 2 ? 2 : 0);
@@ -63,7 +68,7 @@ __device__ __forceinline__ void resid_march_body(double* __restrict__ S, double*
     const int wi = t.pad_[0] > 0 ? t.pad_[0] : 2 * LPR - 4;  // output columns of this tile (see gsrb_fused.hip)
     const int lj = t.j0 - 1 + row;
     const int gj = p.lo[1] + lj;
-    const double sx = 1.0 / P.dx[0], sy = 1.0 / P.dx[1], sz = 1.0 / P.dx[2];
+    const E sx = E(1.0) / E(P.dx[0]), sy = E(1.0) / E(P.dx[1]), sz = E(1.0) / E(P.dx[2]);
 
     // phi may be touched inside the 1-cell ghost layer, coefficients only at the tile's own cells / faces
     const bool fj = (lj >= -1) && (lj <= p.n[1]);
@@ -95,17 +100,17 @@ __device__ __forceinline__ void resid_march_body(double* __restrict__ S, double*
     }
 
     // MODE 2 state: this pair's (res/J, 1/J) of the previous plane, running sums of up to two coarse cells
-    double pv[4] = {0.0, 0.0, 0.0, 0.0}, cs[2] = {0.0, 0.0}, cjs[2] = {0.0, 0.0};
+    E pv[4] = {0, 0, 0, 0}, cs[2] = {0, 0}, cjs[2] = {0, 0};
     const bool leader = (MODE == 2) && any && (r1 == 1 || ((lj & 1) == 0));
     auto accumulate = [&](int kp) {
         // MAPPEDAVERAGE2's loop order: ii2 (planes), ii1 (rows), ii0 (cells of the pair)
         if (!leader) return;
         const bool first = (r2 == 1) || ((kp & 1) == 0);
         const bool last = (r2 == 1) || ((kp & 1) == 1);
-        if (first) { cs[0] = cs[1] = 0.0; cjs[0] = cjs[1] = 0.0; }
-        double q[4] = {0.0, 0.0, 0.0, 0.0};
+        if (first) { cs[0] = cs[1] = 0; cjs[0] = cjs[1] = 0; }
+        E q[4] = {0, 0, 0, 0};
         if (r1 == 2) {
-            const double* src = Tx(kp & 1, row + 1, lane);
+            const E* src = Tx(kp & 1, row + 1, lane);
             q[0] = src[0]; q[1] = src[1]; q[2] = src[2]; q[3] = src[3];
         }
         if (r0 == 2) {
@@ -140,78 +145,80 @@ __device__ __forceinline__ void resid_march_body(double* __restrict__ S, double*
     double vsum = 0.0;
 
     int k = t.k0;
-    double2 Pm = rm_ld2(phi, base + sk * (k - 1), o[0], o[1], p.off);
-    double2 Pc = rm_ld2(phi, base + sk * k, f0, f1, p.off);
-    double2 Gzc = UNI ? rm_uni2(P.uc[2], o[0], o[1]) : rm_ld2(jgz, base + sk * k, o[0], o[1], p.off);
+    E2 Pm = rm_ld2(phi, base + sk * (k - 1), o[0], o[1], p.off);
+    E2 Pc = rm_ld2(phi, base + sk * k, f0, f1, p.off);
+    E2 Gzc = UNI ? rm_uni2<E>(P.uc[2], o[0], o[1]) : rm_ld2(jgz, base + sk * k, o[0], o[1], p.off);
     const int kend = t.k0 + t.nk;
     for (; k < kend; ++k) {
         const int gk = p.lo[2] + k;
         const bool more = (k + 1 < kend);
         // ---- this step's loads ----
-        const double2 Pp = rm_ld2(phi, base + sk * (k + 1), more ? f0 : o[0], more ? f1 : o[1], p.off);
-        const double2 Gzp = UNI ? rm_uni2(P.uc[2], o[0], o[1]) : rm_ld2(jgz, base + sk * (k + 1), o[0], o[1], p.off);
-        double2 Rh = make_double2(0.0, 0.0);
+        const E2 Pp = rm_ld2(phi, base + sk * (k + 1), more ? f0 : o[0], more ? f1 : o[1], p.off);
+        const E2 Gzp = UNI ? rm_uni2<E>(P.uc[2], o[0], o[1]) : rm_ld2(jgz, base + sk * (k + 1), o[0], o[1], p.off);
+        E2 Rh = mk2<E>(E(0), E(0));
         if (MODE != 1) Rh = rm_ld2(rhs, base + sk * k, o[0], o[1], p.off);
-        const double2 Ji = UNI ? rm_uni2(P.uc[3], o[0], o[1]) : rm_ld2(jinv, base + sk * k, o[0], o[1], p.off);
-        const double2 Gx = UNI ? rm_uni2(P.uc[0], gxo0, o[0] || o[1]) : rm_ld2(jgx, base + sk * k, gxo0, o[0] || o[1], p.off);
-        const double2 Gy = UNI ? rm_uni2(P.uc[1], o[0], o[1]) : rm_ld2(jgy, base + sk * k, o[0], o[1], p.off);
-        const double2 Gyh = UNI ? rm_uni2(P.uc[1], o[0], o[1]) : rm_ld2(jgy, base + sk * k + sj, o[0], o[1], p.off);
-        const double gx_next = __shfl_down(Gx.x, 1, 64);
+        const E2 Ji = UNI ? rm_uni2<E>(P.uc[3], o[0], o[1]) : rm_ld2(jinv, base + sk * k, o[0], o[1], p.off);
+        const E2 Gx = UNI ? rm_uni2<E>(P.uc[0], gxo0, o[0] || o[1]) : rm_ld2(jgx, base + sk * k, gxo0, o[0] || o[1], p.off);
+        const E2 Gy = UNI ? rm_uni2<E>(P.uc[1], o[0], o[1]) : rm_ld2(jgy, base + sk * k, o[0], o[1], p.off);
+        const E2 Gyh = UNI ? rm_uni2<E>(P.uc[1], o[0], o[1]) : rm_ld2(jgy, base + sk * k + sj, o[0], o[1], p.off);
+        const E gx_next = __shfl_down(Gx.x, 1, 64);
 
         // ---- stage plane k; slot k&1 was last read two steps ago, one barrier per plane suffices ----
         const int slot = k & 1;
-        *reinterpret_cast<double2*>(&Sx(slot, row, ri)) = Pc;
+        *reinterpret_cast<E2*>(&Sx(slot, row, ri)) = Pc;
         __syncthreads();
         if (MODE == 2 && k > t.k0) accumulate(k - 1);
 
         if (any) {
             const bool zzl = (gk == P.dom_lo[2]) && P.neum[2][0];
             const bool zzh = (gk == P.dom_hi[2]) && P.neum[2][1];
-            double res[2] = {0.0, 0.0};
+            E res[2] = {0, 0};
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 if (!o[s]) continue;
                 const int rc = ri + s;
-                const double pc = s ? Pc.y : Pc.x;
-                const double pxl = s ? Pc.x : Sx(slot, row, rc - 1);
-                const double pxh = s ? Sx(slot, row, rc + 1) : Pc.y;
-                const double pyl = Sx(slot, row - 1, rc), pyh = Sx(slot, row + 1, rc);
-                const double gxl = s ? Gx.y : Gx.x, gxh = s ? gx_next : Gx.y;
-                double fxl = gxl * sx * (pc - pxl);
-                double fxh = gxh * sx * (pxh - pc);
-                double fyl = (s ? Gy.y : Gy.x) * sy * (pc - pyl);
-                double fyh = (s ? Gyh.y : Gyh.x) * sy * (pyh - pc);
-                double fzl = (s ? Gzc.y : Gzc.x) * sz * (pc - (s ? Pm.y : Pm.x));
-                double fzh = (s ? Gzp.y : Gzp.x) * sz * ((s ? Pp.y : Pp.x) - pc);
-                if (zxl[s]) fxl = 0.0;
-                if (zxh[s]) fxh = 0.0;
-                if (zyl) fyl = 0.0;
-                if (zyh) fyh = 0.0;
-                if (zzl) fzl = 0.0;
-                if (zzh) fzh = 0.0;
-                fxl *= P.beta; fxh *= P.beta; fyl *= P.beta; fyh *= P.beta; fzl *= P.beta; fzh *= P.beta;
-                double l = (s ? Ji.y : Ji.x) * ((fxh - fxl) * sx + (fyh - fyl) * sy + (fzh - fzl) * sz);
-                if (P.alpha != 0.0) l = P.alpha * pc + 1.0 * l;
+                const E pc = s ? Pc.y : Pc.x;
+                const E pxl = s ? Pc.x : Sx(slot, row, rc - 1);
+                const E pxh = s ? Sx(slot, row, rc + 1) : Pc.y;
+                const E pyl = Sx(slot, row - 1, rc), pyh = Sx(slot, row + 1, rc);
+                const E gxl = s ? Gx.y : Gx.x, gxh = s ? gx_next : Gx.y;
+                E fxl = gxl * sx * (pc - pxl);
+                E fxh = gxh * sx * (pxh - pc);
+                E fyl = (s ? Gy.y : Gy.x) * sy * (pc - pyl);
+                E fyh = (s ? Gyh.y : Gyh.x) * sy * (pyh - pc);
+                E fzl = (s ? Gzc.y : Gzc.x) * sz * (pc - (s ? Pm.y : Pm.x));
+                E fzh = (s ? Gzp.y : Gzp.x) * sz * ((s ? Pp.y : Pp.x) - pc);
+                if (zxl[s]) fxl = 0;
+                if (zxh[s]) fxh = 0;
+                if (zyl) fyl = 0;
+                if (zyh) fyh = 0;
+                if (zzl) fzl = 0;
+                if (zzh) fzh = 0;
+                const E beta = E(P.beta);
+                fxl *= beta; fxh *= beta; fyl *= beta; fyh *= beta; fzl *= beta; fzh *= beta;
+                E l = (s ? Ji.y : Ji.x) * ((fxh - fxl) * sx + (fyh - fyl) * sy + (fzh - fzl) * sz);
+                if (P.alpha != 0.0) l = E(P.alpha) * pc + E(1.0) * l;
                 res[s] = (MODE != 1) ? ((s ? Rh.y : Rh.x) - l) : l;
             }
             if (MODE == 2) {
                 // coarseSum + fine/J, coarseCCJSum + 1.0/J  (MAPPEDAVERAGE2)
-                pv[0] = o[0] ? res[0] / Ji.x : 0.0;
-                pv[1] = o[1] ? res[1] / Ji.y : 0.0;
-                pv[2] = o[0] ? 1.0 / Ji.x : 0.0;
-                pv[3] = o[1] ? 1.0 / Ji.y : 0.0;
+                pv[0] = o[0] ? res[0] / Ji.x : E(0);
+                pv[1] = o[1] ? res[1] / Ji.y : E(0);
+                pv[2] = o[0] ? E(1.0) / Ji.x : E(0);
+                pv[3] = o[1] ? E(1.0) / Ji.y : E(0);
                 if (volsum) {
-                    if (o[0]) vsum = vsum + dxProduct * pv[2] * Pc.x;
-                    if (o[1]) vsum = vsum + dxProduct * pv[3] * Pc.y;
+                    // fp32 fields: each term and the sum in double
+                    if (o[0]) vsum = vsum + dxProduct * (double)pv[2] * (double)Pc.x;
+                    if (o[1]) vsum = vsum + dxProduct * (double)pv[3] * (double)Pc.y;
                 }
                 if (r1 == 2) {
-                    double* dstT = Tx(k & 1, row, lane);
-                    *reinterpret_cast<double2*>(dstT) = make_double2(pv[0], pv[1]);
-                    *reinterpret_cast<double2*>(dstT + 2) = make_double2(pv[2], pv[3]);
+                    E* dstT = Tx(k & 1, row, lane);
+                    *reinterpret_cast<E2*>(dstT) = mk2<E>(pv[0], pv[1]);
+                    *reinterpret_cast<E2*>(dstT + 2) = mk2<E>(pv[2], pv[3]);
                 }
             } else {
-                double* dst = out + base + sk * k;
-                if (o[0] && o[1]) *reinterpret_cast<double2*>(dst) = make_double2(res[0], res[1]);
+                E* dst = out + base + sk * k;
+                if (o[0] && o[1]) *reinterpret_cast<E2*>(dst) = mk2<E>(res[0], res[1]);
                 else if (o[0]) dst[0] = res[0];
                 else dst[1] = res[1];
             }
@@ -239,29 +246,29 @@ __device__ __forceinline__ void resid_march_body(double* __restrict__ S, double*
 #undef Tx
 }
 
-template <int MODE, bool UNI = false>
+template <int MODE, bool UNI = false, class E = double>
 // uniform metric, plain output: 64 VGPRs, two workgroups per CU (the narrow classes' per-lane row arithmetic must not cost that)
 __global__ __launch_bounds__(64 * RM_J, (UNI && MODE != 2) ? 8 : 4) void k_resid_march(const Tile* __restrict__ tiles,
                                                            const PatchDesc* __restrict__ patches,
-                                                           double* __restrict__ out,
-                                                           const double* __restrict__ phi,
-                                                           const double* __restrict__ rhs,
-                                                           const double* __restrict__ jgx,
-                                                           const double* __restrict__ jgy,
-                                                           const double* __restrict__ jgz,
-                                                           const double* __restrict__ jinv, StencilParams P,
+                                                           E* __restrict__ out,
+                                                           const E* __restrict__ phi,
+                                                           const E* __restrict__ rhs,
+                                                           const E* __restrict__ jgx,
+                                                           const E* __restrict__ jgy,
+                                                           const E* __restrict__ jgz,
+                                                           const E* __restrict__ jinv, StencilParams P,
                                                            const PatchDesc* __restrict__ cpatches, int r0, int r1,
                                                            int r2, double dxProduct, double* __restrict__ volsum)
 {
-    __shared__ __attribute__((aligned(16))) double S[2 * RM_J * 160];   // one slot = the largest class's region (16 RM_J rows of 8 + 2)
+    __shared__ __attribute__((aligned(16))) E S[2 * RM_J * 160];   // one slot = the largest class's region (16 RM_J rows of 8 + 2)
     // MODE 2: (res/J, 1/J) of both cells of every pair, handed from the odd row of a coarse cell to the even one
-    __shared__ __attribute__((aligned(16))) double T[MODE == 2 ? 2 * RM_J * 64 * 4 : 4];
+    __shared__ __attribute__((aligned(16))) E T[MODE == 2 ? 2 * RM_J * 64 * 4 : 4];
     const Tile t = tiles[blockIdx.x];
     const PatchDesc p = patches[t.patch];
     const int cls = t.pad_[1];
-    if (cls == 0) resid_march_body<MODE, UNI, 0>(S, T, t, p, out, phi, rhs, jgx, jgy, jgz, jinv, P, cpatches, r0, r1, r2, dxProduct, volsum);
-    else if (cls == 1) resid_march_body<MODE, UNI, 1>(S, T, t, p, out, phi, rhs, jgx, jgy, jgz, jinv, P, cpatches, r0, r1, r2, dxProduct, volsum);
-    else resid_march_body<MODE, UNI, 4>(S, T, t, p, out, phi, rhs, jgx, jgy, jgz, jinv, P, cpatches, r0, r1, r2, dxProduct, volsum);
+    if (cls == 0) resid_march_body<MODE, UNI, 0, E>(S, T, t, p, out, phi, rhs, jgx, jgy, jgz, jinv, P, cpatches, r0, r1, r2, dxProduct, volsum);
+    else if (cls == 1) resid_march_body<MODE, UNI, 1, E>(S, T, t, p, out, phi, rhs, jgx, jgy, jgz, jinv, P, cpatches, r0, r1, r2, dxProduct, volsum);
+    else resid_march_body<MODE, UNI, 4, E>(S, T, t, p, out, phi, rhs, jgx, jgy, jgz, jinv, P, cpatches, r0, r1, r2, dxProduct, volsum);
 }
 
 void launch_resid_march(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* out,
@@ -288,18 +295,35 @@ void launch_resid_march(hipStream_t st, const Tile* tiles, int ntiles, const Lev
 // restrictResidual in one pass: crse = J-weighted average (MAPPEDAVERAGE2) of rhs - L[phi]; the fine residual is
 // never written.  Needs tiles whose k-extent is even (Level::hrtiles are) and a coarsenable layout.
 // volsum (optional, ntiles doubles): per-block sums of (dxProduct / Jinv) * phi over the block's cells
+template <class E>
+static void launch_resid_restrict_t(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const MetricPtrs<E>& M,
+                                    const LevelDev& C, E* crse, const E* phi, const E* rhs, const int r[3], double dxProduct,
+                                    double* volsum)
+{
+    if (ntiles == 0) return;
+    if (F.P.uniform) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resid_march<2, true, E>), dim3(ntiles), dim3(64, RM_J, 1), 0, st, tiles, F.patches, crse, phi,
+                           rhs, M.jg[0], M.jg[1], M.jg[2], M.jinv, F.P, C.patches, r[0], r[1], r[2], dxProduct, volsum);
+        return;
+    }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resid_march<2, false, E>), dim3(ntiles), dim3(64, RM_J, 1), 0, st, tiles, F.patches, crse, phi, rhs,
+                       M.jg[0], M.jg[1], M.jg[2], M.jinv, F.P, C.patches, r[0], r[1], r[2], dxProduct, volsum);
+}
+
 void launch_resid_restrict(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const LevelDev& C,
                            double* crse, const double* phi, const double* rhs, const int r[3], double dxProduct,
                            double* volsum)
 {
-    if (ntiles == 0) return;
-    if (F.P.uniform) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resid_march<2, true>), dim3(ntiles), dim3(64, RM_J, 1), 0, st, tiles, F.patches, crse, phi,
-                           rhs, F.jg[0], F.jg[1], F.jg[2], F.jinv, F.P, C.patches, r[0], r[1], r[2], dxProduct, volsum);
-        return;
-    }
-    hipLaunchKernelGGL(k_resid_march<2>, dim3(ntiles), dim3(64, RM_J, 1), 0, st, tiles, F.patches, crse, phi, rhs,
-                       F.jg[0], F.jg[1], F.jg[2], F.jinv, F.P, C.patches, r[0], r[1], r[2], dxProduct, volsum);
+    launch_resid_restrict_t<double>(st, tiles, ntiles, F, metric_ptrs(F), C, crse, phi, rhs, r, dxProduct, volsum);
+}
+
+void launch_resid_restrict(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const MetricPtrs<float>& M,
+                           const LevelDev& C, float* crse, const float* phi, const float* rhs, const int r[3],
+                           double dxProduct, double* volsum)
+{
+    SOMAR_CHECK(F.P.uniform || (M.jg[0] && M.jg[1] && M.jg[2] && M.jinv),
+                "internal: the residual restriction streams the metric of this depth, but its fp32 copies are missing");
+    launch_resid_restrict_t<float>(st, tiles, ntiles, F, M, C, crse, phi, rhs, r, dxProduct, volsum);
 }
 
 }  // namespace somar

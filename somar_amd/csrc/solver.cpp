@@ -43,6 +43,7 @@ PressureSolver::PressureSolver(Comm* comm, hipStream_t shared) : comm_(comm ? co
 PressureSolver::~PressureSolver()
 {
     drop_graphs();
+    mp_free();
     for (GhostOp* q : d_diri_ops_) hipFree(q);
     hipFree(d_bcface_);
     for (double* q : f_flux) Level::free_field(q);
@@ -498,6 +499,10 @@ void PressureSolver::detect_zero_planes()
 void PressureSolver::finalize()
 {
     SOMAR_CHECK(!lev.empty() && !finalized, "finalize before define / twice");
+    if (mp_mode_ == 1) {
+        const std::string why = mixed_refusal();   // (the metric kind is only known now)
+        SOMAR_CHECK(why.empty(), "finalize: mixed precision (set_precision mode 1) is not available for " + why);
+    }
     // SOMAR_TIMING=1: wall time of the stages below on stderr (what a re-definition of the hierarchy costs)
     static const bool timing = getenv("SOMAR_TIMING") && atoi(getenv("SOMAR_TIMING")) != 0;
     auto now = [&]() { if (timing) hipDeviceSynchronize(); return std::chrono::steady_clock::now(); };
@@ -614,6 +619,7 @@ void PressureSolver::finalize()
             if (lev[d]->valid_cells_global <= graph_cells_) { graph_from_ = d; break; }
     sync();
     finalized = true;
+    if (mp_mode_ == 1) mp_setup();
 }
 
 // The hierarchy from `depth` on, replicated on every rank (see solver.h).  lev[depth] stays as the sharded
@@ -916,6 +922,7 @@ void PressureSolver::refresh_metric()
             lev[d]->refresh_params();
         }
     drop_graphs();   // captured launches carry the old StencilParams and tile tables in their arguments
+    if (mp_K_ > 0) mp_convert_metric();   // the fp32 copies of a mixed-precision cycle (the uniform flags may have changed)
     sync();
     if (timing)
         fprintf(stderr, "[somar timing] metric refresh %lld cells: coarse depths %.3f s, flags + tiles %.3f s, volumes + probes %.3f s\n",
@@ -1713,6 +1720,10 @@ void PressureSolver::fill_hash(int d, double* f, unsigned long long seed)
 void PressureSolver::vcycle(double* e, const double* res, bool e_zero)
 {
     check_idle("vcycle");
+    if (mp_K_ > 0) {
+        vcycle_mixed(e, res, e_zero, false);
+        return;
+    }
     cycle(0, e, res, e_zero);
 }
 
@@ -2061,6 +2072,214 @@ bool PressureSolver::graph_cycle(int d, double* corr, const double* res, bool co
     if (lev[D - 1]->domain.numPts() != 1) bottom_solve(f_corr[D - 1], f_res[D - 1]);
     SOMAR_HIP(hipGraphLaunch(cg_.up, st_));
     return true;
+}
+
+// ------------------------------------------------------------------------------------
+// Opt-in mixed precision (NOT the reference's arithmetic).  solve() is a defect-correction loop: the cycle only has to
+// produce an approximate correction of the fp64 residual, which the loop then measures in fp64 again.  Depths 0 .. K-1 run
+// the fold path of the cycle (fused sweeps, residual + restriction in one pass, prolongation folded into the first
+// post-smoothing sweep) on fp32 fields and fp32 copies of the metric: half the bytes of those HBM-bound kernels.  Depth K and
+// below run the fp64 code unchanged (graph replay, bottom solver); at the seam the restricted residual is converted to fp64
+// and depth K's correction back to fp32.  Sums (zero-average means, fold sums) read fp32 and accumulate in fp64.
+// ------------------------------------------------------------------------------------
+std::string PressureSolver::mixed_refusal() const
+{
+    if (amr_member_) return "a level of an AMR hierarchy (the composite cycle runs in fp64)";
+    if (full_) return "a non-diagonal metric (19-point operator)";
+    if (prm.relaxMode != RELAX_LEVEL_GSRB) return "a relax_mode other than LevelGSRB";
+    if (prm.numMG != 1) return "num_mg != 1 (W- and F-cycles run plain passes, no folding)";
+    if (comm_->size > 1) return "more than one rank (no fp32 message plans)";
+    if (hasCF_ || !forcedRatios.empty()) return "a level with coarse-fine boundaries";
+    return "";
+}
+
+void PressureSolver::set_precision(int mode, long long min_cells)
+{
+    check_idle("set_precision");
+    SOMAR_CHECK(mode == 0 || mode == 1, "set_precision: mode is 0 (fp64) or 1 (mixed: fp32 cycle on the large depths)");
+    if (mode == 1) {
+        const std::string why = mixed_refusal();
+        SOMAR_CHECK(why.empty(), "set_precision: mixed precision is not available for " + why);
+    }
+    mp_mode_ = mode;
+    mp_min_cells_ = min_cells;
+    if (finalized) mp_setup();
+}
+
+void PressureSolver::mp_free()
+{
+    if (f32_.empty()) return;
+    if (st_) hipStreamSynchronize(st_);
+    for (Depth32& z : f32_) {
+        for (float* f : z.jg) hipFree(f);
+        hipFree(z.jinv);
+        hipFree(z.corr);
+        hipFree(z.res);
+        hipFree(z.pp);
+    }
+    f32_.clear();
+    mp_K_ = 0;
+}
+
+void PressureSolver::mp_setup()
+{
+    mp_free();
+    drop_graphs();
+    if (mp_mode_ != 1) return;
+    static const bool no_fold = getenv("SOMAR_NO_FOLD_PROLONG") != nullptr;   // (fold_prolong's A/B switch)
+    const long long minc = mp_min_cells_ > 0 ? mp_min_cells_ : fused_min_cells_;
+    const int D = (int)lev.size();
+    int K = 0;
+    for (int d = 0; d + 1 < D && !no_fold; ++d) {
+        const Level& L = *lev[d];
+        if (graph_from_ >= 0 && d >= graph_from_) break;   // the graph-replayed legs stay fp64
+        if (!fused_relax(d, prm.num_smooth_down) || !fused_relax(d, prm.num_smooth_up)) break;
+        if (L.valid_cells_global < minc || L.valid_cells_global < march_min_cells_ || ordered(d)) break;
+        bool r12 = true;
+        for (int q = 0; q < 3; ++q) r12 = r12 && (L.mgCrseRefRatio[q] == 1 || L.mgCrseRefRatio[q] == 2);
+        if (!r12) break;
+        K = d + 1;
+    }
+    if (K == 0) return;
+    auto alloc32 = [](long long n) {
+        float* f = nullptr;
+        SOMAR_HIP(hipMalloc(&f, (size_t)std::max(n, 1LL) * sizeof(float)));
+        SOMAR_HIP(hipMemset(f, 0, (size_t)std::max(n, 1LL) * sizeof(float)));
+        return f;
+    };
+    f32_.assign(K + 1, Depth32());
+    for (int d = 0; d <= K; ++d) {
+        const long long n = lev[d]->field_elems;
+        f32_[d].corr = alloc32(n);
+        f32_[d].res = alloc32(n);
+        if (d < K) f32_[d].pp = alloc32(n);
+    }
+    SOMAR_HIP(hipDeviceSynchronize());   // null-stream memsets vs the solver's non-blocking stream
+    mp_K_ = K;
+    mp_convert_metric();
+    sync();
+}
+
+void PressureSolver::mp_convert_metric()
+{
+    for (int d = 0; d < mp_K_; ++d) {
+        Level& L = *lev[d];
+        Depth32& z = f32_[d];
+        // no copy only where neither kernel reads the arrays: k_resid_march takes StencilParams::uc on every uniform depth, the
+        // fused sweep only where its launcher picks the uniform-metric table (not with Dirichlet sides, not in the 8-row form)
+        if (L.dev.P.uniform && fused_uniform_kernel(L.dev)) continue;
+        const long long n = L.field_elems;
+        for (int a = 0; a < 3; ++a)
+            if (!z.jg[a]) SOMAR_HIP(hipMalloc(&z.jg[a], (size_t)n * sizeof(float)));
+        if (!z.jinv) SOMAR_HIP(hipMalloc(&z.jinv, (size_t)n * sizeof(float)));
+        float* const dst[4] = {z.jg[0], z.jg[1], z.jg[2], z.jinv};
+        const double* const src[4] = {L.dev.jg[0], L.dev.jg[1], L.dev.jg[2], L.dev.jinv};
+        launch_convert(st_, dst, src, n);
+    }
+}
+
+MetricPtrs<float> PressureSolver::mp_metric(int d) const
+{
+    const Depth32& z = f32_[d];
+    return MetricPtrs<float>{{z.jg[0], z.jg[1], z.jg[2]}, z.jinv};
+}
+
+// one rank (mixed_refusal): the exchange is the box-to-box copies alone
+void PressureSolver::xchg32(const Level& L, float* f)
+{
+    launch_copy_items(st_, L.dev, L.d_local_items, (int)L.plan.local.size(), f);
+}
+
+// relax() on its fused path
+void PressureSolver::relax32(int d, float* e, const float* res, int iters, bool e_zero, const double* e_shift,
+                             const Level* e_plus_level, const float* e_plus)
+{
+    Level& L = *lev[d];
+    static const bool no_zero_start = getenv("SOMAR_NO_ZERO_START") != nullptr;
+    if (e_zero && no_zero_start) {
+        launch_set(st_, e, L.field_elems, 0.0f);
+        e_zero = false;
+    }
+    xchg32(L, const_cast<float*>(res));
+    float* cur = e;
+    float* alt = f32_[d].pp;
+    for (int it = 0; it < iters; ++it) {
+        const bool zin = e_zero && it == 0;
+        int mode = 0;
+        if (zin) mode = 1;
+        else if (it == 0 && e_plus) mode = e_shift ? 4 : 3;
+        else if (it == 0 && e_shift) mode = 2;
+        if (!zin) xchg32(L, cur);
+        if (profiling_ && d == 0) prof_begin(0);
+        launch_gsrb_fused(st_, L.d_ftiles, L.nftiles, L.dev, mp_metric(d), alt, cur, res, mode, e_shift,
+                          e_plus_level ? &e_plus_level->dev : nullptr, e_plus, L.mgCrseRefRatio);
+        if (profiling_ && d == 0) prof_end(0);
+        std::swap(cur, alt);
+    }
+    if (cur != e) launch_copy(st_, e, cur, L.field_elems);
+}
+
+// restrict_residual() on its marching path, with the fine half of the folded prolongation's mean
+void PressureSolver::restrict32(int d, float* resCoarse, float* phiFine, const float* rhsFine)
+{
+    Level& F = *lev[d];
+    const bool want = F.zeroAvg;   // (never an ordered level)
+    xchg32(F, phiFine);
+    if (diri_) launch_ghost_ops(st_, F.dev, d_diri_ops_[d], n_diri_ops_[d], phiFine);   // homogeneous Dirichlet ghosts
+    if (profiling_ && d == 0) prof_begin(1);
+    launch_resid_restrict(st_, F.d_rtiles, F.nrtiles, F.dev, mp_metric(d), lev[d + 1]->dev, resCoarse, phiFine, rhsFine,
+                          F.mgCrseRefRatio, F.dxProduct, want ? d_partials : nullptr);
+    if (profiling_ && d == 0) prof_end(1);
+    if (want) launch_sum_partials(st_, d_partials, F.nrtiles, d_fold + 8 * d);
+    sf_valid_[d] = want ? 1 : 0;
+}
+
+// cycle_up() on its fold path: the coarse correction (fp32) read by the first post-smoothing sweep
+void PressureSolver::cycle_up32(int d, float* corr, const float* res)
+{
+    Level& F = *lev[d];
+    Level& C = *lev[d + 1];
+    float* cc = f32_[d + 1].corr;
+    if (d + 1 < mp_K_) xchg32(C, cc);   // (at the seam the fp64 correction was exchanged before its conversion)
+    const double* shift = nullptr;
+    if (F.zeroAvg) {
+        double* s = d_fold + 8 * d;
+        launch_reduce(st_, C.dev, cc, f_W[d + 1], 0, d_partials, s + 1);
+        launch_combine_sums(st_, s + 3, s, s + 1, s + 2);
+        shift = s + 3;
+    }
+    relax32(d, corr, res, prm.num_smooth_up, false, shift, &C, cc);
+}
+
+void PressureSolver::cycle32(int d, float* corr, const float* res, bool corr_zero)
+{
+    relax32(d, corr, res, prm.num_smooth_down, corr_zero, nullptr, nullptr, nullptr);
+    float* rc = f32_[d + 1].res;
+    restrict32(d, rc, corr, res);
+    if (d + 1 < mp_K_) {
+        cycle32(d + 1, f32_[d + 1].corr, rc, true);
+    } else {
+        // the seam: depth K runs the fp64 cycle on the converted residual; its exchanged correction comes back in fp32
+        const int K = d + 1;
+        const long long n = lev[K]->field_elems;
+        launch_convert(st_, f_res[K], rc, n);
+        cycle(K, f_corr[K], f_res[K], true);
+        xchg(*lev[K], f_corr[K]);
+        launch_convert(st_, f32_[K].corr, f_corr[K], n);
+    }
+    cycle_up32(d, corr, res);
+}
+
+// e (fp64, depth 0) := the fp32 cycle's correction of res, or (add_to_phi) e += it
+void PressureSolver::vcycle_mixed(double* e, const double* res, bool e_zero, bool add_to_phi)
+{
+    const long long n = lev[0]->field_elems;
+    Depth32& z = f32_[0];
+    launch_convert(st_, z.res, res, n);
+    if (!e_zero) launch_convert(st_, z.corr, e, n);
+    cycle32(0, z.corr, z.res, e_zero);
+    if (add_to_phi) launch_incr(st_, e, z.corr, 1.0, n);
+    else launch_convert(st_, e, z.corr, n);
 }
 
 bool PressureSolver::fold_prolong(int d) const
@@ -2463,8 +2682,12 @@ void PressureSolver::solve(bool zeroPhi, bool forceHomogeneous, SolveStats& s)
     bool goHang = iter < prm.imin || rnorm < (1 - prm.hang) * norm_last;
     while (goIter && goRedu && goHang && goNorm) {
         norm_last = rnorm;
-        vcycle(f_uberCorr, f_uberRes, true);          // uberCorrection is zero here (setToZero, :1203)
-        launch_incr(st_, f_phi, f_uberCorr, 1.0, n);   // postVCycleOps, :1189-1215
+        if (mp_K_ > 0) {
+            vcycle_mixed(f_phi, f_uberRes, true, true);   // the fp32 correction from zero, phi += (double)corr in one pass
+        } else {
+            vcycle(f_uberCorr, f_uberRes, true);          // uberCorrection is zero here (setToZero, :1203)
+            launch_incr(st_, f_phi, f_uberCorr, 1.0, n);   // postVCycleOps, :1189-1215
+        }
         residual(0, f_uberRes, f_phi, f_rhs, forceHomogeneous);
         rnorm = norm(0, f_uberRes, 0);
         ++iter;

@@ -67,7 +67,8 @@ public:
     // (ExtrapolationUtils.cpp:388-420), 1 = ExtrapolateFaceAndCopy(phi, phi, FAB & domain, vertical dir, lo then hi, order 2)
     // (levelVertHorizGradient, LevelLepticSolver.cpp:1107-1176); run on depth 0, in place on phi
     void run_aux_program(int which, double* phi);
-    void set_amr_member() { amr_member_ = true; }  // a level of an AMRSolver hierarchy (whose reflux tables carry beta)
+    void set_amr_member() { amr_member_ = true; }
+    bool amr_member() const { return amr_member_; }  // a level of an AMRSolver hierarchy (whose reflux tables carry beta)
     void finalize();  // builds the semicoarsened hierarchy, coarse metrics, lapDiag, null-space probes
     // ---- metric refresh of a finalized solver (the implicit-gravity projector's per-step AlteredMetric, AMRNavierStokes-
     // AdvancePPMIG.cpp:331-342): between begin and end the set_metric_* producers write the depth-0 arrays in place; end
@@ -178,6 +179,15 @@ public:
     const double* prolong_increment(int d, double* phiFine, const double* corrCoarse, bool defer_mean = false);
     void pre_cond(int d, double* phi, const double* rhs);
     void vcycle(double* e, const double* res, bool e_zero = false);  // MappedMultiGrid::oneCycle
+    // ---- opt-in mixed precision (NOT the reference's arithmetic, which is fp64 throughout) -------------------------------
+    // mode 0: fp64 (the default).  mode 1: the V-cycle's leading depths run in fp32 -- depth d does when the fused sweep runs
+    // there (fused_relax) and it has at least min_cells cells (<= 0: the fused sweep's own threshold); the rest of the cycle,
+    // the residuals and phi stay fp64, so the outer defect-correction loop still drives the fp64 residual.  Before or after
+    // finalize (after: allocates the fp32 copies, converts the metric, drops the graphs); refused while a metric update is
+    // open and where the fp32 path does not reach (mixed_refusal)
+    void set_precision(int mode, long long min_cells);
+    int precision_mode() const { return mp_mode_; }
+    int fp32_depths() const { return mp_K_; }
     // MG ratios imposed on the first depths (set before finalize): the coarsening pattern of the mini V-cycle of a
     // level refined by more than 2 (MappedAMRMultiGrid.H:1455-1482), and that mini V-cycle itself (:742-754)
     std::vector<std::array<int, 3>> forcedRatios;
@@ -240,6 +250,28 @@ public:
 
 private:
     void cycle(int d, double* corr, const double* res, bool corr_zero = false);
+    // ---- mixed precision: the fold path of the cycle (cycle_down / restrict_residual / cycle_up / relax) on fp32 fields ----
+    struct Depth32 {
+        float* jg[3] = {nullptr, nullptr, nullptr};   // fp32 copies of the metric (not made where the depth is uniform)
+        float* jinv = nullptr;
+        float *corr = nullptr, *res = nullptr, *pp = nullptr;   // correction, residual, ping-pong buffer (depth K: corr, res only)
+    };
+    int mp_mode_ = 0;
+    long long mp_min_cells_ = 0;
+    int mp_K_ = 0;                  // depths 0 .. mp_K_ - 1 run in fp32
+    std::vector<Depth32> f32_;      // mp_K_ + 1 entries once set up
+    std::string mixed_refusal() const;   // why mode 1 is not available here ("" = it is)
+    void mp_setup();                // after finalize: K, buffers, metric copies
+    void mp_free();
+    void mp_convert_metric();       // one launch per fp32 depth (finalize, set_precision, metric refresh)
+    MetricPtrs<float> mp_metric(int d) const;
+    void xchg32(const Level& L, float* f);
+    void cycle32(int d, float* corr, const float* res, bool corr_zero);
+    void relax32(int d, float* e, const float* res, int iters, bool e_zero, const double* e_shift, const Level* e_plus_level,
+                 const float* e_plus);
+    void restrict32(int d, float* resCoarse, float* phiFine, const float* rhsFine);
+    void cycle_up32(int d, float* corr, const float* res);
+    void vcycle_mixed(double* e, const double* res, bool e_zero, bool add_to_phi);
     double fetch_scalar(int slot);
     void fetch_scalars(int slot, int n);
     unsigned long long fetch_seq_ = 0;

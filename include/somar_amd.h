@@ -653,8 +653,10 @@ int somar_solver_metric_download(somar_solver_t* s, int depth, int which, int pa
  *    prefix 0 .. K-1.  Depth K and everything below it run the fp64 code unchanged.  The solve's outer loop (solve, the
  *    projections, the heat steps) still computes and tests the fp64 residual and adds the fp32 correction to the fp64 phi,
  *    so it reaches fp64 tolerances; each correction carries a relative error of about 1e-7, far below the cycle's own
- *    contraction.  somar_vcycle / somar_vcycle_from_zero follow the mode; their fields stay fp64.  With K == 0, mode 1
- *    computes exactly what mode 0 does.
+ *    contraction.  The fp32 cycle works on the residual normalized by a power of two (its max norm scaled into [1, 2), the
+ *    correction scaled back exactly), so mode 1 has fp64's range: rhs * 2^k gives phi * 2^k bit for bit, in both modes.
+ *    somar_vcycle / somar_vcycle_from_zero follow the mode (they take the max norm of the residual, and of a non-zero
+ *    correction, for the scale); their fields stay fp64.  With K == 0, mode 1 computes exactly what mode 0 does.
  *  Before or after finalize; after it, the fp32 buffers are allocated, the metric is converted and captured graphs are
  *  dropped (a metric refresh regenerates the fp32 copies).  Refused while a metric update is open, and for mode 1 (here or at
  *  finalize) on a level of an AMR hierarchy, a non-diagonal (19-point) metric, relax_mode other than LevelGSRB, num_mg != 1,

@@ -138,8 +138,8 @@ void launch_incr(hipStream_t st, double* y, const double* x, double a, long long
 void launch_incr(hipStream_t st, double* y, const float* x, double a, long long n);   // y += a * (double)x
 // mixed-precision boundary: n values converted, one launch for up to four arrays (dst[q] = src[q]; null pairs are skipped)
 void launch_convert(hipStream_t st, float* const dst[4], const double* const src[4], long long n);
-void launch_convert(hipStream_t st, double* dst, const float* src, long long n);
-void launch_convert(hipStream_t st, float* dst, const double* src, long long n);
+void launch_convert(hipStream_t st, double* dst, const float* src, long long n, double scale = 1.0);   // dst = scale * src
+void launch_convert(hipStream_t st, float* dst, const double* src, long long n, double scale = 1.0);
 void launch_incr2(hipStream_t st, double* y1, const double* x1, double a1, double* y2, const double* x2, double a2, long long n);
 void launch_bicg_p(hipStream_t st, double* p, const double* v, const double* r, double beta, double bw, long long n);  // p = (p*beta + bw*v) + r
 void launch_incr_copy(hipStream_t st, double* y, double* x, double a, long long n);  // y += a*x; x = y

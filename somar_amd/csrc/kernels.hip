@@ -624,14 +624,15 @@ __global__ void k_copy(T* __restrict__ d, const T* __restrict__ s, long long n)
 // mixed-precision boundary: dst[q] = src[q] converted, for the pairs q < blockIdx.y's range that are set (grid.y = 4)
 template <class TD, class TS>
 struct ConvertArgs { TD* dst[4]; const TS* src[4]; };
+// dst = (TD)(scale * src), the product in fp64: with a power-of-two scale it is exact, so only the conversion rounds
 template <class TD, class TS>
-__global__ void k_convert(ConvertArgs<TD, TS> A, long long n)
+__global__ void k_convert(ConvertArgs<TD, TS> A, long long n, double scale)
 {
     TD* __restrict__ d = A.dst[blockIdx.y];
     const TS* __restrict__ s = A.src[blockIdx.y];
     if (!d) return;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        d[i] = (TD)s[i];
+        d[i] = (TD)((double)s[i] * scale);
 }
 // y += a*x (x in fp64, or the fp32 correction of a mixed-precision cycle, taken to double first)
 template <class TX = double>
@@ -1150,17 +1151,17 @@ void launch_convert(hipStream_t st, float* const dst[4], const double* const src
 {
     ConvertArgs<float, double> A;
     for (int q = 0; q < 4; ++q) { A.dst[q] = dst[q]; A.src[q] = src[q]; }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_convert<float, double>), dim3(flat_grid(n), 4), dim3(256), 0, st, A, n);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_convert<float, double>), dim3(flat_grid(n), 4), dim3(256), 0, st, A, n, 1.0);
 }
-void launch_convert(hipStream_t st, float* dst, const double* src, long long n)
+void launch_convert(hipStream_t st, float* dst, const double* src, long long n, double scale)
 {
     ConvertArgs<float, double> A = {{dst, nullptr, nullptr, nullptr}, {src, nullptr, nullptr, nullptr}};
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_convert<float, double>), dim3(flat_grid(n), 1), dim3(256), 0, st, A, n);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_convert<float, double>), dim3(flat_grid(n), 1), dim3(256), 0, st, A, n, scale);
 }
-void launch_convert(hipStream_t st, double* dst, const float* src, long long n)
+void launch_convert(hipStream_t st, double* dst, const float* src, long long n, double scale)
 {
     ConvertArgs<double, float> A = {{dst, nullptr, nullptr, nullptr}, {src, nullptr, nullptr, nullptr}};
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_convert<double, float>), dim3(flat_grid(n), 1), dim3(256), 0, st, A, n);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_convert<double, float>), dim3(flat_grid(n), 1), dim3(256), 0, st, A, n, scale);
 }
 __global__ void k_publish(const double* __restrict__ src, int n, double* host_dst, unsigned long long* host_seq,
                           unsigned long long seq)

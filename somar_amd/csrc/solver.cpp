@@ -1721,7 +1721,9 @@ void PressureSolver::vcycle(double* e, const double* res, bool e_zero)
 {
     check_idle("vcycle");
     if (mp_K_ > 0) {
-        vcycle_mixed(e, res, e_zero, false);
+        double rnorm = norm(0, res, 0);
+        if (!e_zero) rnorm = std::max(rnorm, norm(0, e, 0));
+        vcycle_mixed(e, res, rnorm, e_zero, false);
         return;
     }
     cycle(0, e, res, e_zero);
@@ -2270,16 +2272,29 @@ void PressureSolver::cycle32(int d, float* corr, const float* res, bool corr_zer
     cycle_up32(d, corr, res);
 }
 
-// e (fp64, depth 0) := the fp32 cycle's correction of res, or (add_to_phi) e += it
-void PressureSolver::vcycle_mixed(double* e, const double* res, bool e_zero, bool add_to_phi)
+// e (fp64, depth 0) := the fp32 cycle's correction of res, or (add_to_phi) e += it.  rnorm: the max norm of res (and of an
+// e that is not zero).  The cycle is linear, so it runs on res * s with s = 2^-ilogb(rnorm): the fp32 fields then hold values
+// of order one whatever the scale of the problem (fp32 alone would flush corrections below 2^-149 to zero and overflow above
+// 2^128), and every scaling is by a power of two, so it is exact and the mixed solve is as scale-equivariant as the fp64 one.
+// The bottom solver of the fp64 seam compares its residual with bottom_metric in absolute terms: it is scaled alike.
+void PressureSolver::vcycle_mixed(double* e, const double* res, double rnorm, bool e_zero, bool add_to_phi)
 {
     const long long n = lev[0]->field_elems;
+    if (rnorm == 0.0) {   // a zero residual (and correction): the correction is zero
+        if (!add_to_phi && e_zero) launch_set(st_, e, n, 0.0);
+        return;
+    }
+    const int ex = std::isfinite(rnorm) ? std::min(std::max(-std::ilogb(rnorm), -1022), 1022) : 0;   // (s, 1 / s normal)
+    const double s = std::ldexp(1.0, ex), inv = std::ldexp(1.0, -ex);
+    const double bm = bottom_metric;
+    bottom_metric = bm * s;
     Depth32& z = f32_[0];
-    launch_convert(st_, z.res, res, n);
-    if (!e_zero) launch_convert(st_, z.corr, e, n);
+    launch_convert(st_, z.res, res, n, s);
+    if (!e_zero) launch_convert(st_, z.corr, e, n, s);
     cycle32(0, z.corr, z.res, e_zero);
-    if (add_to_phi) launch_incr(st_, e, z.corr, 1.0, n);
-    else launch_convert(st_, e, z.corr, n);
+    if (add_to_phi) launch_incr(st_, e, z.corr, inv, n);
+    else launch_convert(st_, e, z.corr, n, inv);
+    bottom_metric = bm;
 }
 
 bool PressureSolver::fold_prolong(int d) const
@@ -2683,7 +2698,7 @@ void PressureSolver::solve(bool zeroPhi, bool forceHomogeneous, SolveStats& s)
     while (goIter && goRedu && goHang && goNorm) {
         norm_last = rnorm;
         if (mp_K_ > 0) {
-            vcycle_mixed(f_phi, f_uberRes, true, true);   // the fp32 correction from zero, phi += (double)corr in one pass
+            vcycle_mixed(f_phi, f_uberRes, rnorm, true, true);   // the fp32 correction from zero, phi += (double)corr in one pass
         } else {
             vcycle(f_uberCorr, f_uberRes, true);          // uberCorrection is zero here (setToZero, :1203)
             launch_incr(st_, f_phi, f_uberCorr, 1.0, n);   // postVCycleOps, :1189-1215

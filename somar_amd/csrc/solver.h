@@ -271,7 +271,7 @@ private:
                  const float* e_plus);
     void restrict32(int d, float* resCoarse, float* phiFine, const float* rhsFine);
     void cycle_up32(int d, float* corr, const float* res);
-    void vcycle_mixed(double* e, const double* res, bool e_zero, bool add_to_phi);
+    void vcycle_mixed(double* e, const double* res, double rnorm, bool e_zero, bool add_to_phi);
     double fetch_scalar(int slot);
     void fetch_scalars(int slot, int n);
     unsigned long long fetch_seq_ = 0;

@@ -1132,7 +1132,10 @@ void AMRSolver::vcycle(double* const* uberCorr, double* const* uberRes, int ilev
     if (l_max == l_base) {
         S[l_base]->vcycle(uberCorr[ilev], uberRes[ilev]);
     } else if (ilev == l_base) {
-        S[l_base]->vcycle(corr_[ilev], res_[ilev], true);  // m_correction was set to zero above
+        // m_correction[l_base] is zero on the first visit only: with numMG > 1 the parent zeroes it once before its loop
+        // and every later oneCycle continues from the previous visit's correction (MappedAMRMultiGrid.H:1528, 1552)
+        S[l_base]->vcycle(corr_[ilev], res_[ilev], visits_[l_base] == 0);
+        ++visits_[l_base];
         launch_incr(st_, uberCorr[ilev], corr_[ilev], 1.0, n);
     } else {
         if (lean) {

@@ -296,3 +296,85 @@ def test_nondiagonal_composite_operator_is_conservative_on_a_one_box_coarse_leve
             for i, gg in enumerate(Lv.grids):
                 tot += float((r[i].view(gg)[..., 0] / Lv.Jinv[i].view(gg)[..., 0]).sum()) * float(np.prod(Lv.dx[:ndim]))
         assert abs(tot) < 1e-12 * max(so.ld_norm(r, 0) for r in res), (ndim, ratios, tot)
+
+
+def _valid_copy(ld):
+    return [np.array(f.view(g)[..., 0]) for g, f in zip(ld.grids, ld.fabs)]
+
+
+def _amr_w_cycle(so, am, layout, numMG, zero_every_base_visit=False):
+    """one AMRVCycle of `layout` with numMG recursions per level; records (level, correction at entry, correction at exit)
+    for every visit of the base level's oneCycle and of the down-sweep relaxation of the levels above it"""
+    levels, comp = _composite(so, am, layout)
+    lmax = len(levels) - 1
+    comp.numMG = numMG
+    phi = [so.LevelData(L.grids, 1, (1, 1, 1)) for L in levels]
+    res = [so.random_field(L.grids, 70 + l, (0, 0, 0), L.domain.box) for l, L in enumerate(levels)]
+    for l in range(lmax):
+        comp.zero_covered(l, res[l])
+    comp.init(phi, res, lmax, 0)
+    comp.set_bottom_solver(lmax, 0)
+    visits = []
+    base_cycle = comp.mg[0].one_cycle
+    level_relax = comp.relax
+
+    def one_cycle(e, r):
+        assert e is comp.m_correction[0]
+        if zero_every_base_visit:
+            so.ld_set(e, 0.0)
+        entry = _valid_copy(e)
+        base_cycle(e, r)
+        visits.append((0, entry, _valid_copy(e)))
+
+    def relax(l, corr, r, n):
+        if corr is not comp.m_correction[l]:      # the up-sweep's dCorr (set to zero right before, :1570-1571)
+            return level_relax(l, corr, r, n)
+        entry = _valid_copy(corr)
+        level_relax(l, corr, r, n)
+        visits.append((l, entry, None))
+
+    comp.mg[0].one_cycle = one_cycle
+    comp.relax = relax
+    inner = comp.amr_vcycle
+
+    def amr_vcycle(uc, ur, ilev, l_max, l_base):
+        inner(uc, ur, ilev, l_max, l_base)
+        if ilev not in (l_base, l_max):   # the level's correction when its visit ends (after its up-sweep)
+            visits.append((-ilev, None, _valid_copy(comp.m_correction[ilev])))
+
+    comp.amr_vcycle = amr_vcycle
+    corr = [so.LevelData(L.grids, 1, (1, 1, 1)) for L in levels]
+    comp.amr_vcycle(corr, res, lmax, lmax, 0)
+    return visits, [_valid_copy(c) for c in corr]
+
+
+@pytest.mark.parametrize("layout", [LAYOUTS[0], LAYOUTS[3]])
+def test_amr_w_cycle_base_level_continues_from_its_previous_visit(oracle, am, layout):
+    """numMG = 2 (every shipped input deck's AMRMG.numMG documents 2 = W-cycle): AMRVCycle zeroes m_correction[ilev - 1] ONCE
+    before its numMG recursions (MappedAMRMultiGrid.H:1528, 1552-1554); the base level's oneCycle (:1517) then runs on
+    m_correction[l_base] as it stands -- zeros on the first visit, the first visit's result on the second.  Likewise the
+    down-sweep relaxation of an intermediate level (:1522) on its second visit starts from that level's correction as its
+    first visit left it.  Restarting every base visit from zero instead changes the cycle's result by O(1)."""
+    so = oracle
+    visits, got = _amr_w_cycle(so, am, layout, 2)
+    lmax = len(layout[1])
+    base = [(e, x) for l, e, x in visits if l == 0]
+    assert len(base) == 2 ** lmax
+    for k, (entry, _) in enumerate(base):
+        if k % 2 == 0:       # first visit after the parent's setToZero
+            assert all(not a.any() for a in entry)
+        else:                # continues from the visit before it, bit for bit
+            assert any(a.any() for a in entry)
+            for a, b in zip(entry, base[k - 1][1]):
+                np.testing.assert_array_equal(a, b)
+    if lmax == 2:
+        # level 1: down-sweep entries (1, entry, None) and visit ends (-1, None, exit), in order
+        lv1 = [(l, e, x) for l, e, x in visits if abs(l) == 1]
+        assert [l for l, _, _ in lv1] == [1, -1, 1, -1]
+        assert all(not a.any() for a in lv1[0][1])
+        for a, b in zip(lv1[2][1], lv1[1][2]):
+            np.testing.assert_array_equal(a, b)
+        assert any(a.any() for a in lv1[2][1])
+    _, restarted = _amr_w_cycle(so, am, layout, 2, zero_every_base_visit=True)
+    den = max(float(np.abs(a).max()) for a in got[0])
+    assert max(float(np.abs(a - b).max()) for a, b in zip(restarted[0], got[0])) > 0.1 * den

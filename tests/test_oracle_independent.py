@@ -195,7 +195,8 @@ def sweep(L, e, rhs, count):
     return e
 
 
-def vcycle(levels, d, e, rhs, pre=2, post=2, bottom=2, singular=True):
+def vcycle(levels, d, e, rhs, pre=2, post=2, bottom=2, singular=True, cycles=1):
+    """cycles = 1: a V-cycle; cycles = 2: a W-cycle (and so on)"""
     L = levels[d]
     if d == len(levels) - 1:
         e = sweep(L, e, rhs, bottom)
@@ -205,7 +206,10 @@ def vcycle(levels, d, e, rhs, pre=2, post=2, bottom=2, singular=True):
         return e
     e = sweep(L, e, rhs, pre)
     rc = L.R @ (rhs - L.A @ e)
-    ec = vcycle(levels, d + 1, np.zeros(rc.size), rc, pre, post, bottom, singular)
+    # the coarse correction is zeroed once; every further recursion continues from the previous one's result
+    ec = np.zeros(rc.size)
+    for _ in range(cycles):
+        ec = vcycle(levels, d + 1, ec, rc, pre, post, bottom, singular, cycles)
     e = e + L.P @ ec
     if singular:
         e = e - np.dot(L.w, e) / L.w.sum()
@@ -225,6 +229,10 @@ def _one_box(so, n, periodic, L):
 
 def _diag_arrays(Jgup, Jinv):
     return [np.array(Jgup[0][d].a[..., d]) for d in range(3)], np.array(Jinv[0].a[..., 0])
+
+
+def valid_of_one(ld):
+    return ld[0].view(ld.grids[0])[..., 0]
 
 
 def _field(so, grids, arr, ghost=(1, 1, 1)):
@@ -421,6 +429,52 @@ def test_whole_vcycle_equals_the_cycle_built_from_formulas(oracle, variant):
     want = vcycle(levels, 0, np.zeros(res.size), res.ravel()).reshape(n)
     # both corrections are defined up to a constant only at the bottom; the mean removal on the way up fixes it
     assert np.abs(got - want).max() <= 1e-9 * np.abs(want).max()
+
+
+@pytest.mark.parametrize("variant", ["stretched", "cartesian"])
+@pytest.mark.parametrize("cycles", [2, 3])
+def test_whole_w_cycle_equals_the_cycle_built_from_formulas(oracle, variant, cycles):
+    """numMG = m_cycle > 1 (MappedMultiGrid.H:628-633): the coarser correction is set to zero ONCE, then `cycles` recursive
+    calls each start from the previous call's result.  Depth 1 of this 3-depth hierarchy is entered `cycles` times, the bottom
+    `cycles`**2 times -- all but the first of them from a non-zero correction."""
+    so = oracle
+    n, per, L = (16, 16, 16), (False, False, False), (1.0, 1.0, 1.0)
+    dom, grids, dx = _one_box(so, n, per, L)
+    Jgup, Jinv = so.make_diagonal_metric(grids, dx, L, 3, variant, domain=dom)
+    jg, jinv = _diag_arrays(Jgup, Jinv)
+    levels = build_hierarchy(jg, jinv, dx, per)
+    fac = so.Factory(dom, grids, dx, so.BCHolder(), Jgup, Jinv)
+    amr = so.AMRMultiGrid(fac, so.BiCGStab(eps=1e-14, reps=1e-14))
+    assert amr.mg.depth == len(levels) == 3     # an intermediate depth that is revisited
+    amr.mg.cycle_type = cycles
+    entries = []
+    inner = amr.mg.cycle
+
+    def counting(depth, correction, residual):
+        entries.append((depth, float(np.abs(valid_of_one(correction)).max())))
+        return inner(depth, correction, residual)
+
+    amr.mg.cycle = counting
+    rng = np.random.default_rng(29)
+    res = rng.uniform(-1, 1, n)
+    res -= (res / jinv).sum() / (1.0 / jinv).sum()
+    corr = so.LevelData(grids, 1, (1, 1, 1))
+    resld = _field(so, grids, res, (0, 0, 0))
+    amr.mg.init(corr, resld)
+    amr.mg.bottomSolver = so.BiCGStab(eps=1e-14, reps=1e-14)
+    amr.mg.bottomSolver.define(amr.mg.ops[-1], True)
+    amr.mg.one_cycle(corr, resld)
+    assert [d for d, _ in entries] == [0] + ([1] + [2] * cycles) * cycles
+    # every revisit of a depth within one parent visit starts from the previous visit's (non-zero) result
+    firsts = {i for i, (d, _) in enumerate(entries) if i == 0 or entries[i - 1][0] < d}
+    for i, (d, m) in enumerate(entries):
+        assert (m == 0.0) == (i in firsts), (i, d, m)
+    got = corr[0].view(grids[0])[..., 0]
+    want = vcycle(levels, 0, np.zeros(res.size), res.ravel(), cycles=cycles).reshape(n)
+    assert np.abs(got - want).max() <= 1e-9 * np.abs(want).max()
+    # and it is not the V-cycle
+    v = vcycle(levels, 0, np.zeros(res.size), res.ravel()).reshape(n)
+    assert np.abs(v - want).max() > 1e-3 * np.abs(want).max()
 
 
 @pytest.mark.parametrize("variant,lo,hi", [("stretched", 0.42, 0.44), ("cartesian", 0.064, 0.074)])

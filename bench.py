@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- pressure-Poisson V-cycles/s on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full]
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 Headline workload (config.workload): BASELINE config C2 -- single-level 512^3 Poisson (alpha=0, beta=1), homogeneous
 Neumann on all faces, "mapped-Cartesian" = separable stretched DIAGONAL metric stored as full coefficient
@@ -11,15 +11,20 @@ BiCGStab bottom solver.  A step = one MappedMultiGrid V-cycle (cycle(0)) from a 
 compatible residual, with every input already resident in HBM.  N > 1: the SAME 512^3 problem, its box
 layout sharded over N GPUs (one box per GPU, one process per GPU, halo exchange + scalar reductions over
 RCCL/xGMI) => strong scaling.  The timed loop runs the shipped code path (HIP-graph replay of the coarse depths,
-no per-kernel events); the per-kernel HIP-event numbers of the `roofline` block come from a separate, untimed,
-profiled pass of the same V-cycle.
+no per-kernel events).
 
-One JSON line on rank 0.  Besides the contract keys it carries
+One JSON line on rank 0.  A plain run sets the headline up, warms it up, times its K steps, writes --dump-outputs and
+prints the contract keys (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) with `config`; nothing else.
+--full measures and checks everything else, and its line also carries
   roofline      dominant kernel (k_gsrb_fused, depth 0): algorithmic bytes (64 B/cell per red+black sweep)
-                / HIP-event launch duration on the solver's stream, against the 8 TB/s HBM3E peak; `measured_copy_GBs`
-                = device-to-device copy bandwidth measured in this run (read + written bytes / time);
+                / HIP-event launch duration on the solver's stream, against the 8 TB/s HBM3E peak (the events come from a
+                separate, untimed, profiled pass of the headline's V-cycle, as do the `residual_*` blocks and, at N > 1,
+                `multi_gpu`); `measured_copy_GBs` = device-to-device copy bandwidth measured in this run (read + written
+                bytes / time);
                 `measured_stream_mix_GBs` = a bare kernel with the sweep's own stream mix (6 read streams + 1 write
                 stream of 512^3 doubles, no stencil, no halo; somar_diag_stream_probe) measured in this run
+  vcycle_contraction  |r1|/|r0| of one untimed headline V-cycle (at N > 1 next to
+                `vcycle_contraction_single_process_same_layout`, see below)
   cpu_baseline  the reference's V-cycle call sequence orchestrated in C over the restated Fortran kernels
                 (oracle/cpu_vcycle.c; the reference itself cannot be built here), OpenMP over k-slabs, timed on the
                 REAL 512^3 problem on all host cores given to this process and on 1 core, with the measured STREAM triad
@@ -30,12 +35,15 @@ One JSON line on rank 0.  Besides the contract keys it carries
                 1024x1024x128 LockExchange hierarchy ((2,2,1) refinements, 128^3 boxes, 940 M cells), every level's boxes
                 sharded in y-slabs over the N GPUs, ms per AMR V-cycle (MappedAMRMultiGrid::AMRVCycle, 4/4/2), measured in
                 the same run at every N
+  c5_amr        BASELINE C5's shape: 4 levels, terrain-following non-diagonal metric produced on the device, ms per AMR
+                V-cycle
+--no-cpu-baseline / --no-cartesian / --no-c4 / --no-c5 / --c4-* narrow what --full does.
 --dump-outputs DIR writes what the headline's last timed V-cycle handed its caller, the correction on the n^3 cells, as
 DIR/c2_correction.npy (float64; above DUMP_SAMPLE cells a fixed seeded sample of them), so that two builds run with the
 same arguments -- hence the same inputs -- can be compared output for output.
-The run FAILS (non-zero exit) when a timed operator does not contract, when the one-GPU contraction departs from the
-recorded value, or when an N > 1 run does not reproduce (to 1e-6) the contraction of the SAME N-box layout held by one
-process, which rank 0 computes next to its shard: a broken exchange must not produce a plausible throughput line.
+A --full run FAILS (non-zero exit) when a timed operator does not contract, when the one-GPU contraction departs from
+the recorded value, or when an N > 1 run does not reproduce (to 1e-6) the contraction of the SAME N-box layout held by
+one process, which rank 0 computes next to its shard: a broken exchange must not produce a plausible throughput line.
 """
 import argparse
 import json
@@ -354,79 +362,16 @@ def bench_c4(api, torch, dist, comm, world, steps, warmup, scale, config="c4"):
         gpu.undefine()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--n", "--size", dest="n", type=int, default=N_FINE, help="fine grid size per direction (512 = BASELINE C2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-c4", action="store_true", help="skip the c4_amr sub-record")
-    ap.add_argument("--no-cartesian", action="store_true", help="skip the c2_cartesian sub-record")
-    ap.add_argument("--no-c5", action="store_true", help="skip the c5_amr sub-record")
-    ap.add_argument("--c4-steps", type=int, default=5)
-    ap.add_argument("--c4-warmup", type=int, default=1)
-    ap.add_argument("--c4-scale", type=int, default=1, help="divide every C4 extent (rehearsals on small boxes)")
-    ap.add_argument("--dump-outputs", metavar="DIR", help="write the headline's last timed V-cycle output as DIR/*.npy")
-    args = ap.parse_args()
-    if args.steps < 1:
-        ap.error("--steps must be at least 1")
-    if args.dump_outputs and args.gpus != 1:
-        ap.error("--dump-outputs needs --gpus 1")
-
-    import torch
-    from somar_amd import api, synthetic   # the measured path never touches oracle/ (only cpu_baseline() above does)
-
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if world != args.gpus:
-        raise SystemExit("--gpus %d but WORLD_SIZE=%d (launch with torch.distributed.run for N>1)" % (args.gpus, world))
-    # SOMAR_BENCH_COMM=shm: rehearsal of the N > 1 path on a box with ONE GPU (all ranks on device 0, host-staged
-    # shared-memory transport, csrc/comm_shm.cpp).  Not a performance mode; the driver's runs use RCCL.
-    use_shm = os.environ.get("SOMAR_BENCH_COMM") == "shm"
-    torch.cuda.set_device(0 if use_shm else local_rank)
-    comm = None
-    dist = None
-    if world > 1:
-        import torch.distributed as dist
-        # control plane only (id broadcast, barrier, max over ranks); the data path is RCCL inside the library
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        if use_shm:
-            names = ["/somar_bench_%d" % os.getpid() if rank == 0 else None]
-            dist.broadcast_object_list(names, src=0)
-            comm = api.comm_create_shm(names[0], rank, world, 256 << 20)
-        else:
-            ids = [api.comm_unique_id() if rank == 0 else None]
-            dist.broadcast_object_list(ids, src=0)
-            comm = api.comm_create(ids[0], rank, world, local_rank)
-        api.comm_selftest(comm)   # all-reduce + ring exchange checked on the host before anything is timed
-
+def c2_full_record(api, synthetic, dist, world, rank, n, gpu, res_host, bandwidths, failures):
+    """--full: what the headline's line carries besides its contract keys -- per-kernel HIP events from a separate,
+    untimed, profiled pass of the same V-cycle, the roofline against `bandwidths` (copy, stream mix, read; measured before
+    the headline), and the first-cycle contraction against the recorded one-GPU value or, at N > 1, rank 0's one-process
+    twin of the same box layout.  Undefines `gpu` before the twin is built.  -> the extra keys of the line"""
     F = api
-    n = args.n
-    failures = []
-    copy_gbs = measured_copy_gbs(torch) if rank == 0 else None
-    # what this device streams for the fused sweep's own mix of streams (6 reads + 1 write, no stencil): the practical ceiling
-    mix_gbs = api.stream_probe(2, 512 ** 3, 10) if rank == 0 else None
-    read_gbs = api.stream_probe(1, 512 ** 3, 10) if rank == 0 else None
-
-    # ---------------- headline: C2, stretched diagonal metric ----------------
-    gpu, boxes, t_def = build_c2(api, synthetic, n, world, rank, comm, "stretched")
-    depth = gpu.depth()
-    ratios = [list(r) for r in gpu.mgRefRatios()]
+    copy_gbs, mix_gbs, read_gbs = bandwidths
     cells_total = n ** 3
     cells_local = cells_total // world
-    # the residual of a solve from phi = 0: std::mt19937_64(12345), uniform(-1,1), minus its J-weighted mean; generated on the host,
-    # resident in HBM before the timed region; the CPU baseline below gets the same array
-    res_host = c2_random_field(n)
-    upload_c2_residual(gpu, F, res_host)
-    dt = time_c2(gpu, F, torch, dist, args.steps, args.warmup)
-    ms_per_step = 1e3 * dt / args.steps
-    value = args.steps / dt
-    if args.dump_outputs:
-        dump_c2_outputs(gpu, F, n, args.dump_outputs)
-
-    # per-kernel HIP events: a separate profiled pass (launch by launch, events around the depth-0 kernels), NOT timed above
+    # per-kernel HIP events: a separate profiled pass (launch by launch, events around the depth-0 kernels), NOT the timed loop
     gpu.profileEnable(True)
     for _ in range(5):
         gpu.vcycleFromZero(F.F_CORR, F.F_RES)
@@ -490,14 +435,7 @@ def main():
         traffic = tj.get("k_gsrb_fused_bytes_per_launch" if fused else "k_gsrb_ortho_bytes_per_launch")
         traffic_src = tj.get("source")
     unit_t = t_sweep + t_op                       # one red+black sweep + one residual (north-star unit)
-    out = {
-        "metric": "pressure-Poisson V-cycles/sec", "value": value, "unit": "V-cycles/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "C2 single-level %d^3 Poisson, diagonal stretched metric, Neumann, LevelGSRB V-cycle "
-                               "2/2/2 + BiCGStab bottom; layout = %d box(es) %s, one per GPU"
-                               % (n, world, "x".join(str(h - l + 1) for l, h in zip(*boxes[0]))),
-                   "mg_depth": depth, "mg_ref_ratios": ratios, "cells": cells_total, "define_seconds": t_def},
+    rec = {
         "roofline": {"bound": "hbm", "kernel": kname, "achieved": achieved,
                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                      "traffic_source": "profiles/traffic.json: HBM bytes per launch of this kernel from separate rocprofv3 --pmc "
@@ -524,7 +462,7 @@ def main():
     }
     if world > 1:
         # what a scaling run is made of (rank 0's view, from the profiled pass: every launch timed, nothing overlapped)
-        out["multi_gpu"] = {
+        rec["multi_gpu"] = {
             "partition": os.environ.get("SOMAR_BENCH_PARTITION", "yz"),
             "exchange_ms_per_vcycle": ms_x / 5.0, "exchanges_per_vcycle": n_x / 5.0,
             "replicated_tail_ms_per_vcycle": ms_tail / 5.0,
@@ -532,9 +470,100 @@ def main():
                     "solver's stream in this pass; in the timed loop the fused sweeps' exchanges travel on a second stream under "
                     "their interior tiles (SOMAR_NO_OVERLAP=1 switches that off).  The replicated tail (every rank runs the depths "
                     "below 128^3 cells redundantly, one allgather in, nothing out) does not shrink with N."}
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--n", "--size", dest="n", type=int, default=N_FINE, help="fine grid size per direction (512 = BASELINE C2)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else (see the module's docstring); the options "
+                         "below narrow what --full does")
+    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-c4", action="store_true", help="skip the c4_amr sub-record")
+    ap.add_argument("--no-cartesian", action="store_true", help="skip the c2_cartesian sub-record")
+    ap.add_argument("--no-c5", action="store_true", help="skip the c5_amr sub-record")
+    ap.add_argument("--c4-steps", type=int, default=5)
+    ap.add_argument("--c4-warmup", type=int, default=1)
+    ap.add_argument("--c4-scale", type=int, default=1, help="divide every C4 extent (rehearsals on small boxes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the headline's last timed V-cycle output as DIR/*.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
+
+    import torch
+    from somar_amd import api, synthetic   # the measured path never touches oracle/ (only cpu_baseline() above does)
+
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if world != args.gpus:
+        raise SystemExit("--gpus %d but WORLD_SIZE=%d (launch with torch.distributed.run for N>1)" % (args.gpus, world))
+    # SOMAR_BENCH_COMM=shm: rehearsal of the N > 1 path on a node with ONE GPU (all ranks on device 0, host-staged
+    # shared-memory transport, csrc/comm_shm.cpp).  Not a performance mode; performance runs use RCCL.
+    use_shm = os.environ.get("SOMAR_BENCH_COMM") == "shm"
+    torch.cuda.set_device(0 if use_shm else local_rank)
+    comm = None
+    dist = None
+    if world > 1:
+        import torch.distributed as dist
+        # control plane only (id broadcast, barrier, max over ranks); the data path is RCCL inside the library
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+        if use_shm:
+            names = ["/somar_bench_%d" % os.getpid() if rank == 0 else None]
+            dist.broadcast_object_list(names, src=0)
+            comm = api.comm_create_shm(names[0], rank, world, 256 << 20)
+        else:
+            ids = [api.comm_unique_id() if rank == 0 else None]
+            dist.broadcast_object_list(ids, src=0)
+            comm = api.comm_create(ids[0], rank, world, local_rank)
+        api.comm_selftest(comm)   # all-reduce + ring exchange checked on the host before anything is timed
+
+    F = api
+    n = args.n
+    failures = []
+    copy_gbs = measured_copy_gbs(torch) if args.full and rank == 0 else None
+    # what this device streams for the fused sweep's own mix of streams (6 reads + 1 write, no stencil): the practical ceiling
+    mix_gbs = api.stream_probe(2, 512 ** 3, 10) if args.full and rank == 0 else None
+    read_gbs = api.stream_probe(1, 512 ** 3, 10) if args.full and rank == 0 else None
+
+    # ---------------- headline: C2, stretched diagonal metric ----------------
+    gpu, boxes, t_def = build_c2(api, synthetic, n, world, rank, comm, "stretched")
+    depth = gpu.depth()
+    ratios = [list(r) for r in gpu.mgRefRatios()]
+    cells_total = n ** 3
+    # the residual of a solve from phi = 0: std::mt19937_64(12345), uniform(-1,1), minus its J-weighted mean; generated on the host,
+    # resident in HBM before the timed region; the CPU baseline below gets the same array
+    res_host = c2_random_field(n)
+    upload_c2_residual(gpu, F, res_host)
+    dt = time_c2(gpu, F, torch, dist, args.steps, args.warmup)
+    ms_per_step = 1e3 * dt / args.steps
+    value = args.steps / dt
+    if args.dump_outputs:
+        dump_c2_outputs(gpu, F, n, args.dump_outputs)
+
+    out = {
+        "metric": "pressure-Poisson V-cycles/sec", "value": value, "unit": "V-cycles/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "C2 single-level %d^3 Poisson, diagonal stretched metric, Neumann, LevelGSRB V-cycle "
+                               "2/2/2 + BiCGStab bottom; layout = %d box(es) %s, one per GPU"
+                               % (n, world, "x".join(str(h - l + 1) for l, h in zip(*boxes[0]))),
+                   "mg_depth": depth, "mg_ref_ratios": ratios, "cells": cells_total, "define_seconds": t_def}}
+    if args.full:
+        out.update(c2_full_record(api, synthetic, dist, world, rank, n, gpu, res_host, (copy_gbs, mix_gbs, read_gbs),
+                                  failures))
+    else:
+        gpu.undefine()
+    del gpu
 
     # ---------------- SURVEY 8d variant (i): true Cartesian metric, the converging case ----------------
-    if not args.no_cartesian:
+    if args.full and not args.no_cartesian:
         g2, _, t_def2 = build_c2(api, synthetic, n, world, rank, comm, "cartesian")
         upload_c2_residual(g2, F, res_host)
         dt2 = time_c2(g2, F, torch, dist, args.steps, args.warmup)
@@ -548,7 +577,7 @@ def main():
         del g2
 
     # ---------------- C4: the workload of the north star's scaling target ----------------
-    if not args.no_c4:
+    if args.full and not args.no_c4:
         c4 = bench_c4(api, torch, dist, comm, world, args.c4_steps, args.c4_warmup, args.c4_scale)
         if not (0.0 < c4["amr_vcycle_contraction"] < 1.0):
             failures.append("C4 AMR V-cycle does not contract: %r" % c4["amr_vcycle_contraction"])
@@ -558,7 +587,7 @@ def main():
         out["c4_amr"] = c4
 
     # ---------------- C5's shape: 4 levels, non-diagonal terrain-following metric (19-point kernels) ----------------
-    if not args.no_c5:
+    if args.full and not args.no_c5:
         try:
             c5 = bench_c4(api, torch, dist, comm, world, args.c4_steps, args.c4_warmup, args.c4_scale, config="c5")
             if not (0.0 < c5["amr_vcycle_contraction"] < 1.0):
@@ -572,10 +601,8 @@ def main():
                 raise
             out["c5_amr"] = {"error": repr(e)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(n, res_host)
-    elif rank == 0:
-        out["cpu_baseline"] = None
+    if args.full and rank == 0:
+        out["cpu_baseline"] = cpu_baseline(n, res_host) if world == 1 and not args.no_cpu_baseline else None
     if comm is not None:
         api.comm_destroy(comm)
     if dist is not None:

@@ -7,9 +7,9 @@ tag=${1:-r03_final}
 export TMPDIR=/tmp
 o=gpurun_out
 mkdir -p $o
-python3 bench.py > $o/${tag}_bench.json 2> $o/${tag}_bench.err
+python3 bench.py --full > $o/${tag}_bench.json 2> $o/${tag}_bench.err
 rm -rf $o/prof_bench
-rocprofv3 --kernel-trace --stats -d $o/prof_bench -o bench --output-format csv -- python3 bench.py --no-c4 --no-c5 --no-cpu-baseline --no-cartesian > $o/${tag}_bench_prof.log 2>&1
+rocprofv3 --kernel-trace --stats -d $o/prof_bench -o bench --output-format csv -- python3 bench.py --full --no-c4 --no-c5 --no-cpu-baseline --no-cartesian > $o/${tag}_bench_prof.log 2>&1
 python3 tools/prof_summary.py stats $o/prof_bench $o/${tag}_c2_kernel_stats.md > /dev/null
 rm -rf $o/prof_bench
 for c in c3 c4 c5; do
@@ -30,7 +30,7 @@ rm -rf $o/pmc_FETCH_SIZE $o/pmc_WRITE_SIZE
 # the same two passes over the bench command: HBM bytes per launch of the headline kernels (profiles/traffic.json is written from this)
 for cnt in FETCH_SIZE WRITE_SIZE; do
   rm -rf $o/pmcb_$cnt
-  rocprofv3 --pmc $cnt -d $o/pmcb_$cnt -o pmc --output-format csv -- python3 bench.py --no-c4 --no-c5 --no-cpu-baseline --no-cartesian --steps 3 --warmup 1 > $o/${tag}_pmcb_$cnt.log 2>&1
+  rocprofv3 --pmc $cnt -d $o/pmcb_$cnt -o pmc --output-format csv -- python3 bench.py --full --no-c4 --no-c5 --no-cpu-baseline --no-cartesian --steps 3 --warmup 1 > $o/${tag}_pmcb_$cnt.log 2>&1
 done
 python3 tools/prof_summary.py pmc $o/pmcb_FETCH_SIZE $o/pmcb_WRITE_SIZE $o/${tag}_c2_pmc_traffic_raw.json $((512*512*512)) > /dev/null
 rm -rf $o/pmcb_FETCH_SIZE $o/pmcb_WRITE_SIZE

@@ -3,7 +3,7 @@
 # several ranks on one device), next to the one-rank run of the same reduced problem: plans, packing, agglomerated tail and
 # box-ordered sums with more than two ranks.  Not a performance run.   usage: tools/rehearse_ranks.sh [outdir]
 OUT=${1:-gpurun_out}
-A="--steps 3 --warmup 1 --size 256 --no-cpu-baseline --c4-scale 2 --c4-steps 2"
+A="--steps 3 --warmup 1 --size 256 --full --no-cpu-baseline --c4-scale 2 --c4-steps 2"
 timeout -k 10 300 python bench.py --gpus 1 $A > $OUT/n1.json 2> $OUT/n1.err
 for N in 2 4; do
     SOMAR_BENCH_COMM=shm timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \

@@ -597,7 +597,8 @@ class AMRComposite:
     """MappedAMRMultiGrid<LevelData<FArrayBox>> over several AMR levels (define :1407-1490)."""
 
     def __init__(self, levels, refRatios, bc, bottomSolver, alpha=0.0, beta=1.0, maxDepth=-1,
-                 relaxMode=so.RELAX_LEVEL_GSRB, precondIters=2, amrmg_eps=1e-6, ndim=3, isDiagonal=True):
+                 relaxMode=so.RELAX_LEVEL_GSRB, precondIters=2, amrmg_eps=1e-6, ndim=3, isDiagonal=True,
+                 precondMode=so.PRECOND_DIAG_RELAX):
         self.ndim = ndim
         self.levels, self.refRatios = levels, [_iv(r) for r in refRatios]
         n = len(levels)
@@ -618,7 +619,7 @@ class AMRComposite:
             dxCrse = levels[l - 1].dx if l > 0 else None
             fac = so.Factory(L.domain, L.grids, L.dx, bc, L.Jgup, L.Jinv, alpha=alpha, beta=beta, maxDepth=maxDepth,
                              precondIters=precondIters, relaxMode=relaxMode, amrmg_eps=amrmg_eps, dxCrse=dxCrse, cf=cf,
-                             ndim=ndim, isDiagonal=isDiagonal)
+                             ndim=ndim, isDiagonal=isDiagonal, precondMode=precondMode)
             # the mini V-cycle's coarsening pattern, MappedAMRMultiGrid.H:1455-1482
             force = None
             if l > 0:

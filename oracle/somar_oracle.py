@@ -26,6 +26,7 @@ _LIB = None
 BC_NONE, BC_NEUM, BC_DIRI = -1, 0, 1  # calculus/BCInterface/BCDescriptor.H:34-39
 
 RELAX_JACOBI, RELAX_LEVEL_GSRB, RELAX_LOOSE_GSRB, RELAX_LINE_GSRB = 0, 1, 2, 3  # utils/ProblemContext.H:322-340
+PRECOND_NONE, PRECOND_DIAG_RELAX, PRECOND_DIAG_LINE_RELAX = -1, 0, 1                # utils/ProblemContext.H:322-328
 S_MAX_COARSE = 4  # AMRElliptic/MappedAMRPoissonOp.cpp:55
 
 
@@ -687,7 +688,8 @@ class PoissonOp:
     """MappedAMRPoissonOp, AMRElliptic/MappedAMRPoissonOp.cpp."""
 
     def __init__(self, grids, domain, dx, bc, Jgup, Jinv, lapDiag, alpha, beta, isDiagonal,
-                 ndim=3, dxCrse=None, cf=None, relaxMode=RELAX_LEVEL_GSRB, precondIters=2):
+                 ndim=3, dxCrse=None, cf=None, relaxMode=RELAX_LEVEL_GSRB, precondIters=2,
+                 precondMode=PRECOND_DIAG_RELAX):
         self.grids, self.domain, self.dx, self.bc = list(grids), domain, tuple(dx), bc
         self.Jgup, self.Jinv, self.lapDiag = Jgup, Jinv, lapDiag
         self.alpha, self.beta, self.isDiagonal, self.ndim = alpha, beta, isDiagonal, ndim
@@ -707,6 +709,16 @@ class PoissonOp:
             self.relaxer = LineGSRB(self)
         else:
             raise NotImplementedError("relaxMode %d" % relaxMode)
+        # m_precondRelaxPtr, MappedAMRPoissonOpFactory.cpp:629-650: none, the level's own relaxer, or a LineGSRB of its own
+        self.precondMode = precondMode
+        if precondMode == PRECOND_NONE:
+            self.precondRelaxer = None
+        elif precondMode == PRECOND_DIAG_RELAX:
+            self.precondRelaxer = self.relaxer
+        elif precondMode == PRECOND_DIAG_LINE_RELAX:
+            self.precondRelaxer = LineGSRB(self)
+        else:
+            raise ValueError("Bad m_precondMode %d" % precondMode)
         self.zeroAvg = False
         self.dxProduct = float(np.prod(self.dx[:ndim]))
 
@@ -792,8 +804,9 @@ class PoissonOp:
         self.residual_i(lhs, phi, rhs, homogeneous)
 
     def pre_cond(self, phi, rhs):
-        """preCond (DiagRelax), MappedAMRPoissonOp.cpp:684-734."""
-        if self.precondIters == 0:
+        """preCond, MappedAMRPoissonOp.cpp:684-734: a copy when there are no iterations or precondMode is None, else the
+        diagonal scaling followed by precondIters sweeps of m_precondRelaxPtr."""
+        if self.precondIters == 0 or self.precondMode == PRECOND_NONE:
             ld_assign(phi, rhs)
             return
         for i, g in enumerate(self.grids):
@@ -801,7 +814,7 @@ class PoissonOp:
             lib().orc_diagprecond(*phi[i].fra(), *rhs[i].fran(), *self.lapDiag[i].fra1(0), lo, hi,
                                   C.c_double(self.alpha), C.c_double(self.beta))
         for _ in range(self.precondIters):
-            self.relaxer.relax(phi, rhs)
+            self.precondRelaxer.relax(phi, rhs)
 
     def relax(self, e, residual, iterations):
         """relax, MappedAMRPoissonOp.cpp:1733-1743."""
@@ -911,10 +924,12 @@ class Factory:
     """MappedAMRPoissonOpFactory (single AMR level so far): MGnewOp, Factory.cpp:363-702."""
 
     def __init__(self, domain, grids, dx, bc, Jgup, Jinv, alpha=0.0, beta=1.0, isDiagonal=True, ndim=3,
-                 maxDepth=-1, precondIters=2, relaxMode=RELAX_LEVEL_GSRB, amrmg_eps=1e-6, dxCrse=None, cf=None):
+                 maxDepth=-1, precondIters=2, relaxMode=RELAX_LEVEL_GSRB, amrmg_eps=1e-6, dxCrse=None, cf=None,
+                 precondMode=PRECOND_DIAG_RELAX):
         self.domain, self.grids, self.dx, self.bc = domain, list(grids), tuple(dx), bc
         self.alpha, self.beta, self.isDiagonal, self.ndim = alpha, beta, isDiagonal, ndim
         self.maxDepth, self.precondIters, self.relaxMode = maxDepth, precondIters, relaxMode
+        self.precondMode = precondMode
         self.amrmg_eps = amrmg_eps
         self.dxCrse, self.cf = dxCrse, cf
         self.maskedMaxCoarse = (S_MAX_COARSE, S_MAX_COARSE, S_MAX_COARSE if ndim == 3 else 1)
@@ -985,7 +1000,7 @@ class Factory:
         grids, Jgup, Jinv, lapDiag = self.metrics[depth]
         cf = self.cf.coarsen(coarsening) if self.cf is not None else None
         op = PoissonOp(grids, domain, dx, self.bc, Jgup, Jinv, lapDiag, self.alpha, self.beta, self.isDiagonal,
-                       ndim, self.dxCrse, cf, self.relaxMode, self.precondIters)
+                       ndim, self.dxCrse, cf, self.relaxMode, self.precondIters, self.precondMode)
         op.mgDepth = depth
         # null-space probe, Factory.cpp:659-693
         phi = LevelData(grids, 1, op.activeDirs)

@@ -21,15 +21,19 @@ def make_oracle_solver(so, dom, grids, dx, Jgup, Jinv, alpha=0.0, beta=1.0, pre=
 
 
 def make_gpu_solver(dom, grids, dx, Jgup, Jinv, alpha=0.0, beta=1.0, pre=2, post=2, bottom=2, maxDepth=-1,
-                    relaxMode=1, owner=None, comm=None, ndim=3, eps=None, bc_type=None, bc_values=None, numMG=None):
+                    relaxMode=1, owner=None, comm=None, ndim=3, eps=None, bc_type=None, bc_values=None, numMG=None,
+                    precondMode=None, numSmoothPrecond=None):
+    """precondMode / numSmoothPrecond None: the deck defaults (AMRMG.precondMode, AMRMG.num_smooth_precond)"""
     from somar_amd import AMRPressureSolver
     s = AMRPressureSolver()
     p = s._p
     s.setSpaceDim(ndim)
     if eps is not None:
         p.eps = eps
-    s.setAMRMGParameters(p.imin, p.imax, p.eps, maxDepth, p.num_smooth_precond, pre, post, bottom, p.precond_mode,
-                         relaxMode, p.num_mg if numMG is None else numMG, p.hang, p.norm_thresh, 0)
+    s.setAMRMGParameters(p.imin, p.imax, p.eps, maxDepth,
+                         p.num_smooth_precond if numSmoothPrecond is None else numSmoothPrecond, pre, post, bottom,
+                         p.precond_mode if precondMode is None else precondMode, relaxMode,
+                         p.num_mg if numMG is None else numMG, p.hang, p.norm_thresh, 0)
     s.define(dom.box.lo, dom.box.hi, dom.periodic, dx, [(g.lo, g.hi) for g in grids], owner=owner, alpha=alpha,
              beta=beta, comm=comm, bc_type=bc_type)
     if bc_values is not None:
@@ -103,15 +107,16 @@ def make_full_amr_levels(so, am, n, L, periodic, ratios, fine_boxes, cbox=8, ndi
 
 
 def make_gpu_amr(levels, ratios, alpha=0.0, beta=1.0, pre=2, post=2, bottom=2, maxDepth=-1, relaxMode=1, ndim=3,
-                 full=False, imin=None, imax=None, numMG=None):
+                 full=False, imin=None, imax=None, numMG=None, precondMode=None, numSmoothPrecond=None):
     """The same hierarchy (oracle AMRLevel list) on the GPU through the C ABI."""
     from somar_amd import AMRPressureSolver
     s = AMRPressureSolver()
     s.setSpaceDim(ndim)
     p = s._p
     s.setAMRMGParameters(p.imin if imin is None else imin, p.imax if imax is None else imax, p.eps, maxDepth,
-                         p.num_smooth_precond, pre, post, bottom, p.precond_mode, relaxMode, p.num_mg if numMG is None else numMG,
-                         p.hang, p.norm_thresh, 0)
+                         p.num_smooth_precond if numSmoothPrecond is None else numSmoothPrecond, pre, post, bottom,
+                         p.precond_mode if precondMode is None else precondMode, relaxMode,
+                         p.num_mg if numMG is None else numMG, p.hang, p.norm_thresh, 0)
     L0 = levels[0]
     s.defineAMR(L0.domain.box.lo, L0.domain.box.hi, L0.domain.periodic, L0.dx, ratios,
                 [[(g.lo, g.hi) for g in L.grids] for L in levels], alpha=alpha, beta=beta)

@@ -61,3 +61,25 @@ def test_header_is_plain_c(tmp_path):
     src.write_text('#include "somar_amd.h"\nint main(void) { int (*f)(void) = somar_abi_version; return f == 0; }\n')
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-fsyntax-only",
                            "-I", os.path.join(ROOT, "include"), str(src)])
+
+
+def _header_defines(prefix):
+    txt = open(os.path.join(ROOT, "include", "somar_amd.h")).read()
+    return {m[0]: int(m[1]) for m in re.findall(r"^#define\s+(%s[A-Z_]+)\s+\(?(-?\d+)\)?\s*$" % prefix, txt, flags=re.M)}
+
+
+def _solver_h_enum(first):
+    txt = open(os.path.join(ROOT, "somar_amd", "csrc", "solver.h")).read()
+    body = re.search(r"enum\s*\{\s*(%s\b[^}]*)\}" % first, txt).group(1)
+    return {k: int(v) for k, v in re.findall(r"\b([A-Z_]+)\s*=\s*(-?\d+)", body)}
+
+
+def test_relax_and_precond_codes_match_the_reference():
+    """The header's relax_mode / precond_mode codes are the ones the input files use, utils/ProblemContext.H:322-340
+    (PrecondMode: None = -1, DiagRelax = 0, DiagLineRelax = 1; RelaxMode: JACOBI = 0, LEVEL_GSRB = 1, LOOSE_GSRB = 2,
+    LINE_GSRB = 3), and the ones the solver compares against (solver.h)."""
+    reference = {"RELAX_JACOBI": 0, "RELAX_LEVEL_GSRB": 1, "RELAX_LOOSE_GSRB": 2, "RELAX_LINE_GSRB": 3,
+                 "PRECOND_NONE": -1, "PRECOND_DIAG_RELAX": 0, "PRECOND_DIAG_LINE_RELAX": 1}
+    header = {k[len("SOMAR_"):]: v for k, v in {**_header_defines("SOMAR_RELAX_"), **_header_defines("SOMAR_PRECOND_")}.items()}
+    assert header == reference
+    assert {**_solver_h_enum("RELAX_JACOBI"), **_solver_h_enum("PRECOND_NONE")} == reference

@@ -320,6 +320,31 @@ def test_restated_bicgstab_solves_the_assembled_system(oracle):
     assert np.abs(d).max() <= 1e-6 * np.abs(ref - ref.mean()).max()
 
 
+@pytest.mark.parametrize("mode", [-1, 0, 1])
+@pytest.mark.parametrize("iters", [0, 1, 3])
+def test_restated_bicgstab_solves_the_assembled_system_with_every_preconditioner(oracle, mode, iters):
+    """preCond's modes (None / DiagRelax / DiagLineRelax) and iteration counts change BiCGStab's iterates, not its answer:
+    each must satisfy the same scipy-assembled system"""
+    so = oracle
+    n, per, L = (8, 8, 8), (False, False, False), (1.0, 2.0, 0.5)
+    dom, grids, dx = _one_box(so, n, per, L)
+    Jgup, Jinv = so.make_diagonal_metric(grids, dx, L, 3, "stretched", domain=dom)
+    jg, jinv = _diag_arrays(Jgup, Jinv)
+    A = assemble_7pt(jg, jinv, dx, per)
+    op = so.Factory(dom, grids, dx, so.BCHolder(), Jgup, Jinv, maxDepth=0, precondIters=iters,
+                    precondMode=mode).mg_new_op(0, None)
+    rng = np.random.default_rng(31)
+    b = rng.uniform(-1, 1, n)
+    w = 1.0 / jinv
+    b = b - (w * b).sum() / w.sum()
+    solver = so.BiCGStab(imax=400, eps=1e-12)
+    solver.define(op, True)
+    phi = _field(so, grids, np.zeros(n))
+    solver.solve(phi, _field(so, grids, b, ghost=(0, 0, 0)))
+    x = phi[0].view(grids[0])[..., 0].ravel()
+    assert np.abs(A @ x - b.ravel()).max() <= 1e-8 * np.abs(b).max()
+
+
 def _full_arrays(Jg, Ji):
     return [np.array(Jg[0][d].a) for d in range(3)], np.array(Ji[0].a[..., 0])
 

@@ -309,3 +309,92 @@ def test_helmholtz_with_dirichlet_walls_converges_fast(oracle):
     x = so.LevelData(grids, 1, (1, 1, 1))
     amr.solve(x, b, forceHomogeneous=True)
     assert amr.exitStatus == 1 and amr.iters <= 6
+
+
+# ---- preCond's three modes (MappedAMRPoissonOp.cpp:684-734, m_precondRelaxPtr at MappedAMRPoissonOpFactory.cpp:629-650) -------
+def _precond_op(so, mode, iters, relax=1, ndim=3, alpha=0.0, beta=1.0):
+    n = (16, 16, 8) if ndim == 3 else (16, 16, 1)
+    dom = so.Domain(so.Box((0, 0, 0), tuple(a - 1 for a in n)), (False, True, False))
+    grids = so.split_domain(dom.box, (8, 8, 8) if ndim == 3 else (8, 16, 1))
+    L = (2.0, 1.0, 0.5)
+    dx = tuple(L[d] / n[d] for d in range(3))
+    Jgup, Jinv = so.make_diagonal_metric(grids, dx, L, ndim, "stretched", domain=dom)
+    fac = so.Factory(dom, grids, dx, so.BCHolder(), Jgup, Jinv, alpha=alpha, beta=beta, ndim=ndim, relaxMode=relax,
+                     precondIters=iters, precondMode=mode)
+    op = fac.mg_new_op(0, None)
+    ghost = (1, 1, 1) if ndim == 3 else (1, 1, 0)
+    rhs = so.random_field(grids, 17, (0, 0, 0), dom.box)
+    return op, grids, ghost, rhs
+
+
+def _diag_scaled(so, op, grids, ghost, rhs):
+    """DIAGPRECOND (MappedAMRPoissonOpF.ChF): phi = rhs / (alpha + beta lapDiag), written out with numpy"""
+    phi = so.LevelData(grids, 1, ghost)
+    for i, g in enumerate(grids):
+        phi[i].view(g)[...] = rhs[i].view(g) / (op.alpha + op.beta * op.lapDiag[i].view(g))
+    return phi
+
+
+def _pre_cond(so, op, grids, ghost, rhs):
+    phi = so.LevelData(grids, 1, ghost, 7.0)    # garbage start: preCond must overwrite it
+    op.pre_cond(phi, rhs)
+    return [np.array(a) for a in (f.view(g)[..., 0] for g, f in zip(grids, phi.fabs))]
+
+
+@pytest.mark.parametrize("iters", [0, 1, 3])
+def test_precond_none_copies_the_rhs(oracle, iters):
+    so = oracle
+    op, grids, ghost, rhs = _precond_op(so, so.PRECOND_NONE, iters)
+    assert op.precondRelaxer is None
+    for got, g, f in zip(_pre_cond(so, op, grids, ghost, rhs), grids, rhs.fabs):
+        np.testing.assert_array_equal(got, f.view(g)[..., 0])
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_precond_zero_iterations_copy_the_rhs_whatever_the_mode(oracle, mode):
+    so = oracle
+    op, grids, ghost, rhs = _precond_op(so, mode, 0)
+    for got, g, f in zip(_pre_cond(so, op, grids, ghost, rhs), grids, rhs.fabs):
+        np.testing.assert_array_equal(got, f.view(g)[..., 0])
+
+
+@pytest.mark.parametrize("ndim,relax,alpha,beta", [(3, 1, 0.0, 1.0), (3, 0, 1.0, -0.05), (3, 2, 0.0, 1.0), (2, 1, 0.0, 1.0)])
+@pytest.mark.parametrize("iters", [1, 3])
+def test_precond_diag_line_relax_is_diagonal_scaling_then_line_gsrb(oracle, ndim, relax, alpha, beta, iters):
+    """DiagLineRelax: DIAGPRECOND, then k sweeps of a LineGSRB of its own, whatever the level's relaxer"""
+    so = oracle
+    op, grids, ghost, rhs = _precond_op(so, so.PRECOND_DIAG_LINE_RELAX, iters, relax, ndim, alpha, beta)
+    assert isinstance(op.precondRelaxer, so.LineGSRB) and op.precondRelaxer is not op.relaxer
+    want = _diag_scaled(so, op, grids, ghost, rhs)
+    line = so.LineGSRB(op)
+    for _ in range(iters):
+        line.relax(want, rhs)
+    got = _pre_cond(so, op, grids, ghost, rhs)
+    for a, g, f in zip(got, grids, want.fabs):
+        np.testing.assert_array_equal(a, f.view(g)[..., 0])
+    # and it is not what DiagRelax gives (the level relaxer is a point smoother here)
+    op2, _, _, _ = _precond_op(so, so.PRECOND_DIAG_RELAX, iters, relax, ndim, alpha, beta)
+    other = _pre_cond(so, op2, grids, ghost, rhs)
+    assert max(float(np.abs(a - b).max()) for a, b in zip(got, other)) > 1e-6 * max(float(np.abs(a).max()) for a in got)
+
+
+@pytest.mark.parametrize("relax", [0, 1, 2, 3])
+@pytest.mark.parametrize("iters", [1, 2, 3])
+def test_precond_diag_relax_is_diagonal_scaling_then_the_level_relaxer(oracle, relax, iters):
+    """DiagRelax (the default mode): DIAGPRECOND, then k sweeps of the level's own relaxer -- as before precondMode existed"""
+    so = oracle
+    op, grids, ghost, rhs = _precond_op(so, so.PRECOND_DIAG_RELAX, iters, relax)
+    assert op.precondRelaxer is op.relaxer
+    want = _diag_scaled(so, op, grids, ghost, rhs)
+    op.relax(want, rhs, iters)
+    for a, g, f in zip(_pre_cond(so, op, grids, ghost, rhs), grids, want.fabs):
+        np.testing.assert_array_equal(a, f.view(g)[..., 0])
+
+
+def test_precond_mode_defaults_to_diag_relax(oracle):
+    so = oracle
+    dom, grids, dx, Jgup, Jinv = _setup(so, (8, 8, 8), 8, "stretched")
+    fac, op = _op(so, dom, grids, dx, Jgup, Jinv)
+    assert fac.precondMode == op.precondMode == so.PRECOND_DIAG_RELAX and op.precondRelaxer is op.relaxer
+    with pytest.raises(ValueError):
+        so.Factory(dom, grids, dx, so.BCHolder(), Jgup, Jinv, precondMode=2).mg_new_op(0, None)

@@ -230,6 +230,13 @@ int somar_bottom_kind(somar_solver_t* s, int* kind);
  * is the one that ran): out4 = {fused sweeps whose ghost exchange travelled on the second stream under their interior tiles,
  * ghost programs executed as one launch (a workgroup per box), ghost programs executed stage by stage, bottom solves} */
 int somar_solver_counters(somar_solver_t* s, long long* out4);
+/* out2 = {fp64, fp32}: the payload bytes this rank has sent so far in the ghost exchanges of this solver's levels, by the element
+ * type of the exchanged field (fp32: the leading depths of a mixed-precision cycle, somar_solver_set_precision).  Zero on one
+ * rank; reset by nothing. */
+int somar_solver_exchange_bytes(somar_solver_t* s, long long* out2);
+/* the same for ONE multigrid depth (a depth inside the replicated tail of a sharded hierarchy exchanges nothing between ranks:
+ * zeros).  The bottom solver's exchanges -- whose number follows its iteration count -- are those of the last sharded depth. */
+int somar_solver_exchange_bytes_depth(somar_solver_t* s, int depth, long long* out2);
 /* sweeps of LevelGSRB with a non-diagonal metric (GSRB.cpp:58-98 with GSRBITER3D) that ran as ONE red+black marching launch plus
  * a shell pass (levels of large boxes; csrc/full19_fused.hip) instead of two colour passes */
 int somar_solver_fused19_sweeps(somar_solver_t* s, long long* n);
@@ -661,7 +668,11 @@ int somar_solver_metric_download(somar_solver_t* s, int depth, int which, int pa
  *  Before or after finalize; after it, the fp32 buffers are allocated, the metric is converted and captured graphs are
  *  dropped (a metric refresh regenerates the fp32 copies).  Refused while a metric update is open, and for mode 1 (here or at
  *  finalize) on a level of an AMR hierarchy, a non-diagonal (19-point) metric, relax_mode other than LevelGSRB, num_mg != 1,
- *  more than one rank, and the handles of a leptic solver.
+ *  and the handles of a leptic solver.
+ *  More than one rank: the fp32 depths exchange their ghost cells in fp32 messages (4 bytes per value), so the mode, min_cells and
+ *  K are part of the message format.  On a finalized sharded solver this call is COLLECTIVE, like finalize itself: every rank
+ *  calls it, with the same mode and min_cells.  The ranks compare (mode, K, min_cells); if they differ, every rank gets an error,
+ *  and the solver is back in mode 0 on all of them.  The replicated tail, the serial-order depths and every sum stay fp64.
  * somar_solver_get_precision: the mode and K, the number of leading depths that run in fp32 (0 before finalize). */
 int somar_solver_set_precision(somar_solver_t* s, int mode, long long min_cells);
 int somar_solver_get_precision(const somar_solver_t* s, int* mode, int* fp32_depths);
@@ -708,7 +719,8 @@ int somar_comm_create(void** comm, const unsigned char* id128, int rank, int nra
  * development box -- with the same message plans.  Synchronous; not for production. */
 int somar_comm_create_shm(void** comm, const char* name, int rank, int nranks, long long outbox_bytes);
 /* Transport self-test: all-reduce (sum, max) of rank-dependent values and a ring neighbour exchange
- * (rank -> rank+1; a self send/recv on one rank), checked on the host.  Collective over the communicator. */
+ * (rank -> rank+1; a self send/recv on one rank), once with fp64 and once with fp32 payloads, checked on the host.
+ * Collective over the communicator. */
 int somar_comm_selftest(void* comm);
 int somar_comm_destroy(void* comm);
 

@@ -105,6 +105,8 @@ _SIGS = {
     "somar_bottom_solve": [_H, C.c_int, C.c_int, _PI, _PI],
     "somar_bottom_kind": [_H, _PI],
     "somar_solver_counters": [_H, C.POINTER(C.c_longlong)],
+    "somar_solver_exchange_bytes": [_H, C.POINTER(C.c_longlong)],
+    "somar_solver_exchange_bytes_depth": [_H, C.c_int, C.POINTER(C.c_longlong)],
     "somar_solver_fused19_sweeps": [_H, C.POINTER(C.c_longlong)],
     "somar_last_history": [_PD, C.c_int, _PI],
     "somar_host_fill_mt19937_64": [_PD, C.c_longlong, C.c_ulonglong, C.c_double, C.c_double],
@@ -556,7 +558,9 @@ class AMRPressureSolver:
     def setPrecision(self, mode, min_cells=0):
         """Opt-in mixed precision (NOT the reference's arithmetic): mode 0 fp64 (the default), 1 an fp32 V-cycle on the
         leading depths with at least min_cells cells (0: the fused sweep's threshold) inside the fp64 defect-correction loop.
-        Before or after finalize; see somar_solver_set_precision for what refuses it."""
+        Before or after finalize; see somar_solver_set_precision for what refuses it.  On a solver sharded over ranks the
+        call is collective once the solver is finalized: every rank makes it with the same arguments (ranks that disagree
+        all get a SomarError and stay in mode 0)."""
         _ck(lib().somar_solver_set_precision(self._h, int(mode), int(min_cells)))
 
     def precision(self):
@@ -704,6 +708,16 @@ class AMRPressureSolver:
         c = (C.c_longlong * 4)()
         _ck(lib().somar_solver_counters(self._h, c))
         return {"overlapped_sweeps": c[0], "ghost_programs_one_launch": c[1], "ghost_programs_staged": c[2], "bottom_solves": c[3]}
+
+    def exchangeBytes(self, depth=None):
+        """(fp64, fp32) payload bytes this rank has sent so far in the ghost exchanges of this solver's levels (depth: of that
+        multigrid depth alone)"""
+        c = (C.c_longlong * 2)()
+        if depth is None:
+            _ck(lib().somar_solver_exchange_bytes(self._h, c))
+        else:
+            _ck(lib().somar_solver_exchange_bytes_depth(self._h, int(depth), c))
+        return c[0], c[1]
 
     def fused19Sweeps(self):
         """19-point LevelGSRB sweeps that ran as one red+black launch plus a shell pass (levels of large boxes)"""

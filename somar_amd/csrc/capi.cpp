@@ -748,6 +748,25 @@ int somar_solver_counters(somar_solver_t* s, long long* out4)
     API_END
 }
 
+int somar_solver_exchange_bytes(somar_solver_t* s, long long* out2)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps && out2, "null argument");
+    s->ps->exchange_bytes(out2);
+    API_END
+}
+
+int somar_solver_exchange_bytes_depth(somar_solver_t* s, int depth, long long* out2)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps && out2, "null argument");
+    SOMAR_CHECK(depth >= 0 && depth < s->ps->depth(), "depth out of range");
+    const Level& L = s->ps->level(depth);
+    out2[0] = L.sent_bytes[0];
+    out2[1] = L.sent_bytes[1];
+    API_END
+}
+
 int somar_solver_fused19_sweeps(somar_solver_t* s, long long* n)
 {
     API_BEGIN
@@ -1867,7 +1886,8 @@ int somar_leptic_solve(somar_leptic_t* h, int homogeneous, somar_leptic_stats_t*
 }
 
 // Pushes real traffic through a transport: an all-reduce (sum and max) of rank-dependent values and a ring
-// neighbour exchange (rank -> rank+1; a self send/recv on one rank).  Returns an error if any value is wrong.
+// neighbour exchange (rank -> rank+1; a self send/recv on one rank), once with fp64 and once with fp32 payloads.  Returns an
+// error if any value is wrong.
 int somar_comm_selftest(void* comm)
 {
     API_BEGIN
@@ -1903,6 +1923,24 @@ int somar_comm_selftest(void* comm)
     SOMAR_HIP(hipMemcpyAsync(g.data(), d_recv, n * sizeof(double), hipMemcpyDeviceToHost, st));
     SOMAR_HIP(hipMemcpyAsync(hr, d_red, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     SOMAR_HIP(hipStreamSynchronize(st));
+    // the same ring with fp32 payloads (the halo messages of a mixed-precision cycle), through the same buffers
+    float* f_send = reinterpret_cast<float*>(d_send);
+    float* f_recv = reinterpret_cast<float*>(d_recv);
+    std::vector<float> hf(n), gf(n);
+    for (int i = 0; i < n; ++i) hf[i] = 8192.0f * c->rank + i + 0.5f;   // (exact in fp32 for up to 16 ranks)
+    SOMAR_HIP(hipMemcpyAsync(f_send, hf.data(), n * sizeof(float), hipMemcpyHostToDevice, st));
+    SOMAR_HIP(hipMemsetAsync(d_recv, 0, n * sizeof(double), st));
+    SOMAR_HIP(hipStreamSynchronize(st));
+    if (nxt == prv) {
+        c->neighbor_exchange(f_send, f_recv, {nxt}, {0}, {n}, {0}, {n}, st);
+    } else {
+        const bool nf = nxt < prv;
+        c->neighbor_exchange(f_send, f_recv, {nf ? nxt : prv, nf ? prv : nxt}, {0, 0},
+                             {nf ? (long long)n : 0, nf ? 0 : (long long)n}, {0, 0},
+                             {nf ? 0 : (long long)n, nf ? (long long)n : 0}, st);
+    }
+    SOMAR_HIP(hipMemcpyAsync(gf.data(), f_recv, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    SOMAR_HIP(hipStreamSynchronize(st));
     hipFree(d_red);
     hipFree(d_send);
     hipFree(d_recv);
@@ -1911,6 +1949,8 @@ int somar_comm_selftest(void* comm)
     SOMAR_CHECK(hr[1] == double(c->size), "comm selftest: all-reduce(max) returned a wrong value");
     for (int i = 0; i < n; ++i)
         SOMAR_CHECK(g[i] == 1000.0 * prv + i, "comm selftest: neighbour exchange delivered wrong data");
+    for (int i = 0; i < n; ++i)
+        SOMAR_CHECK(gf[i] == 8192.0f * prv + i + 0.5f, "comm selftest: fp32 neighbour exchange delivered wrong data");
     API_END
 }
 

@@ -96,6 +96,19 @@ struct RcclComm : Comm {
         }
         SOMAR_NCCL(api().GroupEnd());
     }
+    // fp32 payloads: the same grouped send / receive with ncclFloat, 4 bytes per value on the wire
+    void neighbor_exchange(const float* sendbuf, float* recvbuf, const std::vector<int>& peers,
+                           const std::vector<long long>& soff, const std::vector<long long>& scount,
+                           const std::vector<long long>& roff, const std::vector<long long>& rcount,
+                           hipStream_t st) override
+    {
+        SOMAR_NCCL(api().GroupStart());
+        for (size_t q = 0; q < peers.size(); ++q) {
+            if (scount[q]) SOMAR_NCCL(api().Send(sendbuf + soff[q], (size_t)scount[q], ncclFloat, peers[q], comm, st));
+            if (rcount[q]) SOMAR_NCCL(api().Recv(recvbuf + roff[q], (size_t)rcount[q], ncclFloat, peers[q], comm, st));
+        }
+        SOMAR_NCCL(api().GroupEnd());
+    }
 };
 
 void rccl_unique_id(unsigned char* id128)

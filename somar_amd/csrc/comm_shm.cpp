@@ -33,7 +33,7 @@ struct ShmHeader {
     // the same name left behind by an earlier run (opened before this run's rank 0 unlinks it) never answers.
     std::atomic<long long> hello[16];
     std::atomic<long long> echo[16];
-    // directory: where in src's outbox the message for dst starts, and its length (doubles)
+    // directory: where in src's outbox the message for dst starts, and its length (bytes)
     long long off[16][16];
     long long cnt[16][16];
     std::atomic<long long> seq[16][16];  // seq[src][dst]: messages src has published for dst
@@ -131,6 +131,25 @@ struct ShmComm : Comm {
                            const std::vector<long long>& roff, const std::vector<long long>& rcount,
                            hipStream_t st) override
     {
+        exchange_bytes(reinterpret_cast<const char*>(sendbuf), reinterpret_cast<char*>(recvbuf), peers, soff, scount, roff,
+                       rcount, sizeof(double), st);
+    }
+    void neighbor_exchange(const float* sendbuf, float* recvbuf, const std::vector<int>& peers,
+                           const std::vector<long long>& soff, const std::vector<long long>& scount,
+                           const std::vector<long long>& roff, const std::vector<long long>& rcount,
+                           hipStream_t st) override
+    {
+        exchange_bytes(reinterpret_cast<const char*>(sendbuf), reinterpret_cast<char*>(recvbuf), peers, soff, scount, roff,
+                       rcount, sizeof(float), st);
+    }
+
+    // offsets and counts in elements of es bytes; the directory (off, cnt) is kept in BYTES, so a peer that expects another
+    // element size ends in the count check below instead of reading half a message
+    void exchange_bytes(const char* sendbuf, char* recvbuf, const std::vector<int>& peers,
+                        const std::vector<long long>& soff, const std::vector<long long>& scount,
+                        const std::vector<long long>& roff, const std::vector<long long>& rcount, size_t es,
+                        hipStream_t st)
+    {
         // pairwise handshakes (like grouped send/recv, only the ranks in `peers` take part): publish my outbox
         // with a per-pair sequence number, consume each peer's, acknowledge.  Peer lists are symmetric: if q is
         // in my list I am in q's.
@@ -139,24 +158,25 @@ struct ShmComm : Comm {
             while (hdr->ack[rank][q].load(std::memory_order_acquire) < sent[q]) sched_yield();
         long long tot = 0;
         for (size_t q = 0; q < peers.size(); ++q) tot = std::max(tot, soff[q] + scount[q]);
-        SOMAR_CHECK((size_t)tot * sizeof(double) <= box_bytes, "shm outbox too small for this message");
+        SOMAR_CHECK((size_t)tot * es <= box_bytes, "shm outbox too small for this message");
+        char* const mine = reinterpret_cast<char*>(outbox(rank));
         if (tot) {
-            SOMAR_HIP(hipMemcpyAsync(outbox(rank), sendbuf, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, st));
+            SOMAR_HIP(hipMemcpyAsync(mine, sendbuf, (size_t)tot * es, hipMemcpyDeviceToHost, st));
             SOMAR_HIP(hipStreamSynchronize(st));
         }
         for (size_t q = 0; q < peers.size(); ++q) {
-            hdr->off[rank][peers[q]] = soff[q];
-            hdr->cnt[rank][peers[q]] = scount[q];
+            hdr->off[rank][peers[q]] = soff[q] * (long long)es;
+            hdr->cnt[rank][peers[q]] = scount[q] * (long long)es;
             hdr->seq[rank][peers[q]].store(++sent[peers[q]], std::memory_order_release);
         }
         for (size_t q = 0; q < peers.size(); ++q) {
             const int r = peers[q];
             ++got[r];
             while (hdr->seq[r][rank].load(std::memory_order_acquire) < got[r]) sched_yield();
-            SOMAR_CHECK(hdr->cnt[r][rank] == rcount[q], "shm exchange: send/receive counts disagree");
+            SOMAR_CHECK(hdr->cnt[r][rank] == rcount[q] * (long long)es, "shm exchange: send/receive counts disagree");
             if (rcount[q]) {
-                SOMAR_HIP(hipMemcpyAsync(recvbuf + roff[q], outbox(r) + hdr->off[r][rank],
-                                         (size_t)rcount[q] * sizeof(double), hipMemcpyHostToDevice, st));
+                SOMAR_HIP(hipMemcpyAsync(recvbuf + (size_t)roff[q] * es, reinterpret_cast<const char*>(outbox(r)) + hdr->off[r][rank],
+                                         (size_t)rcount[q] * es, hipMemcpyHostToDevice, st));
                 SOMAR_HIP(hipStreamSynchronize(st));  // the peer may reuse its outbox once acknowledged
             }
             hdr->ack[r][rank].store(got[r], std::memory_order_release);

@@ -127,6 +127,8 @@ void launch_copy_items(hipStream_t st, const LevelDev& L, const CopyItem* items,
 void launch_copy_items(hipStream_t st, const LevelDev& L, const CopyItem* items, int nitems, float* f);
 void launch_pack(hipStream_t st, const LevelDev& L, const CopyItem* items, const long long* bufoff, int nitems,
                  double* f, double* buf, bool pack);
+void launch_pack(hipStream_t st, const LevelDev& L, const CopyItem* items, const long long* bufoff, int nitems,
+                 float* f, float* buf, bool pack);
 void launch_set(hipStream_t st, double* a, long long n, double v);
 void launch_set(hipStream_t st, float* a, long long n, float v);
 // n device values -> coherent host memory, then the sequence number (system-scope release)

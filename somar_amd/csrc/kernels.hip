@@ -585,9 +585,10 @@ __global__ void k_copy_items(const CopyItem* __restrict__ items, const PatchDesc
 }
 
 // pack / unpack of halo regions into contiguous send/recv buffers (multi-GPU path).
-template <bool PACK>
+// T: the element type of the field and of the wire (float on the fp32 depths of a mixed-precision cycle: 4 bytes per value)
+template <bool PACK, class T = double>
 __global__ void k_pack_items(const CopyItem* __restrict__ items, const PatchDesc* __restrict__ patches,
-                             double* __restrict__ f, double* __restrict__ buf, const long long* __restrict__ bufoff)
+                             T* __restrict__ f, T* __restrict__ buf, const long long* __restrict__ bufoff)
 {
     const CopyItem it = items[blockIdx.x];
     const PatchDesc pp = patches[PACK ? it.src_patch : it.dst_patch];
@@ -1130,6 +1131,15 @@ void launch_pack(hipStream_t st, const LevelDev& L, const CopyItem* items, const
         hipLaunchKernelGGL(k_pack_items<true>, dim3(nitems, 16), dim3(256), 0, st, items, L.patches, f, buf, bufoff);
     else
         hipLaunchKernelGGL(k_pack_items<false>, dim3(nitems, 16), dim3(256), 0, st, items, L.patches, f, buf, bufoff);
+}
+void launch_pack(hipStream_t st, const LevelDev& L, const CopyItem* items, const long long* bufoff, int nitems,
+                 float* f, float* buf, bool pack)
+{
+    if (nitems == 0) return;
+    if (pack)
+        hipLaunchKernelGGL((k_pack_items<true, float>), dim3(nitems, 16), dim3(256), 0, st, items, L.patches, f, buf, bufoff);
+    else
+        hipLaunchKernelGGL((k_pack_items<false, float>), dim3(nitems, 16), dim3(256), 0, st, items, L.patches, f, buf, bufoff);
 }
 void launch_set(hipStream_t st, double* a, long long n, double v)
 {

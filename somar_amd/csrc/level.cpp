@@ -962,31 +962,53 @@ void Level::alloc_metric()
     if (!dev.lapdiag) dev.lapdiag = alloc_field();
 }
 
-void Level::exchange_remote(double* f, hipStream_t st) const
+// T = double / float: one code path, the element type decides the pack kernel and the transport's message form
+template <class T>
+static void exchange_remote_t(const Level& L, T* f, hipStream_t st)
 {
+    const ExchangePlan& plan = L.plan;
     if (plan.peers.empty()) return;
-    launch_pack(st, dev, d_send_items, d_send_off, (int)plan.send_items.size(), f, d_sendbuf, true);
-    comm->neighbor_exchange(d_sendbuf, d_recvbuf, plan.peers, plan.soff, plan.scount, plan.roff, plan.rcount, st);
-    launch_pack(st, dev, d_recv_items, d_recv_off, (int)plan.recv_items.size(), f, d_recvbuf, false);
+    T* sb = reinterpret_cast<T*>(L.d_sendbuf);
+    T* rb = reinterpret_cast<T*>(L.d_recvbuf);
+    launch_pack(st, L.dev, L.d_send_items, L.d_send_off, (int)plan.send_items.size(), f, sb, true);
+    L.comm->neighbor_exchange(sb, rb, plan.peers, plan.soff, plan.scount, plan.roff, plan.rcount, st);
+    launch_pack(st, L.dev, L.d_recv_items, L.d_recv_off, (int)plan.recv_items.size(), f, rb, false);
+    L.sent_bytes[sizeof(T) == sizeof(float)] += plan.send_total * (long long)sizeof(T);
 }
+
+template <class T>
+static void exchange_t(const Level& L, T* f, hipStream_t st)
+{
+    // remote first so the wire time overlaps the local copies
+    const ExchangePlan& plan = L.plan;
+    const bool remote = !plan.peers.empty();
+    T* sb = reinterpret_cast<T*>(L.d_sendbuf);
+    T* rb = reinterpret_cast<T*>(L.d_recvbuf);
+    if (remote) {
+        launch_pack(st, L.dev, L.d_send_items, L.d_send_off, (int)plan.send_items.size(), f, sb, true);
+        L.comm->neighbor_exchange(sb, rb, plan.peers, plan.soff, plan.scount, plan.roff, plan.rcount, st);
+    }
+    launch_copy_items(st, L.dev, L.d_local_items, (int)plan.local.size(), f);
+    if (remote) {
+        launch_pack(st, L.dev, L.d_recv_items, L.d_recv_off, (int)plan.recv_items.size(), f, rb, false);
+        L.sent_bytes[sizeof(T) == sizeof(float)] += plan.send_total * (long long)sizeof(T);
+    }
+}
+
+void Level::exchange_remote(double* f, hipStream_t st) const { exchange_remote_t(*this, f, st); }
+void Level::exchange_remote(float* f, hipStream_t st) const { exchange_remote_t(*this, f, st); }
 
 void Level::exchange_local(double* f, hipStream_t st) const
 {
     launch_copy_items(st, dev, d_local_items, (int)plan.local.size(), f);
 }
-
-void Level::exchange(double* f, hipStream_t st) const
+void Level::exchange_local(float* f, hipStream_t st) const
 {
-    // remote first so the wire time overlaps the local copies
-    const bool remote = !plan.peers.empty();
-    if (remote) {
-        launch_pack(st, dev, d_send_items, d_send_off, (int)plan.send_items.size(), f, d_sendbuf, true);
-        comm->neighbor_exchange(d_sendbuf, d_recvbuf, plan.peers, plan.soff, plan.scount, plan.roff, plan.rcount, st);
-    }
     launch_copy_items(st, dev, d_local_items, (int)plan.local.size(), f);
-    if (remote)
-        launch_pack(st, dev, d_recv_items, d_recv_off, (int)plan.recv_items.size(), f, d_recvbuf, false);
 }
+
+void Level::exchange(double* f, hipStream_t st) const { exchange_t(*this, f, st); }
+void Level::exchange(float* f, hipStream_t st) const { exchange_t(*this, f, st); }
 
 static void copy3d(void* dst, size_t dpitchB, size_t dheight, int dx0, int dy0, int dz0, const void* src,
                    size_t spitchB, size_t sheight, int sx0, int sy0, int sz0, const int n[3], hipMemcpyKind kind,

@@ -65,6 +65,15 @@ struct Comm {
     {
         (void)sendbuf; (void)recvbuf; (void)peers; (void)soff; (void)scount; (void)roff; (void)rcount; (void)st;
     }
+    // the same for fp32 payloads (the fp32 depths of a mixed-precision cycle): offsets and counts in floats, 4 bytes per value
+    // on the wire -- never widened.  Both sides of a message must use the same form.
+    virtual void neighbor_exchange(const float* sendbuf, float* recvbuf, const std::vector<int>& peers,
+                                   const std::vector<long long>& soff, const std::vector<long long>& scount,
+                                   const std::vector<long long>& roff, const std::vector<long long>& rcount,
+                                   hipStream_t st)
+    {
+        (void)sendbuf; (void)recvbuf; (void)peers; (void)soff; (void)scount; (void)roff; (void)rcount; (void)st;
+    }
 };
 
 // Host-side plan of the ghost exchange of one level ("Copier(grids,grids,domain,ghost,true)").
@@ -198,6 +207,14 @@ public:
     // copies inside this rank; they write disjoint ghost cells and may run on different streams
     void exchange_remote(double* f, hipStream_t st) const;
     void exchange_local(double* f, hipStream_t st) const;
+    // fp32 fields: the same plan, item order and offsets (counted in elements); the messages carry 4 bytes per value.  They
+    // go through d_sendbuf / d_recvbuf too (sized for doubles, so half used): every exchange of a level, of either element
+    // type, is ordered on the stream(s) of its solver exactly as the fp64 ones are.
+    void exchange(float* f, hipStream_t st) const;
+    void exchange_remote(float* f, hipStream_t st) const;
+    void exchange_local(float* f, hipStream_t st) const;
+    // payload bytes this rank has put on the wire in the exchanges above: [0] fp64 fields, [1] fp32 fields
+    mutable long long sent_bytes[2] = {0, 0};
 
     // host<->device transfer of one patch in Chombo FRA layout.  `hostbox` is the box the host
     // array is defined on (valid grown by the caller's ghosts, or a face box); `region` is

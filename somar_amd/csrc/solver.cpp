@@ -619,7 +619,7 @@ void PressureSolver::finalize()
             if (lev[d]->valid_cells_global <= graph_cells_) { graph_from_ = d; break; }
     sync();
     finalized = true;
-    if (mp_mode_ == 1) mp_setup();
+    if (mp_mode_ == 1 || comm_->size > 1) mp_setup();   // (sharded: every rank's mode has to be the same one, fp64 included)
 }
 
 // The hierarchy from `depth` on, replicated on every rank (see solver.h).  lev[depth] stays as the sharded
@@ -2090,7 +2090,6 @@ std::string PressureSolver::mixed_refusal() const
     if (full_) return "a non-diagonal metric (19-point operator)";
     if (prm.relaxMode != RELAX_LEVEL_GSRB) return "a relax_mode other than LevelGSRB";
     if (prm.numMG != 1) return "num_mg != 1 (W- and F-cycles run plain passes, no folding)";
-    if (comm_->size > 1) return "more than one rank (no fp32 message plans)";
     if (hasCF_ || !forcedRatios.empty()) return "a level with coarse-fine boundaries";
     return "";
 }
@@ -2127,12 +2126,12 @@ void PressureSolver::mp_setup()
 {
     mp_free();
     drop_graphs();
-    if (mp_mode_ != 1) return;
     static const bool no_fold = getenv("SOMAR_NO_FOLD_PROLONG") != nullptr;   // (fold_prolong's A/B switch)
     const long long minc = mp_min_cells_ > 0 ? mp_min_cells_ : fused_min_cells_;
+    // (sharded: lev.back() is the landing layout of the replicated tail, or a serial-order depth comes first -- both stay fp64)
     const int D = (int)lev.size();
     int K = 0;
-    for (int d = 0; d + 1 < D && !no_fold; ++d) {
+    for (int d = 0; d + 1 < D && !no_fold && mp_mode_ == 1; ++d) {
         const Level& L = *lev[d];
         if (graph_from_ >= 0 && d >= graph_from_) break;   // the graph-replayed legs stay fp64
         if (!fused_relax(d, prm.num_smooth_down) || !fused_relax(d, prm.num_smooth_up)) break;
@@ -2141,6 +2140,28 @@ void PressureSolver::mp_setup()
         for (int q = 0; q < 3; ++q) r12 = r12 && (L.mgCrseRefRatio[q] == 1 || L.mgCrseRefRatio[q] == 2);
         if (!r12) break;
         K = d + 1;
+    }
+    if (comm_->size > 1) {
+        // The mode and K decide the element type of every halo message of depths 0 .. K-1: a rank in fp32 talking to a rank in
+        // fp64 would wait in the transport for a message of the other size.  min and max over the ranks in ONE max-allreduce.
+        const double mine[3] = {(double)mp_mode_, (double)K, (double)(mp_mode_ == 1 ? minc : 0)};
+        double v[6];
+        for (int q = 0; q < 3; ++q) { v[q] = mine[q]; v[3 + q] = -mine[q]; }
+        SOMAR_HIP(hipMemcpyAsync(d_scalars + SLOT_SUMS, v, sizeof(v), hipMemcpyHostToDevice, st_));
+        comm_->allreduce(d_scalars + SLOT_SUMS, 6, 1, st_);
+        SOMAR_HIP(hipMemcpyAsync(v, d_scalars + SLOT_SUMS, sizeof(v), hipMemcpyDeviceToHost, st_));
+        SOMAR_HIP(hipStreamSynchronize(st_));
+        bool same = true;
+        for (int q = 0; q < 3; ++q) same = same && v[q] == -v[3 + q];
+        if (!same) {
+            mp_mode_ = 0;   // on every rank alike: the solver stays usable, in fp64
+            mp_min_cells_ = 0;
+            throw Error(-1, "set_precision is collective on a sharded solver: every rank must call it with the same mode and "
+                            "min_cells and arrive at the same fp32 depths (mode " + std::to_string((int)-v[3]) + " .. " +
+                            std::to_string((int)v[0]) + ", fp32 depths " + std::to_string((int)-v[4]) + " .. " +
+                            std::to_string((int)v[1]) + ", min_cells " + std::to_string((long long)-v[5]) + " .. " +
+                            std::to_string((long long)v[2]) + " over the ranks); the solver is back in mode 0");
+        }
     }
     if (K == 0) return;
     auto alloc32 = [](long long n) {
@@ -2186,10 +2207,20 @@ MetricPtrs<float> PressureSolver::mp_metric(int d) const
     return MetricPtrs<float>{{z.jg[0], z.jg[1], z.jg[2]}, z.jinv};
 }
 
-// one rank (mixed_refusal): the exchange is the box-to-box copies alone
+// xchg() of an fp32 field: the same plan, fp32 messages
 void PressureSolver::xchg32(const Level& L, float* f)
 {
-    launch_copy_items(st_, L.dev, L.d_local_items, (int)L.plan.local.size(), f);
+    const bool timed = profiling_ && !L.plan.peers.empty();
+    if (timed) prof_begin(2);
+    L.exchange(f, st_);
+    if (timed) prof_end(2);
+}
+
+void PressureSolver::exchange_bytes(long long out2[2]) const
+{
+    out2[0] = out2[1] = 0;
+    for (const auto& L : lev)
+        for (int q = 0; q < 2; ++q) out2[q] += L->sent_bytes[q];
 }
 
 // relax() on its fused path
@@ -2211,6 +2242,14 @@ void PressureSolver::relax32(int d, float* e, const float* res, int iters, bool 
         if (zin) mode = 1;
         else if (it == 0 && e_plus) mode = e_shift ? 4 : 3;
         else if (it == 0 && e_shift) mode = 2;
+        if (!zin && fused_overlap(L)) {   // as relax(): the remote half of the exchange under the tiles that read none of it
+            overlapped(L, cur, L.d_ftiles_own, L.nftiles_own, L.d_ftiles_rem, L.nftiles_rem, [&](Tile* tl, int nt) {
+                launch_gsrb_fused(st_, tl, nt, L.dev, mp_metric(d), alt, cur, res, mode, e_shift,
+                                  e_plus_level ? &e_plus_level->dev : nullptr, e_plus, L.mgCrseRefRatio);
+            });
+            std::swap(cur, alt);
+            continue;
+        }
         if (!zin) xchg32(L, cur);
         if (profiling_ && d == 0) prof_begin(0);
         launch_gsrb_fused(st_, L.d_ftiles, L.nftiles, L.dev, mp_metric(d), alt, cur, res, mode, e_shift,
@@ -2226,6 +2265,15 @@ void PressureSolver::restrict32(int d, float* resCoarse, float* phiFine, const f
 {
     Level& F = *lev[d];
     const bool want = F.zeroAvg;   // (never an ordered level)
+    if (resid_overlap(F)) {   // as restrict_residual() (never with Dirichlet sides)
+        overlapped(F, phiFine, F.d_rtiles_own, F.nrtiles_own, F.d_rtiles_rem, F.nrtiles_rem, [&](Tile* tl, int nt) {
+            launch_resid_restrict(st_, tl, nt, F.dev, mp_metric(d), lev[d + 1]->dev, resCoarse, phiFine, rhsFine,
+                                  F.mgCrseRefRatio, F.dxProduct, want ? d_partials : nullptr);
+        });
+        if (want) launch_sum_partials(st_, d_partials, F.nrtiles, d_fold + 8 * d);
+        sf_valid_[d] = want ? 1 : 0;
+        return;
+    }
     xchg32(F, phiFine);
     if (diri_) launch_ghost_ops(st_, F.dev, d_diri_ops_[d], n_diri_ops_[d], phiFine);   // homogeneous Dirichlet ghosts
     if (profiling_ && d == 0) prof_begin(1);
@@ -2247,6 +2295,7 @@ void PressureSolver::cycle_up32(int d, float* corr, const float* res)
     if (F.zeroAvg) {
         double* s = d_fold + 8 * d;
         launch_reduce(st_, C.dev, cc, f_W[d + 1], 0, d_partials, s + 1);
+        comm_->allreduce(s, 2, 0, st_);   // (S_f, S_c) over the ranks, in fp64 as in cycle_up()
         launch_combine_sums(st_, s + 3, s, s + 1, s + 2);
         shift = s + 3;
     }

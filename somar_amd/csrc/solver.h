@@ -184,8 +184,12 @@ public:
     // there (fused_relax) and it has at least min_cells cells (<= 0: the fused sweep's own threshold); the rest of the cycle,
     // the residuals and phi stay fp64, so the outer defect-correction loop still drives the fp64 residual.  Before or after
     // finalize (after: allocates the fp32 copies, converts the metric, drops the graphs); refused while a metric update is
-    // open and where the fp32 path does not reach (mixed_refusal)
+    // open and where the fp32 path does not reach (mixed_refusal).  On a sharded solver the fp32 depths exchange their ghosts in
+    // fp32 messages, so mode, min_cells and K are part of the message format: a finalized solver's set_precision (and a
+    // finalize) is COLLECTIVE, every rank calls it with the same arguments -- ranks that disagree all get an error, and mode 0.
     void set_precision(int mode, long long min_cells);
+    // payload bytes this rank has sent in the ghost exchanges of this solver's levels: [0] fp64 fields, [1] fp32 fields
+    void exchange_bytes(long long out2[2]) const;
     int precision_mode() const { return mp_mode_; }
     int fp32_depths() const { return mp_K_; }
     // MG ratios imposed on the first depths (set before finalize): the coarsening pattern of the mini V-cycle of a
@@ -261,7 +265,7 @@ private:
     int mp_K_ = 0;                  // depths 0 .. mp_K_ - 1 run in fp32
     std::vector<Depth32> f32_;      // mp_K_ + 1 entries once set up
     std::string mixed_refusal() const;   // why mode 1 is not available here ("" = it is)
-    void mp_setup();                // after finalize: K, buffers, metric copies
+    void mp_setup();                // after finalize: K (agreed on by every rank), buffers, metric copies
     void mp_free();
     void mp_convert_metric();       // one launch per fp32 depth (finalize, set_precision, metric refresh)
     MetricPtrs<float> mp_metric(int d) const;
@@ -464,9 +468,9 @@ private:
         return overlap_on_ && !L.plan.peers.empty() && L.nrtiles_own > 0 && !capturing_ && !profiling_ && !diri_;
     }
     // exchange of f with its remote half on the second stream; run(tiles, n) is issued for the tiles that read no remote ghost
-    // first, for the others once the messages have landed
-    template <class Run>
-    void overlapped(const Level& L, double* f, Tile* own, int nown, Tile* rem, int nrem, Run run)
+    // first, for the others once the messages have landed.  T: double, or float on the fp32 depths of a mixed cycle.
+    template <class T, class Run>
+    void overlapped(const Level& L, T* f, Tile* own, int nown, Tile* rem, int nrem, Run run)
     {
         if (!st_comm_) {
             SOMAR_HIP(hipStreamCreateWithFlags(&st_comm_, hipStreamNonBlocking));

@@ -491,11 +491,11 @@ static void launch_gsrb_fused_t(hipStream_t st, const Tile* tiles, int ntiles, c
 #undef SOMAR_FUSED_MODES
 }
 
-void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* phi_out,
-                       const double* phi_in, const double* rhs, int in_mode, const double* sums,
+void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, const MetricPtrs<double>& M,
+                       double* phi_out, const double* phi_in, const double* rhs, int in_mode, const double* sums,
                        const LevelDev* C, const double* crse, const int* r)
 {
-    launch_gsrb_fused_t<double>(st, tiles, ntiles, L, metric_ptrs(L), phi_out, phi_in, rhs, in_mode, sums, C, crse, r);
+    launch_gsrb_fused_t<double>(st, tiles, ntiles, L, M, phi_out, phi_in, rhs, in_mode, sums, C, crse, r);
 }
 
 void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, const MetricPtrs<float>& M,

@@ -77,9 +77,10 @@ void launch_gsrb_ortho(hipStream_t st, const LevelDev& L, double* phi, const dou
 // in_mode 0: plain; 1: phi_in is taken to be all zeros and is not read; 2: phi_in is read as
 // (value - sums[0]/sums[1]) (deferred mean removal of the zero-average prolongation); 3: phi_in is read as
 // value + crse(i / r) (prolongation folded in; C = coarse level, crse exchanged one deep); 4: 3 and 2 together
-void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* phi_out,
-                       const double* phi_in, const double* rhs, int in_mode = 0, const double* sums = nullptr,
-                       const LevelDev* C = nullptr, const double* crse = nullptr, const int* r = nullptr);
+// M: the level's coefficient arrays in the fields' element type (metric_ptrs(L), or the fp32 copies)
+void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, const MetricPtrs<double>& M,
+                       double* phi_out, const double* phi_in, const double* rhs, int in_mode, const double* sums,
+                       const LevelDev* C, const double* crse, const int* r);
 // the same sweep on fp32 fields and coefficients (mixed-precision depths); sums stay fp64
 void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, const MetricPtrs<float>& M,
                        float* phi_out, const float* phi_in, const float* rhs, int in_mode, const double* sums,
@@ -90,9 +91,9 @@ bool fused_uniform_kernel(const LevelDev& L);
 // k-marching operator/residual of a large level (resid_march.hip); mode 0: out = rhs - L[phi], 1: out = L[phi]
 void launch_resid_march(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* out,
                         const double* phi, const double* rhs, int mode);
-void launch_resid_restrict(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const LevelDev& C,
-                           double* crse, const double* phi, const double* rhs, const int r[3], double dxProduct = 0.0,
-                           double* volsum = nullptr);
+void launch_resid_restrict(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const MetricPtrs<double>& M,
+                           const LevelDev& C, double* crse, const double* phi, const double* rhs, const int r[3],
+                           double dxProduct, double* volsum);
 // the same on fp32 fields and coefficients (mixed-precision depths); volsum is accumulated in fp64
 void launch_resid_restrict(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const MetricPtrs<float>& M,
                            const LevelDev& C, float* crse, const float* phi, const float* rhs, const int r[3],

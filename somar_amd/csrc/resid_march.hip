@@ -310,11 +310,11 @@ static void launch_resid_restrict_t(hipStream_t st, const Tile* tiles, int ntile
                        M.jg[0], M.jg[1], M.jg[2], M.jinv, F.P, C.patches, r[0], r[1], r[2], dxProduct, volsum);
 }
 
-void launch_resid_restrict(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const LevelDev& C,
-                           double* crse, const double* phi, const double* rhs, const int r[3], double dxProduct,
-                           double* volsum)
+void launch_resid_restrict(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const MetricPtrs<double>& M,
+                           const LevelDev& C, double* crse, const double* phi, const double* rhs, const int r[3],
+                           double dxProduct, double* volsum)
 {
-    launch_resid_restrict_t<double>(st, tiles, ntiles, F, metric_ptrs(F), C, crse, phi, rhs, r, dxProduct, volsum);
+    launch_resid_restrict_t<double>(st, tiles, ntiles, F, M, C, crse, phi, rhs, r, dxProduct, volsum);
 }
 
 void launch_resid_restrict(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const MetricPtrs<float>& M,

@@ -136,7 +136,8 @@ void PressureSolver::profile_get(int kernel, int* count, double* total_ms)
     p.used = 0;
 }
 
-void PressureSolver::xchg(const Level& L, double* f)
+template <class T>
+void PressureSolver::xchg(const Level& L, T* f)
 {
     const bool timed = profiling_ && !L.plan.peers.empty();
     if (timed) prof_begin(2);
@@ -993,53 +994,123 @@ bool PressureSolver::fused_relax(int d, int iters) const
            (L.ncf == 0 || L.cf_fusable) && L.active[2] && !no_cf_fused_(L) && !full_;  // Dirichlet sides: ghosts synthesized in the kernel
 }
 
+// ------------------------------------------------------------------------------------
+// The fold path of the cycle on fields of type T: double, or float on the fp32 depths of the mixed cycle.  The element type
+// shows in pingpong / metric (below), diri_homog / cf_fill (solver.h) and the launchers' overloads, nowhere else.
+// ------------------------------------------------------------------------------------
+static bool no_zero_start()  // A/B switch SOMAR_NO_ZERO_START: the fused sweep gets its zeros from a memset, not from in_mode 1
+{
+    static const bool on = getenv("SOMAR_NO_ZERO_START") != nullptr;
+    return on;
+}
+template <> double* PressureSolver::pingpong<double>(int d) const { return f_pp[d]; }
+template <> float* PressureSolver::pingpong<float>(int d) const { return f32_[d].pp; }
+template <> MetricPtrs<double> PressureSolver::metric<double>(int d) const { return metric_ptrs(lev[d]->dev); }
+template <> MetricPtrs<float> PressureSolver::metric<float>(int d) const
+{
+    const Depth32& z = f32_[d];
+    return MetricPtrs<float>{{z.jg[0], z.jg[1], z.jg[2]}, z.jinv};
+}
+
+// LevelGSRB::relax (GSRB.cpp:58-98) as ONE fused red+black launch per sweep (gsrb_fused.hip):
+// same values bit for bit, one ghost exchange per sweep instead of two, ping-pong buffers.
+template <class T>
+void PressureSolver::fused_sweeps(int d, T* e, const T* res, int iters, bool e_zero, const double* e_shift,
+                                  const Level* e_plus_level, const T* e_plus)
+{
+    Level& L = *lev[d];
+    if (e_zero && no_zero_start()) {
+        launch_set(st_, e, L.field_elems, T(0));
+        e_zero = false;
+    }
+    xchg(L, const_cast<T*>(res));  // rhs ghosts: constant over the sweeps
+    T* cur = e;
+    T* alt = pingpong<T>(d);
+    for (int it = 0; it < iters; ++it) {
+        const bool zin = e_zero && it == 0;  // zeros need neither an exchange nor a read
+        int mode = 0;
+        if (zin) mode = 1;
+        else if (it == 0 && e_plus) mode = e_shift ? 4 : 3;
+        else if (it == 0 && e_shift) mode = 2;
+        auto sweep = [&](Tile* tl, int nt) {
+            launch_gsrb_fused(st_, tl, nt, L.dev, metric<T>(d), alt, cur, res, mode, e_shift,
+                              e_plus_level ? &e_plus_level->dev : nullptr, e_plus, L.mgCrseRefRatio);
+        };
+        if (!zin && fused_overlap(L)) {
+            // the sweep's one exchange in flight on the second stream while the tiles that read none of its cells are swept
+            // (the CF ghosts are other cells, computed from this rank's valid cells: filled before the first tiles run)
+            cf_fill(L, cur, true);
+            overlapped(L, cur, L.d_ftiles_own, L.nftiles_own, L.d_ftiles_rem, L.nftiles_rem, sweep);
+        } else {
+            if (!zin) {
+                xchg(L, cur);
+                cf_fill(L, cur, true);  // CF ghosts (faces + the edge ghosts the red ring reads), pre-sweep values
+            }
+            ProfScope timed(*this, d, 0);
+            sweep(L.d_ftiles, L.nftiles);
+        }
+        std::swap(cur, alt);
+    }
+    if (cur != e) launch_copy(st_, e, cur, L.field_elems);
+}
+
+// restrictResidual on a large level: residual and J-weighted average in one marching pass, the fine residual is never
+// stored; with the fine half of the folded prolongation's mean
+template <class T>
+void PressureSolver::march_restrict(int d, T* resCoarse, T* phiFine, const T* rhsFine)
+{
+    Level& F = *lev[d];
+    cf_fill(F, phiFine, false);
+    const bool want = F.zeroAvg && !ordered(d);  // the fine half of the folded prolongation's mean
+    auto pass = [&](Tile* tl, int nt) {
+        launch_resid_restrict(st_, tl, nt, F.dev, metric<T>(d), lev[d + 1]->dev, resCoarse, phiFine, rhsFine, F.mgCrseRefRatio,
+                              F.dxProduct, want ? d_partials : nullptr);
+    };
+    const bool overlap = resid_overlap(F);  // (never with Dirichlet sides, never in a profiled pass)
+    if (!overlap) {
+        xchg(F, phiFine);
+        if (diri_) diri_homog(d, phiFine);  // homogeneous Dirichlet ghosts, as residual() fills them
+    }
+    ProfScope timed(*this, d, 1);
+    if (overlap) overlapped(F, phiFine, F.d_rtiles_own, F.nrtiles_own, F.d_rtiles_rem, F.nrtiles_rem, pass);
+    else pass(F.d_rtiles, F.nrtiles);
+    if (want) launch_sum_partials(st_, d_partials, F.nrtiles, d_fold + 8 * d);
+    sf_valid_[d] = want ? 1 : 0;
+}
+
+// Large level: neither the prolongation nor the zero-average mean removal gets a pass of its own -- the first
+// post-smoothing sweep reads corr + coarse(i/r) - mean.  mean = (S_f + S_c) / V with S_f = sum dvol * corr
+// (gathered by the fused restriction), S_c = sum over coarse cells of coarse * (volume of its children), V the
+// level's volume: the same number as ZeroAvgConstInterpPS's sum dvol * (corr + coarse) / sum dvol up to the
+// association of the (already tree-ordered) sum.  The sums are fp64 whatever T is.
+template <class T>
+void PressureSolver::fold_up(int d, T* corr, const T* res, T* crse, bool exchange_crse)
+{
+    Level& F = *lev[d];
+    Level& C = *lev[d + 1];
+    if (exchange_crse) xchg(C, crse);
+    const double* shift = nullptr;
+    if (F.zeroAvg) {
+        double* s = d_fold + 8 * d;
+        launch_reduce(st_, C.dev, crse, f_W[d + 1], 0, d_partials, s + 1);
+        comm_->allreduce(s, 2, 0, st_);  // (S_f, S_c) over the ranks
+        launch_combine_sums(st_, s + 3, s, s + 1, s + 2);
+        shift = s + 3;
+    }
+    fused_sweeps(d, corr, res, prm.num_smooth_up, false, shift, &C, crse);
+}
+
 void PressureSolver::relax(int d, double* e, const double* res, int iters, bool e_zero, const double* e_shift,
                            const Level* e_plus_level, const double* e_plus)
 {
     Level& L = *lev[d];
     const bool fused_path = fused_relax(d, iters);
     SOMAR_CHECK((!e_shift && !e_plus) || fused_path, "deferred mean removal / folded prolongation need the fused sweep");
-    static const bool no_zero_start = getenv("SOMAR_NO_ZERO_START") != nullptr;  // A/B switch
-    if (e_zero && (!fused_path || no_zero_start)) {
-        launch_set(st_, e, L.field_elems, 0.0);
-        e_zero = false;
-    }
     if (fused_path) {
-        // LevelGSRB::relax (GSRB.cpp:58-98) as ONE fused red+black launch per sweep (gsrb_fused.hip):
-        // same values bit for bit, one ghost exchange per sweep instead of two, ping-pong buffers.
-        xchg(L, const_cast<double*>(res));  // rhs ghosts: constant over the sweeps
-        double* cur = e;
-        double* alt = f_pp[d];
-        for (int it = 0; it < iters; ++it) {
-            const bool zin = e_zero && it == 0;  // zeros need neither an exchange nor a read
-            int mode = 0;
-            if (zin) mode = 1;
-            else if (it == 0 && e_plus) mode = e_shift ? 4 : 3;
-            else if (it == 0 && e_shift) mode = 2;
-            if (!zin && fused_overlap(L)) {
-                // the sweep's one exchange in flight on the second stream while the tiles that read none of its cells are swept
-                // (the CF ghosts are other cells, computed from this rank's valid cells: filled before the first tiles run)
-                L.cf_homog_ext(cur, st_);
-                overlapped(L, cur, L.d_ftiles_own, L.nftiles_own, L.d_ftiles_rem, L.nftiles_rem, [&](Tile* tl, int nt) {
-                    launch_gsrb_fused(st_, tl, nt, L.dev, alt, cur, res, mode, e_shift, e_plus_level ? &e_plus_level->dev : nullptr,
-                                      e_plus, L.mgCrseRefRatio);
-                });
-                std::swap(cur, alt);
-                continue;
-            }
-            if (!zin) {
-                xchg(L, cur);
-                L.cf_homog_ext(cur, st_);  // CF ghosts (faces + the edge ghosts the red ring reads), pre-sweep values
-            }
-            if (profiling_ && d == 0) prof_begin(0);
-            launch_gsrb_fused(st_, L.d_ftiles, L.nftiles, L.dev, alt, cur, res, mode, e_shift,
-                              e_plus_level ? &e_plus_level->dev : nullptr, e_plus, L.mgCrseRefRatio);
-            if (profiling_ && d == 0) prof_end(0);
-            std::swap(cur, alt);
-        }
-        if (cur != e) launch_copy(st_, e, cur, L.field_elems);
+        fused_sweeps(d, e, res, iters, e_zero, e_shift, e_plus_level, e_plus);
         return;
     }
+    if (e_zero) launch_set(st_, e, L.field_elems, 0.0);
     if (prm.relaxMode == RELAX_LEVEL_GSRB && full_march(d) && fused19(d)) {
         // LevelGSRB::relax with a non-diagonal metric on a level of large boxes: red everywhere and black three layers inside
         // every box in ONE marching launch (full19_fused.hip), the between-colour ghost work on its output exactly as in the
@@ -1051,15 +1122,17 @@ void PressureSolver::relax(int d, double* e, const double* res, int iters, bool 
             xchg(L, cur);
             run_full_program_frames(d, 1, cur);
             copy_frames(d, cur, alt);
-            if (profiling_ && d == 0) prof_begin(0);
-            launch_full_fused(st_, L.d_gtiles, L.ngtiles, L.dev, alt, cur, f_psi[d], res);
-            if (profiling_ && d == 0) prof_end(0);
+            {
+                ProfScope timed(*this, d, 0);
+                launch_full_fused(st_, L.d_gtiles, L.ngtiles, L.dev, alt, cur, f_psi[d], res);
+            }
             L.cf_homog(alt, st_);
             xchg(L, alt);
             run_full_program_frames(d, 1, alt);
-            if (profiling_ && d == 0) prof_begin(0);   // (slot 0 then holds two launches per sweep, as in the two-pass form)
-            launch_gsrb_full_shell(st_, L.d_stiles, L.nstiles, L.dev, alt, cur, f_psi[d], res);
-            if (profiling_ && d == 0) prof_end(0);
+            {
+                ProfScope timed(*this, d, 0);   // (slot 0 then holds two launches per sweep, as in the two-pass form)
+                launch_gsrb_full_shell(st_, L.d_stiles, L.nstiles, L.dev, alt, cur, f_psi[d], res);
+            }
             ++counters[4];
             std::swap(cur, alt);
         }
@@ -1080,9 +1153,8 @@ void PressureSolver::relax(int d, double* e, const double* res, int iters, bool 
                 // the pass rewrites the valid cells only; the ghost frame travels with them (edge / vertex ghosts at
                 // coarse-fine corners keep whatever the last ExtrapolateCFEV left there, as in the reference's in-place sweep)
                 copy_frames(d, cur, alt);
-                if (profiling_ && d == 0) prof_begin(0);
+                ProfScope timed(*this, d, 0);
                 launch_gsrb_full_march(st_, L.d_qtiles, L.nqtiles, L.dev, alt, cur, f_psi[d], res, pass);
-                if (profiling_ && d == 0) prof_end(0);
                 std::swap(cur, alt);
             }
         // an even number of passes: the result is back in e
@@ -1101,10 +1173,9 @@ void PressureSolver::relax(int d, double* e, const double* res, int iters, bool 
                 if (!pull) xchg(L, e);
                 if (diri_ && !full_) apply_diri(d, e, true);  // ... and its physical ghosts (doBCs); non-diagonal: in the program
                 if (full_) run_full_program(d, 1, e);  // psi snapshot + extrapolation (order 1) + Neumann ghosts
-                if (profiling_ && d == 0) prof_begin(0);
+                ProfScope timed(*this, d, 0);
                 if (full_) launch_gsrb_full(st_, L.dev, e, f_psi[d], res, pass);
                 else launch_gsrb_ortho(st_, L.dev, e, res, pass, 0, pull);
-                if (profiling_ && d == 0) prof_end(0);
             }
         } else if (prm.relaxMode == RELAX_LOOSE_GSRB) {
             // LooseGSRB::relax, GSRB.cpp:104-141: ONE exchange per sweep; red+black on the cells strictly inside
@@ -1161,53 +1232,50 @@ void PressureSolver::apply_op(int d, double* out, double* phi, bool homogeneous)
     apply_op_i(d, out, phi, homogeneous);
 }
 
-void PressureSolver::residual_i(int d, double* out, double* phi, const double* rhs, bool homogeneous)
+void PressureSolver::operator_i(int d, int mode, double* out, double* phi, const double* rhs, bool homogeneous)
 {
     Level& L = *lev[d];
     // small levels (direct-load operator): the kernel pulls the ghosts it reads, no copy launch
-    const bool pull = !full_ && L.pull_ready() && !(L.valid_cells_global >= march_min_cells_ && L.active[2]);
+    const bool pull = !full_ && L.pull_ready() && !ortho_march(d);
     if (!pull) xchg(L, phi);  // exchangeComplete, MappedAMRPoissonOp.cpp:2222-2238
     if (diri_ && !full_) apply_diri(d, phi, homogeneous);  // m_bc.setGhosts, :822 (non-diagonal: inside the program)
-    if (profiling_ && d == 0) prof_begin(1);
+    ProfScope timed(*this, d, 1, mode == 0);
     if (full_march(d)) {
         run_full_program_frames(d, 0, phi, homogeneous);
-        launch_full_march(st_, L.d_qtiles, L.nqtiles, L.dev, out, phi, f_psi[d], rhs, 0);
+        launch_full_march(st_, L.d_qtiles, L.nqtiles, L.dev, out, phi, f_psi[d], rhs, mode);
     } else if (full_) {
         // exchangeComplete, fillExtrap (order 2), physical ghosts (Neumann with cross terms / Dirichlet), then the 19-point fluxes
         run_full_program(d, 0, phi, homogeneous);
-        launch_op_full(st_, L.dev, out, phi, f_psi[d], rhs, 0);
-    } else if (L.valid_cells_global >= march_min_cells_ && L.active[2]) launch_resid_march(st_, L.d_rtiles, L.nrtiles, L.dev, out, phi, rhs, 0);  // Dirichlet sides: their ghosts were just written, the kernel only zeroes NEUMANN fluxes
-    else launch_op_ortho(st_, L.dev, out, phi, rhs, 0, pull);
-    if (profiling_ && d == 0) prof_end(1);
-}
-
-void PressureSolver::apply_op_i(int d, double* out, double* phi, bool homogeneous)
-{
-    Level& L = *lev[d];
-    const bool pull = !full_ && L.pull_ready() && !(L.valid_cells_global >= march_min_cells_ && L.active[2]);
-    if (!pull) xchg(L, phi);
-    if (diri_ && !full_) apply_diri(d, phi, homogeneous);
-    if (full_march(d)) {
-        run_full_program_frames(d, 0, phi, homogeneous);
-        launch_full_march(st_, L.d_qtiles, L.nqtiles, L.dev, out, phi, f_psi[d], nullptr, 1);
-    } else if (full_) {
-        run_full_program(d, 0, phi, homogeneous);
-        launch_op_full(st_, L.dev, out, phi, f_psi[d], nullptr, 1);
-    } else if (L.valid_cells_global >= march_min_cells_ && L.active[2]) launch_resid_march(st_, L.d_rtiles, L.nrtiles, L.dev, out, phi, nullptr, 1);
-    else launch_op_ortho(st_, L.dev, out, phi, nullptr, 1, pull);
+        launch_op_full(st_, L.dev, out, phi, f_psi[d], rhs, mode);
+    } else if (ortho_march(d)) launch_resid_march(st_, L.d_rtiles, L.nrtiles, L.dev, out, phi, rhs, mode);  // Dirichlet sides: their ghosts were just written, the kernel only zeroes NEUMANN fluxes
+    else launch_op_ortho(st_, L.dev, out, phi, rhs, mode, pull);
 }
 
 void PressureSolver::prolong_from(const LevelDev& C, const double* crse, const int r[3], double* fine)
 {
-    Level& F = *lev[0];
-    const bool os = F.zeroAvg && ord_sharded(0);
+    prolong_onto(0, C, crse, r, fine, false);
+}
+
+const double* PressureSolver::prolong_increment(int d, double* phiFine, const double* corrCoarse, bool defer_mean)
+{
+    return prolong_onto(d, lev[d + 1]->dev, corrCoarse, lev[d]->mgCrseRefRatio, phiFine, defer_mean);
+}
+
+const double* PressureSolver::prolong_onto(int d, const LevelDev& C, const double* crse, const int r[3], double* fine,
+                                           bool defer_mean)
+{
+    // ConstInterpPS / ZeroAvgConstInterpPS, ProlongationStrategy.cpp:49-164.  The two scalar
+    // MPI_Allreduce calls of the reference become one 2-element device-side reduction.
+    Level& F = *lev[d];
+    const bool os = F.zeroAvg && ord_sharded(d);
     launch_prolong(st_, F.dev, C, fine, crse, r, F.zeroAvg && !os, F.dxProduct, d_partials, d_scalars + SLOT_SUMS,
-                   F.field_elems, ordered(0));
-    if (F.zeroAvg) {
-        if (os) ordered_sums(0, fine, F.dev.jinv, 6, F.dxProduct, d_scalars + SLOT_SUMS);
-        else comm_->allreduce(d_scalars + SLOT_SUMS, 2, 0, st_);
-        launch_sub_mean(st_, fine, F.field_elems, d_scalars + SLOT_SUMS);
-    }
+                   F.field_elems, ordered(d));
+    if (!F.zeroAvg) return nullptr;
+    if (os) ordered_sums(d, fine, F.dev.jinv, 6, F.dxProduct, d_scalars + SLOT_SUMS);
+    else comm_->allreduce(d_scalars + SLOT_SUMS, 2, 0, st_);
+    if (defer_mean) return d_scalars + SLOT_SUMS;
+    launch_sub_mean(st_, fine, F.field_elems, d_scalars + SLOT_SUMS);
+    return nullptr;
 }
 
 double* PressureSolver::amr_field(int which)
@@ -1222,59 +1290,22 @@ bool PressureSolver::residual_restrict_i(const LevelDev& C, double* crse, double
     Level& F = *lev[0];
     for (int d = 0; d < 3; ++d)
         if (r[d] != 1 && r[d] != 2) return false;
-    if (!(F.valid_cells_global >= march_min_cells_ && F.active[2] && !full_)) return false;
+    if (!ortho_march(0)) return false;
     xchg(F, phi);  // exchangeComplete, as residual_i
     if (diri_) apply_diri(0, phi, true);
-    launch_resid_restrict(st_, F.d_rtiles, F.nrtiles, F.dev, C, crse, phi, rhs, r, F.dxProduct, nullptr);
+    launch_resid_restrict(st_, F.d_rtiles, F.nrtiles, F.dev, metric<double>(0), C, crse, phi, rhs, r, F.dxProduct, nullptr);
     return true;
 }
 
 void PressureSolver::restrict_residual(int d, double* resCoarse, double* phiFine, const double* rhsFine)
 {
     // restrictResidual, MappedAMRPoissonOp.cpp:1281-1304
-    Level& F = *lev[d];
-    if (F.valid_cells_global >= march_min_cells_ && F.active[2] && !full_) {
-        // large level: residual and J-weighted average in one marching pass, the fine residual is never stored
-        F.cf_homog(phiFine, st_);
-        const bool want = F.zeroAvg && !ordered(d);  // the fine half of the folded prolongation's mean
-        if (resid_overlap(F)) {
-            overlapped(F, phiFine, F.d_rtiles_own, F.nrtiles_own, F.d_rtiles_rem, F.nrtiles_rem, [&](Tile* tl, int nt) {
-                launch_resid_restrict(st_, tl, nt, F.dev, lev[d + 1]->dev, resCoarse, phiFine, rhsFine, F.mgCrseRefRatio,
-                                      F.dxProduct, want ? d_partials : nullptr);
-            });
-            if (want) launch_sum_partials(st_, d_partials, F.nrtiles, d_fold + 8 * d);
-            sf_valid_[d] = want ? 1 : 0;
-            return;
-        }
-        xchg(F, phiFine);
-        if (diri_) apply_diri(d, phiFine, true);  // homogeneous Dirichlet ghosts, as residual() fills them
-        if (profiling_ && d == 0) prof_begin(1);
-        launch_resid_restrict(st_, F.d_rtiles, F.nrtiles, F.dev, lev[d + 1]->dev, resCoarse, phiFine, rhsFine,
-                              F.mgCrseRefRatio, F.dxProduct, want ? d_partials : nullptr);
-        if (want) launch_sum_partials(st_, d_partials, F.nrtiles, d_fold + 8 * d);
-        sf_valid_[d] = want ? 1 : 0;
-        if (profiling_ && d == 0) prof_end(1);
+    if (ortho_march(d)) {
+        march_restrict(d, resCoarse, phiFine, rhsFine);
         return;
     }
     residual(d, f_scratch[d], phiFine, rhsFine);
     launch_restrict(st_, lev[d + 1]->dev, lev[d]->dev, resCoarse, f_scratch[d], lev[d]->mgCrseRefRatio);
-}
-
-const double* PressureSolver::prolong_increment(int d, double* phiFine, const double* corrCoarse, bool defer_mean)
-{
-    // ConstInterpPS / ZeroAvgConstInterpPS, ProlongationStrategy.cpp:49-164.  The two scalar
-    // MPI_Allreduce calls of the reference become one 2-element device-side reduction.
-    Level& F = *lev[d];
-    const bool os = F.zeroAvg && ord_sharded(d);
-    launch_prolong(st_, F.dev, lev[d + 1]->dev, phiFine, corrCoarse, F.mgCrseRefRatio, F.zeroAvg && !os, F.dxProduct,
-                   d_partials, d_scalars + SLOT_SUMS, F.field_elems, ordered(d));
-    if (F.zeroAvg) {
-        if (os) ordered_sums(d, phiFine, F.dev.jinv, 6, F.dxProduct, d_scalars + SLOT_SUMS);
-        else comm_->allreduce(d_scalars + SLOT_SUMS, 2, 0, st_);
-        if (defer_mean) return d_scalars + SLOT_SUMS;
-        launch_sub_mean(st_, phiFine, F.field_elems, d_scalars + SLOT_SUMS);
-    }
-    return nullptr;
 }
 
 void PressureSolver::pre_cond(int d, double* phi, const double* rhs)
@@ -1753,23 +1784,7 @@ void PressureSolver::cycle_down(int d, double* corr, const double* res, bool cor
 void PressureSolver::cycle_up(int d, double* corr, const double* res)
 {
     if (fold_prolong(d)) {
-        // Large level: neither the prolongation nor the zero-average mean removal gets a pass of its own -- the first
-        // post-smoothing sweep reads corr + coarse(i/r) - mean.  mean = (S_f + S_c) / V with S_f = sum dvol * corr
-        // (gathered by the fused restriction), S_c = sum over coarse cells of coarse * (volume of its children), V the
-        // level's volume: the same number as ZeroAvgConstInterpPS's sum dvol * (corr + coarse) / sum dvol up to the
-        // association of the (already tree-ordered) sum.
-        Level& F = *lev[d];
-        Level& C = *lev[d + 1];
-        xchg(C, f_corr[d + 1]);
-        const double* shift = nullptr;
-        if (F.zeroAvg) {
-            double* s = d_fold + 8 * d;
-            launch_reduce(st_, C.dev, f_corr[d + 1], f_W[d + 1], 0, d_partials, s + 1);
-            comm_->allreduce(s, 2, 0, st_);
-            launch_combine_sums(st_, s + 3, s, s + 1, s + 2);
-            shift = s + 3;
-        }
-        relax(d, corr, res, prm.num_smooth_up, false, shift, &C, f_corr[d + 1]);
+        fold_up(d, corr, res, f_corr[d + 1], true);
         return;
     }
     // the zero-average mean is folded into the first post-smoothing sweep when that sweep is the fused kernel
@@ -2201,21 +2216,6 @@ void PressureSolver::mp_convert_metric()
     }
 }
 
-MetricPtrs<float> PressureSolver::mp_metric(int d) const
-{
-    const Depth32& z = f32_[d];
-    return MetricPtrs<float>{{z.jg[0], z.jg[1], z.jg[2]}, z.jinv};
-}
-
-// xchg() of an fp32 field: the same plan, fp32 messages
-void PressureSolver::xchg32(const Level& L, float* f)
-{
-    const bool timed = profiling_ && !L.plan.peers.empty();
-    if (timed) prof_begin(2);
-    L.exchange(f, st_);
-    if (timed) prof_end(2);
-}
-
 void PressureSolver::exchange_bytes(long long out2[2]) const
 {
     out2[0] = out2[1] = 0;
@@ -2223,90 +2223,11 @@ void PressureSolver::exchange_bytes(long long out2[2]) const
         for (int q = 0; q < 2; ++q) out2[q] += L->sent_bytes[q];
 }
 
-// relax() on its fused path
-void PressureSolver::relax32(int d, float* e, const float* res, int iters, bool e_zero, const double* e_shift,
-                             const Level* e_plus_level, const float* e_plus)
-{
-    Level& L = *lev[d];
-    static const bool no_zero_start = getenv("SOMAR_NO_ZERO_START") != nullptr;
-    if (e_zero && no_zero_start) {
-        launch_set(st_, e, L.field_elems, 0.0f);
-        e_zero = false;
-    }
-    xchg32(L, const_cast<float*>(res));
-    float* cur = e;
-    float* alt = f32_[d].pp;
-    for (int it = 0; it < iters; ++it) {
-        const bool zin = e_zero && it == 0;
-        int mode = 0;
-        if (zin) mode = 1;
-        else if (it == 0 && e_plus) mode = e_shift ? 4 : 3;
-        else if (it == 0 && e_shift) mode = 2;
-        if (!zin && fused_overlap(L)) {   // as relax(): the remote half of the exchange under the tiles that read none of it
-            overlapped(L, cur, L.d_ftiles_own, L.nftiles_own, L.d_ftiles_rem, L.nftiles_rem, [&](Tile* tl, int nt) {
-                launch_gsrb_fused(st_, tl, nt, L.dev, mp_metric(d), alt, cur, res, mode, e_shift,
-                                  e_plus_level ? &e_plus_level->dev : nullptr, e_plus, L.mgCrseRefRatio);
-            });
-            std::swap(cur, alt);
-            continue;
-        }
-        if (!zin) xchg32(L, cur);
-        if (profiling_ && d == 0) prof_begin(0);
-        launch_gsrb_fused(st_, L.d_ftiles, L.nftiles, L.dev, mp_metric(d), alt, cur, res, mode, e_shift,
-                          e_plus_level ? &e_plus_level->dev : nullptr, e_plus, L.mgCrseRefRatio);
-        if (profiling_ && d == 0) prof_end(0);
-        std::swap(cur, alt);
-    }
-    if (cur != e) launch_copy(st_, e, cur, L.field_elems);
-}
-
-// restrict_residual() on its marching path, with the fine half of the folded prolongation's mean
-void PressureSolver::restrict32(int d, float* resCoarse, float* phiFine, const float* rhsFine)
-{
-    Level& F = *lev[d];
-    const bool want = F.zeroAvg;   // (never an ordered level)
-    if (resid_overlap(F)) {   // as restrict_residual() (never with Dirichlet sides)
-        overlapped(F, phiFine, F.d_rtiles_own, F.nrtiles_own, F.d_rtiles_rem, F.nrtiles_rem, [&](Tile* tl, int nt) {
-            launch_resid_restrict(st_, tl, nt, F.dev, mp_metric(d), lev[d + 1]->dev, resCoarse, phiFine, rhsFine,
-                                  F.mgCrseRefRatio, F.dxProduct, want ? d_partials : nullptr);
-        });
-        if (want) launch_sum_partials(st_, d_partials, F.nrtiles, d_fold + 8 * d);
-        sf_valid_[d] = want ? 1 : 0;
-        return;
-    }
-    xchg32(F, phiFine);
-    if (diri_) launch_ghost_ops(st_, F.dev, d_diri_ops_[d], n_diri_ops_[d], phiFine);   // homogeneous Dirichlet ghosts
-    if (profiling_ && d == 0) prof_begin(1);
-    launch_resid_restrict(st_, F.d_rtiles, F.nrtiles, F.dev, mp_metric(d), lev[d + 1]->dev, resCoarse, phiFine, rhsFine,
-                          F.mgCrseRefRatio, F.dxProduct, want ? d_partials : nullptr);
-    if (profiling_ && d == 0) prof_end(1);
-    if (want) launch_sum_partials(st_, d_partials, F.nrtiles, d_fold + 8 * d);
-    sf_valid_[d] = want ? 1 : 0;
-}
-
-// cycle_up() on its fold path: the coarse correction (fp32) read by the first post-smoothing sweep
-void PressureSolver::cycle_up32(int d, float* corr, const float* res)
-{
-    Level& F = *lev[d];
-    Level& C = *lev[d + 1];
-    float* cc = f32_[d + 1].corr;
-    if (d + 1 < mp_K_) xchg32(C, cc);   // (at the seam the fp64 correction was exchanged before its conversion)
-    const double* shift = nullptr;
-    if (F.zeroAvg) {
-        double* s = d_fold + 8 * d;
-        launch_reduce(st_, C.dev, cc, f_W[d + 1], 0, d_partials, s + 1);
-        comm_->allreduce(s, 2, 0, st_);   // (S_f, S_c) over the ranks, in fp64 as in cycle_up()
-        launch_combine_sums(st_, s + 3, s, s + 1, s + 2);
-        shift = s + 3;
-    }
-    relax32(d, corr, res, prm.num_smooth_up, false, shift, &C, cc);
-}
-
 void PressureSolver::cycle32(int d, float* corr, const float* res, bool corr_zero)
 {
-    relax32(d, corr, res, prm.num_smooth_down, corr_zero, nullptr, nullptr, nullptr);
+    fused_sweeps<float>(d, corr, res, prm.num_smooth_down, corr_zero, nullptr, nullptr, nullptr);
     float* rc = f32_[d + 1].res;
-    restrict32(d, rc, corr, res);
+    march_restrict(d, rc, corr, res);
     if (d + 1 < mp_K_) {
         cycle32(d + 1, f32_[d + 1].corr, rc, true);
     } else {
@@ -2318,7 +2239,7 @@ void PressureSolver::cycle32(int d, float* corr, const float* res, bool corr_zer
         xchg(*lev[K], f_corr[K]);
         launch_convert(st_, f32_[K].corr, f_corr[K], n);
     }
-    cycle_up32(d, corr, res);
+    fold_up(d, corr, res, f32_[d + 1].corr, d + 1 < mp_K_);   // (the seam's correction was exchanged in fp64, above)
 }
 
 // e (fp64, depth 0) := the fp32 cycle's correction of res, or (add_to_phi) e += it.  rnorm: the max norm of res (and of an

@@ -8,6 +8,7 @@
 // All level data stay resident in HBM for the life of the solver; the host only sequences
 // kernel launches on one HIP stream and reads back the few scalars the stopping tests need.
 #pragma once
+#include <exception>
 #include <memory>
 #include <vector>
 
@@ -130,12 +131,15 @@ public:
     // homogeneous: physical BC values taken as zero (only Dirichlet sides can carry a value here)
     void residual(int d, double* out, double* phi, const double* rhs, bool homogeneous = true);   // homogeneous CF ghosts, then residual_i
     void apply_op(int d, double* out, double* phi, bool homogeneous = true);
-    void residual_i(int d, double* out, double* phi, const double* rhs, bool homogeneous = true); // residualI: CF ghosts as they are
+    void residual_i(int d, double* out, double* phi, const double* rhs, bool homogeneous = true) // residualI: CF ghosts as they are
+    {
+        operator_i(d, 0, out, phi, rhs, homogeneous);
+    }
     // residualI of depth 0 and its J-weighted average (MAPPEDAVERAGE2) onto the layout C coarsened by r, in ONE marching pass
     // (the fine residual is never stored); CF ghosts of phi as they are.  false: not available here (non-diagonal metric, small
     // level, a ratio entry other than 1 or 2) -- the caller then runs residual_i + launch_restrict
     bool residual_restrict_i(const LevelDev& C, double* crse, double* phi, const double* rhs, const int r[3]);
-    void apply_op_i(int d, double* out, double* phi, bool homogeneous = true);
+    void apply_op_i(int d, double* out, double* phi, bool homogeneous = true) { operator_i(d, 1, out, phi, nullptr, homogeneous); }
     // Dirichlet sides (EllipticConstDiriBCGhostClass, BCInterface/EllipticBCUtils.cpp:382-424): values per
     // {loX,hiX,loY,hiY,loZ,hiZ}, before finalize.  Such a solver runs the two-pass / direct-load kernels.
     void set_bc_values(const double v[6]);
@@ -254,7 +258,12 @@ public:
 
 private:
     void cycle(int d, double* corr, const double* res, bool corr_zero = false);
-    // ---- mixed precision: the fold path of the cycle (cycle_down / restrict_residual / cycle_up / relax) on fp32 fields ----
+    // residual_i (mode 0) and apply_op_i (mode 1) in one: mode 0 out = rhs - L[phi] (timed in a profiled pass), mode 1 out = L[phi] (rhs unused)
+    void operator_i(int d, int mode, double* out, double* phi, const double* rhs, bool homogeneous);
+    // prolong_from and prolong_increment in one: depth d += the coarse field on layout C (ratio r), then the zero-average mean
+    // removal (or its deferral)
+    const double* prolong_onto(int d, const LevelDev& C, const double* crse, const int r[3], double* fine, bool defer_mean);
+    // ---- mixed precision: depths 0 .. mp_K_ - 1 run the fold path of the cycle (below) on fp32 fields ----
     struct Depth32 {
         float* jg[3] = {nullptr, nullptr, nullptr};   // fp32 copies of the metric (not made where the depth is uniform)
         float* jinv = nullptr;
@@ -268,14 +277,34 @@ private:
     void mp_setup();                // after finalize: K (agreed on by every rank), buffers, metric copies
     void mp_free();
     void mp_convert_metric();       // one launch per fp32 depth (finalize, set_precision, metric refresh)
-    MetricPtrs<float> mp_metric(int d) const;
-    void xchg32(const Level& L, float* f);
-    void cycle32(int d, float* corr, const float* res, bool corr_zero);
-    void relax32(int d, float* e, const float* res, int iters, bool e_zero, const double* e_shift, const Level* e_plus_level,
-                 const float* e_plus);
-    void restrict32(int d, float* resCoarse, float* phiFine, const float* rhsFine);
-    void cycle_up32(int d, float* corr, const float* res);
+    void cycle32(int d, float* corr, const float* res, bool corr_zero);   // the fp32 driver: fold path, seam conversion, recursion
     void vcycle_mixed(double* e, const double* res, double rnorm, bool e_zero, bool add_to_phi);
+    // ---- the fold path of the cycle, ONE code path for T = double (relax / restrict_residual / cycle_up on their large-level
+    // branches) and T = float (cycle32): fused sweeps, residual + restriction in one marching pass with the fold sums, the
+    // prolongation folded into the first post-smoothing sweep.  Arguments as relax / restrict_residual take them.
+    template <class T>
+    void fused_sweeps(int d, T* e, const T* res, int iters, bool e_zero, const double* e_shift, const Level* e_plus_level,
+                      const T* e_plus);
+    template <class T>
+    void march_restrict(int d, T* resCoarse, T* phiFine, const T* rhsFine);
+    // crse: depth d + 1's correction; exchange_crse: it still needs its ghost exchange (not at the fp32 / fp64 seam, where the
+    // fp64 field was exchanged before its conversion)
+    template <class T>
+    void fold_up(int d, T* corr, const T* res, T* crse, bool exchange_crse);
+    // the element type shows in these four places only
+    template <class T>
+    T* pingpong(int d) const;                  // f_pp[d] | f32_[d].pp
+    template <class T>
+    MetricPtrs<T> metric(int d) const;         // the level's own arrays | their fp32 copies
+    void diri_homog(int d, double* f) { apply_diri(d, f, true); }   // homogeneous Dirichlet ghosts
+    void diri_homog(int d, float* f) { launch_ghost_ops(st_, lev[d]->dev, d_diri_ops_[d], n_diri_ops_[d], f); }
+    // coarse-fine ghosts (ext: plus the edge ghosts the fused sweep's red ring reads); fp32 depths have none (mixed_refusal)
+    void cf_fill(const Level& L, double* f, bool ext)
+    {
+        if (ext) L.cf_homog_ext(f, st_);
+        else L.cf_homog(f, st_);
+    }
+    void cf_fill(const Level& L, float*, bool) { SOMAR_CHECK(L.ncf == 0, "internal: an fp32 depth with coarse-fine faces"); }
     double fetch_scalar(int slot);
     void fetch_scalars(int slot, int n);
     unsigned long long fetch_seq_ = 0;
@@ -334,6 +363,12 @@ private:
     long long march_min_cells_ = 262144;  // levels at least this big use the k-marching operator/residual
     long long ordered_max_cells_ = 4096;
     bool ordered(int d) const { return lev[d]->valid_cells_global <= ordered_max_cells_; }
+    // large 3-D levels of the diagonal path run the k-marching 7-point kernels (resid_march.hip); full_march is the 19-point twin
+    bool ortho_march(int d) const
+    {
+        const Level& L = *lev[d];
+        return !full_ && L.active[2] && L.valid_cells_global >= march_min_cells_;
+    }
     // A small level that is SHARDED keeps the serial order too: every rank contributes the per-cell terms of its boxes to
     // one vector in the serial (box after box) sequence, a sum-allreduce completes it, one wavefront walks it
     // (k_ord_fill / k_reduce_ordered_flat) -- so a sharded solve adds the same numbers in the same order as one rank.
@@ -455,8 +490,9 @@ private:
     struct Prof { std::vector<hipEvent_t> a, b; int used = 0; };
     Prof prof_[4];   // 0: GSRB launches of depth 0, 1: its operator / residual launches, 2: ghost exchanges with other ranks (any
                      // depth), 3: the replicated tail of a sharded hierarchy (agglom_cycle)
-    // ghost exchange of a level of this solver (timed in a profiled pass when other ranks take part)
-    void xchg(const Level& L, double* f);
+    // ghost exchange of a level of this solver (timed in a profiled pass when other ranks take part); T: double or float
+    template <class T>
+    void xchg(const Level& L, T* f);
     // Sharded large levels: the messages of a sweep's one ghost exchange travel on a second stream while the tiles that read no
     // remote ghost cell are swept (the LooseGSRB idea, GSRB.cpp:122-140, without its change of the iteration: the fused sweep's
     // tiles are independent, so this is the same sweep bit for bit).  SOMAR_NO_OVERLAP=1 is the A/B switch.
@@ -494,6 +530,19 @@ private:
     bool profiling_ = false;
     void prof_begin(int k);
     void prof_end(int k);
+    // times what is enqueued during its life into slot k: only in a profiled pass, on depth 0 (and where `on` holds).  An error
+    // thrown inside the scope passes through it: the end event is then not recorded, as with a begin / end pair it skipped.
+    struct ProfScope {
+        PressureSolver* s;
+        int k, unwinding;
+        ProfScope(PressureSolver& ps, int d, int k_, bool on = true)
+            : s(ps.profiling_ && d == 0 && on ? &ps : nullptr), k(k_), unwinding(std::uncaught_exceptions())
+        {
+            if (s) s->prof_begin(k);
+        }
+        ~ProfScope() noexcept(false) { if (s && std::uncaught_exceptions() == unwinding) s->prof_end(k); }
+        ProfScope(const ProfScope&) = delete;
+    };
 };
 
 }  // namespace somar

@@ -143,3 +143,39 @@ def smooth_cc_velocity(so, dom, grids, ghost, ncomp=3):
             f.a[..., d] = (np.sin(2 * np.pi * (I + 0.5) / n[0] + 0.1 * d) * np.cos(2 * np.pi * (J + 0.5) / n[1] + 0.3)
                            * np.cos(2 * np.pi * (K + 0.5) / n[2] + d)) + 0.25 * d
     return vel
+
+
+def march_columns(n0, classes):
+    """The tile columns [(width, lane class)] of one box n0 cells wide in Level::build_march_tiles' marching tables
+    (somar_amd/csrc/level.cpp:563-582, `columns`, with FT_I = 124 and min_gain = 0.85), restated.  Class 0: 124 output
+    columns, one region row per wavefront; class 1: 60 columns, two rows; class 4: 4 columns, sixteen rows.  classes off
+    (or an odd n0): balanced columns of equal (even) width, all class 0.  With classes on, a box is cut into 124-wide
+    columns and its remainder into the narrow classes, taken where that costs at most 0.85 of the equal columns'
+    workgroup-marches (a class-1 workgroup counted as a half, class 4 as a quarter)."""
+    FT_I = 124
+    ncol = -(-n0 // FT_I)
+    w = -(-n0 // ncol)
+    w = min(w + (w & 1), FT_I)
+    eq = [(w, 0)] * (-(-n0 // w))
+    if not classes or n0 & 1:
+        return eq
+    v, rem, cost = [], n0, 0.0
+    while rem >= FT_I:
+        v.append((FT_I, 0))
+        rem -= FT_I
+        cost += 1.0
+    if rem > 76:
+        v.append((rem, 0))
+        rem = 0
+        cost += 1.0
+    if rem > 16:
+        w = min(rem, 60)
+        v.append((w, 1))
+        rem -= w
+        cost += 0.5
+    while rem > 0:
+        w = min(rem, 4)
+        v.append((w, 4))
+        rem -= w
+        cost += 0.25
+    return v if cost <= 0.85 * len(eq) else eq

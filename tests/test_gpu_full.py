@@ -140,7 +140,7 @@ def _setup2(so, case, **kw):
 
 
 @pytest.mark.parametrize("case", CASES_2D)
-def test_2d_full_operator_and_gsrb_bit_exact(oracle, case):
+def test_2d_full_operator_and_gsrb_bit_exact(oracle, case, kernel_path):
     from somar_amd import api as F
     so = oracle
     dom, grids, fac, gpu = _setup2(so, case)

@@ -508,9 +508,16 @@ int somar_altered_jgup(long long n, double* dest, const double* nsq_fc, const do
  * (:1523-1640) decides from the ends: columns that are Neumann at both ends take the Neumann-Neumann line solver and the
  * horizontal (flat) problem; when NO column is Neumann-Neumann -- a Dirichlet (free-surface) top or bottom, or columns ending
  * under the coarser level -- every order is one LepticLapackVerticalSolver + dptsv pass (LevelLepticSolverF.ChF:161-283) and
- * there is no flat problem; a layout mixing the two kinds is refused.  Diagonal or non-diagonal metric
- * (somar_solver_set_metric_full on the level handle), homogeneous-Neumann lateral boundaries, no periodic direction;
- * coarse-fine boundaries through somar_amr_enable_leptic.
+ * there is no flat problem.  A level of a hierarchy that MIXES the two kinds (refined in the vertical as well, so that some
+ * boxes span the water column and their neighbours stop under the coarser level: m_flatDI / m_flatDIComplement, :318-333) is
+ * taken for a diagonal metric on one rank: the flat problem then holds the spanning boxes only, the other columns take the
+ * dptsv pass.  Such a level needs a coarser one, so it arises through somar_amr_enable_leptic only, never through
+ * somar_leptic_create (a column ending inside the domain of a level without a coarser one is ill-formed).  Such a level solve stalls by itself, as the reference's
+ * does (the horizontal correction reaches the spanning boxes only), and works as the smoother of somar_amr_solve_leptic; keep
+ * max_order where the last order still reduces the residual: the full-multigrid fallback fails on such a level and the solve
+ * then returns an error, not a correction.  Refused: a mixed level with a non-diagonal metric or sharded over ranks.
+ * Diagonal or non-diagonal metric (somar_solver_set_metric_full on the level handle), homogeneous-Neumann lateral
+ * boundaries, no periodic direction; coarse-fine boundaries through somar_amr_enable_leptic.
  * somar_leptic_params_t = setParameters / setHorizMGParameters / setHorizBottomParameters / setFullMGParameters /
  * setFullBottomParameters (:516-640); defaults = setDefaultParameters (:461-508). */
 typedef struct somar_leptic somar_leptic_t; /* opaque */
@@ -578,8 +585,8 @@ int somar_heat_flux_download(somar_solver_t* s, int dir, int patch, double* host
 /* AMRLepticSolver (calculus/LepticSolver/AMRLepticSolver.cpp:68-672; AMRPressureSolver.cpp:383-403, 542-550 when
  * s_useAMRLepticSolver is set): the composite iteration of somar_amr_solve with LevelLepticSolver::solve in place of
  * relax and of the base level's multigrid cycle.  somar_amr_enable_leptic (after somar_amr_finalize) defines one leptic level
- * solver per level on the level's own operator, homogeneous, no coarse phi (init, :185-195); levels must consist of
- * vertically complete columns (refinement ratios (r, r, 1)).  base_from_restricted = 0 is the reference as written: the
+ * solver per level on the level's own operator, homogeneous, no coarse phi (init, :185-195); no box of a level may be split
+ * in the vertical (refinement ratios (r, r, 1), or vertical refinement whose boxes end under the coarser level, see above).  base_from_restricted = 0 is the reference as written: the
  * base level solves a_uberCorrection from a_uberResidual and contributes nothing to the finer levels (:444-449), so a
  * multi-level solve drifts after its first cycles; 1 (NOT the reference) feeds the base level the restricted residual, as
  * MappedAMRMultiGrid::AMRVCycle does.  Stats: exit_status bitfield and history as somar_amr_solve; status 2 ("blew up") is
@@ -587,6 +594,11 @@ int somar_heat_flux_download(somar_solver_t* s, int dir, int patch, double* host
 int somar_amr_enable_leptic(somar_amr_t* a, const somar_leptic_params_t* lp, int base_from_restricted);
 int somar_amr_solve_leptic(somar_amr_t* a, int l_max, int l_base, int zero_phi, int force_homogeneous, somar_stats_t* stats);
 int somar_amr_leptic_stats(somar_amr_t* a, int level, somar_leptic_stats_t* stats); /* of the level's LAST leptic solve */
+/* somar_leptic_part for the leptic level solver of level `level` (after somar_amr_enable_leptic): read-only views for tests
+ * and diagnostics, which = 1 / 2 as there.  On a level that mixes spanning columns with coarse-fine ended ones the flat solver
+ * has one patch per SPANNING box, in the order of the level's boxes.  The views belong to the hierarchy; the next
+ * somar_amr_enable_leptic and somar_amr_destroy end them. */
+int somar_amr_leptic_part(somar_amr_t* a, int level, int which, somar_solver_t** solver);
 
 /* Metric producers.  The coordinate maps themselves stay with the caller (LevelGeometry /
  * GeoSourceInterface subclasses evaluate dx/dXi); what the device takes over is

@@ -184,6 +184,7 @@ _SIGS = {
     "somar_amr_enable_leptic": [_H, C.POINTER(LepticParams), C.c_int],
     "somar_amr_solve_leptic": [_H, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Stats)],
     "somar_amr_leptic_stats": [_H, C.c_int, C.POINTER(LepticStats)],
+    "somar_amr_leptic_part": [_H, C.c_int, C.c_int, C.POINTER(_H)],
     "somar_diag_stream_probe": [C.c_int, C.c_longlong, C.c_int, _PD],
     "somar_metric_jgup_from_dxdxi": [C.c_longlong, C.c_int, _PD, _PD, C.c_double, _PD],
     "somar_solver_set_metric_uniform": [_H, _PD],
@@ -374,6 +375,19 @@ class AMRPressureSolver:
         _ck(lib().somar_amr_leptic_stats(self._amr, level, C.byref(st)))
         return {"exitStatus": st.exit_status, "orders": st.orders, "horizSolves": st.horiz_solves,
                 "usedFullSolver": bool(st.used_full_solver), "resNorms": [st.res_norms[i] for i in range(st.nres)]}
+
+    def lepticPart(self, level, which):
+        """Read-only view of an internal solver of the level's leptic solver: which = 1 the J-scaled 3-D operator (PHI = the
+        last order's correction), 2 the flat solver (PHI / RHS = the last horizontal solution / right-hand side).  Ends
+        with the next enableLeptic or undefine."""
+        v = AMRPressureSolver()
+        lh = _H()
+        _ck(lib().somar_amr_leptic_part(self._amr, level, which, C.byref(lh)))
+        v._h, v._borrowed = lh, True
+        n = C.c_int()
+        _ck(lib().somar_solver_num_local_patches(lh, C.byref(n)))
+        v.num_local_patches = n.value
+        return v
 
     def solveAMRHost(self, phi, rhs, lmin, lmax, zeroPhi=True, forceHomogeneous=False, phi_ghost=(1, 1, 1),
                      rhs_ghost=(0, 0, 0)):

@@ -182,6 +182,7 @@ public:
     void enable_leptic(const LepticParams& lp, bool baseFromRestricted);
     void solve_leptic(int l_max, int l_base, bool zeroPhi, bool forceHomogeneous, SolveStats& st);
     const LepticStats& leptic_stats(int l) const { return lepStats_.at(l); }
+    LepticSolver* leptic_solver(int l) { return l >= 0 && l < (int)leptic_.size() ? leptic_[l].get() : nullptr; }   // null before enable_leptic
 
     // BaseProjector<T>::levelProject -> project(lmin = lmax = l) (projection/BaseProjectorI.H:176-366) on the resident
     // velocity of level l: centring 0 = LevelMACProjector (vel()), 1 = LevelCCProjector (cc_vel(), level l-1's supplies the

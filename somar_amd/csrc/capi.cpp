@@ -34,7 +34,19 @@ struct somar_leptic {
 struct somar_amr {
     AMRSolver* amr = nullptr;
     std::vector<somar_solver*> levels;
+    std::vector<somar_solver*> lepParts;   // views handed out by somar_amr_leptic_part, [2 level + which - 1]; null until asked for
 };
+
+static void drop_leptic_parts(somar_amr* a)
+{
+    for (somar_solver* s : a->lepParts) {
+        if (!s) continue;
+        if (s->ev0) hipEventDestroy(s->ev0);
+        if (s->ev1) hipEventDestroy(s->ev1);
+        delete s;
+    }
+    a->lepParts.clear();
+}
 
 static thread_local std::string g_err;
 
@@ -1062,6 +1074,7 @@ int somar_amr_destroy(somar_amr_t* a)
 {
     API_BEGIN
     if (a) {
+        drop_leptic_parts(a);
         for (somar_solver* s : a->levels) {
             if (s->ev0) hipEventDestroy(s->ev0);
             if (s->ev1) hipEventDestroy(s->ev1);
@@ -1752,7 +1765,31 @@ int somar_amr_enable_leptic(somar_amr_t* a, const somar_leptic_params_t* lp, int
 {
     API_BEGIN
     SOMAR_CHECK(a, "null argument");
+    drop_leptic_parts(a);   // views of the level solvers that enable_leptic replaces
     a->amr->enable_leptic(to_leptic_params(lp), base_from_restricted != 0);
+    API_END
+}
+
+int somar_amr_leptic_part(somar_amr_t* a, int level, int which, somar_solver_t** out)
+{
+    API_BEGIN
+    SOMAR_CHECK(a && out && level >= 0 && level < a->amr->nlevels(), "bad argument");
+    SOMAR_CHECK(which == 1 || which == 2, "which: 1 (J-scaled 3-D solver) or 2 (flat solver)");
+    LepticSolver* lep = a->amr->leptic_solver(level);
+    SOMAR_CHECK(lep, "somar_amr_leptic_part before somar_amr_enable_leptic");
+    PressureSolver* ps = which == 1 ? &lep->vert() : lep->horiz_ptr();
+    SOMAR_CHECK(ps, "this level has no flat problem: no column is Neumann-Neumann "
+                    "(gatherVerticalBCTypes switched the horizontal solves off)");
+    a->lepParts.resize(2 * (size_t)a->amr->nlevels(), nullptr);
+    somar_solver*& s = a->lepParts[2 * level + which - 1];
+    if (!s) {
+        s = new somar_solver;
+        s->ps = ps;
+        s->owned = false;
+        SOMAR_HIP(hipEventCreate(&s->ev0));
+        SOMAR_HIP(hipEventCreate(&s->ev1));
+    }
+    *out = s;
     API_END
 }
 

@@ -2,6 +2,7 @@
 #include "leptic.h"
 
 #include <cmath>
+#include <cstring>
 
 namespace somar {
 
@@ -42,6 +43,8 @@ LepticSolver::~LepticSolver()
     hipFree(d_avg);
     hipFree(d_vbc);
     hipFree(d_bad);
+    hipFree(d_stiles);
+    hipFree(d_flatOf);
     horiz_.reset();
     vert_.reset();
     own_orig_.reset();
@@ -87,6 +90,7 @@ void LepticSolver::define_inner(const IBox& domain, const bool periodic[3], cons
     // or, inside the domain, a coarse-fine interface over the whole box end (anything else: "Vertical grids are ill-formed")
     vbc_.assign(2 * boxes.size(), 0);
     bool anyNN = false, allNN = true;
+    flatDI_.clear();
     for (size_t bi = 0; bi < boxes.size(); ++bi) {
         const IBox& b = boxes[bi];
         SOMAR_CHECK(b.size(2) >= 2, "the vertical line solver wants at least two cells per column");
@@ -108,11 +112,16 @@ void LepticSolver::define_inner(const IBox& domain, const bool periodic[3], cons
         const bool nn = vbc_[2 * bi] == 0 && vbc_[2 * bi + 1] == 0;
         anyNN = anyNN || nn;
         allNN = allNN && nn;
+        if (nn) flatDI_.push_back((int)bi);
     }
     doHorizSolve_ = anyNN;
-    // m_flatDI / m_flatDIComplement (columns that do not span the domain next to columns that do, :318-333) are not built
-    SOMAR_CHECK(!anyNN || allNN, "the leptic solver takes layouts whose columns are ALL Neumann-Neumann or none of them "
-                                 "(Dirichlet / coarse-fine ended): mixed layouts are not implemented");
+    // m_flatDI / m_flatDIComplement (:318-333): the Neumann-Neumann boxes span the domain and carry the flat problem, the others
+    // (the complement) take no part in it.  A Neumann-Neumann column needs Neumann walls, and between Neumann walls every
+    // spanning column is Neumann-Neumann: the two notions cannot come apart.
+    mixed_ = anyNN && !allNN;
+    SOMAR_CHECK(!mixed_ || !comm_ || comm_->size == 1,
+                "the leptic solver takes a level that mixes Neumann-Neumann columns with Dirichlet / coarse-fine ended ones "
+                "on one rank only: the flat problem's patch map is not built per rank");
     dzCrse_ = dxCrse ? dxCrse[2] : 0.0;
     for (int d = 0; d < 3; ++d) dx_[d] = dx[d];
     H_ = prm.domainHeight > 0.0 ? prm.domainHeight : dx[2] * domain.size(2);
@@ -124,20 +133,26 @@ void LepticSolver::define_inner(const IBox& domain, const bool periodic[3], cons
     vert_->define(domain, periodic, dx, bc_type, boxes, owner, 0.0, 1.0, pf, dxCrse);
     vert_->probe_eps = probeEps;
     if (!doHorizSolve_) return;   // no Neumann-Neumann column: no excess, no flat problem (:304)
-    // flat grids: the same boxes, one cell thick at the domain's lowest vertical index           :304-432
+    // flat grids: the Neumann-Neumann boxes, one cell thick at the domain's lowest vertical index :304-432
     IBox flatDom = domain;
     flatDom.hi[2] = flatDom.lo[2];
-    std::vector<IBox> flat(boxes);
+    // createHorizontalSolverGrids (LepticBoxUtils.cpp:100-117): the spanning boxes only.  On a mixed level the footprint of
+    // the complement is then a coarse-fine boundary of the flat problem, and horizRemoveAvg_ comes out false
+    std::vector<IBox> flat;
+    std::vector<int> flatOwner;
     horizCells_ = 0;
-    for (IBox& b : flat) {
-        b.hi[2] = b.lo[2];
+    for (int bi : flatDI_) {
+        IBox b = boxes[bi];
+        b.lo[2] = b.hi[2] = domain.lo[2];
         horizCells_ += b.numPts();
+        flat.push_back(b);
+        flatOwner.push_back(owner[bi]);
     }
     horizRemoveAvg_ = horizCells_ == flatDom.numPts();
     SolverParams ph = prm.horiz;
     ph.spaceDim = 2;
     horiz_.reset(new PressureSolver(comm_, st_));
-    horiz_->define(flatDom, periodic, dx, bc_type, flat, owner, 0.0, 1.0, ph, dxCrse);   // forceDxCrse(m_dxCrse), :381
+    horiz_->define(flatDom, periodic, dx, bc_type, flat, flatOwner, 0.0, 1.0, ph, dxCrse);   // forceDxCrse(m_dxCrse), :381
     horiz_->probe_eps = probeEps;
 }
 
@@ -145,6 +160,9 @@ void LepticSolver::finalize()
 {
     SOMAR_CHECK(orig_ && !finalized_, "finalize before define / twice");
     full_ = orig_->is_full();
+    // levelVertHorizGradient hands the complement's Neumann ends boundary data too, non-zero only with cross terms
+    SOMAR_CHECK(!(mixed_ && full_), "the leptic solver takes a level that mixes Neumann-Neumann columns with Dirichlet / "
+                                    "coarse-fine ended ones for a diagonal metric only: this level has a non-diagonal metric");
     if (full_) {
         // the J-scaled operator and the flat problem inherit LevelGeometry::isDiagonal() == false: 19-point / 9-point kernels
         vert_->make_full();
@@ -170,19 +188,38 @@ void LepticSolver::finalize()
         f_rhsB = V.alloc_field();
         f_gam = V.alloc_field();
         f_efac = V.alloc_field();
-        std::vector<int> local(2 * (size_t)std::max(1, V.npatches()), 0);
-        for (int pi = 0; pi < V.npatches(); ++pi)
-            for (int s2 = 0; s2 < 2; ++s2) local[2 * pi + s2] = vbc_[2 * V.local[pi] + s2];
-        SOMAR_HIP(hipMalloc(&d_vbc, local.size() * sizeof(int)));
-        SOMAR_HIP(hipMemcpy(d_vbc, local.data(), local.size() * sizeof(int), hipMemcpyHostToDevice));
-        SOMAR_HIP(hipMalloc(&d_bad, sizeof(int)));
-        SOMAR_HIP(hipMemset(d_bad, 0, sizeof(int)));
+        upload_vbc();
         SOMAR_HIP(hipDeviceSynchronize());
         finalized_ = true;
         return;
     }
     Level& F = horiz_->level(0);
-    SOMAR_CHECK(V.npatches() == F.npatches(), "internal: layouts differ");
+    if (mixed_) {
+        // the spanning patches' column tiles, and for every vertical patch its flat patch (one rank: patch == box index)
+        std::vector<int> flatPatch(V.boxes.size(), -1);
+        for (size_t h = 0; h < flatDI_.size(); ++h) flatPatch[flatDI_[h]] = (int)h;
+        SOMAR_CHECK(F.npatches() == (int)flatDI_.size(), "internal: layouts differ");
+        std::vector<PatchDesc> flatOf(V.npatches());
+        std::memset(flatOf.data(), 0, flatOf.size() * sizeof(PatchDesc));
+        for (int pi = 0; pi < V.npatches(); ++pi) {
+            const int h = flatPatch[V.local[pi]];
+            if (h < 0) continue;
+            const PatchDesc &vp = V.hpatches[pi], &fp = F.hpatches[h];
+            SOMAR_CHECK(vp.lo[0] == fp.lo[0] && vp.lo[1] == fp.lo[1] && vp.n[0] == fp.n[0] && vp.n[1] == fp.n[1],
+                        "internal: a flat patch is not the footprint of its spanning patch");
+            flatOf[pi] = fp;
+        }
+        std::vector<Tile> st;
+        for (const Tile& t : V.hctiles)
+            if (flatPatch[V.local[t.patch]] >= 0) st.push_back(t);
+        nstiles = (int)st.size();
+        SOMAR_HIP(hipMalloc(&d_stiles, st.size() * sizeof(Tile)));
+        SOMAR_HIP(hipMemcpy(d_stiles, st.data(), st.size() * sizeof(Tile), hipMemcpyHostToDevice));
+        SOMAR_HIP(hipMalloc(&d_flatOf, flatOf.size() * sizeof(PatchDesc)));
+        SOMAR_HIP(hipMemcpy(d_flatOf, flatOf.data(), flatOf.size() * sizeof(PatchDesc), hipMemcpyHostToDevice));
+    } else {
+        SOMAR_CHECK(V.npatches() == F.npatches(), "internal: layouts differ");
+    }
     // metric of the J-scaled operator: the level's J g^{ab}, J^{-1} := 1
     if (full_) {
         for (int a = 0; a < 3; ++a)
@@ -193,7 +230,7 @@ void LepticSolver::finalize()
     launch_set(st_, V.dev.jinv, V.field_elems, 1.0);
     // metric of the flat problem: vertical average of the horizontal components, J^{-1} := 1
     if (full_) launch_lep_avg_metric_full(st_, V.d_ctiles, V.nctiles, V.ctile_j, V.dev, F.dev);
-    else launch_lep_avg_metric(st_, V.d_ctiles, V.nctiles, V.ctile_j, V.dev, F.dev);
+    else launch_lep_avg_metric(st_, span_tiles(), span_ntiles(), V.ctile_j, V.dev, flat_dev());
     launch_set(st_, F.dev.jinv, F.field_elems, 1.0);
     sync();
     vert_->finalize();
@@ -207,9 +244,26 @@ void LepticSolver::finalize()
     h_bcHi = F.alloc_field();
     h_gx = F.alloc_field();
     h_gy = F.alloc_field();
+    if (mixed_) {   // the complement's columns: dptsv factors and end codes
+        f_efac = V.alloc_field();
+        upload_vbc();
+    }
     SOMAR_HIP(hipMalloc(&d_avg, 2 * sizeof(double)));
     SOMAR_HIP(hipDeviceSynchronize());
     finalized_ = true;
+}
+
+// per local patch the (lo, hi) end codes of its columns, and the counter of non-positive dptsv pivots
+void LepticSolver::upload_vbc()
+{
+    Level& V = vert_->level(0);
+    std::vector<int> local(2 * (size_t)std::max(1, V.npatches()), 0);
+    for (int pi = 0; pi < V.npatches(); ++pi)
+        for (int s2 = 0; s2 < 2; ++s2) local[2 * pi + s2] = vbc_[2 * V.local[pi] + s2];
+    SOMAR_HIP(hipMalloc(&d_vbc, local.size() * sizeof(int)));
+    SOMAR_HIP(hipMemcpy(d_vbc, local.data(), local.size() * sizeof(int), hipMemcpyHostToDevice));
+    SOMAR_HIP(hipMalloc(&d_bad, sizeof(int)));
+    SOMAR_HIP(hipMemset(d_bad, 0, sizeof(int)));
 }
 
 void LepticSolver::refresh_metric()
@@ -227,7 +281,7 @@ void LepticSolver::refresh_metric()
     if (doHorizSolve_) {
         Level& F = horiz_->level(0);
         if (full_) launch_lep_avg_metric_full(st_, V.d_ctiles, V.nctiles, V.ctile_j, V.dev, F.dev);
-        else launch_lep_avg_metric(st_, V.d_ctiles, V.nctiles, V.ctile_j, V.dev, F.dev);
+        else launch_lep_avg_metric(st_, span_tiles(), span_ntiles(), V.ctile_j, V.dev, flat_dev());
         launch_set(st_, F.dev.jinv, F.field_elems, 1.0);
     }
     sync();
@@ -306,6 +360,11 @@ void LepticSolver::solve_fields_no_horiz(double* a_phi, const double* a_rhs, Lep
     }
     if (exitStatus != 4) launch_lep_axpy(st_, ct, nct, tj, V.dev, a_phi, f_total, 1.0);
     S.exitStatus = exitStatus;
+    check_bad();
+}
+
+void LepticSolver::check_bad()
+{
     int bad = 0;
     SOMAR_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st_));
     sync();
@@ -327,6 +386,10 @@ void LepticSolver::solve_fields(double* a_phi, const double* a_rhs, LepticStats&
     Level& F = Hs.level(0);
     const Tile* ct = V.d_ctiles;
     const int nct = V.nctiles, tj = V.ctile_j;
+    // the kernels that pair a column with its flat cell run on the spanning boxes: every box, unless the level is mixed
+    const Tile* sct = span_tiles();
+    const int nsct = span_ntiles();
+    const LevelDev Fd = flat_dev();
     const long long n = V.field_elems, hn = F.field_elems;
     const int maxOrder = prm.maxOrder;
     const double dz = dx_[2];
@@ -353,17 +416,20 @@ void LepticSolver::solve_fields(double* a_phi, const double* a_rhs, LepticStats&
             launch_set(st_, h_bcHi, hn, 0.0);
             if (full_) {
                 Vs.run_aux_program(1, vertPhi);   // ExtrapolateFaceAndCopy in z, lo then hi, order 2, in place
-                launch_lep_vhgrad(st_, ct, nct, tj, V.dev, F.dev, vertPhi, h_bcLo, h_bcHi, -1.0);
+                launch_lep_vhgrad(st_, ct, nct, tj, V.dev, Fd, vertPhi, h_bcLo, h_bcHi, -1.0);
             }
         }
         if (order >= 1 && useExcess) launch_incr(st_, h_bcHi, h_excess, 1.0, hn);
         if (useExcess) {
-            launch_lep_excess(st_, ct, nct, tj, V.dev, F.dev, rhsP, h_bcLo, h_bcHi, h_excess, -1.0 * dz);
+            launch_lep_excess(st_, sct, nsct, tj, V.dev, Fd, rhsP, h_bcLo, h_bcHi, h_excess, -1.0 * dz);
             if (order == 1) useExcess = false;
         }
         if (order == 0 && useExcess) launch_incr(st_, h_bcHi, h_excess, -1.0, hn);
 
-        launch_lep_vsolve(st_, ct, nct, tj, V.dev, F.dev, vertPhi, rhsP, f_gam, h_bcLo, h_bcHi, dz);
+        // the complement's Neumann ends roll in boundary data that stay zero for a diagonal metric: rhs + 0
+        if (mixed_) launch_lep_vsolve_mixed(st_, ct, nct, tj, V.dev, d_flatOf, vertPhi, rhsP, f_gam, f_efac, h_bcLo, h_bcHi, d_vbc,
+                                            dz, dzCrse_, d_bad);
+        else launch_lep_vsolve(st_, ct, nct, tj, V.dev, Fd, vertPhi, rhsP, f_gam, h_bcLo, h_bcHi, dz);
 
         if (useHorizPhi) {
             if (full_) {
@@ -374,13 +440,13 @@ void LepticSolver::solve_fields(double* a_phi, const double* a_rhs, LepticStats&
                     Vs.cf_ev(0, vertPhi);
                     V.exchange(vertPhi, st_);
                 }
-                launch_lep_hgrad_full(st_, ct, nct, tj, V.dev, F.dev, vertPhi, h_gx, h_gy);
+                launch_lep_hgrad_full(st_, ct, nct, tj, V.dev, Fd, vertPhi, h_gx, h_gy);
             } else {
                 if (hasCF_) V.cf_homog(vertPhi, st_);
                 V.exchange(vertPhi, st_);
-                launch_lep_hgrad(st_, ct, nct, tj, V.dev, F.dev, vertPhi, h_gx, h_gy);
+                launch_lep_hgrad(st_, sct, nsct, tj, V.dev, Fd, vertPhi, h_gx, h_gy);
             }
-            launch_lep_hrhs(st_, ct, nct, tj, V.dev, F.dev, h_gx, h_gy, h_excess, Hs.rhs(), -1.0 / dx_[0],
+            launch_lep_hrhs(st_, sct, nsct, tj, V.dev, Fd, h_gx, h_gy, h_excess, Hs.rhs(), -1.0 / dx_[0],
                             -1.0 / dx_[1], -1.0 / H_, useExcess);
             const double horizRhsNorm = Hs.norm(0, Hs.rhs(), prm.normType);
             if (prm.horizRhsTol * S.resNorms[0] > horizRhsNorm) useHorizPhi = false;
@@ -388,7 +454,7 @@ void LepticSolver::solve_fields(double* a_phi, const double* a_rhs, LepticStats&
         if (useHorizPhi) {
             Hs.solve(true, true, S.horizStats);
             if (horizRemoveAvg_) set_zero_avg(Hs.phi());
-            launch_lep_extrude(st_, ct, nct, tj, V.dev, F.dev, vertPhi, Hs.phi());
+            launch_lep_extrude(st_, sct, nsct, tj, V.dev, Fd, vertPhi, Hs.phi());
             ++S.horizSolves;
         }
 
@@ -401,6 +467,12 @@ void LepticSolver::solve_fields(double* a_phi, const double* a_rhs, LepticStats&
         if (redu <= prm.hang && order == maxOrder) {
             launch_copy(st_, Vs.rhs(), rhsP, n);
             Vs.solve(true, true, S.fullStats);  // initial guess 0, homogeneous
+            // on a mixed level the level solve stalls by itself and the fallback is known to blow up (so does the restated
+            // reference, which aborts there): an error, never a wrong correction
+            SOMAR_CHECK(!(mixed_ && S.fullStats.status != 0),
+                        "the leptic solver's full-multigrid fallback failed on a level that mixes Neumann-Neumann columns "
+                        "with Dirichlet / coarse-fine ended ones (MappedAMRMultiGrid: kaboom / solver blew up); choose a "
+                        "max_order at which the last order still reduces the residual");
             Vs.residual(0, tmpP, vertPhi, rhsP);
             resNorm = Vs.norm(0, tmpP, prm.normType);
             relResNorm = resNorm / S.resNorms[0];
@@ -425,7 +497,8 @@ void LepticSolver::solve_fields(double* a_phi, const double* a_rhs, LepticStats&
 
     if (exitStatus != 4) launch_lep_axpy(st_, ct, nct, tj, V.dev, a_phi, f_total, 1.0);
     S.exitStatus = exitStatus;
-    sync();
+    if (mixed_) check_bad();
+    else sync();
 }
 
 }  // namespace somar

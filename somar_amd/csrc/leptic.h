@@ -11,9 +11,11 @@
 // kernels (leptic_kernels.hip); the host sequences launches and reads back one norm per order.
 //
 // Scope: diagonal or non-diagonal metric; coarse-fine boundaries on the lateral sides of the columns (the level of an AMR
-// hierarchy refined by (r, r, 1): attach()); columns that are ALL Neumann-Neumann (horizontal solves) or ALL ended by a
-// Dirichlet wall / a coarse-fine interface (LepticLapackVerticalSolver + dptsv, no horizontal solves; layouts mixing the two
-// kinds raise); homogeneous-Neumann lateral boundaries,
+// hierarchy refined by (r, r, 1): attach()); columns that are ALL Neumann-Neumann (horizontal solves), ALL ended by a
+// Dirichlet wall / a coarse-fine interface (LepticLapackVerticalSolver + dptsv, no horizontal solves), or a MIX of the two on
+// one level (a fine level refined in the vertical as well: m_flatDI / m_flatDIComplement, LevelLepticSolver.cpp:318-333 --
+// the flat problem lives on the spanning boxes only, the footprint of the others is its coarse-fine boundary; diagonal
+// metric and one rank only, anything else raises); homogeneous-Neumann lateral boundaries,
 // non-periodic directions (the reference leaves the averaged gradient on a periodic horizontal boundary face
 // unset, LevelLepticSolver.cpp:997-1001, and refuses a periodic vertical, :1315).
 #pragma once
@@ -59,7 +61,9 @@ public:
     PressureSolver& orig() { return *orig_; }
     PressureSolver& vert() { return *vert_; }
     PressureSolver& horiz() { return *horiz_; }
-    PressureSolver* horiz_ptr() { return horiz_.get(); }   // null: no column is Neumann-Neumann, there is no flat problem
+    // null: no column is Neumann-Neumann, there is no flat problem.  On a mixed level (attach() only: it needs a coarser level)
+    // its patches are the spanning boxes only
+    PressureSolver* horiz_ptr() { return horiz_.get(); }
     void finalize();  // after the metric of orig() is set: finalizes all three solvers
     // after a metric refresh of orig(): the J-scaled operator's copy, the flat problem's vertical averages, then both solvers
     void refresh_metric();
@@ -98,6 +102,25 @@ private:
     double* f_efac = nullptr;
     int* d_vbc = nullptr;
     int* d_bad = nullptr;
+    void upload_vbc();
+    void check_bad();   // raises if a dptsv pivot was not positive
+    // a level that mixes Neumann-Neumann (spanning) columns with the other kind: the flat problem holds the spanning boxes only
+    // (the reference's m_flatDI), so the column kernels that touch flat fields run on the spanning boxes' tiles and find the
+    // flat patch of vertical patch p at d_flatOf[p] (complement patches: unused, zeroed)
+    bool mixed_ = false;
+    std::vector<int> flatDI_;          // global box indices of the spanning boxes, ascending
+    Tile* d_stiles = nullptr;          // the whole-column tiles of the spanning patches
+    int nstiles = 0;
+    PatchDesc* d_flatOf = nullptr;
+    // tiles / flat view for the kernels that pair a column with its flat cell: the level's own where nothing is mixed
+    const Tile* span_tiles() const { return mixed_ ? d_stiles : vert_->level(0).d_ctiles; }
+    int span_ntiles() const { return mixed_ ? nstiles : vert_->level(0).nctiles; }
+    LevelDev flat_dev() const
+    {
+        LevelDev H = horiz_->level(0).dev;
+        if (mixed_) H.patches = d_flatOf;
+        return H;
+    }
 };
 
 void launch_lep_avg_metric(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H);
@@ -113,6 +136,11 @@ void launch_lep_vsolve(hipStream_t st, const Tile* ct, int nct, int tj, const Le
                        double* phi, double* rhs, double* gam, const double* bcLo, const double* bcHi, double dz);
 void launch_lep_vsolve_lapack(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, double* phi,
                               const double* rhs, double* dfac, double* efac, const int* vbc, double dz, double dzCrse, int* bad);
+// a mixed level: per tile the Neumann-Neumann sweep or the dptsv restatement, by vbc; flatOf[patch]: the flat patch of a
+// spanning box
+void launch_lep_vsolve_mixed(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const PatchDesc* flatOf,
+                             double* phi, double* rhs, double* dfac, double* efac, const double* bcLo, const double* bcHi,
+                             const int* vbc, double dz, double dzCrse, int* bad);
 void launch_lep_hgrad(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
                       const double* phi, double* gx, double* gy);
 void launch_lep_hrhs(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,

@@ -12,7 +12,9 @@
 // runs along k, the SLOW index, and one lane owns one (i,j) column: 64 adjacent columns per wavefront make every
 // load of the k-march a unit-stride 512-byte row segment, no cross-lane traffic, no LDS.  Flat (one cell thick)
 // companions -- excess, vertical boundary data, averaged gradients, the horizontal right-hand side -- live in
-// fields of the 2-D horizontal level, whose patch p is the flattened patch p of the 3-D level.
+// fields of the 2-D horizontal level, whose patch p is the flattened patch p of the 3-D level; on a level that mixes
+// spanning columns with others the flat level holds the spanning boxes only, and hpp is then the host's table of the flat
+// patch of every 3-D patch, the launch covering the spanning boxes' tiles (LepticSolver::flat_dev / span_tiles).
 // Arithmetic follows the reference term by term (no FMA contraction): results are bit-identical to the oracle.
 #include "common.h"
 #include "kernels.h"
@@ -90,7 +92,63 @@ __global__ __launch_bounds__(512) void k_lep_excess(const Tile* __restrict__ til
 
 // verticalLineSolver, Neumann-Neumann columns: roll the boundary values into the end cells of rhs, Thomas sweep with
 // the reference's special last row, remove the column mean, roll the boundary values out again (which, as in the
-// reference, does not restore the end cells of rhs bit for bit).  gam: scratch field.
+// reference, does not restore the end cells of rhs bit for bit).  gam: scratch field.  One column, cell c0 at its foot;
+// shared by k_lep_vsolve and k_lep_vsolve_mixed.
+__device__ __forceinline__ void lep_column_nn(const long long c0, const int N, const long long sk, double* __restrict__ phi,
+                                              double* __restrict__ rhs, const double* __restrict__ jgz,
+                                              double* __restrict__ gam, const double bLo, const double bHi,
+                                              const double dzsq, const double sLo, const double sHi)
+{
+    const long long cN = c0 + (long long)(N - 1) * sk;
+    const double rollLo = 0.0 + bLo * sLo;
+    const double rollHi = 0.0 + bHi * sHi;
+    const double r0 = rhs[c0] + rollLo;
+    const double rN = rhs[cN] + rollHi;
+    // forward elimination; x goes to phi, gam to the scratch field
+    double sig = jgz[c0 + sk];  // sigma(1)
+    double cc = sig;
+    double bet = -cc;
+    double x = (r0 * dzsq) / bet;
+    double g = cc / bet;
+    phi[c0] = x;
+    gam[c0] = g;
+    double a_prev = 1.2345e10;  // a(0): the reference's sentinel, read by the last row when N == 2
+    long long c = c0 + sk;
+#pragma unroll 4
+    for (int r = 1; r <= N - 2; ++r, c += sk) {
+        const double a = sig;
+        sig = jgz[c + sk];
+        cc = sig;
+        const double b = -(a + cc);
+        bet = b - a * g;
+        x = (rhs[c] * dzsq - a * x) / bet;
+        g = cc / bet;
+        phi[c] = x;
+        gam[c] = g;
+        a_prev = a;
+    }
+    // last row as written in the reference: a(r-1), plain b(r)
+    {
+        const double b = -sig;  // sigma(N-1)
+        x = (rN * dzsq - a_prev * x) / b;
+        phi[cN] = x;
+    }
+    double avg = x;
+    c = cN - sk;
+#pragma unroll 4
+    for (int r = N - 2; r >= 0; --r, c -= sk) {
+        x = phi[c] - gam[c] * x;
+        avg = avg + x;
+        phi[c] = x;
+    }
+    avg = avg / (double)N;
+    c = c0;
+#pragma unroll 8
+    for (int r = 0; r < N; ++r, c += sk) phi[c] = phi[c] - avg;
+    rhs[c0] = r0 + rollLo * (-1.0);
+    rhs[cN] = rN + rollHi * (-1.0);
+}
+
 __global__ __launch_bounds__(512) void k_lep_vsolve(const Tile* __restrict__ tiles, const PatchDesc* __restrict__ vp,
                                                     const PatchDesc* __restrict__ hpp, double* __restrict__ phi,
                                                     double* __restrict__ rhs, const double* __restrict__ jgz,
@@ -99,61 +157,12 @@ __global__ __launch_bounds__(512) void k_lep_vsolve(const Tile* __restrict__ til
 {
     const Tile t = tiles[blockIdx.x];
     const PatchDesc p = vp[t.patch], hp = hpp[t.patch];
-    const int N = p.n[2];
-    const long long sk = p.pk;
     const double dzsq = dz * dz;
     const double sLo = 1.0 / dz, sHi = -1.0 / dz;  // -isign / dz
     for (int q = 0; q < 2; ++q) {
         const Col o = column(t, p, hp, q);
         if (!o.ok) continue;
-        const long long c0 = o.c, cN = o.c + (long long)(N - 1) * sk;
-        const double rollLo = 0.0 + bcLo[o.h] * sLo;
-        const double rollHi = 0.0 + bcHi[o.h] * sHi;
-        const double r0 = rhs[c0] + rollLo;
-        const double rN = rhs[cN] + rollHi;
-        // forward elimination; x goes to phi, gam to the scratch field
-        double sig = jgz[c0 + sk];  // sigma(1)
-        double cc = sig;
-        double bet = -cc;
-        double x = (r0 * dzsq) / bet;
-        double g = cc / bet;
-        phi[c0] = x;
-        gam[c0] = g;
-        double a_prev = 1.2345e10;  // a(0): the reference's sentinel, read by the last row when N == 2
-        long long c = c0 + sk;
-#pragma unroll 4
-        for (int r = 1; r <= N - 2; ++r, c += sk) {
-            const double a = sig;
-            sig = jgz[c + sk];
-            cc = sig;
-            const double b = -(a + cc);
-            bet = b - a * g;
-            x = (rhs[c] * dzsq - a * x) / bet;
-            g = cc / bet;
-            phi[c] = x;
-            gam[c] = g;
-            a_prev = a;
-        }
-        // last row as written in the reference: a(r-1), plain b(r)
-        {
-            const double b = -sig;  // sigma(N-1)
-            x = (rN * dzsq - a_prev * x) / b;
-            phi[cN] = x;
-        }
-        double avg = x;
-        c = cN - sk;
-#pragma unroll 4
-        for (int r = N - 2; r >= 0; --r, c -= sk) {
-            x = phi[c] - gam[c] * x;
-            avg = avg + x;
-            phi[c] = x;
-        }
-        avg = avg / (double)N;
-        c = c0;
-#pragma unroll 8
-        for (int r = 0; r < N; ++r, c += sk) phi[c] = phi[c] - avg;
-        rhs[c0] = r0 + rollLo * (-1.0);
-        rhs[cN] = rN + rollHi * (-1.0);
+        lep_column_nn(o.c, p.n[2], p.pk, phi, rhs, jgz, gam, bcLo[o.h], bcHi[o.h], dzsq, sLo, sHi);
     }
 }
 
@@ -163,6 +172,52 @@ __global__ __launch_bounds__(512) void k_lep_vsolve(const Tile* __restrict__ til
 // LAPACK dptsv (EXTERNAL), restated as dpttrf's L D L^T loop fused with dptts2's forward substitution on the way up and
 // dptts2's back substitution on the way down.  dfac / efac: scratch fields for the factors.  vbc[2 patch + side]: 0 Neum,
 // 1 Diri, 2 CF.  A non-positive pivot (dptsv's INFO != 0) is counted in *bad.
+// One column, cell c0 at its foot; shared by k_lep_vsolve_lapack and k_lep_vsolve_mixed.
+__device__ __forceinline__ void lep_column_lapack(const long long c0, const int N, const long long sk,
+                                                  double* __restrict__ phi, const double* __restrict__ rhs,
+                                                  const double* __restrict__ jgz, double* __restrict__ dfac,
+                                                  double* __restrict__ efac, const int lo, const int hi,
+                                                  const double alpha, const double invdzsq, int* __restrict__ bad)
+{
+    int info = 0;
+    // row k (1-based) sits in cell k-1; Jgzz(IDX(k)) is the low face of cell k
+    auto diag = [&](int k, long long c) {   // D(k), c = cell k-1
+        if (k == 1) {
+            if (lo == 0) return jgz[c + sk] * invdzsq;
+            if (lo == 1) return (2.0 * jgz[c] + jgz[c + sk]) * invdzsq;
+            return ((1.0 - alpha) * jgz[c] + jgz[c + sk]) * invdzsq;
+        }
+        if (k == N) {
+            if (hi == 0) return jgz[c] * invdzsq;
+            if (hi == 1) return (jgz[c] + 2.0 * jgz[c + sk]) * invdzsq;
+            return (jgz[c] + (1.0 - alpha) * jgz[c + sk]) * invdzsq;
+        }
+        return (jgz[c] + jgz[c + sk]) * invdzsq;
+    };
+    long long c = c0;
+    double d = diag(1, c);
+    double b = -rhs[c];
+    for (int k = 1; k <= N - 1; ++k, c += sk) {
+        if (!(d > 0.0)) info = 1;
+        const double ei = -jgz[c + sk] * invdzsq;          // DL(k)
+        const double e = ei / d;
+        dfac[c] = d;
+        efac[c] = e;
+        phi[c] = b;
+        d = diag(k + 1, c + sk) - e * ei;
+        b = -rhs[c + sk] - b * e;
+    }
+    if (!(d > 0.0)) info = 1;
+    double x = b / d;                                        // B(N) / D(N)
+    phi[c] = x;
+    c -= sk;
+    for (int k = N - 1; k >= 1; --k, c -= sk) {
+        x = phi[c] / dfac[c] - x * efac[c];
+        phi[c] = x;
+    }
+    if (info) atomicAdd(bad, 1);
+}
+
 __global__ __launch_bounds__(512) void k_lep_vsolve_lapack(const Tile* __restrict__ tiles, const PatchDesc* __restrict__ vp,
                                                            double* __restrict__ phi, const double* __restrict__ rhs,
                                                            const double* __restrict__ jgz, double* __restrict__ dfac,
@@ -171,8 +226,6 @@ __global__ __launch_bounds__(512) void k_lep_vsolve_lapack(const Tile* __restric
 {
     const Tile t = tiles[blockIdx.x];
     const PatchDesc p = vp[t.patch];
-    const int N = p.n[2];
-    const long long sk = p.pk;
     const double invdzsq = 1.0 / (dz * dz);
     const int lo = vbc[2 * t.patch], hi = vbc[2 * t.patch + 1];
     const double alpha = 1.0 - 2.0 * dz / (dzCrse + dz);
@@ -180,43 +233,45 @@ __global__ __launch_bounds__(512) void k_lep_vsolve_lapack(const Tile* __restric
         const int li = t.i0 + threadIdx.x + 64 * q, lj = t.j0 + threadIdx.y;
         if (li >= p.n[0] || lj >= p.n[1]) continue;
         const long long c0 = p.off + li + (long long)p.pj * lj;
-        int info = 0;
-        // row k (1-based) sits in cell k-1; Jgzz(IDX(k)) is the low face of cell k
-        auto diag = [&](int k, long long c) {   // D(k), c = cell k-1
-            if (k == 1) {
-                if (lo == 0) return jgz[c + sk] * invdzsq;
-                if (lo == 1) return (2.0 * jgz[c] + jgz[c + sk]) * invdzsq;
-                return ((1.0 - alpha) * jgz[c] + jgz[c + sk]) * invdzsq;
-            }
-            if (k == N) {
-                if (hi == 0) return jgz[c] * invdzsq;
-                if (hi == 1) return (jgz[c] + 2.0 * jgz[c + sk]) * invdzsq;
-                return (jgz[c] + (1.0 - alpha) * jgz[c + sk]) * invdzsq;
-            }
-            return (jgz[c] + jgz[c + sk]) * invdzsq;
-        };
-        long long c = c0;
-        double d = diag(1, c);
-        double b = -rhs[c];
-        for (int k = 1; k <= N - 1; ++k, c += sk) {
-            if (!(d > 0.0)) info = 1;
-            const double ei = -jgz[c + sk] * invdzsq;          // DL(k)
-            const double e = ei / d;
-            dfac[c] = d;
-            efac[c] = e;
-            phi[c] = b;
-            d = diag(k + 1, c + sk) - e * ei;
-            b = -rhs[c + sk] - b * e;
+        lep_column_lapack(c0, p.n[2], p.pk, phi, rhs, jgz, dfac, efac, lo, hi, alpha, invdzsq, bad);
+    }
+}
+
+// verticalLineSolver on a level that MIXES the two kinds of column (m_flatDI next to m_flatDIComplement,
+// LevelLepticSolver.cpp:318-333, 1248-1421): one launch over the column tiles of the whole level.  A tile belongs to one
+// patch, so its kind -- Neumann-Neumann (vbc 0, 0: the Thomas sweep above with its roll-in / roll-out) or ended by a
+// Dirichlet wall / a coarse-fine interface (the dptsv restatement) -- is the same for every lane of the workgroup: the
+// branch is taken per tile, never per lane.  hpp[patch] is the flat patch of a spanning box (LepticSolver's patch map); a
+// complement patch has none and its entry is not read.  dfac doubles as the Thomas sweep's gam.
+__global__ __launch_bounds__(512) void k_lep_vsolve_mixed(const Tile* __restrict__ tiles, const PatchDesc* __restrict__ vp,
+                                                          const PatchDesc* __restrict__ hpp, double* __restrict__ phi,
+                                                          double* __restrict__ rhs, const double* __restrict__ jgz,
+                                                          double* __restrict__ dfac, double* __restrict__ efac,
+                                                          const double* __restrict__ bcLo, const double* __restrict__ bcHi,
+                                                          const int* __restrict__ vbc, double dz, double dzCrse,
+                                                          int* __restrict__ bad)
+{
+    const Tile t = tiles[blockIdx.x];
+    const PatchDesc p = vp[t.patch];
+    const int lo = vbc[2 * t.patch], hi = vbc[2 * t.patch + 1];
+    if (lo == 0 && hi == 0) {
+        const PatchDesc hp = hpp[t.patch];
+        const double dzsq = dz * dz;
+        const double sLo = 1.0 / dz, sHi = -1.0 / dz;  // -isign / dz
+        for (int q = 0; q < 2; ++q) {
+            const Col o = column(t, p, hp, q);
+            if (!o.ok) continue;
+            lep_column_nn(o.c, p.n[2], p.pk, phi, rhs, jgz, dfac, bcLo[o.h], bcHi[o.h], dzsq, sLo, sHi);
         }
-        if (!(d > 0.0)) info = 1;
-        double x = b / d;                                        // B(N) / D(N)
-        phi[c] = x;
-        c -= sk;
-        for (int k = N - 1; k >= 1; --k, c -= sk) {
-            x = phi[c] / dfac[c] - x * efac[c];
-            phi[c] = x;
+    } else {
+        const double invdzsq = 1.0 / (dz * dz);
+        const double alpha = 1.0 - 2.0 * dz / (dzCrse + dz);
+        for (int q = 0; q < 2; ++q) {
+            const int li = t.i0 + threadIdx.x + 64 * q, lj = t.j0 + threadIdx.y;
+            if (li >= p.n[0] || lj >= p.n[1]) continue;
+            const long long c0 = p.off + li + (long long)p.pj * lj;
+            lep_column_lapack(c0, p.n[2], p.pk, phi, rhs, jgz, dfac, efac, lo, hi, alpha, invdzsq, bad);
         }
-        if (info) atomicAdd(bad, 1);
     }
 }
 
@@ -440,6 +495,13 @@ void launch_lep_vsolve_lapack(hipStream_t st, const Tile* ct, int nct, int tj, c
 {
     if (nct) hipLaunchKernelGGL(k_lep_vsolve_lapack, LEP_GRID(nct, tj), ct, V.patches, phi, rhs, V.jg[2], dfac, efac, vbc, dz,
                                 dzCrse, bad);
+}
+void launch_lep_vsolve_mixed(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const PatchDesc* flatOf,
+                             double* phi, double* rhs, double* dfac, double* efac, const double* bcLo, const double* bcHi,
+                             const int* vbc, double dz, double dzCrse, int* bad)
+{
+    if (nct) hipLaunchKernelGGL(k_lep_vsolve_mixed, LEP_GRID(nct, tj), ct, V.patches, flatOf, phi, rhs, V.jg[2], dfac, efac, bcLo,
+                                bcHi, vbc, dz, dzCrse, bad);
 }
 void launch_lep_hgrad(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
                       const double* phi, double* gx, double* gy)

@@ -57,11 +57,18 @@ constexpr unsigned BOX_SPIN_MAX = 1u << 26;
 // takes all 19 stencil values from it.  On BASELINE C5 three quarters of the 7 700 dispatches of an AMR V-cycle were the bottom
 // solver's ghost stages, colour passes and reductions on a 4096-cell level.
 
-template <int CPT, int MAXT, bool FULL>
+// LOCAL: a level of ONE box (7-point).  Nothing leaves the workgroup: p~ / s~ (and phi on its way through the residual) live
+// in one LDS array indexed by compact cell number (x fastest) -- s~ is written only after the last read of p~, with a
+// workgroup barrier between, so the two share it --, the neighbour table is translated once from field offsets to compact
+// cell numbers, the box's sums are the level's sums, and a "device-wide barrier" is __syncthreads(): no spin loop, no
+// agent-scope atomic, no traffic on A.z / A.sums / A.sync.  Same expressions in the same order as the multi-box variant.
+template <int CPT, int MAXT, bool FULL, bool LOCAL = false>
 __global__ __launch_bounds__(MAXT) void k_box_bicgstab(BoxBicg A)
 {
     static_assert(!FULL || CPT == 1, "the 19-point variant keeps one cell per thread");
+    static_assert(!(FULL && LOCAL), "the one-box variant is 7-point");
     __shared__ double X[BOX_MAX_CELLS], Y[BOX_MAX_CELLS];
+    __shared__ double Z[LOCAL ? BOX_MAX_CELLS : 1];
     __shared__ double Fp[FULL ? BOX_FAB_MAX : 1], Fe[FULL ? BOX_FAB_MAX : 1];   // the box grown by one cell: phi and its extrapolated copy
     // the box's ghost programs ([0] operator, [1] smoother) as per-cell entries, their stage starts, and the coefficient triples
     // (J g^{ab}, J g^{ac}, J g^{aa} on the boundary face) of their cross-term Neumann ghost cells
@@ -99,6 +106,35 @@ __global__ __launch_bounds__(MAXT) void k_box_bicgstab(BoxBicg A)
         const int* nbp = A.nb + 6ll * (A.cstart[b] + ii);
 #pragma unroll
         for (int s = 0; s < 6; ++s) nbo[q][s] = nbp[s];
+        if constexpr (LOCAL) {
+            // field offsets -> compact cell numbers.  Inside the box the neighbour is one compact stride away.  Across the
+            // box's edge the entry is either a valid cell of this same box (the periodic wrap: decoded from its offset) or
+            // the ghost cell's own offset (a physical side, which no exchange fills): that value never survives -- the
+            // boundary form of the sweep skips it, the operator overwrites its flux with zero -- so it reads the own cell.
+            // (build_box_tables has checked that every entry of a one-box level is one of these.)
+            const int lc[3] = {li, lj, lk};
+            const int cst[3] = {1, p.n[0], p.n[0] * p.n[1]};
+            const long long fst[3] = {1, (long long)p.pj, p.pk};
+#pragma unroll
+            for (int s = 0; s < 6; ++s) {
+                const int a = s >> 1, sg = (s & 1) ? 1 : -1;
+                int m = ii;
+                if (a < 2 || three) {
+                    const int nc = lc[a] + sg;
+                    if (nc >= 0 && nc < p.n[a]) {
+                        m = ii + sg * cst[a];
+                    } else if ((long long)nbo[q][s] != cc + sg * fst[a]) {
+                        const long long rel = (long long)nbo[q][s] - p.off;
+                        if (rel >= 0) {
+                            const int wk = (int)(rel / p.pk), wr = (int)(rel % p.pk);
+                            const int wj = wr / p.pj, wi = wr % p.pj;
+                            if (wi < p.n[0] && wj < p.n[1] && wk < p.n[2]) m = wi + p.n[0] * (wj + p.n[1] * wk);
+                        }
+                    }
+                }
+                nbo[q][s] = m;
+            }
+        }
         jl[q][0] = A.jg[0][cc]; jh[q][0] = A.jg[0][cc + 1];
         jl[q][1] = A.jg[1][cc]; jh[q][1] = A.jg[1][cc + p.pj];
         jl[q][2] = three ? A.jg[2][cc] : 0.0; jh[q][2] = three ? A.jg[2][cc + p.pk] : 0.0;
@@ -201,6 +237,10 @@ __global__ __launch_bounds__(MAXT) void k_box_bicgstab(BoxBicg A)
     // read-modify-write on a shared counter), the first wavefront polls all flags at once, one or two per lane ----
     unsigned epoch = 0;
     auto gsync = [&]() -> bool {
+        if constexpr (LOCAL) {   // one workgroup: the barrier is the workgroup's own.  Not timed: counting it cost the 4-cell
+            __syncthreads();     // instantiation 60 bytes of scratch per lane, so SOMAR_BOX_TIMING reports 0 barrier ticks here
+            return true;
+        }
         const long long t_in = tick();
         struct Acc { long long& a; long long t0; bool on; __device__ ~Acc() { if (on) a += (long long)__builtin_amdgcn_s_memtime() - t0; } } acc{tk[3], t_in, timing};
         __builtin_amdgcn_s_waitcnt(0);   // vmcnt(0) expcnt(0) lgkmcnt(0): this wave's write-through stores have been acknowledged
@@ -229,8 +269,16 @@ __global__ __launch_bounds__(MAXT) void k_box_bicgstab(BoxBicg A)
         __syncthreads();
         return s_ok != 0;
     };
-    auto ld_shared = [](const double* f, int off) { return __hip_atomic_load(f + off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    auto st_shared = [](double* f, int off, double v) { __hip_atomic_store(f + off, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    auto ld_shared = [&](const double* f, int off) {
+        if constexpr (LOCAL) return Z[off];
+        else return __hip_atomic_load(f + off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    auto st_shared = [&](double* f, int off, double v) {
+        if constexpr (LOCAL) Z[off] = v;
+        else __hip_atomic_store(f + off, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    // where this thread's cell q lives in the shared vectors: its field offset, or (LOCAL) its compact cell number
+    auto zc = [&](int q) { return LOCAL ? tid + q * nth : c[q]; };
 
     // ---- 19-point variant: stage the box grown by one cell, run one of its ghost programs on the copy ----
     // zf's valid cells are current everywhere (a device-wide barrier has passed since they were written)
@@ -449,6 +497,34 @@ __global__ __launch_bounds__(MAXT) void k_box_bicgstab(BoxBicg A)
         const long long ts0 = tick();
         struct AccS { long long& a; long long& g; long long t0, g0; bool on; __device__ ~AccS() { if (on) a += ((long long)__builtin_amdgcn_s_memtime() - t0) - (g - g0); } } accs{tk[4], tk[3], ts0, tk[3], timing};
         __syncthreads();
+        if constexpr (LOCAL) {
+            // one box: its chain or tree is the level's sum (added to 0.0 as the first of the box totals is)
+            if (A.serial) {
+                if (tid == 0) S[0][0] = chain(X);
+                if (two && tid == (nth > 64 ? 64 : 0)) S[1][0] = chain(Y);
+            } else {
+                double sa = 0.0, sb = 0.0;
+#pragma unroll
+                for (int q = 0; q < CPT; ++q) if (act[q]) { sa = sa + X[tid + q * nth]; if (two) sb = sb + Y[tid + q * nth]; }
+                sa = wave_sum(sa);
+                if (two) sb = wave_sum(sb);
+                if ((tid & 63) == 0) { M[tid >> 6] = sa; M[8 + (tid >> 6)] = sb; }
+                __syncthreads();
+                if (tid == 0) {
+                    double ta = M[0], tb = M[8];
+                    for (int w = 1; w < (nth + 63) / 64; ++w) { ta = ta + M[w]; tb = tb + M[8 + w]; }
+                    S[0][0] = ta;
+                    S[1][0] = tb;
+                }
+            }
+            __syncthreads();
+            double ta = 0.0, tb = 0.0;
+            ta = ta + S[0][0];
+            if (two) tb = tb + S[1][0];
+            ra = ta;
+            rb = tb;
+            return true;
+        }
         double* mine = A.sums + (nred & 1) * 2 * BOX_MAX_WG;
         ++nred;
         if (A.serial) {
@@ -492,6 +568,12 @@ __global__ __launch_bounds__(MAXT) void k_box_bicgstab(BoxBicg A)
         __syncthreads();
         if ((tid & 63) == 0) M[tid >> 6] = m;
         __syncthreads();
+        if constexpr (LOCAL) {
+            double r = M[0];
+            for (int w = 1; w < (nth + 63) / 64; ++w) r = M[w] > r ? M[w] : r;
+            out = r;
+            return true;
+        }
         double* mine = A.sums + (nred & 1) * 2 * BOX_MAX_WG;
         ++nred;
         if (tid == 0) {
@@ -534,8 +616,8 @@ __global__ __launch_bounds__(MAXT) void k_box_bicgstab(BoxBicg A)
     auto pre_cond = [&](double* zf, const double* w) -> bool {
 #pragma unroll
         for (int q = 0; q < CPT; ++q) if (act[q]) {
-            zo[q] = A.precondIters <= 0 ? w[q] : w[q] / dd[q];
-            st_shared(zf, c[q], zo[q]);
+            zo[q] = A.precondIters == 0 ? w[q] : w[q] / dd[q];
+            st_shared(zf, zc(q), zo[q]);
         }
         if (!gsync()) return false;
         for (int it = 0; it < A.precondIters; ++it)
@@ -544,7 +626,7 @@ __global__ __launch_bounds__(MAXT) void k_box_bicgstab(BoxBicg A)
 #pragma unroll
                 for (int q = 0; q < CPT; ++q) if (act[q] && col[q] == pass) {
                     zo[q] = relax_cell(q, zf, w[q]);
-                    st_shared(zf, c[q], zo[q]);
+                    st_shared(zf, zc(q), zo[q]);
                 }
                 if (!gsync()) return false;
             }
@@ -553,7 +635,7 @@ __global__ __launch_bounds__(MAXT) void k_box_bicgstab(BoxBicg A)
     // r = rhs - L[phi]: phi goes through z[0] (shared reads of the neighbours)
     auto residual = [&](const double* phiv) -> bool {
 #pragma unroll
-        for (int q = 0; q < CPT; ++q) if (act[q]) st_shared(A.z[0], c[q], phiv[q]);
+        for (int q = 0; q < CPT; ++q) if (act[q]) st_shared(A.z[0], zc(q), phiv[q]);
         if (!gsync()) return false;
         if (FULL) stage_fab(A.z[0], 0);
 #pragma unroll
@@ -702,7 +784,8 @@ void launch_box_bicgstab(hipStream_t st, const LevelDev& L, int max_box_cells, B
     A.jinv = L.jinv; A.lapd = L.lapdiag; A.P = L.P;
     SOMAR_CHECK(L.npatches >= 1 && L.npatches <= BOX_MAX_WG && max_box_cells >= 1 && max_box_cells <= BOX_MAX_CELLS,
                 "k_box_bicgstab: level outside the kernel's limits");
-    SOMAR_HIP(hipMemsetAsync(A.sync, 0, (BOX_MAX_WG + 1) * sizeof(unsigned), st));
+    const bool local = L.npatches == 1 && !A.full;   // one box: everything stays inside the workgroup, A.sync is not touched
+    if (!local) SOMAR_HIP(hipMemsetAsync(A.sync, 0, (BOX_MAX_WG + 1) * sizeof(unsigned), st));
     // 512-thread workgroups (256 VGPRs each: a thread's cells, their coefficients and vectors stay in registers), 1 / 2 / 4 cells
     // per thread
     const int nth = std::min(512, (max_box_cells + 63) / 64 * 64);
@@ -713,6 +796,10 @@ void launch_box_bicgstab(hipStream_t st, const LevelDev& L, int max_box_cells, B
         // 256 threads whatever the box size (up to 512 VGPRs each, no spills): the ops of a ghost-program stage run one per
         // wavefront, side by side -- with the 64 threads a 4^3 box asks for a pass took 67 us, most of it ops in single file
         hipLaunchKernelGGL((k_box_bicgstab<1, 256, true>), dim3(L.npatches), dim3(256), 0, st, A);
+    } else if (local) {
+        if (max_box_cells <= 512) hipLaunchKernelGGL((k_box_bicgstab<1, 512, false, true>), dim3(1), dim3(nth), 0, st, A);
+        else if (max_box_cells <= 1024) hipLaunchKernelGGL((k_box_bicgstab<2, 512, false, true>), dim3(1), dim3(nth), 0, st, A);
+        else hipLaunchKernelGGL((k_box_bicgstab<4, 512, false, true>), dim3(1), dim3(nth), 0, st, A);
     } else if (max_box_cells <= 512) hipLaunchKernelGGL((k_box_bicgstab<1, 512, false>), dim3(L.npatches), dim3(nth), 0, st, A);
     else if (max_box_cells <= 1024) hipLaunchKernelGGL((k_box_bicgstab<2, 512, false>), dim3(L.npatches), dim3(nth), 0, st, A);
     else hipLaunchKernelGGL((k_box_bicgstab<4, 512, false>), dim3(L.npatches), dim3(nth), 0, st, A);

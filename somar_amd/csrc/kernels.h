@@ -163,7 +163,7 @@ struct TinyBicg {
     StencilParams P;
     double* phi; const double* rhs;
     double* w[8];
-    int imax, numRestarts, normType, precondIters;
+    int imax, numRestarts, normType, precondIters;   // precondIters: 0 no preconditioner, < 0 the diagonal scaling alone (a level the reference's sweep does not visit)
     double eps, reps, hang, small, metric;
     double* info;
     ScalarPublish pub;
@@ -193,7 +193,7 @@ struct BoxBicg {
     StencilParams P;
     double* phi; const double* rhs;
     double* z[2];        // p~ and s~ in the level's layout: the only fields a workgroup reads outside its own box
-    int imax, numRestarts, normType, precondIters;
+    int imax, numRestarts, normType, precondIters;   // precondIters: 0 no preconditioner, < 0 the diagonal scaling alone (a level the reference's sweep does not visit)
     double eps, reps, hang, small, metric;
     double* sums;        // 4 * BOX_MAX_WG doubles: per-box partial results of the running reduction(s), double-buffered
     unsigned* sync;      // BOX_MAX_WG + 1: per workgroup the number of the last barrier it reached; abort flag (a barrier gave up); zeroed per launch

@@ -826,6 +826,65 @@ __global__ __launch_bounds__(64) void k_reduce_ordered(const PatchDesc* __restri
     }
 }
 
+// MODE 6 for levels of a few boxes, staged by a whole workgroup: the level's cells form ONE sequence (box after box, Fortran
+// order inside a box, the two running sums never restart), so 1024 threads stage ORD6_CAP consecutive terms of it at once
+// -- every load and division in flight together, across box ends -- and the first wavefront then walks them exactly as
+// k_reduce_ordered<6> does.  A level of 4096 cells is two stagings instead of eight (or one per box), each of which put a
+// load + division latency between two pieces of the chain.  Same values in the same order: same bits.  Longer sequences
+// simply take more chunks.
+constexpr int ORD6_CAP = 2048, ORD6_MAXP = 64;
+__global__ __launch_bounds__(1024) void k_reduce_ordered6_staged(const PatchDesc* __restrict__ patches, int npatches,
+                                                                 const double* __restrict__ a, const double* __restrict__ b,
+                                                                 double dxProduct, double* __restrict__ out)
+{
+    __shared__ double X[ORD6_CAP], Y[ORD6_CAP];
+    __shared__ long long START[ORD6_MAXP + 1];   // where each box starts in the sequence (+ its end)
+    const int tid = threadIdx.x;
+    if (tid < npatches) {
+        const PatchDesc q = patches[tid];
+        START[tid + 1] = (long long)q.n[0] * q.n[1] * q.n[2];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        START[0] = 0;
+        for (int q = 0; q < npatches; ++q) START[q + 1] += START[q];
+    }
+    __syncthreads();
+    const long long N = START[npatches];
+    double run_s = 0.0, run_v = 0.0;
+    for (long long base = 0; base < N; base += ORD6_CAP) {
+        const int cnt = (int)((N - base) < ORD6_CAP ? (N - base) : ORD6_CAP);
+        if (base != 0) __syncthreads();   // the previous chunk has been consumed
+        for (int q = tid; q < cnt; q += 1024) {
+            const long long g = base + q;
+            int pi = 0;
+            while (pi + 1 < npatches && g >= START[pi + 1]) ++pi;
+            const PatchDesc p = patches[pi];
+            const long long idx = g - START[pi];
+            const int i = (int)(idx % p.n[0]);
+            const long long r = idx / p.n[0];
+            const int j = (int)(r % p.n[1]), k = (int)(r / p.n[1]);
+            const long long c = cidx(p, i, j, k);
+            const double y = dxProduct / b[c];
+            Y[q] = y;
+            X[q] = y * a[c];
+        }
+        __syncthreads();
+        if (tid < 64) {   // one wavefront walks (uniform LDS reads are broadcasts), 16 values fetched ahead of the chain
+            int q = 0;
+            for (; q + 16 <= cnt; q += 16) {
+                double xv[16], yv[16];
+#pragma unroll
+                for (int j = 0; j < 16; ++j) { xv[j] = X[q + j]; yv[j] = Y[q + j]; }
+#pragma unroll
+                for (int j = 0; j < 16; ++j) { run_s = run_s + xv[j]; run_v = run_v + yv[j]; }
+            }
+            for (; q < cnt; ++q) { run_s = run_s + X[q]; run_v = run_v + Y[q]; }
+        }
+    }
+    if (tid == 0) { out[0] = run_s; out[1] = run_v; }
+}
+
 // The same sums (MODE 0 / 2) with the boxes' chains running SIDE BY SIDE: the reference adds the cells of one box into a
 // running sum of their own (FArrayBox::dotProduct starts at zero per box) and then the box totals in layout order, so the chains
 // of different boxes are independent.  One 1024-thread workgroup stages the terms of up to ORD_CAP cells in LDS (all loads in
@@ -1066,8 +1125,12 @@ void launch_prolong(hipStream_t st, const LevelDev& F, const LevelDev& C, double
     if (zeroAvg && ordered) {
         hipLaunchKernelGGL(k_prolong<false>, dim3(F.ntiles), tile_block(F), 0, st, F.tiles, F.patches, C.patches,
                            fine, crse, F.jinv, r[0], r[1], r[2], dxProduct, partials);
-        hipLaunchKernelGGL(k_reduce_ordered<6>, dim3(1), dim3(64), 0, st, F.patches, F.npatches, fine, F.jinv, dxProduct,
-                           sums, ScalarPublish{nullptr, nullptr, 0ull});
+        if (F.npatches <= ORD6_MAXP)
+            hipLaunchKernelGGL(k_reduce_ordered6_staged, dim3(1), dim3(1024), 0, st, F.patches, F.npatches, fine, F.jinv,
+                               dxProduct, sums);
+        else
+            hipLaunchKernelGGL(k_reduce_ordered<6>, dim3(1), dim3(64), 0, st, F.patches, F.npatches, fine, F.jinv, dxProduct,
+                               sums, ScalarPublish{nullptr, nullptr, 0ull});
         return;
     }
     if (!zeroAvg) {
@@ -1470,7 +1533,7 @@ __global__ __launch_bounds__(1024) void k_tiny_bicgstab(TinyBicg A)
     auto residual = [&](double* out, double* phi, const double* rhs) { exchange(phi); op0(out, phi, rhs); };
     auto apply_op = [&](double* out, double* phi) { exchange(phi); op1(out, phi); };
     auto pre_cond = [&](double* phi, const double* rhs) {
-        if (A.precondIters <= 0) { copy(phi, rhs); return; }
+        if (A.precondIters == 0) { copy(phi, rhs); return; }
         for (int b = vb; b < A.ntiles; b += nvb) diag_body<0>(A.tiles, A.patches, phi, rhs, A.lapd, A.P.alpha, A.P.beta, b, tx, ty);
         sync();
         for (int it = 0; it < A.precondIters; ++it)

@@ -38,6 +38,7 @@ PressureSolver::PressureSolver(Comm* comm, hipStream_t shared) : comm_(comm ? co
     if (const char* e = getenv("SOMAR_BOX_BOTTOM_MIN_CELLS")) box_min_cells_ = atoll(e);
     if (const char* e = getenv("SOMAR_AGGLOM_CELLS")) agglom_cells_ = atoll(e);
     if (const char* e = getenv("SOMAR_GRAPH_CELLS")) graph_cells_ = atoll(e);
+    if (const char* e = getenv("SOMAR_BOTTOM_ASYNC")) bottom_async_ = atoi(e) != 0;
 }
 
 PressureSolver::~PressureSolver()
@@ -163,6 +164,7 @@ void PressureSolver::fetch_scalars(int slot, int n)
         SOMAR_HIP(hipStreamSynchronize(st_));
         return;
     }
+    bottom_collect();   // (the spin below compares for equality with ONE sequence number: nothing may be outstanding)
     const unsigned long long want = ++fetch_seq_;
     launch_publish(st_, d_scalars + slot, n, h_scalars + slot, h_seq_, want);
     wait_published(want);
@@ -182,6 +184,18 @@ void PressureSolver::wait_published(unsigned long long want)
             if (q != hipErrorNotReady) SOMAR_HIP(q);
         }
     }
+}
+
+// the host side of a one-launch bottom solve: its (iterations, exit code), published by the kernel's last thread.  Nothing in
+// the cycle branches on them, so graph_cycle enqueues the up leg first and the GPU never waits for this round trip.
+void PressureSolver::bottom_collect()
+{
+    if (!bottom_pending_) return;
+    const unsigned long long want = bottom_pending_;
+    bottom_pending_ = 0;   // (dropped whatever happens below)
+    wait_published(want);
+    bottom_iters = (int)h_scalars[SLOT_TMP];
+    bottom_exit = (int)h_scalars[SLOT_TMP + 1];
 }
 
 double* PressureSolver::work(int which)
@@ -990,7 +1004,7 @@ bool PressureSolver::fused_relax(int d, int iters) const
 {
     const Level& L = *lev[d];
     // levels with coarse-fine boundaries qualify when their layout allows it (Level::cf_fusable)
-    return prm.relaxMode == RELAX_LEVEL_GSRB && L.valid_cells_global >= fused_min_cells_ && iters > 0 &&
+    return prm.relaxMode == RELAX_LEVEL_GSRB && !unswept(d) && L.valid_cells_global >= fused_min_cells_ && iters > 0 &&
            (L.ncf == 0 || L.cf_fusable) && L.active[2] && !no_cf_fused_(L) && !full_;  // Dirichlet sides: ghosts synthesized in the kernel
 }
 
@@ -1111,6 +1125,7 @@ void PressureSolver::relax(int d, double* e, const double* res, int iters, bool 
         return;
     }
     if (e_zero) launch_set(st_, e, L.field_elems, 0.0);
+    if (unswept(d)) return;   // a domain two cells wide in two directions: the reference's sweep has no cell to visit
     if (prm.relaxMode == RELAX_LEVEL_GSRB && full_march(d) && fused19(d)) {
         // LevelGSRB::relax with a non-diagonal metric on a level of large boxes: red everywhere and black three layers inside
         // every box in ONE marching launch (full19_fused.hip), the between-colour ghost work on its output exactly as in the
@@ -2086,8 +2101,22 @@ bool PressureSolver::graph_cycle(int d, double* corr, const double* res, bool co
         cg_.bottom = prm.num_smooth_bottom;
     }
     SOMAR_HIP(hipGraphLaunch(cg_.down, st_));
-    if (lev[D - 1]->domain.numPts() != 1) bottom_solve(f_corr[D - 1], f_res[D - 1]);
-    SOMAR_HIP(hipGraphLaunch(cg_.up, st_));
+    if (lev[D - 1]->domain.numPts() != 1) {
+        // a one-launch bottom solve leaves its (iterations, exit code) pending until the up leg is in the queue
+        bottom_defer_ = bottom_async_;
+        try {
+            bottom_solve(f_corr[D - 1], f_res[D - 1]);
+        } catch (...) {
+            bottom_defer_ = false;
+            bottom_pending_ = 0;
+            throw;
+        }
+        bottom_defer_ = false;
+    }
+    const hipError_t rc = hipGraphLaunch(cg_.up, st_);
+    if (rc != hipSuccess) bottom_pending_ = 0;
+    SOMAR_HIP(rc);
+    bottom_collect();
     return true;
 }
 
@@ -2303,8 +2332,10 @@ bool PressureSolver::box_bottom(int d) const
     if (!box_bottom_on_ || !poll || diri_ || L.ncf != 0 || !L.plan.peers.empty() || profiling_ || capturing_ ||
         comm_->size != 1 || prm.relaxMode != RELAX_LEVEL_GSRB || prm.precondMode == PRECOND_DIAG_LINE_RELAX || !bicg[7])
         return false;
-    // (the 19-point operator has no single-workgroup kernel: its bottoms come here whatever their size)
-    if ((!full_ && L.valid_cells_global < box_min_cells_) || L.valid_cells_global != L.domain.numPts()) return false;
+    // (the 19-point operator has no single-workgroup kernel: its bottoms come here whatever their size; so does a level of
+    // one box, which takes the kernel's workgroup-local variant)
+    const bool one_box = !full_ && L.npatches() == 1;
+    if ((!full_ && !one_box && L.valid_cells_global < box_min_cells_) || L.valid_cells_global != L.domain.numPts()) return false;
     if (L.npatches() < 1 || L.npatches() > BOX_MAX_WG || L.field_elems > 0x7fffffffll) return false;
     for (const PatchDesc& p : L.hpatches)
         if ((long long)p.n[0] * p.n[1] * p.n[2] > BOX_MAX_CELLS) return false;
@@ -2355,8 +2386,19 @@ void PressureSolver::build_box_tables(int d)
                 for (int i = 0; i < p.n[0]; ++i) {
                     const long long c = at(p, i, j, k);
                     const long long off[6] = {c - 1, c + 1, c - p.pj, c + p.pj, c - p.pk, c + p.pk};
-                    for (int s = 0; s < 6; ++s)   // (a flat level has no z frame: those two entries are never read)
-                        nb.push_back(off[s] >= 0 && off[s] < L.field_elems ? G[(size_t)off[s]] : (int)c);
+                    for (int s = 0; s < 6; ++s) {   // (a flat level has no z frame: those two entries are never read)
+                        const long long v = off[s] >= 0 && off[s] < L.field_elems ? G[(size_t)off[s]] : c;
+                        nb.push_back((int)v);
+                        // a level of one box (the workgroup-local kernel turns the entries into compact cell numbers): the
+                        // neighbour inside the box, a valid cell of the box through a periodic seam, or -- a physical side --
+                        // the ghost cell's own offset; anything else would be read as the own cell, so it is an error here
+                        if (L.hpatches.size() == 1 && !full_ && (s < 4 || L.active[2]) && v != off[s]) {
+                            const long long rel = v - p.off;
+                            const long long wk = rel >= 0 ? rel / p.pk : -1, wr = rel >= 0 ? rel % p.pk : 0;
+                            SOMAR_CHECK(rel >= 0 && wr % p.pj < p.n[0] && wr / p.pj < p.n[1] && wk < p.n[2],
+                                        "box bottom solver: a neighbour of a one-box level that is no valid cell of the box");
+                        }
+                    }
                 }
     }
     SOMAR_HIP(hipMalloc(&d_box_nb_, nb.size() * sizeof(int)));
@@ -2463,8 +2505,10 @@ void PressureSolver::bottom_solve(double* phi, const double* rhs)
     ++counters[3];
     const int d = (int)lev.size() - 1;
     const long long n = lev[d]->field_elems;
-    if (!fused_bottom(d) && box_bottom(d)) build_box_tables(d);   // (the 19-point tables may turn out not to fit: asked again below)
-    if (!fused_bottom(d) && box_bottom(d)) {
+    // a level of one box goes to the workgroup-local k_box_bicgstab whatever its size; other tiny levels to k_tiny_bicgstab first
+    const bool one_box = !full_ && lev[d]->npatches() == 1;
+    if ((one_box || !fused_bottom(d)) && box_bottom(d)) build_box_tables(d);   // (the 19-point tables may turn out not to fit: asked again below)
+    if ((one_box || !fused_bottom(d)) && box_bottom(d)) {
         Level& L = *lev[d];
         BoxBicg A;
         std::memset(&A, 0, sizeof(A));
@@ -2478,6 +2522,7 @@ void PressureSolver::bottom_solve(double* phi, const double* rhs)
         A.numRestarts = prm.bottom_numRestarts;
         A.normType = prm.bottom_normType;
         A.precondIters = (prm.num_smooth_precond == 0 || prm.precondMode == PRECOND_NONE) ? 0 : prm.num_smooth_precond;
+        if (A.precondIters > 0 && unswept(d)) A.precondIters = -1;   // the diagonal scaling, no sweep
         A.eps = bottom_eps_eff;
         A.reps = prm.bottom_reps;
         A.hang = prm.bottom_hang;
@@ -2501,10 +2546,9 @@ void PressureSolver::bottom_solve(double* phi, const double* rhs)
         A.info = d_scalars + SLOT_TMP;
         A.pub = ScalarPublish{h_scalars + SLOT_TMP, h_seq_, ++fetch_seq_};
         launch_box_bicgstab(st_, L.dev, box_max_cells_, A);
-        wait_published(A.pub.seq);
-        bottom_iters = (int)h_scalars[SLOT_TMP];
-        bottom_exit = (int)h_scalars[SLOT_TMP + 1];
+        bottom_pending_ = A.pub.seq;
         bottom_kind = 2;
+        if (!bottom_defer_ || box_timing) bottom_collect();
         if (box_timing) {
             long long t[6];
             SOMAR_HIP(hipMemcpy(t, A.dbg, sizeof(t), hipMemcpyDeviceToHost));
@@ -2524,6 +2568,7 @@ void PressureSolver::bottom_solve(double* phi, const double* rhs)
         A.numRestarts = prm.bottom_numRestarts;
         A.normType = prm.bottom_normType;
         A.precondIters = (prm.num_smooth_precond == 0 || prm.precondMode == PRECOND_NONE) ? 0 : prm.num_smooth_precond;
+        if (A.precondIters > 0 && unswept(d)) A.precondIters = -1;   // the diagonal scaling, no sweep
         A.eps = bottom_eps_eff;
         A.reps = prm.bottom_reps;
         A.hang = prm.bottom_hang;
@@ -2532,10 +2577,9 @@ void PressureSolver::bottom_solve(double* phi, const double* rhs)
         A.info = d_scalars + SLOT_TMP;
         A.pub = ScalarPublish{h_scalars + SLOT_TMP, h_seq_, ++fetch_seq_};
         launch_tiny_bicgstab(st_, L.dev, L.d_local_items, (int)L.plan.local.size(), n, A);
-        wait_published(A.pub.seq);
-        bottom_iters = (int)h_scalars[SLOT_TMP];
-        bottom_exit = (int)h_scalars[SLOT_TMP + 1];
+        bottom_pending_ = A.pub.seq;
         bottom_kind = 1;
+        if (!bottom_defer_) bottom_collect();
         return;
     }
     double *r = bicg[0], *r_tilde = bicg[1], *e = bicg[2], *p = bicg[3], *p_tilde = bicg[4], *s_tilde = bicg[5],

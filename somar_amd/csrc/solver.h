@@ -342,6 +342,17 @@ private:
     bool own_stream_ = true;
     double dxCrse_[3] = {0, 0, 0};
     std::vector<double*> f_pp;  // per-depth ping-pong buffer of the fused sweep
+    // LevelGSRB sweeps the shells of the domain shrunk by one cell (RelaxationMethod::collectBoundaryData) and the cells inside
+    // it: when two or more active directions of the domain are at most two cells wide every one of those boxes is empty, and
+    // a sweep of the reference touches no cell at all (a preconditioner is then its diagonal scaling alone)
+    bool unswept(int d) const
+    {
+        const Level& L = *lev[d];
+        int narrow = 0;
+        for (int a = 0; a < 3; ++a)
+            if (L.active[a] && L.domain.size(a) <= 2) ++narrow;
+        return prm.relaxMode == RELAX_LEVEL_GSRB && narrow >= 2;
+    }
     bool fused_bottom(int d) const;   // the whole BiCGStab bottom solve in one single-workgroup launch (k_tiny_bicgstab)
     // the BiCGStab bottom solve of a multi-box bottom level as one persistent launch, one workgroup per box (k_box_bicgstab);
     // SOMAR_BOX_BOTTOM=0 is the A/B switch (read once, at construction).  The neighbour table is built at the first use.
@@ -349,7 +360,7 @@ private:
     void build_box_tables(int d);
     bool box_bottom_on_ = true;
     long long fused_bottom_max_ = 512;   // k_tiny_bicgstab takes bottoms of at most this many cells (0: off)
-    long long box_min_cells_ = 513;      // smaller single-workgroup bottoms stay with k_tiny_bicgstab
+    long long box_min_cells_ = 513;      // smaller multi-box bottoms stay with k_tiny_bicgstab (a level of ONE box: always k_box_bicgstab)
     int box_depth_ = -1, box_max_cells_ = 0;
     int *d_box_nb_ = nullptr, *d_box_cstart_ = nullptr, *d_box_fab_ = nullptr, *d_box_fabstart_ = nullptr;
     // 19-point variant: the two ghost programs compiled into per-cell entries (kernels.h: BoxProgEntry), per box
@@ -380,6 +391,12 @@ private:
     bool fused_publish(int d) const;
     double reduce_fetch(int d, const double* a, const double* b, int mode);   // reduction + host fetch, published by the reduction
     void wait_published(unsigned long long want);
+    // a one-launch bottom solve whose published (iterations, exit code) the host has not read yet: the sequence number it
+    // publishes (0: none).  graph_cycle defers the read until the up leg is enqueued (SOMAR_BOTTOM_ASYNC=0: the A/B switch,
+    // read once at construction); every other caller of bottom_solve reads at once.
+    void bottom_collect();
+    unsigned long long bottom_pending_ = 0;
+    bool bottom_defer_ = false, bottom_async_ = true;
     void reduce_sum(int d, const double* a, const double* b, int mode, double* out);
 
     Comm* comm_;

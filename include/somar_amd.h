@@ -49,8 +49,9 @@ extern "C" {
  * 6: + somar_amr_tga_step (composite MappedAMRTGA::oneStep); composite operations with heat coefficients installed no
  *    longer fail (the flux-register scales follow beta); somar_solver_set_vel_bc (inflow / outflow sides); somar_solver_set_metric_map (cylindrical and bathymetric
  *    metric producers on the device); somar_k_fillmappedlapdiag3d, somar_k_mappedaverage2 (kernel-level hooks); additions only
- * 11: ... + somar_solver_set_bc_face_values (position-dependent Dirichlet values); additions only, so the number stays 11 */
-#define SOMAR_AMD_ABI_VERSION 11
+ * 11: ... + somar_solver_set_bc_face_values (position-dependent Dirichlet values); additions only, so the number stays 11
+ * 12: + somar_solver_tuning; the SOMAR_* execution-path variables are read when a solver is created and hold for its life */
+#define SOMAR_AMD_ABI_VERSION 12
 
 /* BCType codes, calculus/BCInterface/BCDescriptor.H:34-39 */
 #define SOMAR_BC_NONE (-1)
@@ -226,6 +227,10 @@ int somar_bottom_solve(somar_solver_t* s, int phi_field, int rhs_field, int* ite
  * 1 = one single-workgroup launch (bottoms of at most 512 cells), 2 = one persistent launch with one workgroup per box and
  * device-wide barriers (multi-box bottoms; SOMAR_BOX_BOTTOM=0 switches it off).  Same iterates on every path. */
 int somar_bottom_kind(somar_solver_t* s, int* kind);
+/* the value this solver holds for the execution-path switch SOMAR_<name> (name without the prefix, e.g. "FUSED_ROWS"): what the
+ * environment said when the solver was created, parsed by the switch's own rule, or its default.  Read-only; an unknown name is
+ * an error. */
+int somar_solver_tuning(somar_solver_t* s, const char* name, long long* value);
 /* which of the library's alternative execution paths have run on this solver so far (tests assert that the path under test
  * is the one that ran): out4 = {fused sweeps whose ghost exchange travelled on the second stream under their interior tiles,
  * ghost programs executed as one launch (a workgroup per box), ghost programs executed stage by stage, bottom solves} */

@@ -104,6 +104,7 @@ _SIGS = {
     "somar_mini_vcycle": [_H, C.c_int, C.c_int],
     "somar_bottom_solve": [_H, C.c_int, C.c_int, _PI, _PI],
     "somar_bottom_kind": [_H, _PI],
+    "somar_solver_tuning": [_H, C.c_char_p, C.POINTER(C.c_longlong)],
     "somar_solver_counters": [_H, C.POINTER(C.c_longlong)],
     "somar_solver_exchange_bytes": [_H, C.POINTER(C.c_longlong)],
     "somar_solver_exchange_bytes_depth": [_H, C.c_int, C.POINTER(C.c_longlong)],
@@ -744,6 +745,13 @@ class AMRPressureSolver:
         k = C.c_int()
         _ck(lib().somar_bottom_kind(self._h, C.byref(k)))
         return k.value
+
+    def tuning(self, name):
+        """the value this solver holds for the switch SOMAR_<name> (name without the prefix): read from the environment when
+        the solver was created, fixed since"""
+        v = C.c_longlong()
+        _ck(lib().somar_solver_tuning(self._h, name.encode(), C.byref(v)))
+        return v.value
 
     # -- MAC level projection (LevelMACProjector / BaseProjector::project, velocity in flux form) -------
     def uploadVel(self, d, patch, host):

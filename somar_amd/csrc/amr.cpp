@@ -71,7 +71,7 @@ void PressureSolver::set_metric_uniform(const double c4[4])
     }
 }
 
-AMRSolver::AMRSolver(Comm* comm) : comm_(comm ? comm : &self_)
+AMRSolver::AMRSolver(Comm* comm) : tune_(Tuning::from_env()), comm_(comm ? comm : &self_)
 {
     SOMAR_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
 }
@@ -115,7 +115,7 @@ void AMRSolver::define(const IBox& domain0, const bool periodic[3], const double
                 for (int d = 0; d < 3; ++d)
                     SOMAR_CHECK(b.lo[d] >= dom.lo[d] && b.hi[d] <= dom.hi[d], "fine box outside the domain");
         }
-        std::unique_ptr<PressureSolver> ps(new PressureSolver(comm_, st_));
+        std::unique_ptr<PressureSolver> ps(new PressureSolver(comm_, st_, tune_));
         ps->define(dom, periodic, dx, bc_type, boxes[l], owners[l], alpha, beta, p, l > 0 ? dxc : nullptr);
         ps->set_amr_member();
         if (l > 0) {
@@ -145,10 +145,7 @@ void AMRSolver::finalize()
         corr_[l] = S[l]->amr_field(0);
         res_[l] = S[l]->amr_field(1);
     }
-    {
-        const char* e = getenv("SOMAR_AMR_PLAIN");
-        lean_ = !(e && atoi(e) != 0);
-    }
+    lean_ = !tune_.amr_plain;
     spare_.assign(n, nullptr);
     rcur_ = res_;
     visits_.assign(n, 0);
@@ -173,7 +170,7 @@ void AMRSolver::build_link(int l)
     for (const IBox& b : F.boxes) cb.push_back(b.coarsen(K->r));
     K->cfl.reset(new Level);
     K->cfl->active[2] = C.active[2];
-    K->cfl->define(C.domain, C.periodic, C.dx, C.bc_type, cb, F.owner, comm_);
+    K->cfl->define(C.domain, C.periodic, C.dx, C.bc_type, cb, F.owner, comm_, tune_);
     K->buf = K->cfl->alloc_field();
     K->resC = K->cfl->alloc_field();
     const int g2[3] = {2, 2, 2}, g0[3] = {0, 0, 0};
@@ -196,11 +193,11 @@ void AMRSolver::build_link(int l)
     }
     K->ncover = (int)cover.size();
     K->d_cover = to_device(cover);
-    if (getenv("SOMAR_TIMING") && atoi(getenv("SOMAR_TIMING")) != 0)
+    const bool timing = tune_.timing != 0;
+    if (timing)
         fprintf(stderr, "[somar timing] link %d: coarsened-fine layout + copiers %.3f s\n", l,
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - tl0).count());
     links_[l] = std::move(K);
-    static const bool timing = getenv("SOMAR_TIMING") && atoi(getenv("SOMAR_TIMING")) != 0;
     const auto t0 = std::chrono::steady_clock::now();
     build_quad_tables(l);
     const auto t1 = std::chrono::steady_clock::now();
@@ -709,8 +706,7 @@ void AMRSolver::interp_cf(int l, double* phiFine, const double* phiCoarse, bool 
     for (int d = 0; d < 3; ++d) dxc[d] = F.dx[d] * (double)K.r[d];  // m_dxCrse of MappedQuadCFInterp::define
     // MappedQuadCFInterp copies the coarse data onto the whole coarsened-fine layout and reads its ghost ring; here only the ring
     // travels (the stencils' points, K.d_pts / K.d_cc, all lie outside the coarsened fine boxes)
-    static const bool full_gather = getenv("SOMAR_CF_FULL_GATHER") != nullptr;
-    (full_gather ? K.gather : K.gather_ring).run(phiCoarse, K.buf, st_);
+    (tune_.cf_full_gather ? K.gather : K.gather_ring).run(phiCoarse, K.buf, st_);
     launch_cf_slopes(st_, K.d_cc, K.ncc, K.d_pts, K.buf, K.d_der, dxc);
     launch_cf_quad(st_, K.d_fc, K.nfc, K.d_cc, K.d_der, K.buf, phiFine, F.dx, dxc, K.r);
     if (ev) S[l]->cf_ev(0, phiFine);  // ExtrapolateCFEV: non-diagonal metric only (interpCFGhosts, MappedAMRPoissonOp.cpp:2193-2216)
@@ -971,7 +967,7 @@ void AMRSolver::reflux(int l, double* phiFine, double* phi, double* LofPhi)
     // non-diagonal metric: getFlux = fillExtrap + MAPPEDGETFLUX.  The register reads the fluxes of its own faces only, so they
     // are evaluated there (reg_flux19) from the level's extrapolated copy instead of filling three whole face fields per level
     // (k_flux_full: 1 ms per 16.7 M-cell level, 8 ms of a C5 cycle).  SOMAR_FLUX_FIELDS=1: the face fields, as before (A/B).
-    static const bool fields = getenv("SOMAR_FLUX_FIELDS") != nullptr;
+    const bool fields = tune_.flux_fields != 0;
     double* const* flC = (fields && S[l]->is_full()) ? S[l]->flux_fields(phi) : nullptr;
     double* const* flF = (fields && S[l + 1]->is_full()) ? S[l + 1]->flux_fields(phiFine) : nullptr;
     FullFlux ffC, ffF;
@@ -1375,7 +1371,7 @@ void AMRSolver::enable_leptic(const LepticParams& lp, bool baseFromRestricted)
     leptic_.clear();
     lepStats_.assign(nlevels(), LepticStats());
     for (int l = 0; l < nlevels(); ++l) {
-        leptic_.emplace_back(new LepticSolver(comm_, st_));
+        leptic_.emplace_back(new LepticSolver(comm_, st_, tune_));
         leptic_.back()->attach(S[l].get(), lp);
     }
 }

@@ -144,7 +144,7 @@ struct AMRLink {
 
 class AMRSolver {
 public:
-    explicit AMRSolver(Comm* comm = nullptr);
+    explicit AMRSolver(Comm* comm = nullptr);   // reads the switches (Tuning::from_env) once, for every level, link and leptic solver
     ~AMRSolver();
 
     // levels[l]: boxes + owners in level-l index space; domain/dx are level 0's, refined by ratios
@@ -251,6 +251,7 @@ private:
     void build_quad_tables(int l);
     void build_reflux_tables(int l);
     void build_one_sided_tables(int l);   // link l: the one-sided faces on level l-1
+    const Tuning tune_;
     Comm* comm_;
     Comm self_;
     hipStream_t st_ = nullptr;

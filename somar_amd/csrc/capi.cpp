@@ -343,7 +343,7 @@ int somar_solver_create(somar_solver_t** out, const int* domain_lo, const int* d
     }
     somar_solver* s = new somar_solver;
     try {
-        s->ps = new PressureSolver(static_cast<Comm*>(comm));
+        s->ps = new PressureSolver(static_cast<Comm*>(comm), nullptr, Tuning::from_env());
         s->ps->define(dom, per, dx, bct, bx, own, alpha, beta, to_params(prm));
         SOMAR_HIP(hipEventCreate(&s->ev0));
         SOMAR_HIP(hipEventCreate(&s->ev1));
@@ -750,6 +750,14 @@ int somar_bottom_kind(somar_solver_t* s, int* kind)
 {
     API_BEGIN
     *kind = s->ps->bottom_kind;
+    API_END
+}
+
+int somar_solver_tuning(somar_solver_t* s, const char* name, long long* value)
+{
+    API_BEGIN
+    SOMAR_CHECK(name && value && s->ps->tuning().get(name, value),
+                std::string("somar_solver_tuning: no switch SOMAR_") + (name ? name : "(null)"));
     API_END
 }
 
@@ -1202,7 +1210,7 @@ int somar_k_gsrbiter3dortho(double* phi, const int* iphilo0, const int* iphilo1,
     const int bct[3][2] = {{BC_NEUM, BC_NEUM}, {BC_NEUM, BC_NEUM}, {BC_NEUM, BC_NEUM}};
     Level L;
     Comm self;
-    L.define(dom, per, dx, bct, std::vector<IBox>{region}, std::vector<int>{0}, &self);
+    L.define(dom, per, dx, bct, std::vector<IBox>{region}, std::vector<int>{0}, &self, Tuning::from_env());
     L.alloc_metric();
     L.alpha = *alpha;
     L.beta = *beta;
@@ -1259,7 +1267,7 @@ int somar_k_fillmappedlapdiag3d(double* lapDiag, const int* ilapDiaglo0, const i
     const int bct[3][2] = {{BC_NEUM, BC_NEUM}, {BC_NEUM, BC_NEUM}, {BC_NEUM, BC_NEUM}};
     Level L;
     Comm self;
-    L.define(region.grow(four), per, dx, bct, std::vector<IBox>{region}, std::vector<int>{0}, &self);
+    L.define(region.grow(four), per, dx, bct, std::vector<IBox>{region}, std::vector<int>{0}, &self, Tuning::from_env());
     L.alloc_metric();
     L.refresh_params();
     hipStream_t st = nullptr;
@@ -1314,8 +1322,9 @@ int somar_k_mappedaverage2(double* coarse, const int* icoarselo0, const int* ico
     Level LF, LC;
     Comm self;
     int g4r[3] = {4 * r[0], 4 * r[1], 4 * r[2]};
-    LF.define(fbox.grow(g4r), per, dx1, bct, std::vector<IBox>{fbox}, std::vector<int>{0}, &self);
-    LC.define(cbox.grow(four), per, dx1, bct, std::vector<IBox>{cbox}, std::vector<int>{0}, &self);
+    const Tuning tune = Tuning::from_env();
+    LF.define(fbox.grow(g4r), per, dx1, bct, std::vector<IBox>{fbox}, std::vector<int>{0}, &self, tune);
+    LC.define(cbox.grow(four), per, dx1, bct, std::vector<IBox>{cbox}, std::vector<int>{0}, &self, tune);
     LF.alloc_metric();
     LC.alloc_metric();
     hipStream_t st = nullptr;
@@ -1840,7 +1849,7 @@ int somar_leptic_create(somar_leptic_t** out, const int* domain_lo, const int* d
     const LepticParams P = to_leptic_params(lp);
     somar_leptic* h = new somar_leptic;
     try {
-        h->lep = new LepticSolver(static_cast<Comm*>(comm));
+        h->lep = new LepticSolver(static_cast<Comm*>(comm), nullptr, Tuning::from_env());
         h->lep->define(dom, per, dx, bct, bx, own, alpha, beta, to_params(level_prm), P);
         h->level = new somar_solver;
         h->level->ps = &h->lep->orig();

@@ -125,12 +125,12 @@ struct StencilParams {
     int pad2_;
     int diri[3][2];             // 1 = Dirichlet physical face (ghost = 2 value - first cell)
     // uniform metric (a Cartesian map: CartesianMap.cpp:261-280 fills constants): J g^{aa} == uc[a] on every face and
-    // J^{-1} == uc[3] in every cell of this depth, found by PressureSolver::detect_uniform_metric.  The k-marching kernels
+    // J^{-1} == uc[3] in every cell of this depth, found by PressureSolver::detect_metric_flags.  The k-marching kernels
     // then take the four values from here instead of streaming four arrays of them (56 -> 24 B/cell on a sweep).
     int uniform = 0;
     // non-diagonal metric: J g^{xy} on x-faces and J g^{yx} on y-faces are zero everywhere on this depth (any map with x = xi,
     // y = eta: BathymetricBaseMap and its DEM / Ledge / BeamGenerator subclasses); the marching 19-point kernels then stream
-    // seven coefficient planes instead of nine (PressureSolver::detect_zero_planes)
+    // seven coefficient planes instead of nine (PressureSolver::detect_metric_flags)
     int zero_xy = 0;
     double uc[4] = {0.0, 0.0, 0.0, 0.0};
 };

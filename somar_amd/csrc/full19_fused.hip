@@ -27,7 +27,7 @@
 // holds ONE 8-wave workgroup whose waves march in lock step -- a plane costs the memory latency PLUS both colours' arithmetic
 // (7.1 us against the two-pass kernel's 3.3 us per plane and workgroup) for 4 output rows instead of 6: 1.95 TB/s of its own
 // 132 B/cell.  A second register set to prefetch the next plane (which would overlap the two) does not fit in 256 VGPRs.  The
-// path therefore stays OFF by default (PressureSolver::fused19_min_box_ < 0; SOMAR_FUSED19_MIN_BOX=0 forces it for the parity tests).
+// path therefore stays OFF by default (Tuning::fused19_min_box < 0; SOMAR_FUSED19_MIN_BOX=0 forces it for the parity tests).
 //
 // Arithmetic: GSRBITER3D / GSRBBOUNDARYITER3D's expression order as in k_full_march<2> (GSRBF.ChF:36-282, 1024-1253): same bits.
 #include "common.h"

@@ -356,16 +356,6 @@ __global__ __launch_bounds__(64 * FM_J, (NARROW && !ZXY && MODE == 1) ? 3 : 1) v
     else full_march_body<MODE, FM_J, ZXY, NARROW ? 4 : 0>(SP, SE, t, p, out, phi, psi, rhs, J, jinv, P, color, phi2);
 }
 
-int full_march_rows()
-{
-    static int rows = 0;
-    if (!rows) {
-        const char* e = getenv("SOMAR_FULL_ROWS");
-        rows = (e && atoi(e) == 6) ? 6 : 8;
-    }
-    return rows;
-}
-
 static JgFullM jgfullm(const LevelDev& L)
 {
     JgFullM J;
@@ -379,7 +369,7 @@ template <int MODE>
 static void launch_march(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* out, const double* phi,
                          const double* psi, const double* rhs, int color, const double* phi2 = nullptr, bool narrow = false)
 {
-    const bool six = full_march_rows() == 6, z = L.P.zero_xy != 0, nw = L.narrowq != 0 || narrow;   // (6-row tables never hold narrow classes)
+    const bool six = L.full_rows == 6, z = L.P.zero_xy != 0, nw = L.narrowq != 0 || narrow;   // (6-row tables never hold narrow classes)
 #define SOMAR_FM(ROWS, Z, N)                                                                                                   \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_full_march<MODE, ROWS, Z, N>), dim3(ntiles), dim3(64, ROWS, 1), 0, st, tiles, L.patches, \
                        out, phi, psi, rhs, jgfullm(L), L.jinv, L.P, color, phi2)
@@ -414,7 +404,7 @@ void launch_gsrb_full_shell(hipStream_t st, const Tile* tiles, int ntiles, const
                             const double* psi, const double* rhs)
 {
     if (ntiles == 0) return;
-    SOMAR_CHECK(full_march_rows() == 8, "internal: the shell pass uses the 8-row marching kernels");
+    SOMAR_CHECK(L.full_rows == 8, "internal: the shell pass uses the 8-row marching kernels");
     launch_march<3>(st, tiles, ntiles, L, phi, phi, psi, rhs, 1, phi_in, true);
 }
 }  // namespace somar

@@ -451,12 +451,11 @@ static void launch_gsrb_fused_t(hipStream_t st, const Tile* tiles, int ntiles, c
     if (ntiles == 0) return;
     const PatchDesc* cpatches = C ? C->patches : nullptr;
     const int r0 = r ? r[0] : 1, r1 = r ? r[1] : 1, r2 = r ? r[2] : 1;
-    static const int lean_ok = getenv("SOMAR_NO_LEAN_TILES") == nullptr;   // A/B switch: interior tiles take the general path too
     SOMAR_CHECK(in_mode < 3 || ((r0 == 1 || r0 == 2) && (r1 == 1 || r1 == 2) && (r2 == 1 || r2 == 2)),
                 "internal: the prolongation folded into a sweep takes multigrid ratios of 1 or 2 per direction");
     auto go = [&](auto kern, int rows) {
         hipLaunchKernelGGL(kern, dim3(ntiles), dim3(64, rows, 1), 0, st, tiles, L.patches, phi_out, phi_in, rhs, M.jg[0], M.jg[1],
-                           M.jg[2], M.jinv, L.P, sums, cpatches, crse, r0, r1, r2, lean_ok);
+                           M.jg[2], M.jinv, L.P, sums, cpatches, crse, r0, r1, r2, L.lean_tiles);
     };
     // (rows, mode, Dirichlet sides, uniform metric, narrow lane classes in the tile table)
 #define SOMAR_FUSED_MODES(ROWS, D, U, N, M0, M1, M2, M3, M4)                    \
@@ -467,7 +466,7 @@ static void launch_gsrb_fused_t(hipStream_t st, const Tile* tiles, int ntiles, c
         case 4: go(k_gsrb_fused<ROWS, M4, D, U, N, T>, ROWS); break;            \
         default: go(k_gsrb_fused<ROWS, M0, D, U, N, T>, ROWS);                  \
     }
-    const bool rows16 = fused_rows() == 16;
+    const bool rows16 = L.fused_rows == 16;
     const bool narrow = L.narrow7 != 0 && rows16;   // Level::build_march_tiles hands the 8-row kernels class-0 tiles only
     bool diri = false;
     for (int d = 0; d < 3; ++d) diri = diri || L.P.diri[d][0] || L.P.diri[d][1];
@@ -514,18 +513,7 @@ bool fused_uniform_kernel(const LevelDev& L)
 {
     bool diri = false;
     for (int d = 0; d < 3; ++d) diri = diri || L.P.diri[d][0] || L.P.diri[d][1];
-    return L.P.uniform && fused_rows() == 16 && !diri;
-}
-
-// region rows per workgroup of the fused sweep (tile rows = rows - 4); SOMAR_FUSED_ROWS = 8 | 16
-int fused_rows()
-{
-    static int rows = 0;
-    if (!rows) {
-        const char* e = getenv("SOMAR_FUSED_ROWS");
-        rows = (e && atoi(e) == 8) ? 8 : 16;
-    }
-    return rows;
+    return L.P.uniform && L.fused_rows == 16 && !diri;
 }
 
 }  // namespace somar

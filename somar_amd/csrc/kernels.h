@@ -13,7 +13,6 @@ struct LevelDev {
     // stencil kernel refreshes exactly the ghosts it is about to read, so the separate copy launch disappears (null: not built)
     const CopyItem* tile_items = nullptr;
     const int* tile_item_start = nullptr;
-    unsigned int* red_counter = nullptr;   // arrival counter of the single-launch tree reduction (k_reduce_valid's last workgroup)
     int ghost_gy = 16;                  // workgroups per ghost op (k_ghost_ops): the largest box face / 1024, within [16, 256]
     const PatchDesc* patches = nullptr;
     int npatches = 0;
@@ -28,6 +27,11 @@ struct LevelDev {
     const double* bc_face = nullptr;
     int narrow7 = 0;                    // the 7-point marching kernels' tile tables hold narrow lane classes (Level::build_march_tiles)
     int narrowq = 0;                    // the 19-point marching kernels' tile table does
+    // what the launchers take from the solver's Tuning (Level::define copies it here)
+    int fused_rows = 16;                // region rows per workgroup of the fused 7-point sweep (tile rows = rows - 4): 16 or 8
+    int full_rows = 8;                  // ... of the 19-point marching kernels: 8 or 6
+    int lean_tiles = 1;                 // interior tiles of the uniform-metric fused sweep take the lean body
+    int ordered_serial = 0;             // serial-order sums walk all boxes in one chain (launch_reduce)
 };
 
 // the coefficient arrays a marching kernel streams, in its element type: the level's own (fp64), or their fp32 copies on the
@@ -56,7 +60,6 @@ void launch_full_march(hipStream_t st, const Tile* tiles, int ntiles, const Leve
                        const double* psi, const double* rhs, int mode);
 void launch_gsrb_full_march(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* out,
                             const double* phi, const double* psi, const double* rhs, int color);
-int full_march_rows();
 // red + black in one launch for the cells three layers inside their box (full19_fused.hip), then -- after the between-colour
 // ghost work on `out` -- the black cells of the outer layers in place (full19_march.hip, MODE 3)
 void launch_full_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* out, const double* phi,
@@ -85,7 +88,6 @@ void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const Leve
 void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, const MetricPtrs<float>& M,
                        float* phi_out, const float* phi_in, const float* rhs, int in_mode, const double* sums,
                        const LevelDev* C, const float* crse, const int* r);
-int fused_rows();
 // whether launch_gsrb_fused takes a uniform-metric kernel on this level (it then reads none of the four coefficient arrays)
 bool fused_uniform_kernel(const LevelDev& L);
 // k-marching operator/residual of a large level (resid_march.hip); mode 0: out = rhs - L[phi], 1: out = L[phi]
@@ -217,15 +219,14 @@ struct BoxBicg {
 void launch_box_bicgstab(hipStream_t st, const LevelDev& L, int max_box_cells, BoxBicg A);
 // streaming probe (diagnostics): kind 0 copy, 1 read, 2 six reads + one write; in6: six arrays of `cells` doubles
 void launch_stream_probe(hipStream_t st, int kind, int workgroups, double* const* in6, double* out, long long cells);
-// (min, max) per (patch, k-chunk) of a over the valid cells (dir < 0) or valid dir-faces: out[2 * npatches * MM_CH] (device)
-constexpr int MM_CH = 64;
-void launch_minmax_valid(hipStream_t st, const LevelDev& L, const double* a, int dir, double* out);
+constexpr int MM_CH = 64;   // k-chunks per patch of k_minmax_all
 // metric refresh (metric_refresh.hip): every coarse metric array of one MG depth from the next finer one in one launch --
 // item dir 0..2: arithmetic average over faces(valid, dir) (k_avg_face), dir -1: harmonic cell average (k_avg_harmonic)
 struct CoarsenItem { const double* fine; double* crse; int patch; int dir; };
 void launch_coarsen_metric(hipStream_t st, const LevelDev& C, const LevelDev& F, const CoarsenItem* items, int nitems,
                            int gy, const int r[3]);
-// k_minmax_valid over a table of arrays of any depth: out[2 * (item * MM_CH + chunk)] = (min, max)
+// (min, max) per (item, k-chunk) of a table of arrays of any depth, over the valid cells (dir < 0) or the valid dir-faces of the
+// item's patch: out[2 * (item * MM_CH + chunk)] = min, [... + 1] = max
 struct MinMaxItem { const double* a; const PatchDesc* patches; int patch; int dir; };
 void launch_minmax_all(hipStream_t st, const MinMaxItem* items, int nitems, double* out);
 // mode 0: sum a*b, 1: max|a|, 2: sum|a|, 3: signed max a  -> out[0] (device)

@@ -698,8 +698,7 @@ __global__ __launch_bounds__(512) void k_reduce_valid(const Tile* __restrict__ t
                                                       const PatchDesc* __restrict__ patches,
                                                       const TA* __restrict__ a,
                                                       const double* __restrict__ b,
-                                                      double* __restrict__ partials, unsigned int* __restrict__ counter,
-                                                      double* __restrict__ out, ScalarPublish pub)
+                                                      double* __restrict__ partials)
 {
     const Tile t = tiles[blockIdx.x];
     const PatchDesc p = patches[t.patch];
@@ -722,38 +721,6 @@ __global__ __launch_bounds__(512) void k_reduce_valid(const Tile* __restrict__ t
     }
     acc = (MODE == 1 || MODE == 3) ? block_reduce<true>(acc) : block_reduce<false>(acc);
     if (threadIdx.x == 0 && threadIdx.y == 0) partials[blockIdx.x] = acc;
-    if (!counter) return;   // two-launch form: k_reduce_final follows
-    // Single-launch form: the LAST workgroup to arrive adds the partials up, with k_reduce_final's own arithmetic -- 256
-    // (virtual) threads striding the partials, a shuffle tree per (virtual) wavefront, the four wavefront sums added in order
-    // -- so the result has the same bits as the two-launch form; it then clears the counter and publishes the scalar.
-    constexpr int OP = (MODE == 1) ? 1 : (MODE == 3 ? 2 : 0);
-    __shared__ int isLast;
-    __shared__ double sv[4];
-    const int tid = threadIdx.y * blockDim.x + threadIdx.x;
-    __threadfence();
-    if (tid == 0) isLast = (atomicAdd(counter, 1u) == gridDim.x - 1) ? 1 : 0;
-    __syncthreads();
-    if (!isLast) return;
-    __threadfence();
-    const int lane = tid & 63, w = tid >> 6, nw = (blockDim.x * blockDim.y) >> 6;
-    const int nparts = (int)gridDim.x;
-    for (int q = w; q < 4; q += nw) {
-        double r = (OP == 2) ? -1.7976931348623157e308 : 0.0;
-        for (int i = 64 * q + lane; i < nparts; i += 256) {
-            const double x = __hip_atomic_load(partials + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            r = OP ? fmax(r, x) : r + x;
-        }
-        r = OP ? wave_max(r) : wave_sum(r);
-        if (lane == 0) sv[q] = r;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double r = sv[0];
-        for (int q = 1; q < 4; ++q) r = OP ? fmax(r, sv[q]) : r + sv[q];
-        out[0] = r;
-        *counter = 0u;
-        if (pub.host_seq) publish_scalars(&r, 1, pub);
-    }
 }
 
 // Reference-ordered sums for SMALL levels (one wavefront): box after box, cells in Fortran order, one running
@@ -1286,9 +1253,7 @@ void launch_reduce(hipStream_t st, const LevelDev& L, const double* a, const dou
 {
     const ScalarPublish P = pub ? *pub : ScalarPublish{nullptr, nullptr, 0ull};
     if (ordered && (mode == 0 || mode == 2) && L.ntiles > 0) {
-        // SOMAR_ORDERED_SERIAL=1: the one-wavefront walk over all boxes (A/B switch; same bits)
-        static const bool serial = getenv("SOMAR_ORDERED_SERIAL") != nullptr;
-        if (serial) {
+        if (L.ordered_serial) {   // the one-wavefront walk over all boxes (A/B switch; same bits)
             if (mode == 0)
                 hipLaunchKernelGGL(k_reduce_ordered<0>, dim3(1), dim3(64), 0, st, L.patches, L.npatches, a, b, 0.0, out, P);
             else
@@ -1305,15 +1270,7 @@ void launch_reduce(hipStream_t st, const LevelDev& L, const double* a, const dou
         if (pub) launch_publish(st, out, 1, pub->host_dst, pub->host_seq, pub->seq);
         return;
     }
-    // EXPERIMENT, off by default (SOMAR_ONE_LAUNCH_REDUCE=1): the last workgroup to arrive finishes the reduction, one launch
-    // instead of two.  Bit-identical, but measured slower on every workload -- each workgroup pays a device-scope fence and an
-    // atomic on one counter, and the finishing workgroup's serial tail is longer than a launch: C3 19.4 -> 23.8 ms, C2 95.1 ->
-    // 92.3 V-cycles/s on grids <= 512 tiles; on million-tile levels far worse (C4 147 -> 201 ms).
-    static const bool one = getenv("SOMAR_ONE_LAUNCH_REDUCE") != nullptr;
-    unsigned int* cnt = (!one || L.ntiles > 512) ? nullptr : L.red_counter;
-#define SOMAR_RV(M)                                                                                                           \
-    hipLaunchKernelGGL(k_reduce_valid<M>, dim3(L.ntiles), tile_block(L), 0, st, L.tiles, L.patches, a, b, partials, cnt, out, \
-                       cnt ? P : ScalarPublish{nullptr, nullptr, 0ull})
+#define SOMAR_RV(M) hipLaunchKernelGGL(k_reduce_valid<M>, dim3(L.ntiles), tile_block(L), 0, st, L.tiles, L.patches, a, b, partials)
     if (mode == 0) SOMAR_RV(0);
     else if (mode == 1) SOMAR_RV(1);
     else if (mode == 2) SOMAR_RV(2);
@@ -1321,7 +1278,6 @@ void launch_reduce(hipStream_t st, const LevelDev& L, const double* a, const dou
     else if (mode == 4) SOMAR_RV(4);
     else SOMAR_RV(5);
 #undef SOMAR_RV
-    if (cnt) return;
     hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, st, partials, L.ntiles, 1,
                        mode == 1 ? 1 : (mode == 3 ? 2 : 0), out, P);
 }
@@ -1335,7 +1291,7 @@ void launch_reduce(hipStream_t st, const LevelDev& L, const float* a, const doub
     }
     // the two-launch form of the fp64 reduction (same partition, same tree)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reduce_valid<0, float>), dim3(L.ntiles), tile_block(L), 0, st, L.tiles, L.patches, a, b,
-                       partials, nullptr, out, ScalarPublish{nullptr, nullptr, 0ull});
+                       partials);
     hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, st, partials, L.ntiles, 1, 0, out,
                        ScalarPublish{nullptr, nullptr, 0ull});
 }
@@ -1358,49 +1314,6 @@ void launch_fill_hash(hipStream_t st, const LevelDev& L, double* f, unsigned lon
 {
     if (L.ntiles == 0) return;
     hipLaunchKernelGGL(k_fill_hash, dim3(L.ntiles), tile_block(L), 0, st, L.tiles, L.patches, f, L.P, seed);
-}
-
-// min / max of one coefficient array over the valid cells (dir < 0) or the valid dir-faces of every patch, MM_CH chunks of
-// k-planes per patch: out[2 * (patch * MM_CH + chunk)] = min, [... + 1] = max (+-inf for an empty chunk).  Runs once per depth
-// at finalize (detect_uniform_metric).
-__global__ __launch_bounds__(256) void k_minmax_valid(const PatchDesc* __restrict__ patches, const double* __restrict__ a, int dir,
-                                                      double* __restrict__ out)
-{
-    const PatchDesc p = patches[blockIdx.x];
-    const int n0 = p.n[0] + (dir == 0), n1 = p.n[1] + (dir == 1), n2 = p.n[2] + (dir == 2);
-    const int per = (n2 + MM_CH - 1) / MM_CH;
-    const int k0 = per * blockIdx.y, k1 = k0 + per < n2 ? k0 + per : n2;
-    double lo = HUGE_VAL, hi = -HUGE_VAL;
-    for (int k = k0; k < k1; ++k)
-        for (int j = threadIdx.y; j < n1; j += 4) {
-            const double* row = a + p.off + (long long)p.pj * j + p.pk * k;
-            for (int i = threadIdx.x; i < n0; i += 64) {
-                const double v = row[i];
-                lo = v < lo ? v : lo;
-                hi = v > hi ? v : hi;
-            }
-        }
-    __shared__ double slo[256], shi[256];
-    const int t = threadIdx.x + 64 * threadIdx.y;
-    slo[t] = lo;
-    shi[t] = hi;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) {
-            slo[t] = slo[t + s] < slo[t] ? slo[t + s] : slo[t];
-            shi[t] = shi[t + s] > shi[t] ? shi[t + s] : shi[t];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        const long long o = 2 * ((long long)blockIdx.x * MM_CH + blockIdx.y);
-        out[o] = slo[0];
-        out[o + 1] = shi[0];
-    }
-}
-void launch_minmax_valid(hipStream_t st, const LevelDev& L, const double* a, int dir, double* out)
-{
-    if (L.npatches) hipLaunchKernelGGL(k_minmax_valid, dim3(L.npatches, MM_CH), dim3(64, 4), 0, st, L.patches, a, dir, out);
 }
 
 // ---- the bottom solver of a tiny level in ONE launch -----------------------------------------------------------------------------

@@ -31,7 +31,7 @@ LepticParams::LepticParams()
     full.spaceDim = 3;
 }
 
-LepticSolver::LepticSolver(Comm* comm, hipStream_t shared) : comm_(comm)
+LepticSolver::LepticSolver(Comm* comm, hipStream_t shared, const Tuning& tune) : tune_(tune), comm_(comm)
 {
     if (shared) { st_ = shared; own_stream_ = false; }
     else SOMAR_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
@@ -58,7 +58,7 @@ void LepticSolver::define(const IBox& domain, const bool periodic[3], const doub
     SOMAR_CHECK(!orig_, "leptic solver already defined");
     prm = lp;
     SOMAR_CHECK(prmOrig.spaceDim == 3, "the leptic solver is implemented for space_dim 3");
-    own_orig_.reset(new PressureSolver(comm_, st_));
+    own_orig_.reset(new PressureSolver(comm_, st_, tune_));
     orig_ = own_orig_.get();
     orig_->define(domain, periodic, dx, bc_type, boxes, owner, alpha, beta, prmOrig, dxCrse);
     define_inner(domain, periodic, dx, bc_type, boxes, owner, dxCrse, prmOrig.eps);
@@ -129,7 +129,7 @@ void LepticSolver::define_inner(const IBox& domain, const bool periodic[3], cons
     //                                                                                   LevelLepticSolver.cpp:214-300
     SolverParams pf = prm.full;
     pf.spaceDim = 3;
-    vert_.reset(new PressureSolver(comm_, st_));
+    vert_.reset(new PressureSolver(comm_, st_, tune_));
     vert_->define(domain, periodic, dx, bc_type, boxes, owner, 0.0, 1.0, pf, dxCrse);
     vert_->probe_eps = probeEps;
     if (!doHorizSolve_) return;   // no Neumann-Neumann column: no excess, no flat problem (:304)
@@ -151,7 +151,7 @@ void LepticSolver::define_inner(const IBox& domain, const bool periodic[3], cons
     horizRemoveAvg_ = horizCells_ == flatDom.numPts();
     SolverParams ph = prm.horiz;
     ph.spaceDim = 2;
-    horiz_.reset(new PressureSolver(comm_, st_));
+    horiz_.reset(new PressureSolver(comm_, st_, tune_));
     horiz_->define(flatDom, periodic, dx, bc_type, flat, flatOwner, 0.0, 1.0, ph, dxCrse);   // forceDxCrse(m_dxCrse), :381
     horiz_->probe_eps = probeEps;
 }

@@ -49,7 +49,8 @@ struct LepticStats {
 class LepticSolver {
 public:
     // shared: run on the caller's stream (an AMR hierarchy's) instead of an own one
-    explicit LepticSolver(Comm* comm = nullptr, hipStream_t shared = nullptr);
+    // tune: handed to every internal level solver (an attached solver's hierarchy passes its own)
+    LepticSolver(Comm* comm, hipStream_t shared, const Tuning& tune);
     ~LepticSolver();
     void define(const IBox& domain, const bool periodic[3], const double dx[3], const int bc_type[3][2],
                 const std::vector<IBox>& boxes, const std::vector<int>& owner, double alpha, double beta,
@@ -78,6 +79,7 @@ public:
 private:
     void set_zero_avg(double* hphi);
     void solve_fields_no_horiz(double* phi, const double* rhs, LepticStats& S, bool homogeneous);
+    const Tuning tune_;
     Comm* comm_;
     hipStream_t st_ = nullptr;
     void define_inner(const IBox& domain, const bool periodic[3], const double dx[3], const int bc_type[3][2],

@@ -516,7 +516,6 @@ Level::~Level()
     hipFree(d_stiles);
     hipFree(d_ctiles);
     hipFree(d_local_items);
-    hipFree(d_red_counter);
     hipFree(d_tile_items);
     hipFree(d_tile_item_start);
     hipFree(d_send_items);
@@ -551,13 +550,13 @@ void Level::build_march_tiles(bool narrow7)
     // per wavefront; class 1 = 60 columns, two rows per wavefront; class 4 = 4 columns, sixteen rows per wavefront.  A box
     // is cut into 124-wide columns and its remainder into the narrow classes (128 -> 124 + 4, 64 -> 60 + 4, 512 -> 4 x 124 +
     // 4 x 4), so that a remainder column costs a sixteenth (a half) of a workgroup-march instead of a whole one.
-    // `classes` off (SOMAR_NO_NARROW_TILES, the 6-/8-row A/B variants): columns of equal width, all class 0 (128 -> 2 x 64,
+    // `classes` off (Tuning::no_narrow_tiles, the 6-/8-row A/B variants): columns of equal width, all class 0 (128 -> 2 x 64,
     // 512 -> 5 x 104).  region_rows = blockDim.y of the kernel, hrows = region rows that are halo.
     struct ColSpec { int i0, w, cls; };
-    static const bool narrow_on = getenv("SOMAR_NO_NARROW_TILES") == nullptr;   // A/B switch
+    const int fused_rows = dev.fused_rows, full_rows = dev.full_rows;
     auto march_tiles = [&](int FT_I, int region_rows, int hrows, double halo, int slots, bool classes, double min_gain = 1.0) {
-        classes = classes && narrow_on;
-        static const bool balanced = getenv("SOMAR_NO_BALANCED_TILES") == nullptr;  // A/B switch
+        classes = classes && !tune.no_narrow_tiles;
+        const bool balanced = !tune.no_balanced_tiles;
         // min_gain: the narrow decomposition is taken only where it costs at most that fraction of the equal columns' workgroup-
         // marches (a class-4 workgroup counted as a quarter: it runs long; a class-1 one as a half).  1.0 = always.
         auto columns = [&](int n0) {
@@ -632,7 +631,7 @@ void Level::build_march_tiles(bool narrow7)
         for (int b = 0; b < NF; ++b) perm[b] = fnat[start[b % NX] + b / NX];
         return perm;
     };
-    hftiles = march_tiles(124, fused_rows(), 4, 3.0, 256, narrow7 && fused_rows() == 16, 0.85);
+    hftiles = march_tiles(124, fused_rows, 4, 3.0, 256, narrow7 && fused_rows == 16, 0.85);
     d_ftiles = to_device(hftiles);
     nftiles = (int)hftiles.size();
     hrtiles = march_tiles(124, 16, 2, 2.0, 256, narrow7, 0.85);
@@ -646,7 +645,7 @@ void Level::build_march_tiles(bool narrow7)
     // every table: narrow classes where they save at least 15 % of the workgroup-marches (64-wide boxes: C5 62.8 -> 53.1 ms per
     // AMR V-cycle; 128-wide: C4 136.8 -> 111.6).  One 512-wide box, 5 equal columns against 4 + 4 narrow, is a wash or worse:
     // 19-point colour pass 3.02 -> 3.07 ms, residual 3.17 -> 3.42; c2_cartesian 151 -> 149-158 V-cycles/s depending on tile order)
-    hqtiles = march_tiles(124, full_march_rows(), 2, 2.0, full_march_rows() == 6 ? 512 : 256, full_march_rows() == 8, 0.85);   // 6 rows: two workgroups per CU
+    hqtiles = march_tiles(124, full_rows, 2, 2.0, full_rows == 6 ? 512 : 256, full_rows == 8, 0.85);   // 6 rows: two workgroups per CU
     d_qtiles = to_device(hqtiles);
     nqtiles = (int)hqtiles.size();
     dev.narrowq = 0;
@@ -715,7 +714,7 @@ void Level::build_march_tiles(bool narrow7)
             }
         };
         std::vector<Tile> own, rem;
-        split(hftiles, fused_rows(), 4, FRAME, own, rem);
+        split(hftiles, fused_rows, 4, FRAME, own, rem);
         nftiles_own = (int)own.size();
         nftiles_rem = (int)rem.size();
         d_ftiles_own = to_device(own);
@@ -731,10 +730,15 @@ void Level::build_march_tiles(bool narrow7)
 }
 
 void Level::define(const IBox& dom, const bool per[3], const double dx_[3], const int bct[3][2],
-                   const std::vector<IBox>& bx, const std::vector<int>& own, Comm* c)
+                   const std::vector<IBox>& bx, const std::vector<int>& own, Comm* c, const Tuning& t)
 {
     domain = dom;
     comm = c;
+    tune = t;
+    dev.fused_rows = (int)t.fused_rows;
+    dev.full_rows = (int)t.full_rows;
+    dev.lean_tiles = t.no_lean_tiles ? 0 : 1;
+    dev.ordered_serial = t.ordered_serial ? 1 : 0;
     const int myrank = c ? c->rank : 0;
     for (int d = 0; d < 3; ++d) {
         periodic[d] = per[d];
@@ -854,12 +858,9 @@ void Level::define(const IBox& dom, const bool per[3], const double dx_[3], cons
     dev.ntiles = N;
     dev.patches = d_patches;
     dev.npatches = (int)hpatches.size();
-    SOMAR_HIP(hipMalloc(&d_red_counter, sizeof(unsigned int)));
-    SOMAR_HIP(hipMemset(d_red_counter, 0, sizeof(unsigned int)));
-    dev.red_counter = d_red_counter;
     // ---- pull exchange: per tile, the local copy items clipped to the tile's one-cell halo (k_gsrb_ortho / k_op_ortho) ----
     {
-        static const long long pullMax = getenv("SOMAR_PULL_MAX_CELLS") ? atoll(getenv("SOMAR_PULL_MAX_CELLS")) : 262144;
+        const long long pullMax = tune.pull_max_cells;
         long long cells = 0;
         for (const IBox& b : boxes) cells += b.numPts();
         if (plan.peers.empty() && cells <= pullMax && N > 0) {

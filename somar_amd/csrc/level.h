@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "tuning.h"
 
 namespace somar {
 
@@ -135,13 +136,13 @@ public:
     long long valid_cells_global = 0;
     ExchangePlan plan;
     Comm* comm = nullptr;
+    Tuning tune;               // the owning solver's switches, as define received them (tile tables are rebuilt later)
 
     // device tables
     PatchDesc* d_patches = nullptr;
     Tile* d_tiles = nullptr;
     CopyItem* d_local_items = nullptr;
-    // pull exchange tables (LevelDev::tile_items): built for single-rank levels of at most PULL_MAX_CELLS cells
-    unsigned int* d_red_counter = nullptr;
+    // pull exchange tables (LevelDev::tile_items): built for single-rank levels of at most Tuning::pull_max_cells cells
     CopyItem* d_tile_items = nullptr;
     int* d_tile_item_start = nullptr;
     bool pull_ready() const { return d_tile_item_start != nullptr; }
@@ -191,9 +192,10 @@ public:
     Level(const Level&) = delete;
     Level& operator=(const Level&) = delete;
 
-    // Build tables for a layout.  bc_type codes: BC_NEUM / BC_DIRI per non-periodic side.
+    // Build tables for a layout.  bc_type codes: BC_NEUM / BC_DIRI per non-periodic side.  t: the pull-exchange limit, the tile
+    // column rules and the marching kernels' row counts; what the launchers need of it is copied into dev.
     void define(const IBox& dom, const bool per[3], const double dx_[3], const int bct[3][2],
-                const std::vector<IBox>& bx, const std::vector<int>& own, Comm* c);
+                const std::vector<IBox>& bx, const std::vector<int>& own, Comm* c, const Tuning& t);
     // allocate coefficient planes (zero-filled) and fill dev view
     void alloc_metric();
     void refresh_params();

@@ -75,8 +75,9 @@ void launch_coarsen_metric(hipStream_t st, const LevelDev& C, const LevelDev& F,
                        r[2]);
 }
 
-// k_minmax_valid's reduction for a table of (array, patch table, patch, dir) items: out[2 * (item * MM_CH + chunk)] = min,
-// [... + 1] = max over the valid cells (dir < 0) or the valid dir-faces, +-inf for an empty chunk
+// min / max of a table of (array, patch table, patch, dir) items, MM_CH chunks of k-planes per item: out[2 * (item * MM_CH +
+// chunk)] = min, [... + 1] = max over the valid cells (dir < 0) or the valid dir-faces, +-inf for an empty chunk.  Runs at
+// finalize and at every metric refresh (PressureSolver::detect_metric_flags).
 __global__ __launch_bounds__(256) void k_minmax_all(const MinMaxItem* __restrict__ items, double* __restrict__ out)
 {
     const MinMaxItem it = items[blockIdx.x];

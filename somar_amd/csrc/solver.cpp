@@ -13,7 +13,7 @@ namespace somar {
 static const int S_MAX_COARSE = 4;  // MappedAMRPoissonOp::s_maxCoarse, MappedAMRPoissonOp.cpp:55
 enum { SLOT_TMP = 0, SLOT_SUMS = 8, NSLOTS = 16 };
 
-PressureSolver::PressureSolver(Comm* comm, hipStream_t shared) : comm_(comm ? comm : &self_)
+PressureSolver::PressureSolver(Comm* comm, hipStream_t shared, const Tuning& tune) : tune_(tune), comm_(comm ? comm : &self_)
 {
     if (shared) { st_ = shared; own_stream_ = false; }
     else SOMAR_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
@@ -23,22 +23,6 @@ PressureSolver::PressureSolver(Comm* comm, hipStream_t shared) : comm_(comm ? co
     SOMAR_HIP(hipHostMalloc(&h_scalars, (NSLOTS + 2) * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
     h_seq_ = reinterpret_cast<unsigned long long*>(h_scalars + NSLOTS);
     *h_seq_ = 0;
-    // levels smaller than this use the two-pass colour kernel (launch-latency bound anyway);
-    // SOMAR_FUSED_MIN_CELLS=0 forces the fused sweep everywhere (tests), a huge value disables it.
-    if (const char* e = getenv("SOMAR_FUSED_MIN_CELLS")) fused_min_cells_ = atoll(e);
-    march_min_cells_ = fused_min_cells_;
-    if (const char* e = getenv("SOMAR_MARCH_MIN_CELLS")) march_min_cells_ = atoll(e);
-    // levels up to this many cells sum in the reference's serial order (k_reduce_ordered); tests raise it to
-    // make whole solves reproduce the oracle's histories to the last bits
-    if (const char* e = getenv("SOMAR_ORDERED_REDUCE_MAX")) ordered_max_cells_ = atoll(e);
-    if (const char* e = getenv("SOMAR_FUSED_BOTTOM_MAX_CELLS")) fused_bottom_max_ = atoll(e);
-    if (const char* e = getenv("SOMAR_BOX_BOTTOM")) box_bottom_on_ = atoi(e) != 0;
-    if (const char* e = getenv("SOMAR_GHOST_STAGED")) ghost_box_on_ = atoi(e) == 0;
-    if (const char* e = getenv("SOMAR_NO_OVERLAP")) overlap_on_ = atoi(e) == 0;
-    if (const char* e = getenv("SOMAR_BOX_BOTTOM_MIN_CELLS")) box_min_cells_ = atoll(e);
-    if (const char* e = getenv("SOMAR_AGGLOM_CELLS")) agglom_cells_ = atoll(e);
-    if (const char* e = getenv("SOMAR_GRAPH_CELLS")) graph_cells_ = atoll(e);
-    if (const char* e = getenv("SOMAR_BOTTOM_ASYNC")) bottom_async_ = atoi(e) != 0;
 }
 
 PressureSolver::~PressureSolver()
@@ -158,8 +142,7 @@ double PressureSolver::fetch_scalar(int slot)
 // number: the round trip drops to the latency of a PCIe write (SOMAR_POLL_FETCH=0 restores copy + synchronize).
 void PressureSolver::fetch_scalars(int slot, int n)
 {
-    static const bool poll = !(getenv("SOMAR_POLL_FETCH") && atoi(getenv("SOMAR_POLL_FETCH")) == 0);
-    if (!poll || capturing_) {
+    if (!tune_.poll_fetch || capturing_) {
         SOMAR_HIP(hipMemcpyAsync(h_scalars + slot, d_scalars + slot, n * sizeof(double), hipMemcpyDeviceToHost, st_));
         SOMAR_HIP(hipStreamSynchronize(st_));
         return;
@@ -261,7 +244,7 @@ void PressureSolver::define(const IBox& domain, const bool periodic[3], const do
     }
     L->alpha = alpha;
     L->beta = beta;
-    L->define(domain, periodic, dx, bc_type, boxes, owner, comm_);
+    L->define(domain, periodic, dx, bc_type, boxes, owner, comm_, tune_);
     L->alloc_metric();
     if (hasCF_) {
         L->define_cf(dxCrse_);
@@ -351,7 +334,7 @@ bool PressureSolver::build_coarser(int depth)
     for (const IBox& b : F.boxes) cb.push_back(b.coarsen(r));
     double cdx[3];
     for (int d = 0; d < 3; ++d) cdx[d] = F.dx[d] * (double)r[d];
-    C->define(F.domain.coarsen(r), F.periodic, cdx, F.bc_type, cb, F.owner, comm_);
+    C->define(F.domain.coarsen(r), F.periodic, cdx, F.bc_type, cb, F.owner, comm_, tune_);
     C->alloc_metric();
     if (hasCF_) C->define_cf(dxCrse_);  // CFRegion::coarsen + the AMR coarser level's spacing (Factory.cpp:596-600)
     // coarse metrics: fill_MGfields, MappedAMRPoissonOpFactory.cpp:1164-1234
@@ -411,106 +394,6 @@ void PressureSolver::probe_null_space(int d)
     Level::free_field(res);
 }
 
-// A Cartesian map hands over constant arrays (CartesianMap.cpp:261-280): J g^{aa} and J^{-1} are then the same number on
-// every face / in every cell of a depth -- and of every coarser depth, whose averages of equal numbers are exact.  The
-// k-marching kernels take such coefficients from StencilParams instead of streaming them (same arithmetic, same bits).
-// SOMAR_NO_UNIFORM=1 disables the detection (A/B measurements, parity tests of the streaming path on Cartesian inputs).
-void PressureSolver::detect_uniform_metric()
-{
-    const char* e = getenv("SOMAR_NO_UNIFORM");
-    const bool off = e && atoi(e) != 0;
-    for (auto& Lp : lev) Lp->dev.P.uniform = 0;
-    if (off || full_ || prm.spaceDim != 3) return;
-    // one scratch buffer for the deepest patch table, released whatever happens below
-    size_t nmax = 1;
-    for (auto& Lp : lev) nmax = std::max(nmax, (size_t)std::max(Lp->npatches(), 1));
-    const size_t cap = 2 * nmax * MM_CH;
-    struct Scratch {
-        double* p = nullptr;
-        ~Scratch() { hipFree(p); }
-    } scratch;
-    SOMAR_HIP(hipMalloc(&scratch.p, sizeof(double) * (cap + 8)));
-    double* d_mm = scratch.p;
-    std::vector<double> mm(cap);
-    for (auto& Lp : lev) {
-        Level& L = *Lp;
-        if (!(L.active[0] && L.active[1] && L.active[2])) continue;
-        const int np = L.npatches();
-        // (max, -min) of the four arrays; a rank without boxes on this depth contributes -inf
-        double h[8];
-        for (double& v : h) v = -HUGE_VAL;
-        const size_t nmm = 2 * (size_t)std::max(np, 1) * MM_CH;
-        for (int a = 0; a < 4; ++a) {
-            if (!np) break;
-            launch_minmax_valid(st_, L.dev, a < 3 ? L.dev.jg[a] : L.dev.jinv, a < 3 ? a : -1, d_mm);
-            SOMAR_HIP(hipMemcpyAsync(mm.data(), d_mm, sizeof(double) * nmm, hipMemcpyDeviceToHost, st_));
-            SOMAR_HIP(hipStreamSynchronize(st_));
-            for (size_t q = 0; q < (size_t)np * MM_CH; ++q) {
-                h[2 * a] = std::max(h[2 * a], mm[2 * q + 1]);
-                h[2 * a + 1] = std::max(h[2 * a + 1], -mm[2 * q]);
-            }
-        }
-        if (comm_->size > 1) {
-            double* d8 = d_mm + cap;
-            SOMAR_HIP(hipMemcpyAsync(d8, h, sizeof(h), hipMemcpyHostToDevice, st_));
-            comm_->allreduce(d8, 8, 1, st_);
-            SOMAR_HIP(hipMemcpyAsync(h, d8, sizeof(h), hipMemcpyDeviceToHost, st_));
-            SOMAR_HIP(hipStreamSynchronize(st_));
-        }
-        bool uni = true;
-        for (int a = 0; a < 4; ++a) uni = uni && std::isfinite(h[2 * a]) && h[2 * a] == -h[2 * a + 1];
-        if (!uni) continue;
-        L.dev.P.uniform = 1;
-        for (int a = 0; a < 4; ++a) L.dev.P.uc[a] = h[2 * a];
-    }
-}
-
-// Non-diagonal metric: are J g^{xy} (x-faces) and J g^{yx} (y-faces) identically zero on a depth?  True for every map of the
-// form x = xi, y = eta, z = z(xi, eta, zeta) -- BathymetricBaseMap (geometry/maps/BathymetricBaseMap.cpp:133-313) and all its
-// subclasses: the x-face normal has no eta component.  Coarse depths inherit it (averages of zeros).  SOMAR_NO_ZERO_PLANES=1
-// switches the detection off (A/B; the kernels then multiply the stored zeros, same values).
-void PressureSolver::detect_zero_planes()
-{
-    for (auto& Lp : lev) Lp->dev.P.zero_xy = 0;
-    const char* e = getenv("SOMAR_NO_ZERO_PLANES");
-    if ((e && atoi(e) != 0) || !full_ || prm.spaceDim != 3) return;
-    size_t nmax = 1;
-    for (auto& Lp : lev) nmax = std::max(nmax, (size_t)std::max(Lp->npatches(), 1));
-    const size_t cap = 2 * nmax * MM_CH;
-    struct Scratch {
-        double* p = nullptr;
-        ~Scratch() { hipFree(p); }
-    } scratch;
-    SOMAR_HIP(hipMalloc(&scratch.p, sizeof(double) * (cap + 1)));
-    std::vector<double> mm(cap);
-    for (auto& Lp : lev) {
-        Level& L = *Lp;
-        if (!(L.active[0] && L.active[1] && L.active[2])) continue;
-        const int np = L.npatches();
-        double nonzero = 0.0;   // max |value| over both planes
-        const int pl[2][2] = {{0, 1}, {1, 0}};
-        for (int w = 0; w < 2 && np; ++w) {
-            const double* a = L.dev.jgf[pl[w][0]][pl[w][1]];
-            if (!a) { nonzero = 1.0; break; }
-            launch_minmax_valid(st_, L.dev, a, pl[w][0], scratch.p);
-            SOMAR_HIP(hipMemcpyAsync(mm.data(), scratch.p, sizeof(double) * 2 * (size_t)np * MM_CH, hipMemcpyDeviceToHost, st_));
-            SOMAR_HIP(hipStreamSynchronize(st_));
-            for (size_t q = 0; q < (size_t)np * MM_CH; ++q) {
-                if (std::isfinite(mm[2 * q])) nonzero = std::max(nonzero, std::fabs(mm[2 * q]));
-                if (std::isfinite(mm[2 * q + 1])) nonzero = std::max(nonzero, std::fabs(mm[2 * q + 1]));
-            }
-        }
-        if (comm_->size > 1) {
-            double* d1 = scratch.p + cap;
-            SOMAR_HIP(hipMemcpyAsync(d1, &nonzero, sizeof(double), hipMemcpyHostToDevice, st_));
-            comm_->allreduce(d1, 1, 1, st_);
-            SOMAR_HIP(hipMemcpyAsync(&nonzero, d1, sizeof(double), hipMemcpyDeviceToHost, st_));
-            SOMAR_HIP(hipStreamSynchronize(st_));
-        }
-        L.dev.P.zero_xy = nonzero == 0.0 ? 1 : 0;
-    }
-}
-
 void PressureSolver::finalize()
 {
     SOMAR_CHECK(!lev.empty() && !finalized, "finalize before define / twice");
@@ -518,8 +401,8 @@ void PressureSolver::finalize()
         const std::string why = mixed_refusal();   // (the metric kind is only known now)
         SOMAR_CHECK(why.empty(), "finalize: mixed precision (set_precision mode 1) is not available for " + why);
     }
-    // SOMAR_TIMING=1: wall time of the stages below on stderr (what a re-definition of the hierarchy costs)
-    static const bool timing = getenv("SOMAR_TIMING") && atoi(getenv("SOMAR_TIMING")) != 0;
+    // Tuning::timing: wall time of the stages below on stderr (what a re-definition of the hierarchy costs)
+    const bool timing = tune_.timing != 0;
     auto now = [&]() { if (timing) hipDeviceSynchronize(); return std::chrono::steady_clock::now(); };
     auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
         return std::chrono::duration<double>(b - a).count();
@@ -529,24 +412,23 @@ void PressureSolver::finalize()
     fill_metric_ghosts(*lev[0]);
     int depth = 1;
     while (build_coarser(depth)) {
-        if (comm_->size > 1 && lev[depth]->valid_cells_global <= agglom_cells_ && !full_) {
+        if (comm_->size > 1 && lev[depth]->valid_cells_global <= tune_.agglom_cells && !full_) {
             build_agglomerated_tail(depth);
             break;
         }
         ++depth;
     }
     const auto t1 = now();
-    detect_uniform_metric();
-    detect_zero_planes();
+    detect_metric_flags();
     {
         // the fused red+black 19-point sweep on levels of large boxes
-        if (const char* e = getenv("SOMAR_FUSED19_MIN_BOX")) fused19_min_box_ = atoi(e);
+        const int min_box = (int)tune_.fused19_min_box;
         fused19_.assign(lev.size(), 0);
         for (size_t d = 0; d < lev.size(); ++d) {
             Level& L = *lev[d];
-            bool ok = full_ && fused19_min_box_ >= 0 && full_march((int)d) && full_march_rows() == 8 && !L.boxes.empty();
+            bool ok = full_ && min_box >= 0 && full_march((int)d) && tune_.full_rows == 8 && !L.boxes.empty();
             for (const IBox& b : L.boxes)
-                for (int a = 0; a < 3; ++a) ok = ok && b.size(a) >= std::max(fused19_min_box_, 8) && (a != 0 || b.size(a) % 2 == 0);
+                for (int a = 0; a < 3; ++a) ok = ok && b.size(a) >= std::max(min_box, 8) && (a != 0 || b.size(a) % 2 == 0);
             fused19_[d] = ok ? 1 : 0;
             if (ok != L.want_fused19_) {
                 L.want_fused19_ = ok;
@@ -554,15 +436,7 @@ void PressureSolver::finalize()
             }
         }
     }
-    {
-        // narrow lane classes for the 7-point marching kernels where the metric is uniform (Level::build_march_tiles says why);
-        // SOMAR_NARROW_7PT = 0 | 1 forces never / always (A/B)
-        const char* e = getenv("SOMAR_NARROW_7PT");
-        for (auto& Lp : lev) {
-            const bool want = e ? atoi(e) != 0 : Lp->dev.P.uniform != 0;
-            if (want != Lp->narrow7_) Lp->build_march_tiles(want);
-        }
-    }
+    choose_narrow_tiles();
     const auto t2 = now();
     struct Report {
         bool on; std::chrono::steady_clock::time_point t0, t1, t2; long long cells;
@@ -576,9 +450,6 @@ void PressureSolver::finalize()
         }
     } report{timing, t0, t1, t2, lev[0]->valid_cells_global};
     (void)secs;
-    int maxTiles = 1;
-    for (auto& L : lev) maxTiles = std::max(std::max(maxTiles, L->dev.ntiles), std::max(L->nrtiles, L->nftiles));
-    SOMAR_HIP(hipMalloc(&d_partials, (size_t)maxTiles * 2 * sizeof(double)));
     const int D = (int)lev.size();
     f_res.assign(D, nullptr);
     f_corr.assign(D, nullptr);
@@ -629,9 +500,9 @@ void PressureSolver::finalize()
     for (int d = 0; d < D; ++d) probe_null_space(d);
     // first depth whose V-cycle leg is launch-bound (see solver.h); one rank only, never inside a sharded region
     graph_from_ = -1;
-    if (comm_->size == 1 && !coarse_ && graph_cells_ > 0)
+    if (comm_->size == 1 && !coarse_ && tune_.graph_cells > 0)
         for (int d = 0; d <= D - 2; ++d)
-            if (lev[d]->valid_cells_global <= graph_cells_) { graph_from_ = d; break; }
+            if (lev[d]->valid_cells_global <= tune_.graph_cells) { graph_from_ = d; break; }
     sync();
     finalized = true;
     if (mp_mode_ == 1 || comm_->size > 1) mp_setup();   // (sharded: every rank's mode has to be the same one, fp64 included)
@@ -645,9 +516,10 @@ void PressureSolver::build_agglomerated_tail(int depth)
     Level& T = *lev[depth];
     SolverParams cp = prm;
     if (cp.maxDepth >= 0) cp.maxDepth = std::max(0, cp.maxDepth - depth);
-    coarse_.reset(new PressureSolver(nullptr, st_));
+    Tuning ct = tune_;
+    ct.graph_cells = 0;  // graph replay is exercised (and measured) on single-process runs only
+    coarse_.reset(new PressureSolver(nullptr, st_, ct));
     coarse_->probe_eps = probe_eps > 0.0 ? probe_eps : prm.eps;
-    coarse_->graph_cells_ = 0;  // graph replay is exercised (and measured) on single-process runs only
     for (int a = 0; a < 3; ++a)
         for (int q = 0; q < 2; ++q) coarse_->bc_value_[a][q] = bc_value_[a][q];
     std::vector<int> own(T.boxes.size(), 0);
@@ -758,13 +630,21 @@ bool PressureSolver::metric_update_end(bool only_if_written)
     return run;
 }
 
+// Diagonal metric: a Cartesian map hands over constant arrays (CartesianMap.cpp:261-280): J g^{aa} and J^{-1} are then the same
+// number on every face / in every cell of a depth -- and of every coarser depth, whose averages of equal numbers are exact.  The
+// k-marching kernels take such coefficients from StencilParams instead of streaming them (same arithmetic, same bits).
+// Tuning::no_uniform disables the detection (A/B measurements, parity tests of the streaming path on Cartesian inputs).
+// Non-diagonal metric: are J g^{xy} (x-faces) and J g^{yx} (y-faces) identically zero on a depth?  True for every map of the
+// form x = xi, y = eta, z = z(xi, eta, zeta) -- BathymetricBaseMap (geometry/maps/BathymetricBaseMap.cpp:133-313) and all its
+// subclasses: the x-face normal has no eta component.  Coarse depths inherit it (averages of zeros).  Tuning::no_zero_planes
+// switches the detection off (A/B; the kernels then multiply the stored zeros, same values).
+// One launch and one download for every depth and array; the item table is built at finalize and serves every refresh -- so a
+// depth with a plane missing at finalize (mm_first_ = -1) stays "not zero" for the life of the solver, which is the safe side.
 void PressureSolver::detect_metric_flags()
 {
     const int D = (int)lev.size();
-    const char* eu = getenv("SOMAR_NO_UNIFORM");
-    const char* ez = getenv("SOMAR_NO_ZERO_PLANES");
-    const bool uni_on = !(eu && atoi(eu) != 0) && !full_ && prm.spaceDim == 3;
-    const bool zero_on = !(ez && atoi(ez) != 0) && full_ && prm.spaceDim == 3;
+    const bool uni_on = !tune_.no_uniform && !full_ && prm.spaceDim == 3;
+    const bool zero_on = !tune_.no_zero_planes && full_ && prm.spaceDim == 3;
     for (auto& Lp : lev) { Lp->dev.P.uniform = 0; Lp->dev.P.zero_xy = 0; }
     if (!uni_on && !zero_on) return;
     const int na = uni_on ? 4 : 2;
@@ -779,13 +659,15 @@ void PressureSolver::detect_metric_flags()
         for (int d = 0; d < D; ++d) {
             Level& L = *lev[d];
             mm_first_[d] = (int)items.size();
+            int dir;
             for (int a = 0; a < na; ++a)
+                if (!array(L, a, &dir)) mm_first_[d] = -1;   // a plane that was never allocated: the depth counts as "not zero"
+            for (int a = 0; a < na && mm_first_[d] >= 0; ++a)
                 for (int pi = 0; pi < L.npatches(); ++pi) {
                     MinMaxItem it;
                     it.a = array(L, a, &it.dir);
                     it.patches = L.dev.patches;
                     it.patch = pi;
-                    SOMAR_CHECK(it.a, "internal: metric plane missing");
                     items.push_back(it);
                 }
         }
@@ -804,8 +686,8 @@ void PressureSolver::detect_metric_flags()
         Level& L = *lev[d];
         const int np = L.npatches();
         double* hd = h.data() + 9 * d;
-        hd[8] = 0.0;
-        for (int a = 0; a < na && np; ++a) {
+        hd[8] = (mm_first_[d] < 0 && np) ? 1.0 : 0.0;
+        for (int a = 0; a < na && np && mm_first_[d] >= 0; ++a) {
             const size_t q0 = (size_t)(mm_first_[d] + a * np) * MM_CH, q1 = q0 + (size_t)np * MM_CH;
             for (size_t q = q0; q < q1; ++q) {
                 if (uni_on) {
@@ -838,10 +720,29 @@ void PressureSolver::detect_metric_flags()
     }
 }
 
+// Narrow lane classes for the 7-point marching kernels where the metric is uniform (Level::build_march_tiles says why);
+// Tuning::narrow_7pt = 0 | 1 forces never / always (A/B).  d_partials holds two doubles per tile of the largest table: sized at
+// finalize, again when a table was rebuilt.
+void PressureSolver::choose_narrow_tiles()
+{
+    bool rebuilt = false;
+    for (auto& Lp : lev) {
+        const bool want = tune_.narrow_7pt >= 0 ? tune_.narrow_7pt != 0 : Lp->dev.P.uniform != 0;
+        if (want != Lp->narrow7_) { Lp->build_march_tiles(want); rebuilt = true; }
+    }
+    if (d_partials && !rebuilt) return;
+    int maxTiles = 1;
+    for (auto& L : lev) maxTiles = std::max(std::max(maxTiles, L->dev.ntiles), std::max(L->nrtiles, L->nftiles));
+    SOMAR_HIP(hipStreamSynchronize(st_));
+    hipFree(d_partials);
+    d_partials = nullptr;
+    SOMAR_HIP(hipMalloc(&d_partials, (size_t)maxTiles * 2 * sizeof(double)));
+}
+
 void PressureSolver::refresh_metric()
 {
     SOMAR_CHECK(finalized, "metric refresh before finalize");
-    static const bool timing = getenv("SOMAR_TIMING") && atoi(getenv("SOMAR_TIMING")) != 0;
+    const bool timing = tune_.timing != 0;
     auto now = [&]() { if (timing) SOMAR_HIP(hipStreamSynchronize(st_)); return std::chrono::steady_clock::now(); };
     const auto t0 = now();
     const int D = (int)lev.size();
@@ -895,22 +796,7 @@ void PressureSolver::refresh_metric()
     }
     const auto t1 = now();
     detect_metric_flags();
-    {
-        // finalize's choice of the 7-point marching tiles where the metric is uniform (SOMAR_NARROW_7PT forces it)
-        const char* e = getenv("SOMAR_NARROW_7PT");
-        bool rebuilt = false;
-        for (auto& Lp : lev) {
-            const bool want = e ? atoi(e) != 0 : Lp->dev.P.uniform != 0;
-            if (want != Lp->narrow7_) { Lp->build_march_tiles(want); rebuilt = true; }
-        }
-        if (rebuilt) {
-            int maxTiles = 1;
-            for (auto& L : lev) maxTiles = std::max(std::max(maxTiles, L->dev.ntiles), std::max(L->nrtiles, L->nftiles));
-            SOMAR_HIP(hipStreamSynchronize(st_));
-            hipFree(d_partials);
-            SOMAR_HIP(hipMalloc(&d_partials, (size_t)maxTiles * 2 * sizeof(double)));
-        }
-    }
+    choose_narrow_tiles();
     const auto t2 = now();
     for (int d = 0; d + 1 < D; ++d) {
         Level& F = *lev[d];
@@ -1004,19 +890,14 @@ bool PressureSolver::fused_relax(int d, int iters) const
 {
     const Level& L = *lev[d];
     // levels with coarse-fine boundaries qualify when their layout allows it (Level::cf_fusable)
-    return prm.relaxMode == RELAX_LEVEL_GSRB && !unswept(d) && L.valid_cells_global >= fused_min_cells_ && iters > 0 &&
-           (L.ncf == 0 || L.cf_fusable) && L.active[2] && !no_cf_fused_(L) && !full_;  // Dirichlet sides: ghosts synthesized in the kernel
+    return prm.relaxMode == RELAX_LEVEL_GSRB && !unswept(d) && L.valid_cells_global >= tune_.fused_min_cells && iters > 0 &&
+           (L.ncf == 0 || L.cf_fusable) && L.active[2] && !(tune_.no_cf_fused && L.ncf > 0) && !full_;  // Dirichlet sides: ghosts synthesized in the kernel
 }
 
 // ------------------------------------------------------------------------------------
 // The fold path of the cycle on fields of type T: double, or float on the fp32 depths of the mixed cycle.  The element type
 // shows in pingpong / metric (below), diri_homog / cf_fill (solver.h) and the launchers' overloads, nowhere else.
 // ------------------------------------------------------------------------------------
-static bool no_zero_start()  // A/B switch SOMAR_NO_ZERO_START: the fused sweep gets its zeros from a memset, not from in_mode 1
-{
-    static const bool on = getenv("SOMAR_NO_ZERO_START") != nullptr;
-    return on;
-}
 template <> double* PressureSolver::pingpong<double>(int d) const { return f_pp[d]; }
 template <> float* PressureSolver::pingpong<float>(int d) const { return f32_[d].pp; }
 template <> MetricPtrs<double> PressureSolver::metric<double>(int d) const { return metric_ptrs(lev[d]->dev); }
@@ -1033,7 +914,7 @@ void PressureSolver::fused_sweeps(int d, T* e, const T* res, int iters, bool e_z
                                   const Level* e_plus_level, const T* e_plus)
 {
     Level& L = *lev[d];
-    if (e_zero && no_zero_start()) {
+    if (e_zero && tune_.no_zero_start) {   // A/B switch: the fused sweep gets its zeros from a memset, not from in_mode 1
         launch_set(st_, e, L.field_elems, T(0));
         e_zero = false;
     }
@@ -1367,9 +1248,7 @@ double PressureSolver::norm(int d, const double* a, int ord)
 // single-rank, polling fetch: the reduction's last kernel publishes its result itself (one launch less per scalar)
 bool PressureSolver::fused_publish(int d) const
 {
-    static const bool poll = !(getenv("SOMAR_POLL_FETCH") && atoi(getenv("SOMAR_POLL_FETCH")) == 0);
-    static const bool off = getenv("SOMAR_NO_FUSED_PUBLISH") != nullptr;
-    return poll && !off && !capturing_ && comm_->size == 1 && !ord_sharded(d);
+    return tune_.poll_fetch && !tune_.no_fused_publish && !capturing_ && comm_->size == 1 && !ord_sharded(d);
 }
 
 double PressureSolver::reduce_fetch(int d, const double* a, const double* b, int mode)
@@ -1412,7 +1291,7 @@ void PressureSolver::ordered_sums(int d, const double* a, const double* b, int m
         SOMAR_HIP(hipMemcpy(d_ord_start_[d], ls.data(), ls.size() * sizeof(long long), hipMemcpyHostToDevice));
     }
     const long long n = L.valid_cells_global;
-    if (!d_ordbuf_) SOMAR_HIP(hipMalloc(&d_ordbuf_, (size_t)2 * ordered_max_cells_ * sizeof(double)));
+    if (!d_ordbuf_) SOMAR_HIP(hipMalloc(&d_ordbuf_, (size_t)2 * tune_.ordered_reduce_max * sizeof(double)));
     const int nvec = mode == 6 ? 2 : 1;
     double *X = d_ordbuf_, *Y = d_ordbuf_ + n;
     launch_set(st_, X, nvec * n, 0.0);
@@ -2103,7 +1982,7 @@ bool PressureSolver::graph_cycle(int d, double* corr, const double* res, bool co
     SOMAR_HIP(hipGraphLaunch(cg_.down, st_));
     if (lev[D - 1]->domain.numPts() != 1) {
         // a one-launch bottom solve leaves its (iterations, exit code) pending until the up leg is in the queue
-        bottom_defer_ = bottom_async_;
+        bottom_defer_ = tune_.bottom_async != 0;
         try {
             bottom_solve(f_corr[D - 1], f_res[D - 1]);
         } catch (...) {
@@ -2170,8 +2049,8 @@ void PressureSolver::mp_setup()
 {
     mp_free();
     drop_graphs();
-    static const bool no_fold = getenv("SOMAR_NO_FOLD_PROLONG") != nullptr;   // (fold_prolong's A/B switch)
-    const long long minc = mp_min_cells_ > 0 ? mp_min_cells_ : fused_min_cells_;
+    const bool no_fold = tune_.no_fold_prolong != 0;   // (fold_prolong's A/B switch)
+    const long long minc = mp_min_cells_ > 0 ? mp_min_cells_ : tune_.fused_min_cells;
     // (sharded: lev.back() is the landing layout of the replicated tail, or a serial-order depth comes first -- both stay fp64)
     const int D = (int)lev.size();
     int K = 0;
@@ -2179,7 +2058,7 @@ void PressureSolver::mp_setup()
         const Level& L = *lev[d];
         if (graph_from_ >= 0 && d >= graph_from_) break;   // the graph-replayed legs stay fp64
         if (!fused_relax(d, prm.num_smooth_down) || !fused_relax(d, prm.num_smooth_up)) break;
-        if (L.valid_cells_global < minc || L.valid_cells_global < march_min_cells_ || ordered(d)) break;
+        if (L.valid_cells_global < minc || L.valid_cells_global < tune_.march_min_cells || ordered(d)) break;
         bool r12 = true;
         for (int q = 0; q < 3; ++q) r12 = r12 && (L.mgCrseRefRatio[q] == 1 || L.mgCrseRefRatio[q] == 2);
         if (!r12) break;
@@ -2298,9 +2177,8 @@ void PressureSolver::vcycle_mixed(double* e, const double* res, double rnorm, bo
 
 bool PressureSolver::fold_prolong(int d) const
 {
-    static const bool off = getenv("SOMAR_NO_FOLD_PROLONG") != nullptr;  // A/B switch
     const Level& F = *lev[d];
-    if (off || !fused_relax(d, prm.num_smooth_up) || ordered(d) || hasCF_) return false;
+    if (tune_.no_fold_prolong || !fused_relax(d, prm.num_smooth_up) || ordered(d) || hasCF_) return false;
     return !F.zeroAvg || sf_valid_[d];
 }
 
@@ -2313,10 +2191,9 @@ bool PressureSolver::fold_prolong(int d) const
 // SOMAR_FUSED_BOTTOM_MAX_CELLS (default 512, 0 = off) is the A/B switch.
 bool PressureSolver::fused_bottom(int d) const
 {
-    const long long maxc = fused_bottom_max_;   // SOMAR_FUSED_BOTTOM_MAX_CELLS, read once at construction
-    static const bool poll = !(getenv("SOMAR_POLL_FETCH") && atoi(getenv("SOMAR_POLL_FETCH")) == 0);
+    const long long maxc = tune_.fused_bottom_max_cells;
     const Level& L = *lev[d];
-    return maxc > 0 && poll && !full_ && !diri_ && L.ncf == 0 && L.plan.peers.empty() && !profiling_ && !capturing_ &&
+    return maxc > 0 && tune_.poll_fetch && !full_ && !diri_ && L.ncf == 0 && L.plan.peers.empty() && !profiling_ && !capturing_ &&
            comm_->size == 1 && L.valid_cells_global <= maxc && ordered(d) && !ord_sharded(d) && L.dev.ntiles > 0 &&
            L.dev.tile_j >= 1 && L.dev.tile_j <= 16 && (1024 % (64 * L.dev.tile_j)) == 0 &&
            prm.relaxMode == RELAX_LEVEL_GSRB && prm.precondMode != PRECOND_DIAG_LINE_RELAX && bicg[7] != nullptr;
@@ -2327,15 +2204,14 @@ bool PressureSolver::fused_bottom(int d) const
 // boxes of at most BOX_MAX_CELLS cells.
 bool PressureSolver::box_bottom(int d) const
 {
-    static const bool poll = !(getenv("SOMAR_POLL_FETCH") && atoi(getenv("SOMAR_POLL_FETCH")) == 0);
     const Level& L = *lev[d];
-    if (!box_bottom_on_ || !poll || diri_ || L.ncf != 0 || !L.plan.peers.empty() || profiling_ || capturing_ ||
+    if (!tune_.box_bottom || !tune_.poll_fetch || diri_ || L.ncf != 0 || !L.plan.peers.empty() || profiling_ || capturing_ ||
         comm_->size != 1 || prm.relaxMode != RELAX_LEVEL_GSRB || prm.precondMode == PRECOND_DIAG_LINE_RELAX || !bicg[7])
         return false;
     // (the 19-point operator has no single-workgroup kernel: its bottoms come here whatever their size; so does a level of
     // one box, which takes the kernel's workgroup-local variant)
     const bool one_box = !full_ && L.npatches() == 1;
-    if ((!full_ && !one_box && L.valid_cells_global < box_min_cells_) || L.valid_cells_global != L.domain.numPts()) return false;
+    if ((!full_ && !one_box && L.valid_cells_global < tune_.box_bottom_min_cells) || L.valid_cells_global != L.domain.numPts()) return false;
     if (L.npatches() < 1 || L.npatches() > BOX_MAX_WG || L.field_elems > 0x7fffffffll) return false;
     for (const PatchDesc& p : L.hpatches)
         if ((long long)p.n[0] * p.n[1] * p.n[2] > BOX_MAX_CELLS) return false;
@@ -2531,8 +2407,7 @@ void PressureSolver::bottom_solve(double* phi, const double* rhs)
         A.sums = d_box_sums_;
         A.sync = d_box_sync_;
         A.serial = ordered(d) ? 1 : 0;
-        static const bool box_timing = getenv("SOMAR_BOX_TIMING") != nullptr;
-        A.dbg = box_timing ? reinterpret_cast<long long*>(d_box_sums_ + 4 * BOX_MAX_WG) : nullptr;
+        A.dbg = tune_.box_timing ? reinterpret_cast<long long*>(d_box_sums_ + 4 * BOX_MAX_WG) : nullptr;
         A.full = full_ ? 1 : 0;
         if (full_) {
             A.fab_src = d_box_fab_;
@@ -2548,8 +2423,8 @@ void PressureSolver::bottom_solve(double* phi, const double* rhs)
         launch_box_bicgstab(st_, L.dev, box_max_cells_, A);
         bottom_pending_ = A.pub.seq;
         bottom_kind = 2;
-        if (!bottom_defer_ || box_timing) bottom_collect();
-        if (box_timing) {
+        if (!bottom_defer_ || tune_.box_timing) bottom_collect();
+        if (tune_.box_timing) {
             long long t[6];
             SOMAR_HIP(hipMemcpy(t, A.dbg, sizeof(t), hipMemcpyDeviceToHost));
             fprintf(stderr, "[somar box timing] iterations %d: ticks staging %lld, program %lld, barrier %lld, sums %lld, stagings %lld (100 MHz s_memtime)\n",

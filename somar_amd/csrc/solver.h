@@ -44,7 +44,9 @@ struct SolveStats {
 class PressureSolver {
 public:
     // shared: run on the caller's stream (the levels of an AMR hierarchy share one) instead of an own one
-    explicit PressureSolver(Comm* comm = nullptr, hipStream_t shared = nullptr);
+    // tune: the execution-path switches, fixed for the life of the solver; a composite (AMRSolver, LepticSolver, the
+    // agglomerated tail) reads the environment once and hands every part the same value
+    PressureSolver(Comm* comm, hipStream_t shared, const Tuning& tune);
     ~PressureSolver();
 
     // ---- definition (MappedAMRPoissonOpFactory::define + MappedAMRMultiGrid::define) -----
@@ -123,11 +125,6 @@ public:
     void relax(int d, double* e, const double* res, int iters, bool e_zero = false, const double* e_shift = nullptr,
                const Level* e_plus_level = nullptr, const double* e_plus = nullptr);
     bool fused_relax(int d, int iters) const;
-    static bool no_cf_fused_(const Level& L)  // A/B switch: SOMAR_NO_CF_FUSED=1 keeps CF levels on the two-pass kernel
-    {
-        static const bool off = getenv("SOMAR_NO_CF_FUSED") != nullptr;
-        return off && L.ncf > 0;
-    }
     // homogeneous: physical BC values taken as zero (only Dirichlet sides can carry a value here)
     void residual(int d, double* out, double* phi, const double* rhs, bool homogeneous = true);   // homogeneous CF ghosts, then residual_i
     void apply_op(int d, double* out, double* phi, bool homogeneous = true);
@@ -244,6 +241,7 @@ public:
     void profile_enable(bool on);
     void profile_get(int kernel, int* count, double* total_ms);
     hipStream_t stream() const { return st_; }
+    const Tuning& tuning() const { return tune_; }
 
     SolverParams prm;
     // The null-space probe compares against ProblemContext's GLOBAL AMRMG.eps (MappedAMRPoissonOpFactory.cpp:679), not
@@ -312,10 +310,10 @@ private:
     bool build_coarser(int depth);
     void probe_null_space(int d);
     void fill_metric_ghosts(Level& L);
-    void detect_zero_planes();     // sets StencilParams::zero_xy per depth (non-diagonal metric, 3-D)
-    void detect_uniform_metric();  // sets StencilParams::uniform / uc per depth (diagonal metric, 3-D)
-    // both detections above for every depth in one k_minmax_all launch and one download (metric refresh); same truth table
+    // StencilParams::uniform / uc (diagonal metric) resp. zero_xy (non-diagonal metric) of every 3-D depth, in one k_minmax_all
+    // launch and one download; then the tile tables that follow from them (finalize and metric refresh)
     void detect_metric_flags();
+    void choose_narrow_tiles();    // lane classes of the 7-point marching tables per depth; re-sizes d_partials after a rebuild
     bool updating_ = false, metric_written_ = false;
     void metric_written(const char* producer);   // a producer's check: before finalize, or inside an open update
     std::vector<CoarsenItem*> d_coarsen_;        // per depth d >= 1: k_coarsen_metric's work items (built at the first refresh)
@@ -354,13 +352,10 @@ private:
         return prm.relaxMode == RELAX_LEVEL_GSRB && narrow >= 2;
     }
     bool fused_bottom(int d) const;   // the whole BiCGStab bottom solve in one single-workgroup launch (k_tiny_bicgstab)
-    // the BiCGStab bottom solve of a multi-box bottom level as one persistent launch, one workgroup per box (k_box_bicgstab);
-    // SOMAR_BOX_BOTTOM=0 is the A/B switch (read once, at construction).  The neighbour table is built at the first use.
+    // the BiCGStab bottom solve of a multi-box bottom level as one persistent launch, one workgroup per box (k_box_bicgstab;
+    // Tuning::box_bottom, and box_bottom_min_cells except on a level of ONE box).  The neighbour table is built at the first use.
     bool box_bottom(int d) const;
     void build_box_tables(int d);
-    bool box_bottom_on_ = true;
-    long long fused_bottom_max_ = 512;   // k_tiny_bicgstab takes bottoms of at most this many cells (0: off)
-    long long box_min_cells_ = 513;      // smaller multi-box bottoms stay with k_tiny_bicgstab (a level of ONE box: always k_box_bicgstab)
     int box_depth_ = -1, box_max_cells_ = 0;
     int *d_box_nb_ = nullptr, *d_box_cstart_ = nullptr, *d_box_fab_ = nullptr, *d_box_fabstart_ = nullptr;
     // 19-point variant: the two ghost programs compiled into per-cell entries (kernels.h: BoxProgEntry), per box
@@ -370,21 +365,18 @@ private:
     bool box_full_ok_ = false;   // the compiled programs fit the kernel's LDS tables
     double* d_box_sums_ = nullptr;
     unsigned* d_box_sync_ = nullptr;
-    long long fused_min_cells_ = 262144;
-    long long march_min_cells_ = 262144;  // levels at least this big use the k-marching operator/residual
-    long long ordered_max_cells_ = 4096;
-    bool ordered(int d) const { return lev[d]->valid_cells_global <= ordered_max_cells_; }
+    bool ordered(int d) const { return lev[d]->valid_cells_global <= tune_.ordered_reduce_max; }
     // large 3-D levels of the diagonal path run the k-marching 7-point kernels (resid_march.hip); full_march is the 19-point twin
     bool ortho_march(int d) const
     {
         const Level& L = *lev[d];
-        return !full_ && L.active[2] && L.valid_cells_global >= march_min_cells_;
+        return !full_ && L.active[2] && L.valid_cells_global >= tune_.march_min_cells;
     }
     // A small level that is SHARDED keeps the serial order too: every rank contributes the per-cell terms of its boxes to
     // one vector in the serial (box after box) sequence, a sum-allreduce completes it, one wavefront walks it
     // (k_ord_fill / k_reduce_ordered_flat) -- so a sharded solve adds the same numbers in the same order as one rank.
     bool ord_sharded(int d) const { return ordered(d) && comm_->size > 1; }
-    double* d_ordbuf_ = nullptr;                    // 2 * ordered_max_cells_ doubles
+    double* d_ordbuf_ = nullptr;                    // 2 * Tuning::ordered_reduce_max doubles
     std::vector<long long*> d_ord_start_, d_box_start_;  // per depth: serial start of each LOCAL patch / of every box (+ end)
     void ordered_sums(int d, const double* a, const double* b, int mode, double dxProduct, double* out);
     // out[0] = sum over the level (mode 0: a*b, 2: |a|), every rank: serial order on small levels, tree order on large ones
@@ -392,13 +384,14 @@ private:
     double reduce_fetch(int d, const double* a, const double* b, int mode);   // reduction + host fetch, published by the reduction
     void wait_published(unsigned long long want);
     // a one-launch bottom solve whose published (iterations, exit code) the host has not read yet: the sequence number it
-    // publishes (0: none).  graph_cycle defers the read until the up leg is enqueued (SOMAR_BOTTOM_ASYNC=0: the A/B switch,
-    // read once at construction); every other caller of bottom_solve reads at once.
+    // publishes (0: none).  graph_cycle defers the read until the up leg is enqueued (Tuning::bottom_async); every other caller
+    // of bottom_solve reads at once.
     void bottom_collect();
     unsigned long long bottom_pending_ = 0;
-    bool bottom_defer_ = false, bottom_async_ = true;
+    bool bottom_defer_ = false;
     void reduce_sum(int d, const double* a, const double* b, int mode, double* out);
 
+    const Tuning tune_;
     Comm* comm_;
     Comm self_;
     hipStream_t st_ = nullptr;
@@ -424,9 +417,8 @@ private:
                          std::vector<GhostOp> h_ops; };                                   // ... and of d_ops (refresh_diri_ops)
     void upload_program(FullProgram& P, const std::vector<std::vector<GhostOp>>& stages, int npatches);
     static void free_program(FullProgram& P);
-    // small levels run a ghost program as ONE launch, one workgroup per box (SOMAR_GHOST_STAGED=1: always stage by stage)
-    bool box_program(int d) const { return ghost_box_on_ && !full_march(d) && lev[d]->npatches() > 0; }
-    bool ghost_box_on_ = true;
+    // small levels run a ghost program as ONE launch, one workgroup per box (Tuning::ghost_staged: always stage by stage)
+    bool box_program(int d) const { return !tune_.ghost_staged && !full_march(d) && lev[d]->npatches() > 0; }
     void run_program(int d, const FullProgram& P, double* phi, double* psi, bool homogeneous, bool redirect, bool copy_all);
     bool full_ = false;
     std::vector<double*> f_psi;                            // per depth: the extrapolated copy of phi
@@ -444,18 +436,17 @@ private:
     bool full_march(int d) const
     {
         const Level& L = *lev[d];
-        return full_ && L.active[2] && L.valid_cells_global >= march_min_cells_;
+        return full_ && L.active[2] && L.valid_cells_global >= tune_.march_min_cells;
     }
-    // ... or, where every box of the level is at least fused19_min_box_ cells wide in every direction, red + black in one launch
+    // ... or, where every box of the level is at least Tuning::fused19_min_box cells wide in every direction, red + black in one launch
     // plus a shell pass (full19_fused.hip).  OFF by default (negative): measured on one MI355X it loses at every box size --
     // 512^3 in one box: 9.1 ms (fused) + 0.38 ms (shell) against 2 x 2.85 ms; boxes of 128: 14.9 against 6.6 ms; of 64: 16.0
     // against 6.0 (profiles/r03_fused19.txt).  SOMAR_FUSED19_MIN_BOX = 0 forces it onto every marching level (tests, A/B).
-    int fused19_min_box_ = -1;
     std::vector<char> fused19_;   // per depth, decided in finalize
     bool fused19(int d) const { return d < (int)fused19_.size() && fused19_[d] != 0; }
     std::unique_ptr<PressureSolver> coarse_;   // replicated tail of the hierarchy (agglomeration)
     int agglom_depth_ = -1;
-    long long agglom_cells_ = 2097152;  // 128^3: below this a level costs less to replicate (~0.2 ms of sweeps) than to exchange (~8 x 60 us)
+    // (Tuning::agglom_cells: 128^3 -- below this a level costs less to replicate, ~0.2 ms of sweeps, than to exchange, ~8 x 60 us)
     Copier agglom_gather_;                      // sharded depth agglom_depth_ -> replicated depth 0 of coarse_
     Copier agglom_metric_;                      // the same for the metric (one layer of faces beyond the cells)
     CopyItem* d_agglom_back_ = nullptr;         // my boxes of the replicated correction -> sharded layout
@@ -463,7 +454,7 @@ private:
     void build_agglomerated_tail(int depth);
     void agglom_cycle(double* corr, const double* res, bool corr_zero);
     // ---- launch-bound coarse depths replayed as HIP graphs ----
-    // From the first depth with at most graph_cells_ cells on, one V-cycle is ~20 microsecond-sized launches per
+    // From the first depth with at most Tuning::graph_cells cells on, one V-cycle is ~20 microsecond-sized launches per
     // depth; the legs on either side of the bottom solve (whose loop needs host decisions) are captured once and
     // replayed.  Only where nothing but kernels is enqueued: one rank (which includes the replicated tail).
     struct CoarseGraph {
@@ -472,7 +463,6 @@ private:
         const double *corr = nullptr, *res = nullptr;
     };
     CoarseGraph cg_;
-    long long graph_cells_ = 262144;
     int graph_from_ = -1;
     bool capturing_ = false;
     bool diri_ = false;
@@ -512,13 +502,12 @@ private:
     void xchg(const Level& L, T* f);
     // Sharded large levels: the messages of a sweep's one ghost exchange travel on a second stream while the tiles that read no
     // remote ghost cell are swept (the LooseGSRB idea, GSRB.cpp:122-140, without its change of the iteration: the fused sweep's
-    // tiles are independent, so this is the same sweep bit for bit).  SOMAR_NO_OVERLAP=1 is the A/B switch.
-    bool overlap_on_ = true;
+    // tiles are independent, so this is the same sweep bit for bit).  Tuning::no_overlap is the A/B switch.
     hipStream_t st_comm_ = nullptr;
     hipEvent_t ev_ready_ = nullptr, ev_done_ = nullptr;
     bool resid_overlap(const Level& L) const
     {
-        return overlap_on_ && !L.plan.peers.empty() && L.nrtiles_own > 0 && !capturing_ && !profiling_ && !diri_;
+        return !tune_.no_overlap && !L.plan.peers.empty() && L.nrtiles_own > 0 && !capturing_ && !profiling_ && !diri_;
     }
     // exchange of f with its remote half on the second stream; run(tiles, n) is issued for the tiles that read no remote ghost
     // first, for the others once the messages have landed.  T: double, or float on the fp32 depths of a mixed cycle.
@@ -542,7 +531,7 @@ private:
     }
     bool fused_overlap(const Level& L) const
     {
-        return overlap_on_ && !L.plan.peers.empty() && L.nftiles_own > 0 && !capturing_ && !profiling_;
+        return !tune_.no_overlap && !L.plan.peers.empty() && L.nftiles_own > 0 && !capturing_ && !profiling_;
     }
     bool profiling_ = false;
     void prof_begin(int k);

@@ -248,7 +248,8 @@ static void drop_dead_ops(const Level& L, std::vector<std::vector<GhostOp>>& per
 // Programs of one level.  which = 0: operator (fillExtrap order 2, then the Neumann ghosts of phi);
 // which = 1: smoother (extrapolation order 1 from the domain box, then the Neumann ghosts of phi).
 // The leading full copy psi := phi is done by the caller with one flat copy.
-static std::vector<std::vector<GhostOp>> build_program(const Level& L, int which, const double bcv[3][2], bool frames = false)
+// dce: dead-op elimination (Tuning::no_ghost_dce is the A/B switch)
+static std::vector<std::vector<GhostOp>> build_program(const Level& L, int which, const double bcv[3][2], bool frames, bool dce)
 {
     std::vector<std::vector<GhostOp>> perPatch(L.npatches());
     if (which == 3) {
@@ -373,7 +374,6 @@ static std::vector<std::vector<GhostOp>> build_program(const Level& L, int which
             }
         }
     }
-    static const bool dce = getenv("SOMAR_NO_GHOST_DCE") == nullptr;   // A/B switch
     if (dce && frames) {
         // every op cut along the faces of its box (low ghost layer | valid range | high ghost layer, per direction): dependences
         // and liveness are then judged piece by piece -- an edge strip no longer waits for the strip that only feeds its corner
@@ -468,7 +468,7 @@ void PressureSolver::upload_program(FullProgram& P, const std::vector<std::vecto
         }
     }
     if (flat.empty()) return;
-    if (getenv("SOMAR_TIMING") && atoi(getenv("SOMAR_TIMING")) > 1) {
+    if (tune_.timing > 1) {
         fprintf(stderr, "[somar timing] ghost program: %zu stages, %zu ops, %d boxes; ops per stage:", stages.size(), flat.size(), npatches);
         for (size_t q = 0; q < stages.size(); ++q) {
             long long cells = 0;
@@ -534,7 +534,7 @@ void PressureSolver::build_full_programs(int d)
         if (which == 3 && !hasCF_) continue;
         if (which >= 4 && !full_march(d)) continue;   // [4] / [5]: [0] / [1] for the marching kernels (psi in frames only)
         FullProgram& P = full_prog_[d][which];
-        auto stages = build_program(L, which >= 4 ? which - 4 : which, bc_value_, which >= 4);
+        auto stages = build_program(L, which >= 4 ? which - 4 : which, bc_value_, which >= 4, !tune_.no_ghost_dce);
         if (d == 0 && diri_)
             for (auto& stage : stages)
                 for (GhostOp& op : stage)

@@ -2,7 +2,7 @@
 box, at the layouts where the float code differs from the double one: wide class-0 tiles (124 columns, all 64 lanes), the
 narrow decompositions of wide boxes (128 -> 124 + 4, 64 -> 60 + 4), equal-column tiling, ragged multi-box layouts with seams
 in x and y and periodic seams, semicoarsening ratios, Dirichlet sides, the uniform-metric kernels, a Helmholtz operator, and
-(in a child process, tests/mixed_kernels_rows8.py) the 8-row kernel family.  Also: scale equivariance of fp64 and mixed
+the 8-row kernel family (SOMAR_FUSED_ROWS=8, a solver's own choice: run between two 16-row solvers).  Also: scale equivariance of fp64 and mixed
 solves, rhs * 2^k for k from -110 to +115.
 
 Every case first proves it reaches its target: the number K of fp32 depths, the box widths and MG ratios of those depths, and
@@ -17,9 +17,6 @@ Odd box widths never reach an fp32 depth: a depth with a coarser one below it ha
 bottom level.  Equal columns are reached instead through a stretched metric (no narrow classes unless SOMAR_NARROW_7PT = 1)
 and through SOMAR_NARROW_7PT = 0."""
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -41,7 +38,6 @@ BOUND = 1e-6
 # class's update gives (3.1e-5).  It applies to that cycle alone: the 2/2/2 cycle of the same cases measures 3.9e-7 and
 # 4.6e-7 and is held to 1e-6.
 STRETCHED_POISSON_BOUND = 2e-6
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_march_columns_restatement():
@@ -207,8 +203,9 @@ def per_box_errors(got, ref):
     return [float(np.max(np.abs(g - r)) / np.max(np.abs(r))) for g, r in zip(got, ref)]
 
 
-def check_cycles(so, case):
-    """the two V-cycles from zero of the module docstring against the oracle; returns the measured per-box errors"""
+def check_cycles(so, case, rows=16):
+    """the two V-cycles from zero of the module docstring against the oracle; returns the measured per-box errors.  rows:
+    the region rows of the fused sweep its solvers must hold (SOMAR_FUSED_ROWS as the caller set it)"""
     from somar_amd import api as F
     prob = problem(so, case)
     grids = prob[1]
@@ -218,6 +215,7 @@ def check_cycles(so, case):
         ref, oratios = oracle_cycle(so, case, prob, res, sweeps)
         s = gpu_solver(case, prob, sweeps=sweeps)
         try:
+            assert s.tuning("FUSED_ROWS") == rows
             if full_K:
                 s.setPrecision(1)
             else:
@@ -275,17 +273,55 @@ def test_mixed_solve_on_wide_narrow_and_ragged_layouts(oracle, monkeypatch, case
     check_solve(oracle, case)
 
 
-# ---- the 8-row kernel family: SOMAR_FUSED_ROWS is read once per process ----------------------------------------------
-def test_8_row_kernels_in_a_child_process():
-    """tests/mixed_kernels_rows8.py with SOMAR_FUSED_ROWS=8 and this process's environment otherwise: the fp64 fused sweep
-    bit for bit against the oracle on two layouts, and the fp32 cycle on a uniform-metric case, whose 8-row sweep streams
-    the fp32 metric copies"""
-    env = dict(os.environ, SOMAR_FUSED_ROWS="8")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "mixed_kernels_rows8.py")], env=env, cwd=ROOT,
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
-    print(r.stdout)
-    assert r.returncode == 0, r.returncode
-    assert "rows8 ok" in r.stdout
+# ---- the 8-row kernel family: SOMAR_FUSED_ROWS is a solver's own value, read when it is created ---------------------------
+# (name, n, box, variant, periodic, L, bc types)
+SWEEP_LAYOUTS = [
+    ("stretched-neumann", (64, 16, 8), (64, 8, 8), "stretched", (False, True, False), (2.0, 1.0, 0.5), None),
+    ("cartesian-dirichlet", (64, 32, 16), 32, "cartesian", (False, False, False), (1.0, 0.5, 0.25), [D] * 6),
+]
+
+
+def sweep_bit_exact(so, layout, rows):
+    """the fp64 fused sweep of a solver that holds `rows` region rows, bit for bit against the oracle's relax, 1-3 sweeps"""
+    from somar_amd import api as F
+    name, n, box, variant, periodic, L, bc = layout
+    case = Case(name, n, box, variant, periodic, L, bc, 0.0, 1.0, None, 0, None, None, None)
+    prob = problem(so, case)
+    dom, grids, dx, Jgup, Jinv = prob
+    fac = so.Factory(dom, grids, dx, _bc_holder(so, case), Jgup, Jinv)
+    op = so.AMRMultiGrid(fac, so.BiCGStab()).mg.ops[0]
+    for sweeps in (1, 2, 3):
+        s = gpu_solver(case, prob)
+        try:
+            assert s.tuning("FUSED_ROWS") == rows
+            phi = so.random_field(grids, 41, (1, 1, 1), dom.box)
+            rhs = so.random_field(grids, 42, (0, 0, 0), dom.box)
+            upload(s, F.F_PHI, phi)
+            upload(s, F.F_RHS, rhs)
+            op.relax(phi, rhs, sweeps)
+            s.relax(0, F.F_PHI, F.F_RHS, sweeps)
+            got = download_valid(s, F.F_PHI, grids)
+        finally:
+            s.undefine()
+        for g, w in zip(got, [f.view(b)[..., 0] for b, f in zip(phi.grids, phi.fabs)]):
+            np.testing.assert_array_equal(g, w)
+        print("%s: fp64 fused sweep x%d with %d rows bit-exact" % (name, sweeps, rows))
+
+
+def test_8_row_kernels_between_16_row_solvers(oracle, monkeypatch):
+    """16-row solvers, then 8-row solvers, then 16-row solvers again in one process.  The 8-row fused sweep takes no narrow
+    lane classes and no uniform-metric kernel: the fp64 sweep bit for bit against the oracle on two layouts (stretched
+    Neumann in 64-wide boxes, Cartesian with Dirichlet sides), and the fp32 cycle per box on the wide Cartesian (uniform-
+    metric) case, whose 8-row sweep streams the coefficient arrays -- mp_convert_metric must have made their fp32 copies"""
+    for rows in (16, 8, 16):
+        if rows == 8:
+            monkeypatch.setenv("SOMAR_FUSED_ROWS", "8")
+        else:
+            monkeypatch.delenv("SOMAR_FUSED_ROWS", raising=False)
+        for layout in SWEEP_LAYOUTS:
+            sweep_bit_exact(oracle, layout, rows)
+        if rows == 8:
+            check_cycles(oracle, next(c for c in CASES if c.name == "wide-cartesian"), rows=8)
 
 
 # ---- scale equivariance ---------------------------------------------------------------------------------------------------

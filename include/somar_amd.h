@@ -50,8 +50,9 @@ extern "C" {
  *    longer fail (the flux-register scales follow beta); somar_solver_set_vel_bc (inflow / outflow sides); somar_solver_set_metric_map (cylindrical and bathymetric
  *    metric producers on the device); somar_k_fillmappedlapdiag3d, somar_k_mappedaverage2 (kernel-level hooks); additions only
  * 11: ... + somar_solver_set_bc_face_values (position-dependent Dirichlet values); additions only, so the number stays 11
- * 12: + somar_solver_tuning; the SOMAR_* execution-path variables are read when a solver is created and hold for its life */
-#define SOMAR_AMD_ABI_VERSION 12
+ * 12: + somar_solver_tuning; the SOMAR_* execution-path variables are read when a solver is created and hold for its life
+ * 13: + somar_device_bytes_live; additions only */
+#define SOMAR_AMD_ABI_VERSION 13
 
 /* BCType codes, calculus/BCInterface/BCDescriptor.H:34-39 */
 #define SOMAR_BC_NONE (-1)
@@ -113,6 +114,9 @@ int somar_last_history(double* out, int capacity, int* n);
 int somar_abi_version(void);
 const char* somar_last_error(void);
 int somar_device_count(int* count);
+/* Bytes of device memory this library holds in the calling process right now, over every handle: it returns to its earlier
+ * value when a handle is destroyed.  An exact count kept by the library, not a query of the device. */
+int somar_device_bytes_live(long long* bytes);
 /* Synthetic inputs of the benchmark configurations: out[0 .. n) = successive draws of
  * std::uniform_real_distribution<double>(lo, hi) from std::mt19937_64(seed).  Host memory, host arithmetic (no GPU): the
  * SAME array then goes to the GPU path and to the CPU baseline of bench.py. */

@@ -65,6 +65,7 @@ _H = C.c_void_p
 _SIGS = {
     "somar_abi_version": [],
     "somar_device_count": [_PI],
+    "somar_device_bytes_live": [C.POINTER(C.c_longlong)],
     "somar_params_default": [C.POINTER(Params)],
     "somar_solver_create": [C.POINTER(_H), _PI, _PI, _PI, _PD, _PI, C.c_int, _PI, _PI, C.c_double, C.c_double,
                             C.POINTER(Params), _H],
@@ -1092,6 +1093,13 @@ def last_history():
 def device_count():
     n = C.c_int()
     _ck(lib().somar_device_count(C.byref(n)))
+    return n.value
+
+
+def device_bytes_live():
+    """Bytes of device memory the library holds in this process right now (its own count, exact)."""
+    n = C.c_longlong(0)
+    _ck(lib().somar_device_bytes_live(C.byref(n)))
     return n.value
 
 

@@ -10,16 +10,6 @@
 
 namespace somar {
 
-template <class T>
-static T* to_device(const std::vector<T>& v)
-{
-    if (v.empty()) return nullptr;
-    T* d = nullptr;
-    SOMAR_HIP(hipMalloc(&d, v.size() * sizeof(T)));
-    SOMAR_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return d;
-}
-
 static IBox adj_cell(const IBox& b, int d, int s)
 {
     IBox g = b;
@@ -32,14 +22,6 @@ static bool contains(const IBox& b, const int iv[3])
     for (int d = 0; d < 3; ++d)
         if (iv[d] < b.lo[d] || iv[d] > b.hi[d]) return false;
     return true;
-}
-
-AMRLink::~AMRLink()
-{
-    Level::free_field(buf);
-    Level::free_field(resC);
-    hipFree(d_cc); hipFree(d_pts); hipFree(d_fc); hipFree(d_der); hipFree(d_cover); hipFree(d_reg); hipFree(d_regvals);
-    hipFree(d_reflux); hipFree(d_A); hipFree(d_B); hipFree(d_sendidx); hipFree(d_sendbuf); hipFree(d_osg);
 }
 
 // ------------------------------------------------------------------------------------
@@ -64,10 +46,9 @@ void PressureSolver::set_metric_uniform(const double c4[4])
             for (int d = 0; d < 3; ++d) { it.lo[d] = 0; it.n[d] = valid.size(d) + ((a < 3 && d == a) ? 1 : 0); }
             items.push_back(it);
         }
-        FillItem* d_items = to_device(items);
+        const DevBuf<FillItem> d_items = DevBuf<FillItem>::from(items);
         launch_fill_items(st_, L.dev.patches, d_items, (int)items.size(), a < 3 ? L.dev.jg[a] : L.dev.jinv, c4[a]);
         sync();
-        hipFree(d_items);
     }
 }
 
@@ -79,7 +60,6 @@ AMRSolver::AMRSolver(Comm* comm) : tune_(Tuning::from_env()), comm_(comm ? comm 
 AMRSolver::~AMRSolver()
 {
     if (st_) hipStreamSynchronize(st_);
-    for (double* f : spare_) Level::free_field(f);
     links_.clear();
     leptic_.clear();
     S.clear();
@@ -146,7 +126,8 @@ void AMRSolver::finalize()
         res_[l] = S[l]->amr_field(1);
     }
     lean_ = !tune_.amr_plain;
-    spare_.assign(n, nullptr);
+    spare_.clear();
+    spare_.resize(n);
     rcur_ = res_;
     visits_.assign(n, 0);
     // the residual of an intermediate level ping-pongs between res_ and spare_ in AMRUpdateResidual (the finest level's
@@ -192,7 +173,7 @@ void AMRSolver::build_link(int l)
         }
     }
     K->ncover = (int)cover.size();
-    K->d_cover = to_device(cover);
+    K->d_cover = DevBuf<FillItem>::from(cover);
     const bool timing = tune_.timing != 0;
     if (timing)
         fprintf(stderr, "[somar timing] link %d: coarsened-fine layout + copiers %.3f s\n", l,
@@ -489,10 +470,10 @@ void AMRSolver::build_quad_tables(int l)
     }
     K.ncc = (int)ccs.size();
     K.nfc = (int)fcs.size();
-    K.d_cc = to_device(ccs);
-    K.d_pts = to_device(pts);
-    K.d_fc = to_device(fcs);
-    if (K.ncc) SOMAR_HIP(hipMalloc(&K.d_der, (size_t)K.ncc * 5 * sizeof(double)));
+    K.d_cc = DevBuf<QCoarse>::from(ccs);
+    K.d_pts = DevBuf<QPoint>::from(pts);
+    K.d_fc = DevBuf<QFine>::from(fcs);
+    K.d_der = K.ncc ? DevBuf<double>((size_t)K.ncc * 5) : DevBuf<double>();
 }
 
 // ------------------------------------------------------------------------------------
@@ -663,8 +644,8 @@ void AMRSolver::build_reflux_tables(int l)
     }
     K.nsend = (long long)sendidx.size();
     K.nreg_recv = (int)rtot;
-    K.d_sendidx = to_device(sendidx);
-    if (K.nsend) SOMAR_HIP(hipMalloc(&K.d_sendbuf, K.nsend * sizeof(double)));
+    K.d_sendidx = DevBuf<int>::from(sendidx);
+    K.d_sendbuf = K.nsend ? DevBuf<double>(K.nsend) : DevBuf<double>();
     // flatten
     std::vector<RefluxCell> cells;
     std::vector<RefluxA> A;
@@ -683,14 +664,13 @@ void AMRSolver::build_reflux_tables(int l)
         cells.push_back(c);
     }
     K.nreflux = (int)cells.size();
-    K.d_reg = to_device(reg);
-    K.d_reflux = to_device(cells);
-    K.d_A = to_device(A);
+    K.d_reg = DevBuf<FRegCell>::from(reg);
+    K.d_reflux = DevBuf<RefluxCell>::from(cells);
+    K.d_A = DevBuf<RefluxA>::from(A);
     K.nA = (long long)A.size();
-    K.d_B = to_device(B);
+    K.d_B = DevBuf<int>::from(B);
     const size_t nvals = (size_t)std::max(1, K.nreg_local + K.nreg_recv);
-    SOMAR_HIP(hipMalloc(&K.d_regvals, nvals * sizeof(double)));
-    SOMAR_HIP(hipMemset(K.d_regvals, 0, nvals * sizeof(double)));
+    K.d_regvals = DevBuf<double>::zeros(nvals);
 }
 
 // ------------------------------------------------------------------------------------
@@ -826,7 +806,7 @@ void AMRSolver::build_one_sided_tables(int l)
             if (e.stage == sgi) flat.push_back(e.o);
         K.osg_count.push_back((int)flat.size() - K.osg_first.back());
     }
-    K.d_osg = to_device(flat);
+    K.d_osg = DevBuf<OneSided>::from(flat);
     K.osg_built = true;
 }
 

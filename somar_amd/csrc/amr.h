@@ -101,8 +101,8 @@ void launch_reflux(hipStream_t st, const RefluxCell* cells, int n, const RefluxA
 struct AMRLink {
     int r[3] = {1, 1, 1};
     std::unique_ptr<Level> cfl;  // coarsened fine layout, owned by the fine boxes' ranks
-    double* buf = nullptr;       // coarse values under and around the fine boxes (2 ghosts)
-    double* resC = nullptr;      // restricted fine residual
+    DevBuf<double> buf;          // coarse values under and around the fine boxes (2 ghosts)
+    DevBuf<double> resC;         // restricted fine residual
     Copier gather;               // coarse level -> buf (valid + 2 ghosts, periodic)
     Copier gather_ring;          // the same onto the 2-cell ring around each coarsened fine box only: all the coarse-fine
                                  // interpolation reads (a 64 x 64 x 128 box: 86 K of 610 K cells; SOMAR_CF_FULL_GATHER=1: A/B)
@@ -110,36 +110,35 @@ struct AMRLink {
     // quadratic CF interpolation
     bool hasCF = false;          // false: the fine level covers the whole domain
     int ncc = 0, nfc = 0;
-    QCoarse* d_cc = nullptr;
-    QPoint* d_pts = nullptr;
-    QFine* d_fc = nullptr;
-    double* d_der = nullptr;
+    DevBuf<QCoarse> d_cc;
+    DevBuf<QPoint> d_pts;
+    DevBuf<QFine> d_fc;
+    DevBuf<double> d_der;
     // zeroCovered on the coarse level
     int ncover = 0;
-    FillItem* d_cover = nullptr;
+    DevBuf<FillItem> d_cover;
     // flux register
     bool fluxDefined = false;
     int nreg_local = 0, nreg_recv = 0, nreflux = 0;
-    FRegCell* d_reg = nullptr;
-    double* d_regvals = nullptr;       // [local | received]
-    RefluxCell* d_reflux = nullptr;
-    RefluxA* d_A = nullptr;
+    DevBuf<FRegCell> d_reg;
+    DevBuf<double> d_regvals;    // [local | received]
+    DevBuf<RefluxCell> d_reflux;
+    DevBuf<RefluxA> d_A;
     long long nA = 0;
-    int* d_B = nullptr;
+    DevBuf<int> d_B;
     // register values that travel between ranks
     std::vector<int> peers;
     std::vector<long long> soff, scount, roff, rcount;
-    int* d_sendidx = nullptr;
+    DevBuf<int> d_sendidx;
     long long nsend = 0;
-    double* d_sendbuf = nullptr;
+    DevBuf<double> d_sendbuf;
     double sc_fine[3][2];
     double beta_built = 0.0;   // the coarse operator's beta the register scales were built with
     // compGradientCC's one-sided faces on the COARSE level next to this (fine) level, in stages (entries of one stage are
     // independent; normally there is one stage)
     bool osg_built = false;
-    OneSided* d_osg = nullptr;
+    DevBuf<OneSided> d_osg;
     std::vector<int> osg_first, osg_count;
-    ~AMRLink();
 };
 
 class AMRSolver {
@@ -261,7 +260,8 @@ private:
     std::vector<double*> corr_, res_;
     // lean V-cycle (default; SOMAR_AMR_PLAIN=1 restores the reference's pass-by-pass structure): where level l's residual
     // currently lives (res_[l], spare_[l], or -- finest level -- the caller's uberResidual, which is then never written)
-    std::vector<double*> spare_, rcur_;
+    std::vector<DevBuf<double>> spare_;
+    std::vector<double*> rcur_;
     std::vector<int> visits_;
     bool lean_ = true;
     bool finalized_ = false;

@@ -280,6 +280,14 @@ int somar_device_count(int* count)
     API_END
 }
 
+int somar_device_bytes_live(long long* bytes)
+{
+    API_BEGIN
+    SOMAR_CHECK(bytes, "null argument");
+    *bytes = device_bytes_live().load();
+    API_END
+}
+
 static void from_params(const SolverParams& d, somar_params_t* p)
 {
     p->imin = d.imin; p->imax = d.imax; p->eps = d.eps; p->hang = d.hang; p->norm_thresh = d.normThresh;
@@ -1216,8 +1224,7 @@ int somar_k_gsrbiter3dortho(double* phi, const int* iphilo0, const int* iphilo1,
     L.beta = *beta;
     L.refresh_params();
     hipStream_t st = nullptr;
-    double* dphi = L.alloc_field();
-    double* drhs = L.alloc_field();
+    const DevBuf<double> dphi = L.alloc_field(), drhs = L.alloc_field();
     for (int d = 0; d < 3; ++d) {
         IBox fr = region;
         fr.hi[d] += 1;  // faces(region, d)
@@ -1234,8 +1241,6 @@ int somar_k_gsrbiter3dortho(double* phi, const int* iphilo0, const int* iphilo1,
         L.download(dphi, 0, hp, fphi.box, region, st);
     }
     SOMAR_HIP(hipStreamSynchronize(st));
-    Level::free_field(dphi);
-    Level::free_field(drhs);
     API_END
 }
 
@@ -1329,16 +1334,13 @@ int somar_k_mappedaverage2(double* coarse, const int* icoarselo0, const int* ico
     LC.alloc_metric();
     hipStream_t st = nullptr;
     LF.upload(LF.dev.jinv, 0, fj.p, fj.box, fbox, st);
-    double* dfine = LF.alloc_field();
-    double* dcrse = LC.alloc_field();
+    const DevBuf<double> dfine = LF.alloc_field(), dcrse = LC.alloc_field();
     for (int n = 0; n < fc.ncomp; ++n) {
         LF.upload(dfine, 0, fine + (size_t)n * ff.box.numPts(), ff.box, fbox, st);
         launch_restrict(st, LC.dev, LF.dev, dcrse, dfine, r);
         LC.download(dcrse, 0, coarse + (size_t)n * fc.box.numPts(), fc.box, cbox, st);
     }
     SOMAR_HIP(hipStreamSynchronize(st));
-    Level::free_field(dfine);
-    Level::free_field(dcrse);
     API_END
 }
 
@@ -1522,22 +1524,15 @@ int somar_altered_jgup(long long n, double* dest, const double* nsq_fc, const do
     SOMAR_CHECK(!offdiag || (ix && jy && iy && jx), "the four horizontal map derivatives come together (mu != nu) or not at all");
     const int nin = offdiag ? 9 : 5;
     const double* in[9] = {nsq_fc, dximu_dz, dxinu_dz, gup, J, ix, jy, iy, jx};
-    double* dev = nullptr;
-    SOMAR_HIP(hipMalloc(&dev, (size_t)(nin + 1) * n * sizeof(double)));
-    try {
-        for (int q = 0; q < nin; ++q)
-            SOMAR_HIP(hipMemcpy(dev + (size_t)(q + 1) * n, in[q], (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-        double* d[10];
-        for (int q = 0; q <= 9; ++q) d[q] = q <= nin ? dev + (size_t)q * n : nullptr;
-        SOMAR_HIP(hipDeviceSynchronize());
-        launch_altered_jgup(nullptr, n, d[0], d[1], d[2], d[3], d[6], d[7], d[8], d[9], d[4], d[5], dt_theta, coriolis_f, offdiag);
-        SOMAR_HIP(hipDeviceSynchronize());
-        SOMAR_HIP(hipMemcpy(dest, dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    } catch (...) {
-        hipFree(dev);
-        throw;
-    }
-    hipFree(dev);
+    const DevBuf<double> dev((size_t)(nin + 1) * n);
+    for (int q = 0; q < nin; ++q)
+        SOMAR_HIP(hipMemcpy(dev + (size_t)(q + 1) * n, in[q], (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    double* d[10];
+    for (int q = 0; q <= 9; ++q) d[q] = q <= nin ? dev + (size_t)q * n : nullptr;
+    SOMAR_HIP(hipDeviceSynchronize());
+    launch_altered_jgup(nullptr, n, d[0], d[1], d[2], d[3], d[6], d[7], d[8], d[9], d[4], d[5], dt_theta, coriolis_f, offdiag);
+    SOMAR_HIP(hipDeviceSynchronize());
+    SOMAR_HIP(hipMemcpy(dest, dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     API_END
 }
 
@@ -1546,21 +1541,14 @@ int somar_metric_jgup_from_dxdxi(long long n, int mu, const double* dxdxi9, cons
 {
     API_BEGIN
     SOMAR_CHECK(n > 0 && mu >= 0 && mu < 3 && dxdxi9 && detJ && jgup3, "null/empty argument");
-    double* dev = nullptr;
-    SOMAR_HIP(hipMalloc(&dev, (size_t)13 * n * sizeof(double)));
-    try {
-        SOMAR_HIP(hipMemcpy(dev, dxdxi9, (size_t)9 * n * sizeof(double), hipMemcpyHostToDevice));
-        SOMAR_HIP(hipMemcpy(dev + (size_t)9 * n, detJ, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-        const double* x9[9];
-        for (int q = 0; q < 9; ++q) x9[q] = dev + (size_t)q * n;
-        launch_jgup_from_dxdxi(nullptr, n, mu, x9, dev + (size_t)9 * n, scale, dev + (size_t)10 * n);
-        SOMAR_HIP(hipDeviceSynchronize());
-        SOMAR_HIP(hipMemcpy(jgup3, dev + (size_t)10 * n, (size_t)3 * n * sizeof(double), hipMemcpyDeviceToHost));
-    } catch (...) {
-        hipFree(dev);
-        throw;
-    }
-    hipFree(dev);
+    const DevBuf<double> dev((size_t)13 * n);
+    SOMAR_HIP(hipMemcpy(dev, dxdxi9, (size_t)9 * n * sizeof(double), hipMemcpyHostToDevice));
+    SOMAR_HIP(hipMemcpy(dev + (size_t)9 * n, detJ, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    const double* x9[9];
+    for (int q = 0; q < 9; ++q) x9[q] = dev + (size_t)q * n;
+    launch_jgup_from_dxdxi(nullptr, n, mu, x9, dev + (size_t)9 * n, scale, dev + (size_t)10 * n);
+    SOMAR_HIP(hipDeviceSynchronize());
+    SOMAR_HIP(hipMemcpy(jgup3, dev + (size_t)10 * n, (size_t)3 * n * sizeof(double), hipMemcpyDeviceToHost));
     API_END
 }
 
@@ -1652,17 +1640,15 @@ int somar_diag_stream_probe(int kind, long long cells, int reps, double* gbs)
 {
     API_BEGIN
     SOMAR_CHECK(gbs && kind >= 0 && kind <= 2 && cells >= 1024 && cells % 2 == 0 && reps >= 1, "bad argument");
-    double* buf[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    DevBuf<double> own[7];
+    double* buf[7];
     const int nin = kind == 2 ? 6 : 1;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     try {
-        for (int q = 0; q < nin; ++q) {
-            SOMAR_HIP(hipMalloc(&buf[q], cells * sizeof(double)));
-            SOMAR_HIP(hipMemset(buf[q], 0, cells * sizeof(double)));
+        for (int q = 0; q < 7; ++q) {
+            if (q < nin || q == 6) own[q] = DevBuf<double>::zeros(cells);
+            buf[q] = own[q] ? own[q].get() : own[0].get();
         }
-        for (int q = nin; q < 6; ++q) buf[q] = buf[0];
-        SOMAR_HIP(hipMalloc(&buf[6], cells * sizeof(double)));
-        SOMAR_HIP(hipMemset(buf[6], 0, cells * sizeof(double)));
         SOMAR_HIP(hipEventCreate(&e0));
         SOMAR_HIP(hipEventCreate(&e1));
         const double bytes = (kind == 0 ? 16.0 : kind == 1 ? 8.0 : 56.0) * (double)cells;
@@ -1680,14 +1666,10 @@ int somar_diag_stream_probe(int kind, long long cells, int reps, double* gbs)
         }
         *gbs = best;
     } catch (...) {
-        for (int q = 0; q < nin; ++q) hipFree(buf[q]);
-        hipFree(buf[6]);
         if (e0) hipEventDestroy(e0);
         if (e1) hipEventDestroy(e1);
         throw;
     }
-    for (int q = 0; q < nin; ++q) hipFree(buf[q]);
-    hipFree(buf[6]);
     hipEventDestroy(e0);
     hipEventDestroy(e1);
     API_END
@@ -1942,10 +1924,7 @@ int somar_comm_selftest(void* comm)
     const int n = 4096;
     hipStream_t st;
     SOMAR_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    double *d_red = nullptr, *d_send = nullptr, *d_recv = nullptr;
-    SOMAR_HIP(hipMalloc(&d_red, 2 * sizeof(double)));
-    SOMAR_HIP(hipMalloc(&d_send, n * sizeof(double)));
-    SOMAR_HIP(hipMalloc(&d_recv, n * sizeof(double)));
+    const DevBuf<double> d_red(2), d_send(n), d_recv(n);
     std::vector<double> h(n);
     for (int i = 0; i < n; ++i) h[i] = 1000.0 * c->rank + i;
     SOMAR_HIP(hipMemcpyAsync(d_send, h.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
@@ -1970,8 +1949,8 @@ int somar_comm_selftest(void* comm)
     SOMAR_HIP(hipMemcpyAsync(hr, d_red, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     SOMAR_HIP(hipStreamSynchronize(st));
     // the same ring with fp32 payloads (the halo messages of a mixed-precision cycle), through the same buffers
-    float* f_send = reinterpret_cast<float*>(d_send);
-    float* f_recv = reinterpret_cast<float*>(d_recv);
+    float* f_send = reinterpret_cast<float*>(d_send.get());
+    float* f_recv = reinterpret_cast<float*>(d_recv.get());
     std::vector<float> hf(n), gf(n);
     for (int i = 0; i < n; ++i) hf[i] = 8192.0f * c->rank + i + 0.5f;   // (exact in fp32 for up to 16 ranks)
     SOMAR_HIP(hipMemcpyAsync(f_send, hf.data(), n * sizeof(float), hipMemcpyHostToDevice, st));
@@ -1987,9 +1966,6 @@ int somar_comm_selftest(void* comm)
     }
     SOMAR_HIP(hipMemcpyAsync(gf.data(), f_recv, n * sizeof(float), hipMemcpyDeviceToHost, st));
     SOMAR_HIP(hipStreamSynchronize(st));
-    hipFree(d_red);
-    hipFree(d_send);
-    hipFree(d_recv);
     hipStreamDestroy(st);
     SOMAR_CHECK(hr[0] == 0.5 * c->size * (c->size + 1), "comm selftest: all-reduce(sum) returned a wrong value");
     SOMAR_CHECK(hr[1] == double(c->size), "comm selftest: all-reduce(max) returned a wrong value");

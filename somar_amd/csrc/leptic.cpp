@@ -39,12 +39,6 @@ LepticSolver::LepticSolver(Comm* comm, hipStream_t shared, const Tuning& tune) :
 
 LepticSolver::~LepticSolver()
 {
-    for (double* f : {f_total, f_rhsA, f_rhsB, f_gam, f_efac, h_excess, h_bcLo, h_bcHi, h_gx, h_gy}) Level::free_field(f);
-    hipFree(d_avg);
-    hipFree(d_vbc);
-    hipFree(d_bad);
-    hipFree(d_stiles);
-    hipFree(d_flatOf);
     horiz_.reset();
     vert_.reset();
     own_orig_.reset();
@@ -213,10 +207,8 @@ void LepticSolver::finalize()
         for (const Tile& t : V.hctiles)
             if (flatPatch[V.local[t.patch]] >= 0) st.push_back(t);
         nstiles = (int)st.size();
-        SOMAR_HIP(hipMalloc(&d_stiles, st.size() * sizeof(Tile)));
-        SOMAR_HIP(hipMemcpy(d_stiles, st.data(), st.size() * sizeof(Tile), hipMemcpyHostToDevice));
-        SOMAR_HIP(hipMalloc(&d_flatOf, flatOf.size() * sizeof(PatchDesc)));
-        SOMAR_HIP(hipMemcpy(d_flatOf, flatOf.data(), flatOf.size() * sizeof(PatchDesc), hipMemcpyHostToDevice));
+        d_stiles = DevBuf<Tile>::from(st);
+        d_flatOf = DevBuf<PatchDesc>::from(flatOf);
     } else {
         SOMAR_CHECK(V.npatches() == F.npatches(), "internal: layouts differ");
     }
@@ -248,7 +240,7 @@ void LepticSolver::finalize()
         f_efac = V.alloc_field();
         upload_vbc();
     }
-    SOMAR_HIP(hipMalloc(&d_avg, 2 * sizeof(double)));
+    d_avg = DevBuf<double>(2);
     SOMAR_HIP(hipDeviceSynchronize());
     finalized_ = true;
 }
@@ -260,10 +252,8 @@ void LepticSolver::upload_vbc()
     std::vector<int> local(2 * (size_t)std::max(1, V.npatches()), 0);
     for (int pi = 0; pi < V.npatches(); ++pi)
         for (int s2 = 0; s2 < 2; ++s2) local[2 * pi + s2] = vbc_[2 * V.local[pi] + s2];
-    SOMAR_HIP(hipMalloc(&d_vbc, local.size() * sizeof(int)));
-    SOMAR_HIP(hipMemcpy(d_vbc, local.data(), local.size() * sizeof(int), hipMemcpyHostToDevice));
-    SOMAR_HIP(hipMalloc(&d_bad, sizeof(int)));
-    SOMAR_HIP(hipMemset(d_bad, 0, sizeof(int)));
+    d_vbc = DevBuf<int>::from(local);
+    d_bad = DevBuf<int>::zeros(1);
 }
 
 void LepticSolver::refresh_metric()

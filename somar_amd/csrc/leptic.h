@@ -94,16 +94,15 @@ private:
     bool finalized_ = false;
     bool full_ = false;   // non-diagonal metric (decided when orig()'s metric has been set)
     // 3-D work fields (vertical layout) and flat ones (horizontal layout)
-    double *f_total = nullptr, *f_rhsA = nullptr, *f_rhsB = nullptr, *f_gam = nullptr;
-    double *h_excess = nullptr, *h_bcLo = nullptr, *h_bcHi = nullptr, *h_gx = nullptr, *h_gy = nullptr;
-    double* d_avg = nullptr;  // (sum, count) for setZeroAvg
+    DevBuf<double> f_total, f_rhsA, f_rhsB, f_gam;
+    DevBuf<double> h_excess, h_bcLo, h_bcHi, h_gx, h_gy;
+    DevBuf<double> d_avg;  // (sum, count) for setZeroAvg
     // columns ending at Dirichlet walls / coarse-fine interfaces (gatherVerticalBCTypes): per box (lo, hi) 0 Neum, 1 Diri, 2 CF
     std::vector<int> vbc_;
     bool doHorizSolve_ = true;
     double dzCrse_ = 0.0;
-    double* f_efac = nullptr;
-    int* d_vbc = nullptr;
-    int* d_bad = nullptr;
+    DevBuf<double> f_efac;
+    DevBuf<int> d_vbc, d_bad;
     void upload_vbc();
     void check_bad();   // raises if a dptsv pivot was not positive
     // a level that mixes Neumann-Neumann (spanning) columns with the other kind: the flat problem holds the spanning boxes only
@@ -111,9 +110,9 @@ private:
     // flat patch of vertical patch p at d_flatOf[p] (complement patches: unused, zeroed)
     bool mixed_ = false;
     std::vector<int> flatDI_;          // global box indices of the spanning boxes, ascending
-    Tile* d_stiles = nullptr;          // the whole-column tiles of the spanning patches
+    DevBuf<Tile> d_stiles;             // the whole-column tiles of the spanning patches
     int nstiles = 0;
-    PatchDesc* d_flatOf = nullptr;
+    DevBuf<PatchDesc> d_flatOf;
     // tiles / flat view for the kernels that pair a column with its flat cell: the level's own where nothing is mixed
     const Tile* span_tiles() const { return mixed_ ? d_stiles : vert_->level(0).d_ctiles; }
     int span_ntiles() const { return mixed_ ? nstiles : vert_->level(0).nctiles; }

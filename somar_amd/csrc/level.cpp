@@ -16,16 +16,6 @@ bool coarsenable(const std::vector<IBox>& boxes, const int* r)
     return true;
 }
 
-template <class T>
-static T* to_device(const std::vector<T>& v)
-{
-    if (v.empty()) return nullptr;
-    T* d = nullptr;
-    SOMAR_HIP(hipMalloc(&d, v.size() * sizeof(T)));
-    SOMAR_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return d;
-}
-
 // Pure host logic (no GPU): the ghost-exchange plan of rank `myrank` for the layout -- Chombo's
 // Copier(grids, grids, domain, ghost, exchange=true).  Items carry GLOBAL box indices in
 // src_patch/dst_patch.  Both sides of a rank pair enumerate (dst box, src box, periodic shift) in the
@@ -177,8 +167,7 @@ void Level::define_cf(const double dxCrse[3])
             }
         }
     }
-    hipFree(d_cf);
-    d_cf = to_device(hcf);
+    d_cf = DevBuf<CFCell>::from(hcf);
     ncf = (int)hcf.size();
     for (int d = 0; d < 3; ++d) {
         const double Df = dx[d], Dc = dxCrse[d];
@@ -275,11 +264,9 @@ void Level::define_cf(const double dxCrse[3])
             cf_faces[d]->define_faces(domain, periodic, *this, d, gh, comm);
         }
     }
-    hipFree(d_cfx);
-    d_cfx = to_device(hcfx);
+    d_cfx = DevBuf<CFCell>::from(hcfx);
     ncfx = (int)hcfx.size();
-    hipFree(d_patches);
-    d_patches = to_device(hpatches);  // the flag bits
+    d_patches = DevBuf<PatchDesc>::from(hpatches);  // the flag bits
     dev.patches = d_patches;
     refresh_params();
     SOMAR_HIP(hipDeviceSynchronize());
@@ -365,11 +352,6 @@ ExchangePlan build_copy_plan(const IBox& domain, const bool periodic[3], const s
     return plan;
 }
 
-Copier::~Copier()
-{
-    hipFree(d_local); hipFree(d_send); hipFree(d_recv); hipFree(d_soff); hipFree(d_roff); hipFree(d_sbuf); hipFree(d_rbuf);
-}
-
 void Copier::define(const IBox& domain, const bool periodic[3], const Level& src, const Level& dst, const int ghost[3],
                     Comm* comm, bool ring_only)
 {
@@ -417,13 +399,13 @@ void Copier::define_faces(const IBox& domain, const bool periodic[3], const Leve
 
 void Copier::upload_tables()
 {
-    d_local = to_device(plan.local);
-    d_send = to_device(plan.send_items);
-    d_recv = to_device(plan.recv_items);
-    d_soff = to_device(plan.send_itemoff);
-    d_roff = to_device(plan.recv_itemoff);
-    if (plan.send_total) SOMAR_HIP(hipMalloc(&d_sbuf, plan.send_total * sizeof(double)));
-    if (plan.recv_total) SOMAR_HIP(hipMalloc(&d_rbuf, plan.recv_total * sizeof(double)));
+    d_local = DevBuf<CopyItem>::from(plan.local);
+    d_send = DevBuf<CopyItem>::from(plan.send_items);
+    d_recv = DevBuf<CopyItem>::from(plan.recv_items);
+    d_soff = DevBuf<long long>::from(plan.send_itemoff);
+    d_roff = DevBuf<long long>::from(plan.recv_itemoff);
+    d_sbuf = plan.send_total ? DevBuf<double>(plan.send_total) : DevBuf<double>();
+    d_rbuf = plan.recv_total ? DevBuf<double>(plan.recv_total) : DevBuf<double>();
     SOMAR_HIP(hipDeviceSynchronize());
 }
 
@@ -499,36 +481,6 @@ void Copier::run(const double* s, double* d, hipStream_t st) const
     if (remote) launch_pack(st, dst_->dev, d_recv, d_roff, (int)plan.recv_items.size(), d, d_rbuf, false);
 }
 
-Level::~Level()
-{
-    hipFree(d_cf);
-    hipFree(d_cfx);
-    hipFree(d_patches);
-    hipFree(d_tiles);
-    hipFree(d_ftiles);
-    hipFree(d_ftiles_own);
-    hipFree(d_ftiles_rem);
-    hipFree(d_rtiles_own);
-    hipFree(d_rtiles_rem);
-    hipFree(d_rtiles);
-    hipFree(d_qtiles);
-    hipFree(d_gtiles);
-    hipFree(d_stiles);
-    hipFree(d_ctiles);
-    hipFree(d_local_items);
-    hipFree(d_tile_items);
-    hipFree(d_tile_item_start);
-    hipFree(d_send_items);
-    hipFree(d_recv_items);
-    hipFree(d_send_off);
-    hipFree(d_recv_off);
-    hipFree(d_sendbuf);
-    hipFree(d_recvbuf);
-    for (int d = 0; d < 3; ++d) hipFree(dev.jg[d]);
-    hipFree(dev.jinv);
-    hipFree(dev.lapdiag);
-}
-
 // Tile tables of the k-marching kernels (fused 7-point sweep, 7-point operator / residual, 19-point kernels) and, on a sharded
 // level, their split into tiles that read no remote ghost cell and the rest.  narrow7: the 7-point tables use the narrow lane
 // classes for remainder columns.  That pays where the kernels are latency-bound -- a uniform metric, two or three streams
@@ -537,10 +489,8 @@ Level::~Level()
 // on the depths whose metric it found uniform; the 19-point tables always use the classes.
 void Level::build_march_tiles(bool narrow7)
 {
-    for (Tile** q : {&d_ftiles, &d_ftiles_own, &d_ftiles_rem, &d_rtiles, &d_rtiles_own, &d_rtiles_rem, &d_qtiles, &d_gtiles, &d_stiles}) {
-        hipFree(*q);
-        *q = nullptr;
-    }
+    for (DevBuf<Tile>* q : {&d_ftiles, &d_ftiles_own, &d_ftiles_rem, &d_rtiles, &d_rtiles_own, &d_rtiles_rem, &d_qtiles, &d_gtiles, &d_stiles})
+        q->reset();
     nftiles_own = nftiles_rem = nrtiles_own = nrtiles_rem = 0;
     narrow7_ = narrow7;
     // ---- tiles of the k-marching kernels: (FT_I x FT_J) columns, k split into chunks so that the launch
@@ -632,11 +582,11 @@ void Level::build_march_tiles(bool narrow7)
         return perm;
     };
     hftiles = march_tiles(124, fused_rows, 4, 3.0, 256, narrow7 && fused_rows == 16, 0.85);
-    d_ftiles = to_device(hftiles);
+    d_ftiles = DevBuf<Tile>::from(hftiles);
     nftiles = (int)hftiles.size();
     hrtiles = march_tiles(124, 16, 2, 2.0, 256, narrow7, 0.85);
     for (size_t q = 0; q < hrtiles.size(); ++q) hrtiles[q].pad_[2] = (int)q;   // its slot in per-tile partial sums (k_resid_march<2>)
-    d_rtiles = to_device(hrtiles);
+    d_rtiles = DevBuf<Tile>::from(hrtiles);
     nrtiles = (int)hrtiles.size();
     // the three-body instantiation of the fused sweep only where the table really holds a narrow tile (on class-0 tiles alone it
     // is the slower kernel: c2_cartesian 151 -> 140 V-cycles/s)
@@ -646,14 +596,14 @@ void Level::build_march_tiles(bool narrow7)
     // AMR V-cycle; 128-wide: C4 136.8 -> 111.6).  One 512-wide box, 5 equal columns against 4 + 4 narrow, is a wash or worse:
     // 19-point colour pass 3.02 -> 3.07 ms, residual 3.17 -> 3.42; c2_cartesian 151 -> 149-158 V-cycles/s depending on tile order)
     hqtiles = march_tiles(124, full_rows, 2, 2.0, full_rows == 6 ? 512 : 256, full_rows == 8, 0.85);   // 6 rows: two workgroups per CU
-    d_qtiles = to_device(hqtiles);
+    d_qtiles = DevBuf<Tile>::from(hqtiles);
     nqtiles = (int)hqtiles.size();
     dev.narrowq = 0;
     for (const Tile& t : hqtiles) if (t.pad_[1]) dev.narrowq = 1;
     ngtiles = nstiles = 0;
     if (want_fused19_) {
         const std::vector<Tile> g = march_tiles(124, 8, 4, 3.0, 256, false);
-        d_gtiles = to_device(g);
+        d_gtiles = DevBuf<Tile>::from(g);
         ngtiles = (int)g.size();
         // shell pass: per box the two x faces (4-wide class-4 columns, 126 rows each), the two y faces (one 6-row band of class-0
         // columns each) in k-chunks of 32 planes, and the two z faces (3 planes over every class-0 tile).  The sets overlap at
@@ -687,7 +637,7 @@ void Level::build_march_tiles(bool narrow7)
                 for (int j0 = 0; j0 < p.n[1]; j0 += 6)
                     for (int i0 = 0; i0 < p.n[0]; i0 += wcol) add(i0, wcol, 0, j0, zk, std::min(3, p.n[2] - zk));
         }
-        d_stiles = to_device(sh);
+        d_stiles = DevBuf<Tile>::from(sh);
         nstiles = (int)sh.size();
     }
 
@@ -717,15 +667,15 @@ void Level::build_march_tiles(bool narrow7)
         split(hftiles, fused_rows, 4, FRAME, own, rem);
         nftiles_own = (int)own.size();
         nftiles_rem = (int)rem.size();
-        d_ftiles_own = to_device(own);
-        d_ftiles_rem = to_device(rem);
+        d_ftiles_own = DevBuf<Tile>::from(own);
+        d_ftiles_rem = DevBuf<Tile>::from(rem);
         own.clear();
         rem.clear();
         split(hrtiles, 16, 2, 1, own, rem);
         nrtiles_own = (int)own.size();
         nrtiles_rem = (int)rem.size();
-        d_rtiles_own = to_device(own);
-        d_rtiles_rem = to_device(rem);
+        d_rtiles_own = DevBuf<Tile>::from(own);
+        d_rtiles_rem = DevBuf<Tile>::from(rem);
     }
 }
 
@@ -824,7 +774,7 @@ void Level::define(const IBox& dom, const bool per[3], const double dx_[3], cons
                     hctiles.push_back(t);
                 }
         }
-        d_ctiles = to_device(hctiles);
+        d_ctiles = DevBuf<Tile>::from(hctiles);
         nctiles = (int)hctiles.size();
     }
 
@@ -843,16 +793,16 @@ void Level::define(const IBox& dom, const bool per[3], const double dx_[3], cons
     }
 
     // ---- device tables ----------------------------------------------------------------
-    d_patches = to_device(hpatches);
-    d_tiles = to_device(htiles);
-    d_local_items = to_device(plan.local);
-    d_send_items = to_device(plan.send_items);
-    d_recv_items = to_device(plan.recv_items);
-    d_send_off = to_device(plan.send_itemoff);
-    d_recv_off = to_device(plan.recv_itemoff);
+    d_patches = DevBuf<PatchDesc>::from(hpatches);
+    d_tiles = DevBuf<Tile>::from(htiles);
+    d_local_items = DevBuf<CopyItem>::from(plan.local);
+    d_send_items = DevBuf<CopyItem>::from(plan.send_items);
+    d_recv_items = DevBuf<CopyItem>::from(plan.recv_items);
+    d_send_off = DevBuf<long long>::from(plan.send_itemoff);
+    d_recv_off = DevBuf<long long>::from(plan.recv_itemoff);
     build_march_tiles(false);
-    if (plan.send_total) SOMAR_HIP(hipMalloc(&d_sendbuf, plan.send_total * sizeof(double)));
-    if (plan.recv_total) SOMAR_HIP(hipMalloc(&d_recvbuf, plan.recv_total * sizeof(double)));
+    d_sendbuf = plan.send_total ? DevBuf<double>(plan.send_total) : DevBuf<double>();
+    d_recvbuf = plan.recv_total ? DevBuf<double>(plan.recv_total) : DevBuf<double>();
 
     dev.tiles = d_tiles;
     dev.ntiles = N;
@@ -892,8 +842,8 @@ void Level::define(const IBox& dom, const bool per[3], const double dx_[3], cons
             }
             tstart[N] = (int)titems.size();
             if (titems.empty()) titems.push_back(CopyItem());   // keep the table pointer non-null (one box, no ghosts to move)
-            d_tile_items = to_device(titems);
-            d_tile_item_start = to_device(tstart);
+            d_tile_items = DevBuf<CopyItem>::from(titems);
+            d_tile_item_start = DevBuf<int>::from(tstart);
             dev.tile_items = d_tile_items;
             dev.tile_item_start = d_tile_item_start;
         }
@@ -944,23 +894,32 @@ void Level::refresh_params()
     dxProduct = active[2] ? dx[0] * dx[1] * dx[2] : dx[0] * dx[1];
 }
 
-double* Level::alloc_field() const
+DevBuf<double> Level::alloc_field() const
 {
-    double* f = nullptr;
-    const long long n = field_elems > 0 ? field_elems : 1;
-    SOMAR_HIP(hipMalloc(&f, n * sizeof(double)));
-    SOMAR_HIP(hipMemset(f, 0, n * sizeof(double)));
+    DevBuf<double> f = DevBuf<double>::zeros(field_elems > 0 ? field_elems : 1);
     SOMAR_HIP(hipDeviceSynchronize());  // null-stream memset vs the solver's non-blocking stream
     return f;
 }
-void Level::free_field(double* f) { hipFree(f); }
 
 void Level::alloc_metric()
 {
+    for (int d = 0; d < 3; ++d) {
+        if (!jg[d]) jg[d] = alloc_field();
+        dev.jg[d] = jg[d];
+    }
+    if (!jinv) jinv = alloc_field();
+    if (!lapdiag) lapdiag = alloc_field();
+    dev.jinv = jinv;
+    dev.lapdiag = lapdiag;
+}
+
+void Level::alloc_cross_metric()
+{
     for (int d = 0; d < 3; ++d)
-        if (!dev.jg[d]) dev.jg[d] = alloc_field();
-    if (!dev.jinv) dev.jinv = alloc_field();
-    if (!dev.lapdiag) dev.lapdiag = alloc_field();
+        for (int c = 0; c < 3; ++c) {
+            if (c != d && !jgx[d][c]) jgx[d][c] = alloc_field();
+            dev.jgf[d][c] = c == d ? dev.jg[d] : jgx[d][c].get();
+        }
 }
 
 // T = double / float: one code path, the element type decides the pack kernel and the transport's message form
@@ -969,8 +928,8 @@ static void exchange_remote_t(const Level& L, T* f, hipStream_t st)
 {
     const ExchangePlan& plan = L.plan;
     if (plan.peers.empty()) return;
-    T* sb = reinterpret_cast<T*>(L.d_sendbuf);
-    T* rb = reinterpret_cast<T*>(L.d_recvbuf);
+    T* sb = reinterpret_cast<T*>(L.d_sendbuf.get());
+    T* rb = reinterpret_cast<T*>(L.d_recvbuf.get());
     launch_pack(st, L.dev, L.d_send_items, L.d_send_off, (int)plan.send_items.size(), f, sb, true);
     L.comm->neighbor_exchange(sb, rb, plan.peers, plan.soff, plan.scount, plan.roff, plan.rcount, st);
     launch_pack(st, L.dev, L.d_recv_items, L.d_recv_off, (int)plan.recv_items.size(), f, rb, false);
@@ -983,8 +942,8 @@ static void exchange_t(const Level& L, T* f, hipStream_t st)
     // remote first so the wire time overlaps the local copies
     const ExchangePlan& plan = L.plan;
     const bool remote = !plan.peers.empty();
-    T* sb = reinterpret_cast<T*>(L.d_sendbuf);
-    T* rb = reinterpret_cast<T*>(L.d_recvbuf);
+    T* sb = reinterpret_cast<T*>(L.d_sendbuf.get());
+    T* rb = reinterpret_cast<T*>(L.d_recvbuf.get());
     if (remote) {
         launch_pack(st, L.dev, L.d_send_items, L.d_send_off, (int)plan.send_items.size(), f, sb, true);
         L.comm->neighbor_exchange(sb, rb, plan.peers, plan.soff, plan.scount, plan.roff, plan.rcount, st);

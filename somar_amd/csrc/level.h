@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.h"
+#include "devbuf.h"
 #include "kernels.h"
 #include "tuning.h"
 
@@ -107,30 +108,27 @@ public:
     void build_march_tiles(bool narrow7);   // (re)builds the marching kernels' tile tables below
     bool narrow7_ = false;
     std::vector<Tile> hftiles;   // tiles of the fused red-black sweep (gsrb_fused.hip)
-    Tile* d_ftiles = nullptr;
+    DevBuf<Tile> d_ftiles;
     int nftiles = 0;
     // sharded levels: hftiles split into the tiles that read no ghost cell another rank fills (they may run while the
     // messages are in flight) and the rest (fused_overlap in solver.cpp); both lists keep the XCD-contiguous order
-    Tile* d_ftiles_own = nullptr;
-    Tile* d_ftiles_rem = nullptr;
+    DevBuf<Tile> d_ftiles_own, d_ftiles_rem;
     int nftiles_own = 0, nftiles_rem = 0;
-    Tile* d_rtiles_own = nullptr;   // the same split of the marching operator / residual's tiles (they read phi one cell around)
-    Tile* d_rtiles_rem = nullptr;
+    DevBuf<Tile> d_rtiles_own, d_rtiles_rem;   // the same split of the marching operator / residual's tiles (they read phi one cell around)
     int nrtiles_own = 0, nrtiles_rem = 0;
     std::vector<Tile> hrtiles;   // tiles of the k-marching operator/residual (resid_march.hip): 124 x 14 columns
-    Tile* d_rtiles = nullptr;
+    DevBuf<Tile> d_rtiles;
     int nrtiles = 0;
     std::vector<Tile> hqtiles;   // tiles of the k-marching 19-point kernels (full19_march.hip): 124 x (rows - 2) columns
-    Tile* d_qtiles = nullptr;
+    DevBuf<Tile> d_qtiles;
     int nqtiles = 0;
     // fused red+black 19-point sweep (full19_fused.hip), built when PressureSolver asks (want_fused19_): its 124 x 4 column tiles
     // and the tiles of the shell pass that follows it (the three outer cell layers of every box)
     bool want_fused19_ = false;
-    Tile* d_gtiles = nullptr;
-    Tile* d_stiles = nullptr;
+    DevBuf<Tile> d_gtiles, d_stiles;
     int ngtiles = 0, nstiles = 0;
     std::vector<Tile> hctiles;   // whole-column tiles (line relaxation): 128 x ctile_j columns, all of k
-    Tile* d_ctiles = nullptr;
+    DevBuf<Tile> d_ctiles;
     int nctiles = 0, ctile_j = 2;
     long long field_elems = 0;
     long long valid_cells_global = 0;
@@ -139,19 +137,18 @@ public:
     Tuning tune;               // the owning solver's switches, as define received them (tile tables are rebuilt later)
 
     // device tables
-    PatchDesc* d_patches = nullptr;
-    Tile* d_tiles = nullptr;
-    CopyItem* d_local_items = nullptr;
+    DevBuf<PatchDesc> d_patches;
+    DevBuf<Tile> d_tiles;
+    DevBuf<CopyItem> d_local_items;
     // pull exchange tables (LevelDev::tile_items): built for single-rank levels of at most Tuning::pull_max_cells cells
-    CopyItem* d_tile_items = nullptr;
-    int* d_tile_item_start = nullptr;
-    bool pull_ready() const { return d_tile_item_start != nullptr; }
-    CopyItem* d_send_items = nullptr;
-    CopyItem* d_recv_items = nullptr;
-    long long* d_send_off = nullptr;
-    long long* d_recv_off = nullptr;
-    double* d_sendbuf = nullptr;
-    double* d_recvbuf = nullptr;
+    DevBuf<CopyItem> d_tile_items;
+    DevBuf<int> d_tile_item_start;
+    bool pull_ready() const { return bool(d_tile_item_start); }
+    DevBuf<CopyItem> d_send_items, d_recv_items;
+    DevBuf<long long> d_send_off, d_recv_off;
+    DevBuf<double> d_sendbuf, d_recvbuf;
+    // metric planes: J g^{aa} on a-faces, J^{-1}, lapDiag; jgx[a][b] (a != b): the cross planes of a non-diagonal metric
+    DevBuf<double> jg[3], jinv, lapdiag, jgx[3][3];
     LevelDev dev;  // kernel view (tables + metric planes)
 
     // operator state
@@ -164,7 +161,7 @@ public:
     // coarse-fine ghost cells (only on levels that sit on a coarser AMR level): the cells of the 1-deep
     // ghost layer that lie inside the (periodically extended) domain and are covered by no box of this level
     std::vector<CFCell> hcf;
-    CFCell* d_cf = nullptr;
+    DevBuf<CFCell> d_cf;
     int ncf = 0;
     double cf_c1[3] = {0, 0, 0}, cf_c2[3] = {0, 0, 0}, cf_fac[3] = {0, 0, 0};
     // The fused red-black sweep on a level with CF boundaries needs (a) every box face to be CF either entirely
@@ -172,7 +169,7 @@ public:
     // also in the EDGE ghosts that the recomputed red ring of a neighbouring box reads -- hcfx = hcf + those.  A
     // re-entrant corner of the refined region (one edge ghost wanted with two different values) rules it out.
     std::vector<CFCell> hcfx;
-    CFCell* d_cfx = nullptr;
+    DevBuf<CFCell> d_cfx;
     int ncfx = 0;
     bool cf_fusable = true;
     std::unique_ptr<class Copier> cf_faces[3];  // high-face coefficients of neighbouring boxes (Copier::define_faces): CF levels, Dirichlet hi walls
@@ -188,7 +185,6 @@ public:
     }
 
     Level() {}
-    ~Level();
     Level(const Level&) = delete;
     Level& operator=(const Level&) = delete;
 
@@ -198,10 +194,11 @@ public:
                 const std::vector<IBox>& bx, const std::vector<int>& own, Comm* c, const Tuning& t);
     // allocate coefficient planes (zero-filled) and fill dev view
     void alloc_metric();
+    // the same for the cross planes behind dev.jgf[a][b] of a non-diagonal metric; dev.jgf[a][a] aliases dev.jg[a]
+    void alloc_cross_metric();
     void refresh_params();
 
-    double* alloc_field() const;        // zero-initialised, field_elems doubles
-    static void free_field(double* f);
+    DevBuf<double> alloc_field() const;   // zero-initialised, field_elems doubles
 
     // ghost exchange of one field (faces, edges and corners, 1 cell deep in active dirs)
     void exchange(double* f, hipStream_t st) const;
@@ -234,7 +231,6 @@ public:
 // cells) into a replicated layout `dst` that holds all boxes locally (coarse-level agglomeration).
 class Copier {
 public:
-    ~Copier();
     // ring_only: only the part of each destination box's grown region that lies OUTSIDE the box (its ghost ring)
     void define(const IBox& domain, const bool periodic[3], const Level& src, const Level& dst, const int ghost[3],
                 Comm* comm, bool ring_only = false);
@@ -249,9 +245,9 @@ private:
     const Level* src_ = nullptr;
     const Level* dst_ = nullptr;
     Comm* comm_ = nullptr;
-    CopyItem *d_local = nullptr, *d_send = nullptr, *d_recv = nullptr;
-    long long *d_soff = nullptr, *d_roff = nullptr;
-    double *d_sbuf = nullptr, *d_rbuf = nullptr;
+    DevBuf<CopyItem> d_local, d_send, d_recv;
+    DevBuf<long long> d_soff, d_roff;
+    DevBuf<double> d_sbuf, d_rbuf;
 };
 
 ExchangePlan build_copy_plan(const IBox& domain, const bool periodic[3], const std::vector<IBox>& srcBoxes,

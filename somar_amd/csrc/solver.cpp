@@ -17,8 +17,7 @@ PressureSolver::PressureSolver(Comm* comm, hipStream_t shared, const Tuning& tun
 {
     if (shared) { st_ = shared; own_stream_ = false; }
     else SOMAR_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-    SOMAR_HIP(hipMalloc(&d_scalars, NSLOTS * sizeof(double)));
-    SOMAR_HIP(hipMemset(d_scalars, 0, NSLOTS * sizeof(double)));
+    d_scalars = DevBuf<double>::zeros(NSLOTS);
     SOMAR_HIP(hipDeviceSynchronize());
     SOMAR_HIP(hipHostMalloc(&h_scalars, (NSLOTS + 2) * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
     h_seq_ = reinterpret_cast<unsigned long long*>(h_scalars + NSLOTS);
@@ -29,49 +28,15 @@ PressureSolver::~PressureSolver()
 {
     drop_graphs();
     mp_free();
-    for (GhostOp* q : d_diri_ops_) hipFree(q);
-    hipFree(d_bcface_);
-    for (double* q : f_flux) Level::free_field(q);
-    for (double* q : f_ccvel) Level::free_field(q);
-    for (double* q : f_heat) Level::free_field(q);
-    hipFree(d_extrapbc_ops_);
     if (st_) hipStreamSynchronize(st_);
     if (st_comm_) { hipStreamSynchronize(st_comm_); hipStreamDestroy(st_comm_); }
     if (ev_ready_) hipEventDestroy(ev_ready_);
     if (ev_done_) hipEventDestroy(ev_done_);
-    for (int w = 0; w < 2; ++w) { hipFree(f_sc_cc[w]); for (int d = 0; d < 3; ++d) hipFree(f_sc_face[w][d]); }
-    for (double* f : f_res) hipFree(f);
-    for (double* f : f_corr) hipFree(f);
-    for (double* f : f_scratch) hipFree(f);
-    for (double* f : f_pp) hipFree(f);
-    for (double* f : f_vel) hipFree(f);
-    for (double* f : f_amr) hipFree(f);
-    for (double* f : f_psi) hipFree(f);
-    for (double* f : f_W) hipFree(f);
-    hipFree(d_fold);
-    for (CoarsenItem* q : d_coarsen_) hipFree(q);
-    hipFree(d_mm_items_);
-    hipFree(d_mm_out_);
-    for (FullProgram& q : aux_prog_) free_program(q);
-    for (double* f : f_heatflux) Level::free_field(f);
-    for (auto& pr : full_prog_)
-        for (auto& q : pr) free_program(q);
-    for (auto& L : lev)
-        for (int d = 0; d < 3; ++d)
-            for (int c = 0; c < 3; ++c)
-                if (c != d && L->dev.jgf[d][c]) { hipFree(L->dev.jgf[d][c]); L->dev.jgf[d][c] = nullptr; }
-    hipFree(f_phi); hipFree(f_rhs); hipFree(f_uberRes); hipFree(f_uberCorr); hipFree(f_best);
-    for (double* f : bicg) hipFree(f);
-    hipFree(d_box_nb_); hipFree(d_box_cstart_); hipFree(d_box_sums_); hipFree(d_box_sync_); hipFree(d_box_fab_); hipFree(d_box_fabstart_);
-    for (int w = 0; w < 2; ++w) { hipFree(d_box_ent_[w]); hipFree(d_box_entfirst_[w]); hipFree(d_box_stg_[w]); hipFree(d_box_stgfirst_[w]); hipFree(d_box_nfg_[w]); hipFree(d_box_nfgfirst_[w]); }
-    hipFree(d_partials);
-    hipFree(d_scalars);
     for (Prof& p : prof_) {
         for (hipEvent_t e : p.a) hipEventDestroy(e);
         for (hipEvent_t e : p.b) hipEventDestroy(e);
     }
     if (h_scalars) hipHostFree(h_scalars);
-    hipFree(d_agglom_back_);
     coarse_.reset();
     lev.clear();
     if (st_ && own_stream_) hipStreamDestroy(st_);
@@ -342,7 +307,7 @@ bool PressureSolver::build_coarser(int depth)
         for (int d = 0; d < nd; ++d)
             launch_avg_face(st_, C->dev, F.dev, pi, C->hpatches[pi].n, C->dev.jg[d], F.dev.jg[d], d, r);
     if (full_) {
-        alloc_full_metric(*C);
+        C->alloc_cross_metric();
         for (int pi = 0; pi < C->npatches(); ++pi)
             for (int d = 0; d < nd; ++d)
                 for (int c = 0; c < nd; ++c)
@@ -378,9 +343,7 @@ void PressureSolver::fill_metric_ghosts(Level& L)
 void PressureSolver::probe_null_space(int d)
 {
     Level& L = *lev[d];
-    double* phi = L.alloc_field();
-    double* rhs0 = L.alloc_field();
-    double* res = L.alloc_field();
+    DevBuf<double> phi = L.alloc_field(), rhs0 = L.alloc_field(), res = L.alloc_field();
     launch_set(st_, phi, L.field_elems, 0.0);
     apply_op(d, rhs0, phi);
     launch_set(st_, phi, L.field_elems, 1.0);
@@ -389,9 +352,6 @@ void PressureSolver::probe_null_space(int d)
     comm_->allreduce(d_scalars + SLOT_TMP, 1, 1, st_);
     const double maxNorm = std::fabs(fetch_scalar(SLOT_TMP));
     L.zeroAvg = maxNorm < 0.01 * (probe_eps > 0.0 ? probe_eps : prm.eps);
-    Level::free_field(phi);
-    Level::free_field(rhs0);
-    Level::free_field(res);
 }
 
 void PressureSolver::finalize()
@@ -451,23 +411,25 @@ void PressureSolver::finalize()
     } report{timing, t0, t1, t2, lev[0]->valid_cells_global};
     (void)secs;
     const int D = (int)lev.size();
-    f_res.assign(D, nullptr);
-    f_corr.assign(D, nullptr);
-    f_scratch.assign(D, nullptr);
-    f_pp.assign(D, nullptr);
+    for (auto* v : {&f_res, &f_corr, &f_scratch, &f_pp}) {
+        v->clear();
+        v->resize(D);
+    }
     if (diri_) build_face_slices();   // before the op lists of depth 0, which take their slices from it
     if (full_) {
         SOMAR_CHECK(prm.relaxMode == RELAX_LEVEL_GSRB || prm.relaxMode == RELAX_JACOBI || prm.relaxMode == RELAX_LINE_GSRB,
                     "the non-diagonal metric path offers LevelGSRB, LineGSRB and Jacobi");
         // (space_dim 2: LineGSRBIter2D with its two cross terms, line_gsrb.hip)
-        f_psi.assign(D, nullptr);
+        f_psi.clear();
+        f_psi.resize(D);
         full_prog_.resize(D);
         for (int d = 0; d < D; ++d) {
             f_psi[d] = lev[d]->alloc_field();
             build_full_programs(d);
         }
     }
-    d_diri_ops_.assign(D, nullptr);
+    d_diri_ops_.clear();
+    d_diri_ops_.resize(D);
     n_diri_ops_.assign(D, 0);
     if (diri_)
         for (int d = 0; d < D; ++d) build_diri_ops(d);
@@ -483,10 +445,10 @@ void PressureSolver::finalize()
     f_uberCorr = L0.alloc_field();
     f_best = L0.alloc_field();
     // folded prolongation: child volumes and total volume per depth
-    f_W.assign(D, nullptr);
+    f_W.clear();
+    f_W.resize(D);
     sf_valid_.assign(D, 0);
-    SOMAR_HIP(hipMalloc(&d_fold, (size_t)D * 8 * sizeof(double)));
-    SOMAR_HIP(hipMemset(d_fold, 0, (size_t)D * 8 * sizeof(double)));
+    d_fold = DevBuf<double>::zeros((size_t)D * 8);
     SOMAR_HIP(hipDeviceSynchronize());
     for (int d = 0; d + 1 < D; ++d) {
         Level& F = *lev[d];
@@ -545,8 +507,7 @@ void PressureSolver::build_agglomerated_tail(int depth)
     }
     n_agglom_back_ = (int)back.size();
     if (n_agglom_back_) {
-        SOMAR_HIP(hipMalloc(&d_agglom_back_, back.size() * sizeof(CopyItem)));
-        SOMAR_HIP(hipMemcpy(d_agglom_back_, back.data(), back.size() * sizeof(CopyItem), hipMemcpyHostToDevice));
+        d_agglom_back_ = DevBuf<CopyItem>::from(back);
         SOMAR_HIP(hipDeviceSynchronize());
     }
 }
@@ -580,16 +541,6 @@ void PressureSolver::agglom_cycle(double* corr, const double* res, bool corr_zer
 // derived from the metric is recomputed, in finalize's order, into the buffers it allocated -- so the result is what a
 // fresh define + set_metric + finalize with the new metric computes, bit for bit.
 // ------------------------------------------------------------------------------------
-template <class T>
-static T* table_to_device(const std::vector<T>& v)
-{
-    T* d = nullptr;
-    SOMAR_HIP(hipMalloc(&d, v.size() * sizeof(T)));
-    SOMAR_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    SOMAR_HIP(hipDeviceSynchronize());   // null-stream copy vs the solver's non-blocking stream
-    return d;
-}
-
 void PressureSolver::check_idle(const char* what) const
 {
     SOMAR_CHECK(!updating_, std::string(what) + " while a metric update is open (end it first: somar_solver_metric_update_end / "
@@ -672,9 +623,11 @@ void PressureSolver::detect_metric_flags()
                 }
         }
         n_mm_items_ = (int)items.size();
-        SOMAR_HIP(hipMalloc(&d_mm_out_, sizeof(double) * (2 * (size_t)std::max(n_mm_items_, 1) * MM_CH + 9 * (size_t)D)));
-        if (n_mm_items_) d_mm_items_ = table_to_device(items);
-        else SOMAR_HIP(hipMalloc(&d_mm_items_, sizeof(MinMaxItem)));
+        d_mm_out_ = DevBuf<double>(2 * (size_t)std::max(n_mm_items_, 1) * MM_CH + 9 * (size_t)D);
+        if (n_mm_items_) {
+            d_mm_items_ = DevBuf<MinMaxItem>::from(items);
+            SOMAR_HIP(hipDeviceSynchronize());   // null-stream copy vs the solver's non-blocking stream
+        } else d_mm_items_ = DevBuf<MinMaxItem>(1);
     }
     std::vector<double> mm(2 * (size_t)n_mm_items_ * MM_CH);
     launch_minmax_all(st_, d_mm_items_, n_mm_items_, d_mm_out_);
@@ -734,9 +687,8 @@ void PressureSolver::choose_narrow_tiles()
     int maxTiles = 1;
     for (auto& L : lev) maxTiles = std::max(std::max(maxTiles, L->dev.ntiles), std::max(L->nrtiles, L->nftiles));
     SOMAR_HIP(hipStreamSynchronize(st_));
-    hipFree(d_partials);
-    d_partials = nullptr;
-    SOMAR_HIP(hipMalloc(&d_partials, (size_t)maxTiles * 2 * sizeof(double)));
+    d_partials.reset();
+    d_partials = DevBuf<double>((size_t)maxTiles * 2);
 }
 
 void PressureSolver::refresh_metric()
@@ -749,7 +701,7 @@ void PressureSolver::refresh_metric()
     const int nd = prm.spaceDim;
     if (d_coarsen_.empty()) {
         // k_coarsen_metric's work items per depth: the (face direction, component) arrays build_coarser averages, then J^{-1}
-        d_coarsen_.assign(D, nullptr);
+        d_coarsen_.resize(D);
         n_coarsen_.assign(D, 0);
         gy_coarsen_.assign(D, 1);
         for (int d = 1; d < D; ++d) {
@@ -774,7 +726,10 @@ void PressureSolver::refresh_metric()
             n_coarsen_[d] = (int)items.size();
             // enough workgroups to fill the device a few times over, spread evenly over the items
             gy_coarsen_[d] = (int)std::min<long long>(maxGroups, std::max<long long>(1, 8192 / std::max<int>(1, n_coarsen_[d])));
-            if (!items.empty()) d_coarsen_[d] = table_to_device(items);
+            if (!items.empty()) {
+                d_coarsen_[d] = DevBuf<CoarsenItem>::from(items);
+                SOMAR_HIP(hipDeviceSynchronize());   // null-stream copy vs the solver's non-blocking stream
+            }
         }
     }
     launch_lapdiag(st_, lev[0]->dev);
@@ -1280,18 +1235,16 @@ void PressureSolver::ordered_sums(int d, const double* a, const double* b, int m
 {
     Level& L = *lev[d];
     const int nb = (int)L.boxes.size();
-    if ((int)d_ord_start_.size() <= d) { d_ord_start_.resize(lev.size(), nullptr); d_box_start_.resize(lev.size(), nullptr); }
+    if ((int)d_ord_start_.size() <= d) { d_ord_start_.resize(lev.size()); d_box_start_.resize(lev.size()); }
     if (!d_box_start_[d]) {
         std::vector<long long> bs(nb + 1, 0), ls(std::max<size_t>(L.local.size(), 1), 0);
         for (int i = 0; i < nb; ++i) bs[i + 1] = bs[i] + L.boxes[i].numPts();
         for (size_t q = 0; q < L.local.size(); ++q) ls[q] = bs[L.local[q]];
-        SOMAR_HIP(hipMalloc(&d_box_start_[d], bs.size() * sizeof(long long)));
-        SOMAR_HIP(hipMalloc(&d_ord_start_[d], ls.size() * sizeof(long long)));
-        SOMAR_HIP(hipMemcpy(d_box_start_[d], bs.data(), bs.size() * sizeof(long long), hipMemcpyHostToDevice));
-        SOMAR_HIP(hipMemcpy(d_ord_start_[d], ls.data(), ls.size() * sizeof(long long), hipMemcpyHostToDevice));
+        d_box_start_[d] = DevBuf<long long>::from(bs);
+        d_ord_start_[d] = DevBuf<long long>::from(ls);   // (ls holds one entry at least: never a null table)
     }
     const long long n = L.valid_cells_global;
-    if (!d_ordbuf_) SOMAR_HIP(hipMalloc(&d_ordbuf_, (size_t)2 * tune_.ordered_reduce_max * sizeof(double)));
+    if (!d_ordbuf_) d_ordbuf_ = DevBuf<double>((size_t)2 * tune_.ordered_reduce_max);
     const int nvec = mode == 6 ? 2 : 1;
     double *X = d_ordbuf_, *Y = d_ordbuf_ + n;
     launch_set(st_, X, nvec * n, 0.0);
@@ -1405,6 +1358,14 @@ void PressureSolver::scale_vel(int centring, int which)
     }
 }
 
+void PressureSolver::alloc_flux(int ndir)
+{
+    for (int a = 0; a < ndir; ++a) {
+        if (!flux_own_[a]) flux_own_[a] = lev[0]->alloc_field();
+        f_flux[a] = flux_own_[a];
+    }
+}
+
 double* const* PressureSolver::mac_grad(double* phi)
 {
     Level& L = *lev[0];
@@ -1412,8 +1373,7 @@ double* const* PressureSolver::mac_grad(double* phi)
         mac_grad_full(phi);
         return f_flux;
     }
-    for (int a = 0; a < 3; ++a)
-        if (!f_flux[a]) f_flux[a] = L.alloc_field();
+    alloc_flux(3);
     // G = 0 + 1.0 * (dxinv * Jg * dphi): k_mac_correct's own expression, stored instead of subtracted (exact)
     double* g[3] = {f_flux[0], f_flux[1], prm.spaceDim == 3 ? f_flux[2] : nullptr};
     for (int a = 0; a < prm.spaceDim; ++a) launch_set(st_, f_flux[a], L.field_elems, 0.0);
@@ -1678,7 +1638,7 @@ void PressureSolver::cycle_down(int d, double* corr, const double* res, bool cor
 void PressureSolver::cycle_up(int d, double* corr, const double* res)
 {
     if (fold_prolong(d)) {
-        fold_up(d, corr, res, f_corr[d + 1], true);
+        fold_up(d, corr, res, f_corr[d + 1].get(), true);
         return;
     }
     // the zero-average mean is folded into the first post-smoothing sweep when that sweep is the fused kernel
@@ -1792,10 +1752,7 @@ void PressureSolver::build_diri_ops(int d)
     }
     if (d == 0) h_diri_ops0_ = ops;
     n_diri_ops_[d] = (int)ops.size();
-    if (!ops.empty()) {
-        SOMAR_HIP(hipMalloc(&d_diri_ops_[d], ops.size() * sizeof(GhostOp)));
-        SOMAR_HIP(hipMemcpy(d_diri_ops_[d], ops.data(), ops.size() * sizeof(GhostOp), hipMemcpyHostToDevice));
-    }
+    d_diri_ops_[d] = DevBuf<GhostOp>::from(ops);
 }
 
 void PressureSolver::apply_diri(int d, double* phi, bool homogeneous)
@@ -1849,7 +1806,7 @@ void PressureSolver::build_face_slices()
         }
     }
     h_bcface_.assign((size_t)std::max(total, 1LL), 0.0);
-    SOMAR_HIP(hipMalloc(&d_bcface_, h_bcface_.size() * sizeof(double)));
+    d_bcface_ = DevBuf<double>(h_bcface_.size());
     lev[0]->dev.bc_face = d_bcface_;
     fill_face_values();
 }
@@ -2034,13 +1991,6 @@ void PressureSolver::mp_free()
 {
     if (f32_.empty()) return;
     if (st_) hipStreamSynchronize(st_);
-    for (Depth32& z : f32_) {
-        for (float* f : z.jg) hipFree(f);
-        hipFree(z.jinv);
-        hipFree(z.corr);
-        hipFree(z.res);
-        hipFree(z.pp);
-    }
     f32_.clear();
     mp_K_ = 0;
 }
@@ -2087,18 +2037,12 @@ void PressureSolver::mp_setup()
         }
     }
     if (K == 0) return;
-    auto alloc32 = [](long long n) {
-        float* f = nullptr;
-        SOMAR_HIP(hipMalloc(&f, (size_t)std::max(n, 1LL) * sizeof(float)));
-        SOMAR_HIP(hipMemset(f, 0, (size_t)std::max(n, 1LL) * sizeof(float)));
-        return f;
-    };
-    f32_.assign(K + 1, Depth32());
+    f32_.resize(K + 1);   // (mp_free left it empty)
     for (int d = 0; d <= K; ++d) {
-        const long long n = lev[d]->field_elems;
-        f32_[d].corr = alloc32(n);
-        f32_[d].res = alloc32(n);
-        if (d < K) f32_[d].pp = alloc32(n);
+        const size_t n = (size_t)std::max(lev[d]->field_elems, 1LL);
+        f32_[d].corr = DevBuf<float>::zeros(n);
+        f32_[d].res = DevBuf<float>::zeros(n);
+        if (d < K) f32_[d].pp = DevBuf<float>::zeros(n);
     }
     SOMAR_HIP(hipDeviceSynchronize());   // null-stream memsets vs the solver's non-blocking stream
     mp_K_ = K;
@@ -2116,8 +2060,8 @@ void PressureSolver::mp_convert_metric()
         if (L.dev.P.uniform && fused_uniform_kernel(L.dev)) continue;
         const long long n = L.field_elems;
         for (int a = 0; a < 3; ++a)
-            if (!z.jg[a]) SOMAR_HIP(hipMalloc(&z.jg[a], (size_t)n * sizeof(float)));
-        if (!z.jinv) SOMAR_HIP(hipMalloc(&z.jinv, (size_t)n * sizeof(float)));
+            if (!z.jg[a]) z.jg[a] = DevBuf<float>((size_t)n);
+        if (!z.jinv) z.jinv = DevBuf<float>((size_t)n);
         float* const dst[4] = {z.jg[0], z.jg[1], z.jg[2], z.jinv};
         const double* const src[4] = {L.dev.jg[0], L.dev.jg[1], L.dev.jg[2], L.dev.jinv};
         launch_convert(st_, dst, src, n);
@@ -2144,10 +2088,10 @@ void PressureSolver::cycle32(int d, float* corr, const float* res, bool corr_zer
         const long long n = lev[K]->field_elems;
         launch_convert(st_, f_res[K], rc, n);
         cycle(K, f_corr[K], f_res[K], true);
-        xchg(*lev[K], f_corr[K]);
+        xchg(*lev[K], f_corr[K].get());
         launch_convert(st_, f32_[K].corr, f_corr[K], n);
     }
-    fold_up(d, corr, res, f32_[d + 1].corr, d + 1 < mp_K_);   // (the seam's correction was exchanged in fp64, above)
+    fold_up(d, corr, res, f32_[d + 1].corr.get(), d + 1 < mp_K_);   // (the seam's correction was exchanged in fp64, above)
 }
 
 // e (fp64, depth 0) := the fp32 cycle's correction of res, or (add_to_phi) e += it.  rnorm: the max norm of res (and of an
@@ -2277,10 +2221,8 @@ void PressureSolver::build_box_tables(int d)
                     }
                 }
     }
-    SOMAR_HIP(hipMalloc(&d_box_nb_, nb.size() * sizeof(int)));
-    SOMAR_HIP(hipMalloc(&d_box_cstart_, cstart.size() * sizeof(int)));
-    SOMAR_HIP(hipMalloc(&d_box_sums_, ((size_t)4 * BOX_MAX_WG + 8) * sizeof(double)));   // + 6 debug counters (SOMAR_BOX_TIMING)
-    SOMAR_HIP(hipMalloc(&d_box_sync_, (BOX_MAX_WG + 1) * sizeof(unsigned)));
+    box_.sums = DevBuf<double>((size_t)4 * BOX_MAX_WG + 8);   // + 6 debug counters (SOMAR_BOX_TIMING)
+    box_.sync = DevBuf<unsigned>(BOX_MAX_WG + 1);
     if (full_) {
         // the box grown by one cell: where each of its cells' values comes from
         std::vector<int> fab, fstart(L.hpatches.size() + 1, 0);
@@ -2296,10 +2238,8 @@ void PressureSolver::build_box_tables(int d)
                     }
         }
         fstart[L.hpatches.size()] = (int)fab.size();
-        SOMAR_HIP(hipMalloc(&d_box_fab_, fab.size() * sizeof(int)));
-        SOMAR_HIP(hipMalloc(&d_box_fabstart_, fstart.size() * sizeof(int)));
-        SOMAR_HIP(hipMemcpy(d_box_fab_, fab.data(), fab.size() * sizeof(int), hipMemcpyHostToDevice));
-        SOMAR_HIP(hipMemcpy(d_box_fabstart_, fstart.data(), fstart.size() * sizeof(int), hipMemcpyHostToDevice));
+        box_.fab = DevBuf<int>::from(fab);
+        box_.fabstart = DevBuf<int>::from(fstart);
         // the two ghost programs ([0] operator, [1] smoother), one entry per written cell, stage after stage: what the kernel
         // runs on its LDS copy with one thread per entry (decoding ops and their regions there cost 20 us per program)
         box_full_ok_ = true;
@@ -2357,22 +2297,20 @@ void PressureSolver::build_box_tables(int d)
             efirst[L.hpatches.size()] = (int)ent.size();
             sfirst[L.hpatches.size()] = (int)stg.size();
             nfirst[L.hpatches.size()] = (int)nfg.size();
-            auto up = [](auto*& dptr, const auto& v) {
-                using T = typename std::remove_reference<decltype(v)>::type::value_type;
-                const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-                SOMAR_HIP(hipMalloc(&dptr, bytes));
-                if (!v.empty()) SOMAR_HIP(hipMemcpy(dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-            };
-            up(d_box_ent_[w], ent);
-            up(d_box_entfirst_[w], efirst);
-            up(d_box_stg_[w], stg);
-            up(d_box_stgfirst_[w], sfirst);
-            up(d_box_nfg_[w], nfg);
-            up(d_box_nfgfirst_[w], nfirst);
+            // an empty table still goes up as one element: the kernel takes no null pointer
+            if (ent.empty()) ent.resize(1);
+            if (stg.empty()) stg.resize(1);
+            if (nfg.empty()) nfg.resize(1);
+            box_.ent[w] = DevBuf<BoxProgEntry>::from(ent);
+            box_.entfirst[w] = DevBuf<int>::from(efirst);
+            box_.stg[w] = DevBuf<int>::from(stg);
+            box_.stgfirst[w] = DevBuf<int>::from(sfirst);
+            box_.nfg[w] = DevBuf<int>::from(nfg);
+            box_.nfgfirst[w] = DevBuf<int>::from(nfirst);
         }
     }
-    SOMAR_HIP(hipMemcpy(d_box_nb_, nb.data(), nb.size() * sizeof(int), hipMemcpyHostToDevice));
-    SOMAR_HIP(hipMemcpy(d_box_cstart_, cstart.data(), cstart.size() * sizeof(int), hipMemcpyHostToDevice));
+    box_.nb = DevBuf<int>::from(nb);
+    box_.cstart = DevBuf<int>::from(cstart);
     box_depth_ = d;
 }
 
@@ -2388,8 +2326,8 @@ void PressureSolver::bottom_solve(double* phi, const double* rhs)
         Level& L = *lev[d];
         BoxBicg A;
         std::memset(&A, 0, sizeof(A));
-        A.nb = d_box_nb_;
-        A.cstart = d_box_cstart_;
+        A.nb = box_.nb;
+        A.cstart = box_.cstart;
         A.phi = phi;
         A.rhs = rhs;
         A.z[0] = bicg[4];
@@ -2404,18 +2342,18 @@ void PressureSolver::bottom_solve(double* phi, const double* rhs)
         A.hang = prm.bottom_hang;
         A.small = prm.bottom_small;
         A.metric = bottom_metric;
-        A.sums = d_box_sums_;
-        A.sync = d_box_sync_;
+        A.sums = box_.sums;
+        A.sync = box_.sync;
         A.serial = ordered(d) ? 1 : 0;
-        A.dbg = tune_.box_timing ? reinterpret_cast<long long*>(d_box_sums_ + 4 * BOX_MAX_WG) : nullptr;
+        A.dbg = tune_.box_timing ? reinterpret_cast<long long*>(box_.sums + 4 * BOX_MAX_WG) : nullptr;
         A.full = full_ ? 1 : 0;
         if (full_) {
-            A.fab_src = d_box_fab_;
-            A.fab_start = d_box_fabstart_;
+            A.fab_src = box_.fab;
+            A.fab_start = box_.fabstart;
             for (int w = 0; w < 2; ++w) {
-                A.ent[w] = d_box_ent_[w]; A.ent_first[w] = d_box_entfirst_[w];
-                A.stg[w] = d_box_stg_[w]; A.stg_first[w] = d_box_stgfirst_[w];
-                A.nfg[w] = d_box_nfg_[w]; A.nfg_first[w] = d_box_nfgfirst_[w];
+                A.ent[w] = box_.ent[w]; A.ent_first[w] = box_.entfirst[w];
+                A.stg[w] = box_.stg[w]; A.stg_first[w] = box_.stgfirst[w];
+                A.nfg[w] = box_.nfg[w]; A.nfg_first[w] = box_.nfgfirst[w];
             }
         }
         A.info = d_scalars + SLOT_TMP;

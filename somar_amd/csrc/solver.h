@@ -263,9 +263,9 @@ private:
     const double* prolong_onto(int d, const LevelDev& C, const double* crse, const int r[3], double* fine, bool defer_mean);
     // ---- mixed precision: depths 0 .. mp_K_ - 1 run the fold path of the cycle (below) on fp32 fields ----
     struct Depth32 {
-        float* jg[3] = {nullptr, nullptr, nullptr};   // fp32 copies of the metric (not made where the depth is uniform)
-        float* jinv = nullptr;
-        float *corr = nullptr, *res = nullptr, *pp = nullptr;   // correction, residual, ping-pong buffer (depth K: corr, res only)
+        DevBuf<float> jg[3];   // fp32 copies of the metric (not made where the depth is uniform)
+        DevBuf<float> jinv;
+        DevBuf<float> corr, res, pp;   // correction, residual, ping-pong buffer (depth K: corr, res only)
     };
     int mp_mode_ = 0;
     long long mp_min_cells_ = 0;
@@ -316,30 +316,26 @@ private:
     void choose_narrow_tiles();    // lane classes of the 7-point marching tables per depth; re-sizes d_partials after a rebuild
     bool updating_ = false, metric_written_ = false;
     void metric_written(const char* producer);   // a producer's check: before finalize, or inside an open update
-    std::vector<CoarsenItem*> d_coarsen_;        // per depth d >= 1: k_coarsen_metric's work items (built at the first refresh)
+    std::vector<DevBuf<CoarsenItem>> d_coarsen_;        // per depth d >= 1: k_coarsen_metric's work items (built at the first refresh)
     std::vector<int> n_coarsen_, gy_coarsen_;
-    MinMaxItem* d_mm_items_ = nullptr;
+    DevBuf<MinMaxItem> d_mm_items_;
     int n_mm_items_ = 0;
     std::vector<int> mm_first_;                  // per depth: first item of (jg0, jg1, jg2, jinv) resp. (jgf01, jgf10), 4 / 2 arrays
-    double* d_mm_out_ = nullptr;
+    DevBuf<double> d_mm_out_;
     void line_relax(int d, double* e, const double* res);
-    double* f_vel[3] = {nullptr, nullptr, nullptr};
-    double* f_ccvel[3] = {nullptr, nullptr, nullptr};
-    double* f_heat[3] = {nullptr, nullptr, nullptr};
-    double* f_sc_cc[2] = {nullptr, nullptr};
-    double* f_sc_face[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    DevBuf<double> f_vel[3], f_ccvel[3], f_heat[3], f_sc_cc[2], f_sc_face[2][3];
     double aCoef_ = 0.0, bCoef_ = 1.0;  // the factory's alpha / beta (MappedAMRPoissonOpFactory.cpp:585-586)
     bool coefs_saved_ = false;
     bool velbc_default_ = true;                      // every non-periodic side a solid wall
     int velbc_kind_[6] = {0, 0, 0, 0, 0, 0};
     double velbc_value_[6] = {0, 0, 0, 0, 0, 0};
     bool amr_member_ = false;
-    double* f_amr[2] = {nullptr, nullptr};
+    DevBuf<double> f_amr[2];
     bool hasCF_ = false;
-    double* f_heatflux[3] = {nullptr, nullptr, nullptr};
+    DevBuf<double> f_heatflux[3];
     bool own_stream_ = true;
     double dxCrse_[3] = {0, 0, 0};
-    std::vector<double*> f_pp;  // per-depth ping-pong buffer of the fused sweep
+    std::vector<DevBuf<double>> f_pp;  // per-depth ping-pong buffer of the fused sweep
     // LevelGSRB sweeps the shells of the domain shrunk by one cell (RelaxationMethod::collectBoundaryData) and the cells inside
     // it: when two or more active directions of the domain are at most two cells wide every one of those boxes is empty, and
     // a sweep of the reference touches no cell at all (a preconditioner is then its diagonal scaling alone)
@@ -357,14 +353,16 @@ private:
     bool box_bottom(int d) const;
     void build_box_tables(int d);
     int box_depth_ = -1, box_max_cells_ = 0;
-    int *d_box_nb_ = nullptr, *d_box_cstart_ = nullptr, *d_box_fab_ = nullptr, *d_box_fabstart_ = nullptr;
-    // 19-point variant: the two ghost programs compiled into per-cell entries (kernels.h: BoxProgEntry), per box
-    BoxProgEntry* d_box_ent_[2] = {nullptr, nullptr};
-    int *d_box_entfirst_[2] = {nullptr, nullptr}, *d_box_stg_[2] = {nullptr, nullptr}, *d_box_stgfirst_[2] = {nullptr, nullptr};
-    int *d_box_nfg_[2] = {nullptr, nullptr}, *d_box_nfgfirst_[2] = {nullptr, nullptr};
+    struct BoxTables {
+        DevBuf<int> nb, cstart, fab, fabstart;
+        DevBuf<double> sums;
+        DevBuf<unsigned> sync;
+        // 19-point variant: the two ghost programs compiled into per-cell entries (kernels.h: BoxProgEntry), per box
+        DevBuf<BoxProgEntry> ent[2];
+        DevBuf<int> entfirst[2], stg[2], stgfirst[2], nfg[2], nfgfirst[2];
+    };
+    BoxTables box_;
     bool box_full_ok_ = false;   // the compiled programs fit the kernel's LDS tables
-    double* d_box_sums_ = nullptr;
-    unsigned* d_box_sync_ = nullptr;
     bool ordered(int d) const { return lev[d]->valid_cells_global <= tune_.ordered_reduce_max; }
     // large 3-D levels of the diagonal path run the k-marching 7-point kernels (resid_march.hip); full_march is the 19-point twin
     bool ortho_march(int d) const
@@ -376,8 +374,8 @@ private:
     // one vector in the serial (box after box) sequence, a sum-allreduce completes it, one wavefront walks it
     // (k_ord_fill / k_reduce_ordered_flat) -- so a sharded solve adds the same numbers in the same order as one rank.
     bool ord_sharded(int d) const { return ordered(d) && comm_->size > 1; }
-    double* d_ordbuf_ = nullptr;                    // 2 * Tuning::ordered_reduce_max doubles
-    std::vector<long long*> d_ord_start_, d_box_start_;  // per depth: serial start of each LOCAL patch / of every box (+ end)
+    DevBuf<double> d_ordbuf_;                // 2 * Tuning::ordered_reduce_max doubles
+    std::vector<DevBuf<long long>> d_ord_start_, d_box_start_;  // per depth: serial start of each LOCAL patch / of every box (+ end)
     void ordered_sums(int d, const double* a, const double* b, int mode, double dxProduct, double* out);
     // out[0] = sum over the level (mode 0: a*b, 2: |a|), every rank: serial order on small levels, tree order on large ones
     bool fused_publish(int d) const;
@@ -396,38 +394,39 @@ private:
     Comm self_;
     hipStream_t st_ = nullptr;
     std::vector<std::unique_ptr<Level>> lev;
-    std::vector<double*> f_res, f_corr, f_scratch;  // per depth
-    double *f_phi = nullptr, *f_rhs = nullptr, *f_uberRes = nullptr, *f_uberCorr = nullptr, *f_best = nullptr;
-    double* bicg[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    double* d_partials = nullptr;
-    double* d_scalars = nullptr;  // device scalar slots
+    std::vector<DevBuf<double>> f_res, f_corr, f_scratch;  // per depth
+    DevBuf<double> f_phi, f_rhs, f_uberRes, f_uberCorr, f_best;
+    DevBuf<double> bicg[8];
+    DevBuf<double> d_partials;
+    DevBuf<double> d_scalars;  // device scalar slots
     double* h_scalars = nullptr;  // pinned
     bool finalized = false;
     // ---- prolongation folded into the first post-smoothing sweep (large levels) ----
     // f_W[d+1]: per coarse cell the volume of its children on depth d; d_fold: per depth {S_f, S_c, V, sum, V}
-    std::vector<double*> f_W;
-    double* d_fold = nullptr;
+    std::vector<DevBuf<double>> f_W;
+    DevBuf<double> d_fold;
     std::vector<char> sf_valid_;
     bool fold_prolong(int d) const;
     // ---- non-diagonal metric (19-point) path, solver_full.cpp ----
     // d_ops: the ops stage by stage (first / count per stage) for the staged form, one launch per stage; d_box_ops / d_box_first:
     // the same ops sorted by box, then stage (GhostOp::pad_), for the one-launch form (k_ghost_program, small levels)
-    struct FullProgram { GhostOp* d_ops = nullptr; std::vector<int> first, count; GhostOp* d_box_ops = nullptr; int* d_box_first = nullptr; int max_box_ops = 0;
+    struct FullProgram { DevBuf<GhostOp> d_ops; std::vector<int> first, count; DevBuf<GhostOp> d_box_ops; DevBuf<int> d_box_first; int max_box_ops = 0;
                          std::vector<GhostOp> h_box_ops; std::vector<int> h_box_first;   // host copy of the box-sorted list (k_box_bicgstab's tables)
                          std::vector<GhostOp> h_ops; };                                   // ... and of d_ops (refresh_diri_ops)
     void upload_program(FullProgram& P, const std::vector<std::vector<GhostOp>>& stages, int npatches);
-    static void free_program(FullProgram& P);
     // small levels run a ghost program as ONE launch, one workgroup per box (Tuning::ghost_staged: always stage by stage)
     bool box_program(int d) const { return !tune_.ghost_staged && !full_march(d) && lev[d]->npatches() > 0; }
     void run_program(int d, const FullProgram& P, double* phi, double* psi, bool homogeneous, bool redirect, bool copy_all);
     bool full_ = false;
-    std::vector<double*> f_psi;                            // per depth: the extrapolated copy of phi
+    std::vector<DevBuf<double>> f_psi;                         // per depth: the extrapolated copy of phi
     // per depth: [0] operator, [1] smoother, [2] fillExtrap alone (getFlux of the flux register), [3] ExtrapolateCFEV
     FullProgram aux_prog_[2];
     bool aux_built_[2] = {false, false};
     std::vector<std::array<FullProgram, 7>> full_prog_;   // + [4] / [5]: [0] / [1] writing psi in the boxes' frames only (marching kernels); [6]: the plain frame copy (copy_frames)
-    double* f_flux[3] = {nullptr, nullptr, nullptr};  // face fluxes of depth 0 (refluxing with a non-diagonal metric)
-    void alloc_full_metric(Level& L);
+    // face fluxes of depth 0 (refluxing with a non-diagonal metric, MAC gradient); alloc_flux: the first ndir of them, on first use
+    DevBuf<double> flux_own_[3];
+    double* f_flux[3] = {nullptr, nullptr, nullptr};   // their view, in the form the launchers take
+    void alloc_flux(int ndir);
     void build_full_programs(int d);
     void run_full_program(int d, int which, double* phi, bool homogeneous = true);
     void run_full_program_frames(int d, int which, double* phi, bool homogeneous = true);
@@ -449,7 +448,7 @@ private:
     // (Tuning::agglom_cells: 128^3 -- below this a level costs less to replicate, ~0.2 ms of sweeps, than to exchange, ~8 x 60 us)
     Copier agglom_gather_;                      // sharded depth agglom_depth_ -> replicated depth 0 of coarse_
     Copier agglom_metric_;                      // the same for the metric (one layer of faces beyond the cells)
-    CopyItem* d_agglom_back_ = nullptr;         // my boxes of the replicated correction -> sharded layout
+    DevBuf<CopyItem> d_agglom_back_;       // my boxes of the replicated correction -> sharded layout
     int n_agglom_back_ = 0;
     void build_agglomerated_tail(int depth);
     void agglom_cycle(double* corr, const double* res, bool corr_zero);
@@ -467,9 +466,9 @@ private:
     bool capturing_ = false;
     bool diri_ = false;
     double bc_value_[3][2] = {{0, 0}, {0, 0}, {0, 0}};
-    std::vector<GhostOp*> d_diri_ops_;
+    std::vector<DevBuf<GhostOp>> d_diri_ops_;
     std::vector<int> n_diri_ops_;
-    GhostOp* d_extrapbc_ops_ = nullptr;  // order-2 extrapolation BC on the physical ghosts of depth 0 (gradient BC)
+    DevBuf<GhostOp> d_extrapbc_ops_;  // order-2 extrapolation BC on the physical ghosts of depth 0 (gradient BC)
     int n_extrapbc_ops_ = 0;
     void build_diri_ops(int d);
     void apply_diri(int d, double* phi, bool homogeneous);
@@ -481,7 +480,7 @@ private:
     std::vector<double> face_plane_[3][2];
     std::vector<long long> face_off_;
     std::vector<double> h_bcface_;
-    double* d_bcface_ = nullptr;
+    DevBuf<double> d_bcface_;
     std::vector<GhostOp> h_diri_ops0_;   // host copy of d_diri_ops_[0]
     void build_face_slices();
     void fill_face_values();

@@ -437,20 +437,12 @@ static std::vector<GhostOp> frame_copy_stage(const Level& L)
     return out;
 }
 
-void PressureSolver::free_program(FullProgram& P)
-{
-    hipFree(P.d_ops);
-    hipFree(P.d_box_ops);
-    hipFree(P.d_box_first);
-    P.d_ops = nullptr;
-    P.d_box_ops = nullptr;
-    P.d_box_first = nullptr;
-}
-
 // stages (the ops of stage s may run together, stage s + 1 after them) -> the device tables of both forms
 void PressureSolver::upload_program(FullProgram& P, const std::vector<std::vector<GhostOp>>& stages, int npatches)
 {
-    free_program(P);
+    P.d_ops.reset();
+    P.d_box_ops.reset();
+    P.d_box_first.reset();
     std::vector<GhostOp> flat;
     P.first.clear();
     P.count.clear();
@@ -497,15 +489,12 @@ void PressureSolver::upload_program(FullProgram& P, const std::vector<std::vecto
     first[npatches] = (int)sorted.size();
     P.max_box_ops = 0;
     for (int b = 0; b < npatches; ++b) P.max_box_ops = std::max(P.max_box_ops, first[b + 1] - first[b]);
-    SOMAR_HIP(hipMalloc(&P.d_ops, flat.size() * sizeof(GhostOp)));
-    SOMAR_HIP(hipMemcpy(P.d_ops, flat.data(), flat.size() * sizeof(GhostOp), hipMemcpyHostToDevice));
-    SOMAR_HIP(hipMalloc(&P.d_box_ops, sorted.size() * sizeof(GhostOp)));
-    SOMAR_HIP(hipMemcpy(P.d_box_ops, sorted.data(), sorted.size() * sizeof(GhostOp), hipMemcpyHostToDevice));
+    P.d_ops = DevBuf<GhostOp>::from(flat);
+    P.d_box_ops = DevBuf<GhostOp>::from(sorted);
     P.h_box_ops = sorted;
     P.h_box_first = first;
     P.h_ops = flat;
-    SOMAR_HIP(hipMalloc(&P.d_box_first, first.size() * sizeof(int)));
-    SOMAR_HIP(hipMemcpy(P.d_box_first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice));
+    P.d_box_first = DevBuf<int>::from(first);
 }
 
 // One application of a ghost program: on small levels ONE launch (a workgroup per box walks the box's ops, a workgroup barrier
@@ -571,7 +560,7 @@ void PressureSolver::make_full()
 {
     SOMAR_CHECK(!lev.empty() && !finalized, "make_full before define / after finalize");
     full_ = true;
-    alloc_full_metric(*lev[0]);
+    lev[0]->alloc_cross_metric();
 }
 
 void PressureSolver::run_aux_program(int which, double* phi)
@@ -620,8 +609,7 @@ double* const* PressureSolver::flux_fields(double* phi)
 {
     SOMAR_CHECK(full_ && finalized, "flux fields are for the non-diagonal path");
     Level& L = *lev[0];
-    for (int a = 0; a < prm.spaceDim; ++a)
-        if (!f_flux[a]) f_flux[a] = L.alloc_field();
+    alloc_flux(prm.spaceDim);
     run_program(0, full_prog_[0][2], phi, f_psi[0], true, false, true);
     launch_flux_full(st_, L.dev, f_flux, phi, f_psi[0]);
     return f_flux;
@@ -671,13 +659,11 @@ void PressureSolver::mac_grad_full(double* phi)
         }
         n_extrapbc_ops_ = (int)ops.size();
         if (!ops.empty()) {
-            SOMAR_HIP(hipMalloc(&d_extrapbc_ops_, ops.size() * sizeof(GhostOp)));
-            SOMAR_HIP(hipMemcpy(d_extrapbc_ops_, ops.data(), ops.size() * sizeof(GhostOp), hipMemcpyHostToDevice));
+            d_extrapbc_ops_ = DevBuf<GhostOp>::from(ops);
             SOMAR_HIP(hipDeviceSynchronize());
         }
     }
-    for (int a = 0; a < prm.spaceDim; ++a)
-        if (!f_flux[a]) f_flux[a] = L.alloc_field();
+    alloc_flux(prm.spaceDim);
     run_program(0, full_prog_[0][2], phi, f_psi[0], true, false, true);
     // one op per (box, side): different sides of a box write different cells and read only valid ones
     launch_ghost_ops(st_, L.dev, d_extrapbc_ops_, n_extrapbc_ops_, phi, phi);
@@ -691,7 +677,7 @@ void PressureSolver::set_metric_full(int patch, const double* jg0, const double*
     Level& L = *lev[0];
     SOMAR_CHECK(patch >= 0 && patch < L.npatches(), "bad patch index");
     full_ = true;
-    alloc_full_metric(L);  // SpaceDim 2: the planes with a z index stay zero, the 3-D operator / ghost kernels see 0 * finite
+    L.alloc_cross_metric();  // SpaceDim 2: the planes with a z index stay zero, the 3-D operator / ghost kernels see 0 * finite
     const IBox valid = L.boxes[L.local[patch]];
     const double* jg[3] = {jg0, jg1, jg2};
     const int nd = prm.spaceDim;
@@ -717,7 +703,7 @@ void PressureSolver::set_metric_map(int kind, const double Lc[3], const double* 
     metric_written(kind == 1 ? "cylindrical" : "map");
     Level& L = *lev[0];
     SOMAR_CHECK(L.npatches() < 65536, "too many local patches for one launch");
-    double* d_depth = nullptr;
+    DevBuf<double> d_depth;
     int lo[2] = {0, 0}, n[2] = {0, 0};
     if (kind == 2) {
         SOMAR_CHECK(depth && dn[0] > 0 && dn[1] > 0, "the bathymetric map needs the nodal depth");
@@ -729,18 +715,17 @@ void PressureSolver::set_metric_map(int kind, const double Lc[3], const double* 
                 SOMAR_CHECK(dlo[d] <= b.lo[d] - 1 && dlo[d] + dn[d] - 1 >= b.hi[d] + 2,
                             "nodal depth must cover nodes lo-1 .. hi+2 of every local box in both horizontal directions");
         }
-        const size_t bytes = (size_t)dn[0] * dn[1] * sizeof(double);
-        SOMAR_HIP(hipMalloc(&d_depth, bytes));
-        SOMAR_HIP(hipMemcpy(d_depth, depth, bytes, hipMemcpyHostToDevice));
+        d_depth = DevBuf<double>((size_t)dn[0] * dn[1]);
+        SOMAR_HIP(hipMemcpy(d_depth, depth, d_depth.size() * sizeof(double), hipMemcpyHostToDevice));
         for (int d = 0; d < 2; ++d) { lo[d] = dlo[d]; n[d] = dn[d]; }
         full_ = true;
-        alloc_full_metric(L);
+        L.alloc_cross_metric();
     } else if (kind == 3 || kind == 4) {
         // TwistedMap, m_twistType 0 / 1: Lc = the amplitudes m_pert; 2 pi |pert| < 1 keeps the Jacobian positive.  Type 1 takes its
         // derivatives and its Jacobian from differences of the coordinate functions (GeoSourceInterface's defaults) over the domain
         // lengths m_L = dx * cells
         full_ = true;
-        alloc_full_metric(L);
+        L.alloc_cross_metric();
     } else {
         SOMAR_CHECK(!full_, "the cylindrical map is diagonal: the level already holds a non-diagonal metric");
         // r = dXi0 (i + offset) > 0 on every face / cell the level owns
@@ -750,16 +735,6 @@ void PressureSolver::set_metric_map(int kind, const double Lc[3], const double* 
     for (int d = 0; d < 3; ++d) domLen[d] = L.dx[d] * (double)L.domain.size(d);
     launch_map_metric(st_, L.dev, kind, L.dx, Lc, d_depth, lo, n, kind == 1, domLen);
     sync();
-    if (d_depth) hipFree(d_depth);
-}
-
-void PressureSolver::alloc_full_metric(Level& L)
-{
-    for (int d = 0; d < 3; ++d)
-        for (int c = 0; c < 3; ++c) {
-            if (c == d) L.dev.jgf[d][c] = L.dev.jg[d];
-            else if (!L.dev.jgf[d][c]) L.dev.jgf[d][c] = L.alloc_field();
-        }
 }
 
 }  // namespace somar

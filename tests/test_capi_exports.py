@@ -32,7 +32,7 @@ def test_library_exports_every_declared_symbol(built_lib):
     lib = C.CDLL(built_lib)
     for name in _header_functions():
         assert hasattr(lib, name), "missing export " + name
-    assert lib.somar_abi_version() == 12
+    assert lib.somar_abi_version() == 13
 
 
 def test_no_cpu_fallback_without_gpu(built_lib):
@@ -83,3 +83,43 @@ def test_relax_and_precond_codes_match_the_reference():
     header = {k[len("SOMAR_"):]: v for k, v in {**_header_defines("SOMAR_RELAX_"), **_header_defines("SOMAR_PRECOND_")}.items()}
     assert header == reference
     assert {**_solver_h_enum("RELAX_JACOBI"), **_solver_h_enum("PRECOND_NONE")} == reference
+
+
+def _csrc_sources():
+    d = os.path.join(ROOT, "somar_amd", "csrc")
+    return {f: open(os.path.join(d, f)).read() for f in sorted(os.listdir(d)) if f.endswith((".cpp", ".h", ".hip"))}
+
+
+def test_device_memory_has_one_owner():
+    """csrc/devbuf.h is the only place that allocates or frees device memory (the stand-alone probes under tools/ are their
+    own programs); the hand-written upload / free helpers it replaced stay gone, and no destructor names a device buffer --
+    DevBuf members release themselves"""
+    srcs = _csrc_sources()
+    assert "devbuf.h" in srcs
+    for f, txt in srcs.items():
+        if f != "devbuf.h":
+            for call in ("hipMalloc(", "hipMallocAsync(", "hipFree(", "hipFreeAsync("):
+                assert call not in txt, "%s calls %s" % (f, call)
+        for gone in ("free_field", "free_program", "table_to_device", "to_device"):
+            assert not re.search(r"\b%s\b" % gone, txt), "%s still has %s" % (f, gone)
+    # every buffer member: declared as DevBuf<...> name[, name...] in a header
+    members = set()
+    for f, txt in srcs.items():
+        if f.endswith(".h"):
+            for decl in re.findall(r"^\s*(?:std::vector<)?DevBuf<[^;()]*?>+\s+([^;()]+);", txt, flags=re.M):
+                members.update(re.findall(r"\b([A-Za-z_]\w*)\b(?:\[\d+\])*\s*(?:,|$)", decl))
+    assert {"f_phi", "d_patches", "jinv", "d_ordbuf_", "buf", "d_avg", "d_sbuf"} <= members
+    ndtor = 0
+    for f, txt in srcs.items():
+        if f == "devbuf.h" or f.endswith(".hip"):
+            continue
+        for m in re.finditer(r"~\w+\(\)[^;{]*\{", txt):
+            depth, i = 1, m.end()
+            while depth:
+                depth += {"{": 1, "}": -1}.get(txt[i], 0)
+                i += 1
+            body = txt[m.end():i - 1]
+            ndtor += 1
+            named = sorted(set(re.findall(r"\b\w+\b", body)) & members)
+            assert not named, "%s: %s names %s" % (f, m.group(0), named)
+    assert ndtor >= 4

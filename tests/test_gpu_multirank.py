@@ -36,6 +36,7 @@ def _worker(rank, nranks, name, mode, q):
         from helpers import (download_valid, make_amr_levels, make_gpu_solver, make_oracle_solver, make_problem, upload,
                              valid_of)
         comm = F.comm_create_shm(name, rank, nranks)
+        live0 = F.device_bytes_live()   # every solver below gives back all the device memory it took
 
         def mine(got, want, what):
             n = 0
@@ -94,6 +95,7 @@ def _worker(rank, nranks, name, mode, q):
         assert st["iters"] == amr.iters and st["exitStatus"] == amr.exitStatus
         np.testing.assert_allclose(st["history"], amr.history, rtol=1e-10, atol=1e-10 * amr.history[0])
         gpu.undefine()
+        assert F.device_bytes_live() == live0
 
         if mode == "fused":
             # ---- exchange / compute overlap: boxes large enough to have tiles that read no remote ghost cell; the sweeps'
@@ -138,6 +140,7 @@ def _worker(rank, nranks, name, mode, q):
             os.environ.pop("SOMAR_MARCH_MIN_CELLS", None)
 
         if nranks != 2:
+            assert F.device_bytes_live() == live0
             F.comm_destroy(comm)
             q.put((rank, "ok"))
             return
@@ -196,6 +199,7 @@ def _worker(rank, nranks, name, mode, q):
                 if g is not None:
                     np.testing.assert_allclose(g, w, rtol=0, atol=1e-10 * float(np.max(np.abs(w))))
         s.undefine()
+        assert F.device_bytes_live() == live0
         F.comm_destroy(comm)
         q.put((rank, "ok"))
     except Exception:

@@ -22,7 +22,7 @@ def test_library_exports_exchange_bytes(built_lib):
     lib = C.CDLL(built_lib)
     assert hasattr(lib, "somar_solver_exchange_bytes")
     assert hasattr(lib, "somar_solver_exchange_bytes_depth")
-    assert lib.somar_abi_version() == 12
+    assert lib.somar_abi_version() == 13
 
 
 def test_header_binding_and_python_method_name_it(built_lib):

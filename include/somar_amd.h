@@ -51,7 +51,8 @@ extern "C" {
  *    metric producers on the device); somar_k_fillmappedlapdiag3d, somar_k_mappedaverage2 (kernel-level hooks); additions only
  * 11: ... + somar_solver_set_bc_face_values (position-dependent Dirichlet values); additions only, so the number stays 11
  * 12: + somar_solver_tuning; the SOMAR_* execution-path variables are read when a solver is created and hold for its life
- * 13: + somar_device_bytes_live; additions only */
+ * 13: + somar_device_bytes_live; additions only
+ * 13: ... + the *_dev entry points (caller arrays in device memory); additions only, so the number stays 13 */
 #define SOMAR_AMD_ABI_VERSION 13
 
 /* BCType codes, calculus/BCInterface/BCDescriptor.H:34-39 */
@@ -469,6 +470,39 @@ int somar_amr_level_project(somar_amr_t* a, int level, int centring, double dt, 
  * tools/inspect_solve.py dumps them as .npz for diffing against such files.  fn = NULL removes the inspector. */
 typedef void (*somar_inspector_fn)(void* user, int kind, int iter, int l_min, int l_max);
 int somar_amr_set_inspector(somar_amr_t* a, somar_inspector_fn fn, void* user);
+
+/* ---- Callers whose data already lives in DEVICE memory (a GPU build of the code around the projector, a torch program) ----
+ * The twins of the host transfers, solves and projections above, without the trip through the host.
+ * dev / phi / rhs / u0.. / vel: a HOST array of one DEVICE pointer per local patch of the level, in local-patch order; each
+ * points to the Fortran-order fp64 array the host call of the same name takes for that patch (over valid.grow(ghost), over
+ * faces(valid, dir) without ghosts, or space_dim components over valid.grow(ghost), component slowest).  A NULL entry skips
+ * its patch: nothing of it is read or written.  ghost: 0..2 per direction (the device frame).  The regions moved are the
+ * host calls': somar_field_*_dev the whole array, frame cells outside it untouched; a solve's rhs and phi go up over the
+ * valid cells and phi comes back over valid.grow(phi_ghost); the cell-centred velocity goes up with one ghost layer and
+ * comes back over the valid cells.  All local patches of a level move in ONE kernel launch per call and direction.
+ * Every pointer of a call is checked before anything is launched (hipPointerGetAttributes): plain device memory on the
+ * solver's device, and -- where the runtime knows the allocation's extent -- large enough for its array; otherwise the call
+ * fails, naming the patch ("... is not a device pointer ..."), and nothing has run.  Managed and host-registered memory
+ * are refused.  fp64 only.
+ * The calls BLOCK, as their host twins do: the caller finishes (synchronises) its own stream work on the arrays first; the
+ * library works on its own stream and drains it before it returns, so the arrays are the caller's again on return.
+ * Each *_dev solve / projection does what its *_host twin does -- which levels' phi are read and written, phi[l_base-1]
+ * supplying the coarse-fine values, stats and residual history -- bit for bit. */
+int somar_field_upload_dev(somar_solver_t* s, int field, const double* const* dev, const int* ghost);
+int somar_field_download_dev(somar_solver_t* s, int field, double* const* dev, const int* ghost);
+int somar_vel_upload_dev(somar_solver_t* s, int dir, const double* const* dev);
+int somar_vel_download_dev(somar_solver_t* s, int dir, double* const* dev);
+int somar_ccvel_upload_dev(somar_solver_t* s, const double* const* dev, const int* ghost);
+int somar_ccvel_download_dev(somar_solver_t* s, double* const* dev, const int* ghost);
+int somar_solver_solve_dev(somar_solver_t* s, double* const* phi, const int* phi_ghost, const double* const* rhs,
+                           const int* rhs_ghost, int zero_phi, int force_homogeneous, somar_stats_t* stats);
+int somar_amr_solve_dev(somar_amr_t* a, double* const* const* phi, const int* phi_ghost, const double* const* const* rhs,
+                        const int* rhs_ghost, int l_max, int l_base, int zero_phi, int force_homogeneous,
+                        somar_stats_t* stats);
+int somar_mac_project_dev(somar_solver_t* s, double* const* u0, double* const* u1, double* const* u2, double dt,
+                          int zero_pressure, int force_homogeneous, somar_stats_t* stats);
+int somar_cc_project_dev(somar_solver_t* s, double* const* vel, const int* ghost, double dt, int zero_pressure,
+                         int force_homogeneous, int wall_bc, somar_stats_t* stats);
 
 /* The COMPOSITE cell-centred projection over levels l_min..l_max -- SOMAR's sync / initialisation / post-regrid projection
  * (NavierStokes/AMRNavierStokesSync.cpp:280-295), velocities in flux form (J u at cell centres, the levels'

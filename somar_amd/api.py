@@ -62,6 +62,7 @@ def lib_path():
 # name -> argtypes; every function returns int (0 ok) except somar_last_error
 _PD, _PI = C.POINTER(C.c_double), C.POINTER(C.c_int)
 _H = C.c_void_p
+_PV = C.POINTER(C.c_void_p)
 _SIGS = {
     "somar_abi_version": [],
     "somar_device_count": [_PI],
@@ -197,6 +198,18 @@ _SIGS = {
     "somar_solver_metric_download": [_H, C.c_int, C.c_int, C.c_int, _PD],
     "somar_solver_set_precision": [_H, C.c_int, C.c_longlong],
     "somar_solver_get_precision": [_H, _PI, _PI],
+    # caller arrays in device memory: HOST tables of device addresses, one per local patch
+    "somar_field_upload_dev": [_H, C.c_int, _PV, _PI],
+    "somar_field_download_dev": [_H, C.c_int, _PV, _PI],
+    "somar_vel_upload_dev": [_H, C.c_int, _PV],
+    "somar_vel_download_dev": [_H, C.c_int, _PV],
+    "somar_ccvel_upload_dev": [_H, _PV, _PI],
+    "somar_ccvel_download_dev": [_H, _PV, _PI],
+    "somar_solver_solve_dev": [_H, _PV, _PI, _PV, _PI, C.c_int, C.c_int, C.POINTER(Stats)],
+    "somar_amr_solve_dev": [_H, C.POINTER(_PV), _PI, C.POINTER(_PV), _PI, C.c_int, C.c_int, C.c_int, C.c_int,
+                            C.POINTER(Stats)],
+    "somar_mac_project_dev": [_H, _PV, _PV, _PV, C.c_double, C.c_int, C.c_int, C.POINTER(Stats)],
+    "somar_cc_project_dev": [_H, _PV, _PI, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Stats)],
     "somar_comm_unique_id": [C.POINTER(C.c_ubyte)],
     "somar_comm_create": [C.POINTER(_H), C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int],
     "somar_comm_create_shm": [C.POINTER(_H), C.c_char_p, C.c_int, C.c_int, C.c_longlong],
@@ -331,6 +344,7 @@ class AMRPressureSolver:
             lh = _H()
             _ck(lib().somar_amr_level(h, l, C.byref(lh)))
             v._h, v._borrowed = lh, True
+            v._p.space_dim = self._p.space_dim
             n = C.c_int()
             _ck(lib().somar_solver_num_local_patches(lh, C.byref(n)))
             v.num_local_patches = n.value
@@ -525,6 +539,7 @@ class AMRPressureSolver:
         return self._h is not None or getattr(self, "_amr", None) is not None
 
     def undefine(self):
+        self.__dict__.pop("_dev_numels", None)
         if getattr(self, "_amr", None) is not None:
             for v in self.levels:
                 v._h = None
@@ -835,6 +850,174 @@ class AMRPressureSolver:
         st = Stats()
         _ck(lib().somar_cc_project_host(self._h, U, _ia(ghost), float(dt), int(zeroPressure), int(forceHomogeneous),
                                         int(wall), C.byref(st)))
+        return self._stats(st)
+
+    # -- callers whose arrays live in device memory (somar_*_dev): lists of flat torch.float64 CUDA tensors, one per local
+    #    patch, each the Fortran-order array of the host call of the same name unravelled; None skips a patch.  torch is
+    #    touched in these methods only.  They synchronise torch's current stream, then block like their host twins. ----
+    def _dev_ready(self):
+        try:
+            import torch
+        except ImportError:
+            raise SomarError("the device-pointer methods take torch CUDA tensors and torch is not installed")
+        if not torch.cuda.is_available():
+            raise SomarError("the device-pointer methods need a GPU: torch.cuda.is_available() is False (no CPU fallback)")
+        if self._h is None and getattr(self, "_amr", None) is None:
+            raise SomarError("solver not defined")
+        return torch
+
+    def _dev_numel(self, ghost=(0, 0, 0), face=None, ncomp=1, depth=0):
+        """elements of every local patch's array; the boxes of a defined solver never change, so each shape is asked once"""
+        key = (self._h.value, tuple(ghost), face, ncomp, depth)
+        cache = self.__dict__.setdefault("_dev_numels", {})
+        if key not in cache:
+            out = []
+            for patch in range(self.num_local_patches):
+                lo, hi, _ = self.patch_box(patch, depth)
+                n = ncomp
+                for d in range(3):
+                    n *= hi[d] - lo[d] + 1 + 2 * int(ghost[d]) + (1 if d == face else 0)
+                out.append(n)
+            cache[key] = out
+        return cache[key]
+
+    def _dev_table(self, torch, tensors, what, **shape):
+        """checks one level's list of tensors; returns the HOST table of their device addresses"""
+        np_ = self.num_local_patches
+        if tensors is None or len(tensors) != np_:
+            raise SomarError("%s: expected a list of %d tensors (one per local patch)" % (what, np_))
+        tab = (C.c_void_p * max(np_, 1))()
+        cur = torch.cuda.current_device()
+        numel = self._dev_numel(**shape)
+        for p, t in enumerate(tensors):
+            if t is None:
+                tab[p] = None
+                continue
+            at = "%s[%d]" % (what, p)
+            if not isinstance(t, torch.Tensor):
+                raise SomarError("%s is not a torch tensor" % at)
+            if t.dtype != torch.float64:
+                raise SomarError("%s has dtype %s, not torch.float64" % (at, t.dtype))
+            if not t.is_cuda or t.device.index != cur:
+                raise SomarError("%s lives on %s, not on the current device cuda:%d" % (at, t.device, cur))
+            if not t.is_contiguous():
+                raise SomarError("%s is not contiguous" % at)
+            want = numel[p]
+            if t.numel() != want:
+                raise SomarError("%s has %d elements, the array of local patch %d has %d" % (at, t.numel(), p, want))
+            tab[p] = t.data_ptr()
+        return tab
+
+    @staticmethod
+    def _dev_ghost(ghost):
+        g = [int(x) for x in ghost]
+        if len(g) != 3 or min(g) < 0:
+            raise SomarError("ghost %r: three widths >= 0" % (tuple(ghost),))
+        return g   # the library refuses one wider than its frame
+
+    def uploadDev(self, field, tensors, ghost):
+        torch = self._dev_ready()
+        g = self._dev_ghost(ghost)
+        tab = self._dev_table(torch, tensors, "tensors", ghost=g, depth=field >> 8)
+        torch.cuda.current_stream().synchronize()
+        _ck(lib().somar_field_upload_dev(self._h, field, tab, _ia(g)))
+
+    def downloadDev(self, field, tensors, ghost):
+        """fills the tensors in place"""
+        torch = self._dev_ready()
+        g = self._dev_ghost(ghost)
+        tab = self._dev_table(torch, tensors, "tensors", ghost=g, depth=field >> 8)
+        torch.cuda.current_stream().synchronize()
+        _ck(lib().somar_field_download_dev(self._h, field, tab, _ia(g)))
+
+    def uploadVelDev(self, d, tensors):
+        torch = self._dev_ready()
+        tab = self._dev_table(torch, tensors, "tensors", face=int(d))
+        torch.cuda.current_stream().synchronize()
+        _ck(lib().somar_vel_upload_dev(self._h, int(d), tab))
+
+    def downloadVelDev(self, d, tensors):
+        torch = self._dev_ready()
+        tab = self._dev_table(torch, tensors, "tensors", face=int(d))
+        torch.cuda.current_stream().synchronize()
+        _ck(lib().somar_vel_download_dev(self._h, int(d), tab))
+
+    def uploadCCVelDev(self, tensors, ghost):
+        torch = self._dev_ready()
+        g = self._dev_ghost(ghost)
+        tab = self._dev_table(torch, tensors, "tensors", ghost=g, ncomp=self._p.space_dim)
+        torch.cuda.current_stream().synchronize()
+        _ck(lib().somar_ccvel_upload_dev(self._h, tab, _ia(g)))
+
+    def downloadCCVelDev(self, tensors, ghost):
+        """writes the valid cells of the tensors in place"""
+        torch = self._dev_ready()
+        g = self._dev_ghost(ghost)
+        tab = self._dev_table(torch, tensors, "tensors", ghost=g, ncomp=self._p.space_dim)
+        torch.cuda.current_stream().synchronize()
+        _ck(lib().somar_ccvel_download_dev(self._h, tab, _ia(g)))
+
+    def solveDev(self, phi, rhs, zeroPhi=True, forceHomogeneous=False, phi_ghost=(1, 1, 1), rhs_ghost=(0, 0, 0)):
+        """solve() on device tensors; phi is updated in place"""
+        torch = self._dev_ready()
+        pg, rg = self._dev_ghost(phi_ghost), self._dev_ghost(rhs_ghost)
+        P = self._dev_table(torch, phi, "phi", ghost=pg)
+        R = self._dev_table(torch, rhs, "rhs", ghost=rg)
+        torch.cuda.current_stream().synchronize()
+        st = Stats()
+        _ck(lib().somar_solver_solve_dev(self._h, P, _ia(pg), R, _ia(rg), int(zeroPhi), int(forceHomogeneous), C.byref(st)))
+        return self._stats(st)
+
+    def solveAMRDev(self, phi, rhs, lmin, lmax, zeroPhi=True, forceHomogeneous=False, phi_ghost=(1, 1, 1),
+                    rhs_ghost=(0, 0, 0)):
+        """solveAMRHost() on device tensors: phi[l] / rhs[l] = list of tensors of level l, or None for levels outside
+        [lmin-1, lmax]; phi is updated in place"""
+        torch = self._dev_ready()
+        pg, rg = self._dev_ghost(phi_ghost), self._dev_ghost(rhs_ghost)
+        nl = len(self.levels)
+        if len(phi) != nl or len(rhs) != nl:
+            raise SomarError("phi / rhs: expected one entry per level (%d)" % nl)
+        keep = []
+
+        def table(v, what, g):
+            rows = (_PV * nl)()
+            for l in range(nl):
+                if v[l] is None:
+                    rows[l] = None
+                    continue
+                row = self.levels[l]._dev_table(torch, v[l], "%s[%d]" % (what, l), ghost=g)
+                keep.append(row)
+                rows[l] = C.cast(row, _PV)
+            return rows
+
+        P, R = table(phi, "phi", pg), table(rhs, "rhs", rg)
+        torch.cuda.current_stream().synchronize()
+        st = Stats()
+        _ck(lib().somar_amr_solve_dev(self._amr, P, _ia(pg), R, _ia(rg), lmax, lmin, int(zeroPhi), int(forceHomogeneous),
+                                      C.byref(st)))
+        return self._stats(st)
+
+    def levelProjectDev(self, vel, dt, zeroPressure=True, forceHomogeneous=False):
+        """levelProject() on device tensors: vel = [u0, u1, u2], each a list of face tensors; projected in place"""
+        torch = self._dev_ready()
+        if vel is None or len(vel) != 3:
+            raise SomarError("vel: expected [u0, u1, u2]")
+        U = [self._dev_table(torch, vel[d], "u%d" % d, face=d) for d in range(3)]
+        torch.cuda.current_stream().synchronize()
+        st = Stats()
+        _ck(lib().somar_mac_project_dev(self._h, U[0], U[1], U[2], float(dt), int(zeroPressure), int(forceHomogeneous),
+                                        C.byref(st)))
+        return self._stats(st)
+
+    def levelProjectCCDev(self, vel, ghost, dt, zeroPressure=True, forceHomogeneous=False, wall=True):
+        """levelProjectCC() on device tensors; projected in place"""
+        torch = self._dev_ready()
+        g = self._dev_ghost(ghost)
+        U = self._dev_table(torch, vel, "vel", ghost=g, ncomp=self._p.space_dim)
+        torch.cuda.current_stream().synchronize()
+        st = Stats()
+        _ck(lib().somar_cc_project_dev(self._h, U, _ia(g), float(dt), int(zeroPressure), int(forceHomogeneous), int(wall),
+                                       C.byref(st)))
         return self._stats(st)
 
     def sync(self):

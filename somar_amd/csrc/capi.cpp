@@ -1157,6 +1157,103 @@ int somar_amr_solve_host(somar_amr_t* a, double* const* const* phi, const int* p
     API_END
 }
 
+// ---- caller arrays in device memory: the *_host / per-patch calls above with the copies replaced by one launch per level ----
+int somar_field_upload_dev(somar_solver_t* s, int field, const double* const* dev, const int* ghost)
+{
+    API_BEGIN
+    int depth;
+    double* f = field_ptr(s, field, &depth);
+    SOMAR_CHECK(dev && ghost, "null pointer");
+    s->ps->upload_field_dev(f, depth, dev, ghost, true);
+    API_END
+}
+
+int somar_field_download_dev(somar_solver_t* s, int field, double* const* dev, const int* ghost)
+{
+    API_BEGIN
+    int depth;
+    double* f = field_ptr(s, field, &depth);
+    SOMAR_CHECK(dev && ghost, "null pointer");
+    s->ps->download_field_dev(f, depth, dev, ghost);
+    API_END
+}
+
+int somar_vel_upload_dev(somar_solver_t* s, int dir, const double* const* dev)
+{
+    API_BEGIN
+    SOMAR_CHECK(dev, "null pointer");
+    s->ps->upload_vel_dev(dir, dev);
+    API_END
+}
+
+int somar_vel_download_dev(somar_solver_t* s, int dir, double* const* dev)
+{
+    API_BEGIN
+    SOMAR_CHECK(dev, "null pointer");
+    s->ps->download_vel_dev(dir, dev);
+    API_END
+}
+
+int somar_ccvel_upload_dev(somar_solver_t* s, const double* const* dev, const int* ghost)
+{
+    API_BEGIN
+    SOMAR_CHECK(dev && ghost, "null pointer");
+    s->ps->upload_cc_vel_dev(dev, ghost);
+    API_END
+}
+
+int somar_ccvel_download_dev(somar_solver_t* s, double* const* dev, const int* ghost)
+{
+    API_BEGIN
+    SOMAR_CHECK(dev && ghost, "null pointer");
+    s->ps->download_cc_vel_dev(dev, ghost);
+    API_END
+}
+
+int somar_solver_solve_dev(somar_solver_t* s, double* const* phi, const int* phi_ghost, const double* const* rhs,
+                           const int* rhs_ghost, int zero_phi, int force_homogeneous, somar_stats_t* stats)
+{
+    API_BEGIN
+    SOMAR_CHECK(phi && rhs && phi_ghost && rhs_ghost, "null pointer");
+    SolveStats st;
+    s->ps->solve_dev(phi, phi_ghost, rhs, rhs_ghost, zero_phi != 0, force_homogeneous != 0, st);
+    fill_stats(st, stats);
+    API_END
+}
+
+int somar_amr_solve_dev(somar_amr_t* a, double* const* const* phi, const int* phi_ghost, const double* const* const* rhs,
+                        const int* rhs_ghost, int l_max, int l_base, int zero_phi, int force_homogeneous,
+                        somar_stats_t* stats)
+{
+    API_BEGIN
+    SolveStats st;
+    a->amr->solve_dev(phi, phi_ghost, rhs, rhs_ghost, l_max, l_base, zero_phi != 0, force_homogeneous != 0, st);
+    fill_stats(st, stats);
+    API_END
+}
+
+int somar_mac_project_dev(somar_solver_t* s, double* const* u0, double* const* u1, double* const* u2, double dt,
+                          int zero_pressure, int force_homogeneous, somar_stats_t* stats)
+{
+    API_BEGIN
+    double* const* const u[3] = {u0, u1, u2};
+    SolveStats st;
+    s->ps->mac_project_dev(u, dt, zero_pressure != 0, force_homogeneous != 0, st);
+    fill_stats(st, stats);
+    API_END
+}
+
+int somar_cc_project_dev(somar_solver_t* s, double* const* vel, const int* ghost, double dt, int zero_pressure,
+                         int force_homogeneous, int wall_bc, somar_stats_t* stats)
+{
+    API_BEGIN
+    SOMAR_CHECK(vel && ghost, "null pointer");
+    SolveStats st;
+    s->ps->cc_project_dev(vel, ghost, dt, zero_pressure != 0, force_homogeneous != 0, wall_bc != 0, st);
+    fill_stats(st, stats);
+    API_END
+}
+
 // ---- kernel-level box-by-box hook: one colour pass of GSRBITER3DORTHO on host FABs, Fortran argument shapes ---------
 extern "C++" {
 namespace {

@@ -265,5 +265,27 @@ void launch_cf_homog(hipStream_t st, const CFCell* cells, int n, double* phi, co
 void launch_copy_items2(hipStream_t st, const PatchDesc* spatches, const PatchDesc* dpatches, const CopyItem* items,
                         int nitems, const double* src, double* dst);
 void launch_fill_hash(hipStream_t st, const LevelDev& L, double* f, unsigned long long seed);
+// box I/O between caller arrays in DEVICE memory and the level's layout (box_io.hip): one launch for every local patch and
+// component.  An item is one (patch, component): the caller's box (low corner, pitches; Fortran order) and the region to move,
+// both in global indices.  The caller's pointers are a column of their own (ptrs[slot]; NULL skips the item), the only part of
+// a table that changes between calls.  Item i owns the tiles [tile0, tile0 of item i + 1): tiles_ij tiles of BIO_THREADS
+// (i, j) pairs of the region's flattened i-j plane for each chunk of BIO_KC k-planes.
+constexpr int BIO_THREADS = 256, BIO_KC = 8;
+struct BoxIoItem {
+    int clo[3];      // low corner of the caller's box
+    int cpj;         // caller j pitch (elements)
+    long long cpk;   // caller k pitch
+    long long coff;  // where this item's component starts in the caller's array (elements)
+    int rlo[3];      // low corner of the region
+    int n[3];        // its size; never empty
+    int patch;
+    int comp;        // which of the launch's fields (the cell-centred velocity: its component)
+    int slot;        // row of the pointer column: the local patch
+    int tile0, tiles_ij;
+    int pad_;
+};
+// field[comp]: the level's arrays (unused entries null); to_level: caller -> level, else level -> caller
+void launch_box_io(hipStream_t st, const LevelDev& L, const BoxIoItem* items, double* const* ptrs, int nitems, int ntiles,
+                   double* const field[3], bool to_level);
 
 }  // namespace somar

@@ -1020,4 +1020,119 @@ void Level::download(const double* field, int patch, double* host, const IBox& h
            region.lo[2] - p.lo[2] + FRAME, n, hipMemcpyDeviceToHost, st);
 }
 
+// ---- caller arrays in device memory (box_io.hip) -------------------------------------------------------------------
+IBox Level::io_caller_box(int patch, const BoxIoShape& s) const
+{
+    IBox b = boxes[local[patch]];
+    if (s.face >= 0) { b.hi[s.face] += 1; return b; }
+    return b.grow(s.ghost);
+}
+
+static void check_shape(const BoxIoShape& s)
+{
+    SOMAR_CHECK(s.face >= -1 && s.face < 3 && s.ncomp >= 1 && s.ncomp <= 3, "box I/O: bad face direction / component count");
+    for (int d = 0; d < 3; ++d) {
+        SOMAR_CHECK(s.ghost[d] >= 0 && s.ghost[d] <= FRAME, "ghost wider than device frame");
+        SOMAR_CHECK(s.grow[d] >= 0 && s.grow[d] <= s.ghost[d], "box I/O: region outside the caller's box");
+        SOMAR_CHECK(s.face < 0 || s.ghost[d] == 0, "box I/O: face arrays carry no ghosts");
+    }
+}
+
+void Level::check_dev_ptrs(const double* const* dev, const BoxIoShape& s, const char* what) const
+{
+    check_shape(s);
+    SOMAR_CHECK(dev != nullptr, std::string(what) + ": null pointer table");
+    if (npatches() == 0) return;
+    hipPointerAttribute_t mine;
+    SOMAR_HIP(hipPointerGetAttributes(&mine, d_patches.get()));
+    for (int p = 0; p < npatches(); ++p) {
+        if (!dev[p]) continue;
+        hipPointerAttribute_t a;
+        const hipError_t e = hipPointerGetAttributes(&a, dev[p]);
+        if (e != hipSuccess) (void)hipGetLastError();   // an unknown pointer leaves a sticky error behind
+        if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.isManaged || a.device != mine.device)
+            throw Error(-1, std::string(what) + "[" + std::to_string(p) + "] (local patch " + std::to_string(p) + ", box " +
+                                std::to_string(local[p]) + ") is not a device pointer on this solver's device " +
+                                std::to_string(mine.device));
+        // where the runtime knows the allocation the pointer lies in, the whole array must fit into it
+        void* base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, const_cast<double*>(dev[p])) != hipSuccess) { (void)hipGetLastError(); continue; }
+        const size_t need = (size_t)io_caller_box(p, s).numPts() * s.ncomp * sizeof(double);
+        const size_t at = (size_t)(reinterpret_cast<const char*>(dev[p]) - static_cast<const char*>(base));
+        if (at > size || need > size - at)
+            throw Error(-1, std::string(what) + "[" + std::to_string(p) + "]: the allocation ends before the array of local patch " +
+                                std::to_string(p) + " does (" + std::to_string(need) + " bytes needed, " + std::to_string(size - at) + " there)");
+    }
+}
+
+Level::BoxIoTable& Level::io_table(const BoxIoShape& s)
+{
+    for (auto& t : io_tables_)
+        if (t->shape == s) return *t;
+    check_shape(s);
+    std::vector<BoxIoItem> items;
+    long long ntiles = 0;
+    for (int p = 0; p < npatches(); ++p) {
+        const PatchDesc& pd = hpatches[p];
+        const IBox cb = io_caller_box(p, s);
+        const IBox region = s.face >= 0 ? cb : boxes[local[p]].grow(s.grow);
+        if (region.empty()) continue;
+        for (int d = 0; d < 3; ++d)
+            SOMAR_CHECK(region.lo[d] - pd.lo[d] >= -FRAME && region.hi[d] - pd.lo[d] < pd.n[d] + FRAME &&
+                            region.lo[d] >= cb.lo[d] && region.hi[d] <= cb.hi[d],
+                        "box I/O region outside patch frame or caller box");
+        for (int c = 0; c < s.ncomp; ++c) {
+            BoxIoItem it;
+            std::memset(&it, 0, sizeof(it));
+            for (int d = 0; d < 3; ++d) { it.clo[d] = cb.lo[d]; it.rlo[d] = region.lo[d]; it.n[d] = region.size(d); }
+            it.cpj = cb.size(0);
+            it.cpk = (long long)cb.size(0) * cb.size(1);
+            it.coff = (long long)c * cb.numPts();
+            it.patch = p;
+            it.comp = c;
+            it.slot = p;
+            const long long nij = (long long)it.n[0] * it.n[1];
+            SOMAR_CHECK(nij < (1LL << 31), "box I/O: an i-j plane of 2^31 cells or more");
+            it.tiles_ij = (int)((nij + BIO_THREADS - 1) / BIO_THREADS);
+            SOMAR_CHECK(ntiles < (1LL << 31), "box I/O: too many tiles");
+            it.tile0 = (int)ntiles;
+            ntiles += (long long)it.tiles_ij * ((it.n[2] + BIO_KC - 1) / BIO_KC);
+            items.push_back(it);
+        }
+    }
+    SOMAR_CHECK(ntiles < (1LL << 31), "box I/O: too many tiles");
+    std::unique_ptr<BoxIoTable> t(new BoxIoTable);
+    t->shape = s;
+    t->nitems = (int)items.size();
+    t->ntiles = (int)ntiles;
+    t->d_items = DevBuf<BoxIoItem>::from(items);
+    t->hptrs.assign(std::max(npatches(), 1), nullptr);
+    t->d_ptrs = DevBuf<double*>(t->hptrs.size());
+    io_tables_.push_back(std::move(t));
+    return *io_tables_.back();
+}
+
+void Level::run_box_io(double* const field[3], double* const* dev, const BoxIoShape& s, hipStream_t st, bool to_level, bool checked)
+{
+    if (!checked) check_dev_ptrs(dev, s, to_level ? "upload_dev" : "download_dev");
+    for (int c = 0; c < s.ncomp; ++c) SOMAR_CHECK(field[c] != nullptr, "box I/O: no such level array");
+    BoxIoTable& t = io_table(s);
+    if (t.nitems == 0) return;
+    for (int p = 0; p < npatches(); ++p) t.hptrs[p] = dev[p];
+    SOMAR_HIP(hipMemcpyAsync(t.d_ptrs, t.hptrs.data(), t.hptrs.size() * sizeof(double*), hipMemcpyHostToDevice, st));
+    launch_box_io(st, this->dev, t.d_items, t.d_ptrs, t.nitems, t.ntiles, field, to_level);
+    SOMAR_HIP(hipStreamSynchronize(st));   // the calls block; t.hptrs and the caller's table are free again
+}
+
+void Level::upload_dev(double* const field[3], const double* const* dev, const BoxIoShape& s, hipStream_t st, bool checked)
+{
+    run_box_io(field, const_cast<double* const*>(dev), s, st, true, checked);   // the kernel only reads them in this direction
+}
+
+void Level::download_dev(double* const field[3], double* const* dev, const BoxIoShape& s, hipStream_t st, bool checked)
+{
+    run_box_io(field, dev, s, st, false, checked);
+}
+
 }  // namespace somar

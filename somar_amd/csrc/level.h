@@ -92,6 +92,29 @@ struct ExchangePlan {
 ExchangePlan build_exchange_plan(const IBox& domain, const bool periodic[3], const int ghost[3],
                                  const std::vector<IBox>& boxes, const std::vector<int>& owner, int myrank);
 
+// What one device-pointer transfer moves, per local patch (Level::upload_dev / download_dev).  The caller's array is defined
+// on valid.grow(ghost) -- or, face >= 0, on faces(valid, face) without ghosts -- with ncomp components, component slowest;
+// the region moved is valid.grow(grow) resp. the whole face box.  The host calls' regions: a field transfer grow = ghost,
+// a solve's phi / rhs upload grow = 0, the cell-centred velocity up grow = 1 in the space directions and down grow = 0.
+struct BoxIoShape {
+    int ghost[3] = {0, 0, 0};
+    int grow[3] = {0, 0, 0};
+    int face = -1;
+    int ncomp = 1;
+    bool operator==(const BoxIoShape& o) const
+    {
+        for (int d = 0; d < 3; ++d) if (ghost[d] != o.ghost[d] || grow[d] != o.grow[d]) return false;
+        return face == o.face && ncomp == o.ncomp;
+    }
+    static BoxIoShape cells(const int g[3], bool with_ghosts)
+    {
+        BoxIoShape s;
+        for (int d = 0; d < 3; ++d) { s.ghost[d] = g[d]; s.grow[d] = with_ghosts ? g[d] : 0; }
+        return s;
+    }
+    static BoxIoShape faces(int dir) { BoxIoShape s; s.face = dir; return s; }
+};
+
 class Level {
 public:
     // layout
@@ -223,7 +246,32 @@ public:
     void download(const double* field, int patch, double* host, const IBox& hostbox, const IBox& region,
                   hipStream_t st) const;
 
+    // The same transfers for caller arrays in DEVICE memory, every local patch (and component) in one launch (box_io.hip).
+    // dev: HOST array of npatches() device pointers in local-patch order, a null entry skips its patch; field[c]: the level
+    // array component c goes to / comes from.  Every pointer is checked before the launch (check_dev_ptrs); the item table
+    // is built on the first call with a given shape and reused, only its pointer column is written per call.  The calls
+    // enqueue on st and drain it before they return.
+    void upload_dev(double* const field[3], const double* const* dev, const BoxIoShape& shape, hipStream_t st, bool checked = false);
+    void download_dev(double* const field[3], double* const* dev, const BoxIoShape& shape, hipStream_t st, bool checked = false);
+    // throws unless every non-null dev[p] is device memory on this level's device (and, where the runtime knows the
+    // allocation's extent, holds the whole array of patch p); `what` names the argument in the message
+    void check_dev_ptrs(const double* const* dev, const BoxIoShape& shape, const char* what) const;
+
     int npatches() const { return (int)hpatches.size(); }
+
+private:
+    struct BoxIoTable {
+        BoxIoShape shape;
+        DevBuf<BoxIoItem> d_items;
+        DevBuf<double*> d_ptrs;
+        std::vector<double*> hptrs;   // staging of the pointer column; stable until the stream is drained
+        int nitems = 0, ntiles = 0;
+    };
+    std::vector<std::unique_ptr<BoxIoTable>> io_tables_;
+    BoxIoTable& io_table(const BoxIoShape& shape);
+    IBox io_caller_box(int patch, const BoxIoShape& shape) const;
+    void run_box_io(double* const field[3], double* const* dev, const BoxIoShape& shape, hipStream_t st, bool to_level,
+                    bool checked);
 };
 
 // Copier between two layouts of one index space: valid cells of `src` boxes (and their periodic images) into

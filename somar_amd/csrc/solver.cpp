@@ -838,6 +838,88 @@ void PressureSolver::download_field(const double* field, int depth, int patch, d
     sync();
 }
 
+// ---- caller arrays in device memory: one launch per call for all local patches (box_io.hip) ----
+void PressureSolver::upload_field_dev(double* field, int depth, const double* const* dev, const int ghost[3], bool with_ghosts,
+                                      bool checked)
+{
+    SOMAR_CHECK(field && ghost, "upload_field_dev: no such field / null ghost");
+    double* const f[3] = {field, nullptr, nullptr};
+    level(depth).upload_dev(f, dev, BoxIoShape::cells(ghost, with_ghosts), st_, checked);
+}
+void PressureSolver::download_field_dev(double* field, int depth, double* const* dev, const int ghost[3], bool checked)
+{
+    SOMAR_CHECK(field && ghost, "download_field_dev: no such field / null ghost");
+    double* const f[3] = {field, nullptr, nullptr};
+    level(depth).download_dev(f, dev, BoxIoShape::cells(ghost, true), st_, checked);
+}
+void PressureSolver::upload_vel_dev(int dir, const double* const* dev, bool checked)
+{
+    double* const f[3] = {vel(dir), nullptr, nullptr};
+    lev[0]->upload_dev(f, dev, BoxIoShape::faces(dir), st_, checked);
+}
+void PressureSolver::download_vel_dev(int dir, double* const* dev, bool checked)
+{
+    double* const f[3] = {vel(dir), nullptr, nullptr};
+    lev[0]->download_dev(f, dev, BoxIoShape::faces(dir), st_, checked);
+}
+BoxIoShape PressureSolver::cc_vel_shape(const int ghost[3], bool up) const
+{
+    SOMAR_CHECK(ghost, "null ghost");
+    BoxIoShape s = BoxIoShape::cells(ghost, false);
+    s.ncomp = prm.spaceDim;
+    for (int d = 0; d < prm.spaceDim; ++d) {
+        SOMAR_CHECK(ghost[d] >= 1, "the cell-centred velocity needs one ghost layer (CellToEdge reads it)");
+        if (up) s.grow[d] = 1;
+    }
+    return s;
+}
+void PressureSolver::upload_cc_vel_dev(const double* const* dev, const int ghost[3], bool checked)
+{
+    const BoxIoShape s = cc_vel_shape(ghost, true);
+    double* const f[3] = {cc_vel(0), cc_vel(1), prm.spaceDim > 2 ? cc_vel(2) : nullptr};
+    lev[0]->upload_dev(f, dev, s, st_, checked);
+}
+void PressureSolver::download_cc_vel_dev(double* const* dev, const int ghost[3], bool checked)
+{
+    const BoxIoShape s = cc_vel_shape(ghost, false);
+    double* const f[3] = {cc_vel(0), cc_vel(1), prm.spaceDim > 2 ? cc_vel(2) : nullptr};
+    lev[0]->download_dev(f, dev, s, st_, checked);
+}
+
+void PressureSolver::solve_dev(double* const* phi, const int phi_ghost[3], const double* const* rhs, const int rhs_ghost[3],
+                               bool zeroPhi, bool forceHomogeneous, SolveStats& st)
+{
+    SOMAR_CHECK(finalized && phi_ghost && rhs_ghost, "solve_dev: solver not finalized / null ghost");
+    Level& L = *lev[0];
+    L.check_dev_ptrs(phi, BoxIoShape::cells(phi_ghost, true), "phi");
+    L.check_dev_ptrs(rhs, BoxIoShape::cells(rhs_ghost, false), "rhs");
+    upload_field_dev(f_rhs, 0, rhs, rhs_ghost, false, true);
+    if (!zeroPhi) upload_field_dev(f_phi, 0, phi, phi_ghost, false, true);
+    solve(zeroPhi, forceHomogeneous, st);
+    download_field_dev(f_phi, 0, phi, phi_ghost, true);
+}
+
+void PressureSolver::mac_project_dev(double* const* const u[3], double dt, bool zeroPressure, bool forceHomogeneous, SolveStats& st)
+{
+    SOMAR_CHECK(finalized && u && u[0] && u[1] && u[2], "mac_project_dev: solver not finalized / null pointer table");
+    Level& L = *lev[0];
+    static const char* const name[3] = {"u0", "u1", "u2"};
+    for (int d = 0; d < 3; ++d) L.check_dev_ptrs(u[d], BoxIoShape::faces(d), name[d]);
+    for (int d = 0; d < 3; ++d) upload_vel_dev(d, u[d], true);
+    mac_project(dt, zeroPressure, forceHomogeneous, st);
+    for (int d = 0; d < 3; ++d) download_vel_dev(d, u[d], true);
+}
+
+void PressureSolver::cc_project_dev(double* const* vel, const int ghost[3], double dt, bool zeroPressure, bool forceHomogeneous,
+                                    bool wall, SolveStats& st)
+{
+    SOMAR_CHECK(finalized, "cc_project_dev: solver not finalized");
+    lev[0]->check_dev_ptrs(vel, cc_vel_shape(ghost, true), "vel");
+    upload_cc_vel_dev(vel, ghost, true);
+    cc_project(dt, zeroPressure, forceHomogeneous, wall, st);
+    download_cc_vel_dev(vel, ghost, true);
+}
+
 // ------------------------------------------------------------------------------------
 // level operator
 // ------------------------------------------------------------------------------------

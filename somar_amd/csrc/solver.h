@@ -92,6 +92,23 @@ public:
     void upload_rhs(int patch, const double* host, const int ghost[3]);
     void download_phi(int patch, double* host, const int ghost[3]);
     void download_field(const double* field, int depth, int patch, double* host, const int ghost[3]);
+    // ---- the same for caller arrays in DEVICE memory: every local patch in one launch (Level::upload_dev / download_dev).
+    // dev: HOST array of one device pointer per local patch (null skips the patch); regions as in the host calls.  Every
+    // pointer of a call is checked before its first launch; the calls run on this solver's stream and drain it.
+    void upload_field_dev(double* field, int depth, const double* const* dev, const int ghost[3], bool with_ghosts,
+                          bool checked = false);
+    void download_field_dev(double* field, int depth, double* const* dev, const int ghost[3], bool checked = false);
+    void upload_vel_dev(int dir, const double* const* dev, bool checked = false);
+    void download_vel_dev(int dir, double* const* dev, bool checked = false);
+    void upload_cc_vel_dev(const double* const* dev, const int ghost[3], bool checked = false);
+    void download_cc_vel_dev(double* const* dev, const int ghost[3], bool checked = false);
+    BoxIoShape cc_vel_shape(const int ghost[3], bool up) const;
+    // the *_host solves and projections of the C ABI with the copies replaced
+    void solve_dev(double* const* phi, const int phi_ghost[3], const double* const* rhs, const int rhs_ghost[3], bool zeroPhi,
+                   bool forceHomogeneous, SolveStats& st);
+    void mac_project_dev(double* const* const u[3], double dt, bool zeroPressure, bool forceHomogeneous, SolveStats& st);
+    void cc_project_dev(double* const* vel, const int ghost[3], double dt, bool zeroPressure, bool forceHomogeneous, bool wall,
+                        SolveStats& st);
 
     // ---- AMREllipticSolver::solve on the resident phi/rhs (AMREllipticSolver.H:33-48) -----
     void solve(bool zeroPhi, bool forceHomogeneous, SolveStats& st);

@@ -1,0 +1,431 @@
+"""The device-pointer boundary (somar_*_dev, csrc/box_io.hip) against the host boundary it stands next to: field, MAC and
+cell-centred velocity transfers in both directions, untouched frame cells, skipped patches, solves and projections equal to
+their *_host twins bit for bit, refusals, and no device memory left behind.  A copy has no tolerance: every comparison is
+assert_array_equal.
+
+Layouts: a 44 x 24 x 10 domain cut into six boxes of unequal size, i-widths 12 / 20 / 12 (every box narrower than a
+wavefront, none a multiple of it; one launch covers them all); one 130 x 6 x 4 box (two full wavefronts and a tail of 2 in
+the first row); a 2-D level one cell thick in z.  None of these boxes can be coarsened by 8, so their multigrid
+hierarchies have depth 0 only (MappedAMRPoissonOp::s_maxCoarse = 4 asks for it); SOMAR_F_RES at depth 1 is moved on a
+fourth layout, 48 x 16 x 8 with i-widths 8 / 24 / 16, whose depth 1 has boxes 4, 12 and 8 wide."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = -7.25
+GHOSTS = [(0, 0, 0), (1, 1, 1), (2, 0, 1)]
+
+
+def _cut(edges_i, edges_j, nk):
+    return [((i0, j0, 0), (i1 - 1, j1 - 1, nk - 1)) for j0, j1 in zip(edges_j[:-1], edges_j[1:])
+            for i0, i1 in zip(edges_i[:-1], edges_i[1:])]
+
+
+LAYOUTS = {
+    "unequal": ((44, 24, 10), _cut([0, 12, 32, 44], [0, 8, 24], 10), 3),
+    "wide": ((130, 6, 4), [((0, 0, 0), (129, 5, 3))], 3),
+    "flat2d": ((44, 24, 1), _cut([0, 12, 32, 44], [0, 8, 24], 1), 2),
+    "deep": ((48, 16, 8), _cut([0, 8, 32, 48], [0, 8, 16], 8), 3),
+}
+
+
+def _solver(n, boxes, ndim=3, periodic=(False, False, False)):
+    from somar_amd import AMRPressureSolver
+    s = AMRPressureSolver()
+    s.setSpaceDim(ndim)
+    s.define((0, 0, 0), tuple(a - 1 for a in n), periodic, tuple(1.0 / a for a in n), boxes)
+    s.setMetricUniform(1.0, 1.0, 1.0, 1.0)
+    s.finalize()
+    return s
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch
+    return torch
+
+
+def _to_dev(torch, a):
+    """a Fortran-order array unravelled, as a flat CUDA tensor"""
+    return torch.from_numpy(np.ravel(a, order="F").copy()).cuda()
+
+
+def _to_host(t, shape):
+    return t.cpu().numpy().reshape(shape, order="F")
+
+
+def _shape(s, p, ghost=(0, 0, 0), face=None, depth=0):
+    lo, hi, _ = s.patch_box(p, depth)
+    return tuple(h - l + 1 + 2 * g + (1 if d == face else 0) for d, (l, h, g) in enumerate(zip(lo, hi, ghost)))
+
+
+def _values(shape, seed):
+    """distinct values, so a cell that lands in the wrong place shows"""
+    n = int(np.prod(shape))
+    return (1000.0 * seed + np.arange(n, dtype=np.float64) + 0.5).reshape(shape, order="F")
+
+
+@pytest.mark.parametrize("ghost", GHOSTS)
+@pytest.mark.parametrize("layout", sorted(LAYOUTS))
+def test_field_round_trips_through_the_other_path(torch, layout, ghost):
+    from somar_amd import api as F
+    n, boxes, ndim = LAYOUTS[layout]
+    s = _solver(n, boxes, ndim)
+    try:
+        assert (s.depth() >= 2) == (layout == "deep")
+        rdepth = 1 if layout == "deep" else 0
+        for field, depth in ((F.F_PHI, 0), (F.FIELD(rdepth, F.F_RES), rdepth)):
+            npatch = s.num_local_patches
+            src = [_values(_shape(s, p, ghost, depth=depth), p + 1) for p in range(npatch)]
+            # device tensors up, host arrays down
+            s.setVal(field, SENTINEL)
+            s.uploadDev(field, [_to_dev(torch, a) for a in src], ghost)
+            for p in range(npatch):
+                np.testing.assert_array_equal(s.download(field, p, ghost, depth), src[p])
+                # the frame cells outside the caller's box keep what they held
+                full = s.download(field, p, (2, 2, 2), depth)
+                inner = tuple(slice(2 - g, full.shape[d] - (2 - g)) for d, g in enumerate(ghost))
+                np.testing.assert_array_equal(full[inner], src[p])
+                mask = np.ones(full.shape, dtype=bool)
+                mask[inner] = False
+                assert mask.sum() > 0 and np.all(full[mask] == SENTINEL)
+            # host arrays up, device tensors down
+            s.setVal(field, SENTINEL)
+            src2 = [a + 0.25 for a in src]
+            for p in range(npatch):
+                s.upload(field, p, src2[p], ghost)
+            out = [torch.full((a.size,), float("nan"), dtype=torch.float64, device="cuda") for a in src2]
+            s.downloadDev(field, out, ghost)
+            for p in range(npatch):
+                np.testing.assert_array_equal(_to_host(out[p], src2[p].shape), src2[p])
+    finally:
+        s.undefine()
+
+
+def test_upload_without_ghosts_leaves_the_frame_untouched(torch):
+    from somar_amd import api as F
+    n, boxes, ndim = LAYOUTS["unequal"]
+    s = _solver(n, boxes, ndim)
+    try:
+        s.setVal(F.F_PHI, SENTINEL)
+        src = [_values(_shape(s, p), p + 1) for p in range(s.num_local_patches)]
+        s.uploadDev(F.F_PHI, [_to_dev(torch, a) for a in src], (0, 0, 0))
+        for p in range(s.num_local_patches):
+            got = s.download(F.F_PHI, p, (1, 1, 1))
+            np.testing.assert_array_equal(got[1:-1, 1:-1, 1:-1], src[p])
+            got[1:-1, 1:-1, 1:-1] = SENTINEL
+            assert np.all(got == SENTINEL)   # every ghost cell
+    finally:
+        s.undefine()
+
+
+def test_null_entry_skips_its_patch(torch):
+    from somar_amd import api as F
+    n, boxes, ndim = LAYOUTS["unequal"]
+    s = _solver(n, boxes, ndim)
+    try:
+        s.setVal(F.F_PHI, SENTINEL)
+        src = [_values(_shape(s, p, (1, 1, 1)), p + 1) for p in range(s.num_local_patches)]
+        tens = [_to_dev(torch, a) for a in src]
+        tens[1] = tens[4] = None
+        s.uploadDev(F.F_PHI, tens, (1, 1, 1))
+        for p in range(s.num_local_patches):
+            got = s.download(F.F_PHI, p, (1, 1, 1))
+            if p in (1, 4):
+                assert np.all(got == SENTINEL)
+            else:
+                np.testing.assert_array_equal(got, src[p])
+        # and the way back: a skipped patch's tensor does not exist, the others are filled
+        out = [None if t is None else torch.zeros_like(t) for t in tens]
+        s.downloadDev(F.F_PHI, out, (1, 1, 1))
+        for p in (0, 2, 3, 5):
+            np.testing.assert_array_equal(_to_host(out[p], src[p].shape), src[p])
+    finally:
+        s.undefine()
+
+
+def test_mac_velocity_face_layout(torch):
+    n, boxes, ndim = LAYOUTS["unequal"]
+    s = _solver(n, boxes, ndim)
+    try:
+        for d in range(3):
+            src = [_values(_shape(s, p, face=d), 10 * d + p + 1) for p in range(s.num_local_patches)]
+            s.uploadVelDev(d, [_to_dev(torch, a) for a in src])
+            for p in range(s.num_local_patches):
+                np.testing.assert_array_equal(s.downloadVel(d, p), src[p])
+            src2 = [a + 0.25 for a in src]
+            for p in range(s.num_local_patches):
+                s.uploadVel(d, p, src2[p])
+            out = [torch.zeros(a.size, dtype=torch.float64, device="cuda") for a in src2]
+            s.downloadVelDev(d, out)
+            for p in range(s.num_local_patches):
+                np.testing.assert_array_equal(_to_host(out[p], src2[p].shape), src2[p])
+    finally:
+        s.undefine()
+
+
+@pytest.mark.parametrize("layout", ["unequal", "flat2d"])
+def test_cell_centred_velocity_component_layout(torch, layout):
+    """space_dim components, component slowest, one ghost layer up and the valid cells down -- as the host calls move them;
+    the ghost layer is seen through the divergence, which reads it (CellToEdge)"""
+    from somar_amd import api as F
+    n, boxes, ndim = LAYOUTS[layout]
+    s = _solver(n, boxes, ndim)
+    ghost = (1, 1, 1)
+    try:
+        npatch = s.num_local_patches
+        rng = np.random.default_rng(3)
+        src = [np.asfortranarray(rng.standard_normal(_shape(s, p, ghost) + (ndim,))) for p in range(npatch)]
+        zero = [np.zeros_like(a) for a in src]
+
+        def divergence():
+            s.divergenceCC(F.F_RHS, 0.5)
+            return [s.download(F.F_RHS, p, (0, 0, 0)) for p in range(npatch)]
+
+        for p in range(npatch):
+            s.uploadCCVel(p, src[p], ghost)
+        want_div = divergence()
+        want = [np.full_like(a, 99.0) for a in src]
+        for p in range(npatch):
+            s.downloadCCVel(p, want[p], ghost)   # the valid cells; the ghosts keep 99
+        for p in range(npatch):
+            s.uploadCCVel(p, zero[p], ghost)
+        assert all(not d.any() for d in divergence())
+        s.uploadCCVelDev([_to_dev(torch, a) for a in src], ghost)
+        for got, w in zip(divergence(), want_div):
+            assert w.any()
+            np.testing.assert_array_equal(got, w)
+        out = [torch.full((a.size,), 99.0, dtype=torch.float64, device="cuda") for a in src]
+        s.downloadCCVelDev(out, ghost)
+        for p in range(npatch):
+            np.testing.assert_array_equal(_to_host(out[p], src[p].shape), want[p])
+    finally:
+        s.undefine()
+
+
+def _same_stats(a, b):
+    assert a["iters"] == b["iters"] and a["exitStatus"] == b["exitStatus"] and a["status"] == b["status"]
+    assert a["iters"] > 0 and len(a["history"]) > 1
+    np.testing.assert_array_equal(np.array(a["history"]), np.array(b["history"]))
+    assert a["initial_rnorm"] == b["initial_rnorm"] and a["final_rnorm"] == b["final_rnorm"]
+
+
+def test_solve_dev_equals_solve_host(oracle, torch):
+    """32^3 in 16^3 boxes, stretched metric; from zero and from a given phi"""
+    from helpers import make_gpu_solver, make_problem
+    so = oracle
+    dom, grids, dx, Jgup, Jinv = make_problem(so, (32, 32, 32), 16, "stretched", (False, True, False), (2.0, 1.0, 0.5))
+    # two solvers with the same life: the ghost cells beyond a wall come back as the solver leaves them, and those depend on
+    # the solves before (the correction's wall ghosts are never reset)
+    gpu = make_gpu_solver(dom, grids, dx, Jgup, Jinv)
+    twin = make_gpu_solver(dom, grids, dx, Jgup, Jinv)
+    try:
+        rhs = so.random_field(grids, 12345, (0, 0, 0), dom.box)
+        so.remove_weighted_mean(rhs, Jinv)
+        order = [gpu.patch_box(p)[2] for p in range(gpu.num_local_patches)]
+        hrhs = [np.asfortranarray(rhs.fabs[gi].a[..., 0]) for gi in order]
+        shp = [_shape(gpu, p, (1, 1, 1)) for p in range(len(order))]
+        rng = np.random.default_rng(5)
+        for zero_phi in (True, False):
+            start = [np.asfortranarray(0.0 * rng.standard_normal(sh) if zero_phi else 0.01 * rng.standard_normal(sh)) for sh in shp]
+            hphi = [a.copy(order="F") for a in start]
+            st_h = dict(gpu.solve(hphi, hrhs, 0, 0, zero_phi, False))
+            dphi = [_to_dev(torch, a) for a in start]
+            drhs = [_to_dev(torch, a) for a in hrhs]
+            st_d = dict(twin.solveDev(dphi, drhs, zero_phi, False))
+            _same_stats(st_h, st_d)
+            for p in range(len(order)):
+                assert hphi[p].any()
+                np.testing.assert_array_equal(_to_host(dphi[p], shp[p]), hphi[p])
+                np.testing.assert_array_equal(_to_host(drhs[p], hrhs[p].shape), hrhs[p])   # rhs is read only
+    finally:
+        gpu.undefine()
+        twin.undefine()
+
+
+def test_amr_solve_dev_equals_amr_solve_host(oracle, torch):
+    """the two-level hierarchy of test_gpu_amr.py, l_base = 1: phi[0] feeds the coarse-fine values and is not written"""
+    from helpers import make_amr_levels, make_gpu_amr
+    from oracle import somar_amr as am
+    so = oracle
+    ratios = [(2, 2, 2)]
+    fb = [[so.Box((8, 8, 4), (23, 23, 11))]]
+    levels = make_amr_levels(so, am, (16, 16, 8), (2.0, 1.0, 0.5), (False, False, False), ratios, fb)
+    gpu = make_gpu_amr(levels, ratios)
+    twin = make_gpu_amr(levels, ratios)   # the same life for both, see test_solve_dev_equals_solve_host
+    try:
+        coarse = so.random_field(levels[0].grids, 11, (1, 1, 1), levels[0].domain.box)
+        rhs1 = so.random_field(levels[1].grids, 12, (0, 0, 0), levels[1].domain.box)
+        v0, v1 = gpu.levels
+        hc = [np.asfortranarray(coarse.fabs[v0.patch_box(p)[2]].a[..., 0]) for p in range(v0.num_local_patches)]
+        hr = [np.asfortranarray(rhs1.fabs[v1.patch_box(p)[2]].a[..., 0]) for p in range(v1.num_local_patches)]
+        shp1 = [_shape(v1, p, (1, 1, 1)) for p in range(v1.num_local_patches)]
+        hphi1 = [np.zeros(sh, order="F") for sh in shp1]
+        hc_in = [a.copy(order="F") for a in hc]
+        st_h = dict(gpu.solveAMRHost([hc_in, hphi1], [None, hr], 1, 1))
+        dc = [_to_dev(torch, a) for a in hc]
+        dphi1 = [torch.zeros(int(np.prod(sh)), dtype=torch.float64, device="cuda") for sh in shp1]
+        dr = [_to_dev(torch, a) for a in hr]
+        st_d = dict(twin.solveAMRDev([dc, dphi1], [None, dr], 1, 1))
+        _same_stats(st_h, st_d)
+        for p in range(len(shp1)):
+            assert hphi1[p].any()
+            np.testing.assert_array_equal(_to_host(dphi1[p], shp1[p]), hphi1[p])
+        for p in range(len(hc)):
+            np.testing.assert_array_equal(_to_host(dc[p], hc[p].shape), hc[p])
+            np.testing.assert_array_equal(hc_in[p], hc[p])
+    finally:
+        gpu.undefine()
+        twin.undefine()
+
+
+def _face_velocity(s, n):
+    """smooth, identical on faces shared by two boxes, zero normal flux on the walls"""
+    vel = [[], [], []]
+    for p in range(s.num_local_patches):
+        lo, hi, _ = s.patch_box(p)
+        for d in range(3):
+            ax = [np.arange(lo[a], hi[a] + 1 + (1 if a == d else 0)) for a in range(3)]
+            I, J, K = np.meshgrid(*ax, indexing="ij")
+            v = (np.sin(2 * np.pi * I / n[0] + 0.1 * d) * np.cos(2 * np.pi * J / n[1]) * np.cos(2 * np.pi * K / n[2] + d))
+            idx = [I, J, K][d]
+            vel[d].append(np.asfortranarray(np.where((idx == 0) | (idx == n[d]), 0.0, v)))
+    return vel
+
+
+def test_mac_project_dev_equals_mac_project_host(torch):
+    n = (16, 16, 16)
+    s, twin = (_solver(n, _cut([0, 8, 16], [0, 8, 16], 16)) for _ in range(2))   # the same life for both
+    try:
+        vel = _face_velocity(s, n)
+        hvel = [[a.copy(order="F") for a in vel[d]] for d in range(3)]
+        st_h = dict(s.levelProject(hvel, 0.5))
+        dvel = [[_to_dev(torch, a) for a in vel[d]] for d in range(3)]
+        st_d = dict(twin.levelProjectDev(dvel, 0.5))
+        _same_stats(st_h, st_d)
+        for d in range(3):
+            for p in range(s.num_local_patches):
+                assert not np.array_equal(hvel[d][p], vel[d][p])
+                np.testing.assert_array_equal(_to_host(dvel[d][p], vel[d][p].shape), hvel[d][p])
+    finally:
+        s.undefine()
+        twin.undefine()
+
+
+def test_cc_project_dev_equals_cc_project_host(torch):
+    n = (16, 16, 16)
+    s, twin = (_solver(n, _cut([0, 8, 16], [0, 8, 16], 16)) for _ in range(2))   # the same life for both
+    ghost = (1, 1, 1)
+    try:
+        vel = []
+        for p in range(s.num_local_patches):
+            lo, hi, _ = s.patch_box(p)
+            I, J, K = np.meshgrid(*[np.arange(lo[a] - 1, hi[a] + 2) for a in range(3)], indexing="ij")
+            a = np.zeros(I.shape + (3,), order="F")
+            for d in range(3):
+                a[..., d] = (np.sin(2 * np.pi * (I + 0.5) / n[0] + 0.1 * d) * np.cos(2 * np.pi * (J + 0.5) / n[1] + 0.3)
+                             * np.cos(2 * np.pi * (K + 0.5) / n[2] + d)) + 0.25 * d
+            vel.append(a)
+        hvel = [a.copy(order="F") for a in vel]
+        st_h = dict(s.levelProjectCC(hvel, ghost, 0.5))
+        dvel = [_to_dev(torch, a) for a in vel]
+        st_d = dict(twin.levelProjectCCDev(dvel, ghost, 0.5))
+        _same_stats(st_h, st_d)
+        for p in range(s.num_local_patches):
+            assert not np.array_equal(hvel[p], vel[p])
+            np.testing.assert_array_equal(_to_host(dvel[p], vel[p].shape), hvel[p])
+    finally:
+        s.undefine()
+        twin.undefine()
+
+
+def test_refusals_launch_nothing(torch):
+    """a host pointer, a NULL table, a ghost wider than the frame (the library), and tensors of the wrong size, dtype or
+    device (the binding): each is an error, and the field still holds the sentinel afterwards"""
+    from somar_amd import SomarError, lib
+    from somar_amd import api as F
+    n, boxes, ndim = LAYOUTS["unequal"]
+    s = _solver(n, boxes, ndim)
+    try:
+        npatch = s.num_local_patches
+        s.setVal(F.F_PHI, SENTINEL)
+        good = [_to_dev(torch, _values(_shape(s, p), p + 1)) for p in range(npatch)]
+        g0 = (C.c_int * 3)(0, 0, 0)
+
+        def table(ptrs):
+            return (C.c_void_p * npatch)(*ptrs)
+
+        # a numpy (host) pointer in the table, after valid entries
+        host = np.zeros(_shape(s, 3), order="F")
+        ptrs = [t.data_ptr() for t in good]
+        ptrs[3] = host.ctypes.data
+        for fn in (lib().somar_field_upload_dev, lib().somar_field_download_dev):
+            assert fn(s._h, F.F_PHI, table(ptrs), g0) != 0
+            msg = lib().somar_last_error().decode()
+            assert "not a device pointer" in msg and "patch 3" in msg, msg
+        assert not host.any()
+        # the library still works after the refused pointer (no sticky HIP error)
+        s.sync()
+        # a NULL table
+        assert lib().somar_field_upload_dev(s._h, F.F_PHI, None, g0) != 0
+        assert lib().somar_vel_upload_dev(s._h, 0, None) != 0
+        st = F.Stats()
+        assert lib().somar_solver_solve_dev(s._h, None, g0, table([t.data_ptr() for t in good]), g0, 1, 0, C.byref(st)) != 0
+        # a ghost wider than the frame
+        wide = [torch.zeros(int(np.prod(_shape(s, p, (3, 3, 3)))), dtype=torch.float64, device="cuda") for p in range(npatch)]
+        with pytest.raises(SomarError, match="ghost wider"):
+            s.uploadDev(F.F_PHI, wide, (3, 3, 3))
+        with pytest.raises(SomarError, match="ghost wider"):
+            s.downloadDev(F.F_PHI, wide, (3, 3, 3))
+        # the binding: numel, dtype, device, contiguity, list length
+        bad = list(good)
+        bad[2] = torch.zeros(good[2].numel() + 1, dtype=torch.float64, device="cuda")
+        with pytest.raises(SomarError, match="elements"):
+            s.uploadDev(F.F_PHI, bad, (0, 0, 0))
+        bad[2] = good[2].to(torch.float32)
+        with pytest.raises(SomarError, match="float64"):
+            s.uploadDev(F.F_PHI, bad, (0, 0, 0))
+        bad[2] = good[2].cpu()
+        with pytest.raises(SomarError, match="lives on"):
+            s.uploadDev(F.F_PHI, bad, (0, 0, 0))
+        bad[2] = torch.zeros(2 * good[2].numel(), dtype=torch.float64, device="cuda")[::2]
+        with pytest.raises(SomarError, match="contiguous"):
+            s.uploadDev(F.F_PHI, bad, (0, 0, 0))
+        with pytest.raises(SomarError, match="one per local patch"):
+            s.uploadDev(F.F_PHI, good[:-1], (0, 0, 0))
+        # nothing was launched: every cell of every patch still holds the sentinel
+        for p in range(npatch):
+            assert np.all(s.download(F.F_PHI, p, (2, 2, 2)) == SENTINEL)
+        # and a good call still goes through
+        s.uploadDev(F.F_PHI, good, (0, 0, 0))
+        np.testing.assert_array_equal(s.download(F.F_PHI, 3, (0, 0, 0)), _values(_shape(s, 3), 4))
+    finally:
+        s.undefine()
+
+
+def test_no_device_memory_left_behind(torch):
+    from somar_amd import api as F
+    from somar_amd import lib
+
+    def live():
+        b = C.c_longlong()
+        assert lib().somar_device_bytes_live(C.byref(b)) == 0
+        return b.value
+
+    before = live()
+    n, boxes, ndim = LAYOUTS["unequal"]
+    s = _solver(n, boxes, ndim)
+    base = live()
+    tens = [_to_dev(torch, _values(_shape(s, p, (1, 1, 1)), p + 1)) for p in range(s.num_local_patches)]
+    s.uploadDev(F.F_PHI, tens, (1, 1, 1))
+    first = live()
+    assert first > base   # the item table of this (level, kind, ghost) ...
+    s.uploadDev(F.F_PHI, tens, (1, 1, 1))
+    s.downloadDev(F.F_RHS, tens, (1, 1, 1))
+    assert live() == first   # ... is built once and serves every later call of that shape, either way
+    s.uploadVelDev(1, [_to_dev(torch, _values(_shape(s, p, face=1), p)) for p in range(s.num_local_patches)])
+    s.undefine()
+    assert live() == before

@@ -186,7 +186,8 @@ int somar_solver_metric_uniform(somar_solver_t* s, int depth, int* flag, double*
 int somar_solver_level_info(somar_solver_t* s, int depth, int* domain6, double* dx3, long long* cells,
                             long long* field_elems);
 
-/* host <-> HBM, one local patch; host array spans valid.grow(ghost). */
+/* host <-> HBM, one local patch; host array spans valid.grow(ghost), ghost 0..2 per direction (the device frame).  A NULL
+ * host pointer or a patch index outside 0 .. num_local_patches - 1 is an error. */
 int somar_field_upload(somar_solver_t* s, int field, int patch, const double* host, const int* ghost);
 int somar_field_download(somar_solver_t* s, int field, int patch, double* host, const int* ghost);
 int somar_field_set(somar_solver_t* s, int field, double value);
@@ -199,7 +200,12 @@ int somar_field_dot(somar_solver_t* s, int field_a, int field_b, double* out);
 
 /* the solve on resident PHI/RHS */
 int somar_solver_solve(somar_solver_t* s, int zero_phi, int force_homogeneous, somar_stats_t* stats);
-/* AMREllipticSolver::solve on caller-owned host LevelData (one pointer per local patch). */
+/* AMREllipticSolver::solve on caller-owned host LevelData (one pointer per local patch).  The rules are those of every call
+ * on caller arrays, in host or device memory (the *_dev calls below): (1) every table and ghost width is checked before
+ * anything is uploaded or solved -- a phi_ghost wider than the device frame (2) is refused with nothing changed; (2) only
+ * the valid cells of rhs move, so rhs_ghost is not bounded by the frame; (3) a NULL table entry skips its patch, whose
+ * resident values stay as they are.  The same holds for somar_amr_solve_host, somar_mac_project_host and
+ * somar_cc_project_host (whose velocity comes back over the valid cells only). */
 int somar_solver_solve_host(somar_solver_t* s, double* const* phi, const int* phi_ghost,
                             const double* const* rhs, const int* rhs_ghost, int l_max, int l_base,
                             int zero_phi, int force_homogeneous, somar_stats_t* stats);
@@ -476,10 +482,12 @@ int somar_amr_set_inspector(somar_amr_t* a, somar_inspector_fn fn, void* user);
  * dev / phi / rhs / u0.. / vel: a HOST array of one DEVICE pointer per local patch of the level, in local-patch order; each
  * points to the Fortran-order fp64 array the host call of the same name takes for that patch (over valid.grow(ghost), over
  * faces(valid, dir) without ghosts, or space_dim components over valid.grow(ghost), component slowest).  A NULL entry skips
- * its patch: nothing of it is read or written.  ghost: 0..2 per direction (the device frame).  The regions moved are the
- * host calls': somar_field_*_dev the whole array, frame cells outside it untouched; a solve's rhs and phi go up over the
- * valid cells and phi comes back over valid.grow(phi_ghost); the cell-centred velocity goes up with one ghost layer and
- * comes back over the valid cells.  All local patches of a level move in ONE kernel launch per call and direction.
+ * its patch: nothing of it is read or written.  The regions moved are the host calls' -- host and device memory share one
+ * description of them: somar_field_*_dev the whole array, frame cells outside it untouched; a solve's rhs and phi go up
+ * over the valid cells and phi comes back over valid.grow(phi_ghost); the cell-centred velocity goes up with one ghost layer
+ * and comes back over the valid cells.  Only the region moved has to fit the device frame (2 cells): the ghost of a field
+ * transfer and phi_ghost are 0..2 per direction, rhs_ghost and the velocity's ghost are not bounded.  All local patches of a
+ * level move in ONE kernel launch per call and direction.
  * Every pointer of a call is checked before anything is launched (hipPointerGetAttributes): plain device memory on the
  * solver's device, and -- where the runtime knows the allocation's extent -- large enough for its array; otherwise the call
  * fails, naming the patch ("... is not a device pointer ..."), and nothing has run.  Managed and host-registered memory

@@ -267,6 +267,11 @@ def _dp(a):
     return a.ctypes.data_as(_PD)
 
 
+def _dp_or_null(a):
+    """an entry of a per-patch table: None is a NULL entry, which skips its patch"""
+    return None if a is None else _dp(a)
+
+
 class AMRPressureSolver:
     """Mirror of projection/AMRPressureSolver.H.  Boxes are (lo, hi) integer 3-tuples; host FABs are
     Fortran-ordered numpy arrays over valid.grow(ghost)."""
@@ -666,11 +671,12 @@ class AMRPressureSolver:
     # -- solve (AMRPressureSolver::solve, projection/AMRPressureSolver.cpp:494-561) -----------------------
     def solve(self, phi, rhs, lmin=0, lmax=0, zeroPhi=True, forceHomogeneous=False, phi_ghost=(1, 1, 1),
               rhs_ghost=(0, 0, 0)):
-        """phi, rhs: lists (one per local patch) of Fortran-ordered float64 arrays; phi is updated in place."""
+        """phi, rhs: lists (one per local patch) of Fortran-ordered float64 arrays; phi is updated in place.  None skips a
+        patch: its resident values stay as they are."""
         n = self.num_local_patches
         assert len(phi) == n and len(rhs) == n
-        P = (_PD * n)(*[_dp(a) for a in phi])
-        R = (_PD * n)(*[_dp(a) for a in rhs])
+        P = (_PD * n)(*[_dp_or_null(a) for a in phi])
+        R = (_PD * n)(*[_dp_or_null(a) for a in rhs])
         st = Stats()
         # note the reference's call order solve(phi, rhs, a_lmax, a_lmin, ...) (AMRPressureSolver.cpp:529-534)
         _ck(lib().somar_solver_solve_host(self._h, P, _ia(phi_ghost), R, _ia(rhs_ghost), lmax, lmin, int(zeroPhi),
@@ -798,9 +804,10 @@ class AMRPressureSolver:
         _ck(lib().somar_level_mac_correct(self._h, phi_field, float(dt)))
 
     def levelProject(self, vel, dt, zeroPressure=True, forceHomogeneous=False):
-        """vel: [u0, u1, u2], each a list (per local patch) of F-ordered face arrays; projected in place."""
+        """vel: [u0, u1, u2], each a list (per local patch) of F-ordered face arrays; projected in place.  None skips a
+        patch: its resident values stay as they are."""
         n = self.num_local_patches
-        U = [( _PD * n)(*[_dp(a) for a in vel[d]]) for d in range(3)]
+        U = [( _PD * n)(*[_dp_or_null(a) for a in vel[d]]) for d in range(3)]
         st = Stats()
         _ck(lib().somar_mac_project_host(self._h, U[0], U[1], U[2], float(dt), int(zeroPressure),
                                          int(forceHomogeneous), C.byref(st)))

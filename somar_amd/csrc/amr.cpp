@@ -1362,27 +1362,27 @@ void AMRSolver::solve(int l_max, int l_base, bool zeroPhi, bool forceHomogeneous
     solve_impl(l_max, l_base, zeroPhi, forceHomogeneous, s);
 }
 
-void AMRSolver::solve_dev(double* const* const* phi, const int phi_ghost[3], const double* const* const* rhs,
-                          const int rhs_ghost[3], int l_max, int l_base, bool zeroPhi, bool forceHomogeneous, SolveStats& s)
+void AMRSolver::solve_on(PressureSolver::Mem where, double* const* const* phi, const int phi_ghost[3], const double* const* const* rhs,
+                         const int rhs_ghost[3], int l_max, int l_base, bool zeroPhi, bool forceHomogeneous, SolveStats& s)
 {
     SOMAR_CHECK(phi && rhs && phi_ghost && rhs_ghost, "null pointer");
     SOMAR_CHECK(0 <= l_base && l_base <= l_max && l_max < nlevels(), "bad level range");
     for (int l = l_base; l <= l_max; ++l) SOMAR_CHECK(phi[l] && rhs[l], "phi / rhs of a solved level is null");
     if (l_base > 0) SOMAR_CHECK(phi[l_base - 1], "phi of level l_base - 1 supplies the coarse-fine values and must be given");
     const int l0 = l_base > 0 ? l_base - 1 : 0;
-    for (int l = l0; l <= l_max; ++l) {   // every pointer, before the first launch
-        Level& L = level(l).level(0);
+    for (int l = l0; l <= l_max; ++l) {   // every table, shape and pointer, before anything moves
+        PressureSolver& ps = level(l);
         const std::string at = "[" + std::to_string(l) + "]";
-        L.check_dev_ptrs(phi[l], BoxIoShape::cells(phi_ghost, true), ("phi" + at).c_str());
-        if (l >= l_base) L.check_dev_ptrs(rhs[l], BoxIoShape::cells(rhs_ghost, false), ("rhs" + at).c_str());
+        ps.check_table(where, ps.io_field(ps.phi(), 0, phi_ghost, true), phi[l], ("phi" + at).c_str());
+        if (l >= l_base) ps.check_table(where, ps.io_field(ps.rhs(), 0, rhs_ghost, false), rhs[l], ("rhs" + at).c_str());
     }
     for (int l = l0; l <= l_max; ++l) {
         PressureSolver& ps = level(l);
-        if (l >= l_base) ps.upload_field_dev(ps.rhs(), 0, rhs[l], rhs_ghost, false, true);
-        if (l < l_base || !zeroPhi) ps.upload_field_dev(ps.phi(), 0, phi[l], phi_ghost, false, true);
+        if (l >= l_base) ps.move_table(where, ps.io_field(ps.rhs(), 0, rhs_ghost, false), const_cast<double* const*>(rhs[l]), true);
+        if (l < l_base || !zeroPhi) ps.move_table(where, ps.io_field(ps.phi(), 0, phi_ghost, false), phi[l], true);
     }
     solve(l_max, l_base, zeroPhi, forceHomogeneous, s);
-    for (int l = l_base; l <= l_max; ++l) level(l).download_field_dev(level(l).phi(), 0, phi[l], phi_ghost, true);
+    for (int l = l_base; l <= l_max; ++l) level(l).move_table(where, level(l).io_field(level(l).phi(), 0, phi_ghost, true), phi[l], false);
 }
 
 void AMRSolver::solve_leptic(int l_max, int l_base, bool zeroPhi, bool forceHomogeneous, SolveStats& s)

@@ -157,11 +157,12 @@ public:
     // MappedAMRMultiGrid::solve on the resident phi/rhs of levels l_base..l_max (phi of l_base-1 supplies the
     // CF values when l_base > 0)
     void solve(int l_max, int l_base, bool zeroPhi, bool forceHomogeneous, SolveStats& st);
-    // the same on caller arrays in DEVICE memory: phi[l] / rhs[l] = HOST arrays of one device pointer per local patch of level
-    // l (PressureSolver::upload_field_dev).  Levels, regions and results as somar_amr_solve_host; every pointer is checked
-    // before the first launch.
-    void solve_dev(double* const* const* phi, const int phi_ghost[3], const double* const* const* rhs, const int rhs_ghost[3],
-                   int l_max, int l_base, bool zeroPhi, bool forceHomogeneous, SolveStats& st);
+    // the same on caller arrays, in host or device memory: phi[l] / rhs[l] = HOST arrays of one pointer per local patch of
+    // level l (a null entry skips its patch).  rhs moves on levels l_base..l_max, phi goes up there unless zeroPhi and always
+    // on l_base - 1, and comes back on l_base..l_max.  Every level range, table, shape and (device memory) pointer is checked
+    // before anything moves (PressureSolver::check_table).
+    void solve_on(PressureSolver::Mem where, double* const* const* phi, const int phi_ghost[3], const double* const* const* rhs,
+                  const int rhs_ghost[3], int l_max, int l_base, bool zeroPhi, bool forceHomogeneous, SolveStats& st);
     // AMRLepticSolver (calculus/LepticSolver/AMRLepticSolver.cpp): the same composite iteration with LevelLepticSolver::solve
     // in place of relax / the base level's multigrid cycle.  enable_leptic (after finalize) builds one leptic level solver per
     // level on the level's own operator (init, :185-195).  baseFromRestricted = false is the reference: the base level solves

@@ -493,13 +493,8 @@ int somar_field_upload(somar_solver_t* s, int field, int patch, const double* ho
     API_BEGIN
     int depth;
     double* f = field_ptr(s, field, &depth);
-    Level& L = s->ps->level(depth);
-    SOMAR_CHECK(patch >= 0 && patch < L.npatches() && host && ghost, "bad patch / null pointer");
-    for (int d = 0; d < 3; ++d) SOMAR_CHECK(ghost[d] >= 0 && ghost[d] <= FRAME, "ghost wider than device frame");
-    const IBox valid = L.boxes[L.local[patch]];
-    const IBox hb = valid.grow(ghost);
-    L.upload(f, patch, host, hb, hb, s->ps->stream());
-    s->ps->sync();
+    SOMAR_CHECK(host && ghost, "null pointer");
+    s->ps->upload(s->ps->io_field(f, depth, ghost, true), patch, host);
     API_END
 }
 
@@ -509,7 +504,7 @@ int somar_field_download(somar_solver_t* s, int field, int patch, double* host, 
     int depth;
     double* f = field_ptr(s, field, &depth);
     SOMAR_CHECK(host && ghost, "null pointer");
-    s->ps->download_field(f, depth, patch, host, ghost);
+    s->ps->download(s->ps->io_field(f, depth, ghost, true), patch, host);
     API_END
 }
 
@@ -603,15 +598,8 @@ int somar_solver_solve_host(somar_solver_t* s, double* const* phi, const int* ph
     API_BEGIN
     SOMAR_CHECK(l_max == 0 && l_base == 0, "a somar_solver_t is ONE level (l_max = l_base = 0); hierarchies go through somar_amr_solve_host");
     SOMAR_CHECK(phi && rhs && phi_ghost && rhs_ghost, "null pointer");
-    PressureSolver& ps = *s->ps;
-    const int np = ps.level(0).npatches();
-    for (int p = 0; p < np; ++p) {
-        ps.upload_rhs(p, rhs[p], rhs_ghost);
-        if (!zero_phi) ps.upload_phi(p, phi[p], phi_ghost);
-    }
     SolveStats st;
-    ps.solve(zero_phi != 0, force_homogeneous != 0, st);
-    for (int p = 0; p < np; ++p) ps.download_phi(p, phi[p], phi_ghost);
+    s->ps->solve_on(PressureSolver::Mem::Host, phi, phi_ghost, rhs, rhs_ghost, zero_phi != 0, force_homogeneous != 0, st);
     fill_stats(st, stats);
     API_END
 }
@@ -806,7 +794,7 @@ int somar_vel_upload(somar_solver_t* s, int dir, int patch, const double* host)
 {
     API_BEGIN
     SOMAR_CHECK(host, "null pointer");
-    s->ps->upload_vel(dir, patch, host);
+    s->ps->upload(s->ps->io_vel(dir), patch, host);
     API_END
 }
 
@@ -814,7 +802,7 @@ int somar_vel_download(somar_solver_t* s, int dir, int patch, double* host)
 {
     API_BEGIN
     SOMAR_CHECK(host, "null pointer");
-    s->ps->download_vel(dir, patch, host);
+    s->ps->download(s->ps->io_vel(dir), patch, host);
     API_END
 }
 
@@ -867,15 +855,9 @@ int somar_mac_project_host(somar_solver_t* s, double* const* u0, double* const* 
 {
     API_BEGIN
     SOMAR_CHECK(u0 && u1 && u2, "null pointer");
-    PressureSolver& ps = *s->ps;
-    const int np = ps.level(0).npatches();
-    double* const* u[3] = {u0, u1, u2};
-    for (int p = 0; p < np; ++p)
-        for (int d = 0; d < 3; ++d) ps.upload_vel(d, p, u[d][p]);
+    double* const* const u[3] = {u0, u1, u2};
     SolveStats st;
-    ps.mac_project(dt, zero_pressure != 0, force_homogeneous != 0, st);
-    for (int p = 0; p < np; ++p)
-        for (int d = 0; d < 3; ++d) ps.download_vel(d, p, u[d][p]);
+    s->ps->mac_project_on(PressureSolver::Mem::Host, u, dt, zero_pressure != 0, force_homogeneous != 0, st);
     fill_stats(st, stats);
     API_END
 }
@@ -900,7 +882,7 @@ int somar_ccvel_upload(somar_solver_t* s, int patch, const double* host, const i
 {
     API_BEGIN
     SOMAR_CHECK(host && ghost, "null pointer");
-    s->ps->upload_cc_vel(patch, host, ghost);
+    s->ps->upload(s->ps->io_cc_vel(ghost, true), patch, host);
     API_END
 }
 
@@ -908,7 +890,7 @@ int somar_ccvel_download(somar_solver_t* s, int patch, double* host, const int* 
 {
     API_BEGIN
     SOMAR_CHECK(host && ghost, "null pointer");
-    s->ps->download_cc_vel(patch, host, ghost);
+    s->ps->download(s->ps->io_cc_vel(ghost, false), patch, host);
     API_END
 }
 
@@ -947,12 +929,8 @@ int somar_cc_project_host(somar_solver_t* s, double* const* vel, const int* ghos
 {
     API_BEGIN
     SOMAR_CHECK(vel && ghost, "null pointer");
-    PressureSolver& ps = *s->ps;
-    const int np = ps.level(0).npatches();
-    for (int p = 0; p < np; ++p) ps.upload_cc_vel(p, vel[p], ghost);
     SolveStats st;
-    ps.cc_project(dt, zero_pressure != 0, force_homogeneous != 0, wall_bc != 0, st);
-    for (int p = 0; p < np; ++p) ps.download_cc_vel(p, vel[p], ghost);
+    s->ps->cc_project_on(PressureSolver::Mem::Host, vel, ghost, dt, zero_pressure != 0, force_homogeneous != 0, wall_bc != 0, st);
     fill_stats(st, stats);
     API_END
 }
@@ -1133,38 +1111,20 @@ int somar_amr_solve_host(somar_amr_t* a, double* const* const* phi, const int* p
                          somar_stats_t* stats)
 {
     API_BEGIN
-    AMRSolver& A = *a->amr;
-    SOMAR_CHECK(phi && rhs && phi_ghost && rhs_ghost, "null pointer");
-    SOMAR_CHECK(0 <= l_base && l_base <= l_max && l_max < A.nlevels(), "bad level range");
-    for (int l = l_base; l <= l_max; ++l) SOMAR_CHECK(phi[l] && rhs[l], "phi / rhs of a solved level is null");
-    if (l_base > 0) SOMAR_CHECK(phi[l_base - 1], "phi of level l_base - 1 supplies the coarse-fine values and must be given");
-    for (int l = (l_base > 0 ? l_base - 1 : 0); l <= l_max; ++l) {
-        PressureSolver& ps = A.level(l);
-        const int np = ps.level(0).npatches();
-        for (int p = 0; p < np; ++p) {
-            if (l >= l_base) ps.upload_rhs(p, rhs[l][p], rhs_ghost);
-            if (l < l_base || !zero_phi) ps.upload_phi(p, phi[l][p], phi_ghost);
-        }
-    }
     SolveStats st;
-    A.solve(l_max, l_base, zero_phi != 0, force_homogeneous != 0, st);
-    for (int l = l_base; l <= l_max; ++l) {
-        PressureSolver& ps = A.level(l);
-        const int np = ps.level(0).npatches();
-        for (int p = 0; p < np; ++p) ps.download_phi(p, phi[l][p], phi_ghost);
-    }
+    a->amr->solve_on(PressureSolver::Mem::Host, phi, phi_ghost, rhs, rhs_ghost, l_max, l_base, zero_phi != 0, force_homogeneous != 0, st);
     fill_stats(st, stats);
     API_END
 }
 
-// ---- caller arrays in device memory: the *_host / per-patch calls above with the copies replaced by one launch per level ----
+// ---- caller arrays in device memory: a table of one device pointer per local patch, one launch per level array group ----
 int somar_field_upload_dev(somar_solver_t* s, int field, const double* const* dev, const int* ghost)
 {
     API_BEGIN
     int depth;
     double* f = field_ptr(s, field, &depth);
     SOMAR_CHECK(dev && ghost, "null pointer");
-    s->ps->upload_field_dev(f, depth, dev, ghost, true);
+    s->ps->move_dev(s->ps->io_field(f, depth, ghost, true), const_cast<double* const*>(dev), true);
     API_END
 }
 
@@ -1174,7 +1134,7 @@ int somar_field_download_dev(somar_solver_t* s, int field, double* const* dev, c
     int depth;
     double* f = field_ptr(s, field, &depth);
     SOMAR_CHECK(dev && ghost, "null pointer");
-    s->ps->download_field_dev(f, depth, dev, ghost);
+    s->ps->move_dev(s->ps->io_field(f, depth, ghost, true), dev, false);
     API_END
 }
 
@@ -1182,7 +1142,7 @@ int somar_vel_upload_dev(somar_solver_t* s, int dir, const double* const* dev)
 {
     API_BEGIN
     SOMAR_CHECK(dev, "null pointer");
-    s->ps->upload_vel_dev(dir, dev);
+    s->ps->move_dev(s->ps->io_vel(dir), const_cast<double* const*>(dev), true);
     API_END
 }
 
@@ -1190,7 +1150,7 @@ int somar_vel_download_dev(somar_solver_t* s, int dir, double* const* dev)
 {
     API_BEGIN
     SOMAR_CHECK(dev, "null pointer");
-    s->ps->download_vel_dev(dir, dev);
+    s->ps->move_dev(s->ps->io_vel(dir), dev, false);
     API_END
 }
 
@@ -1198,7 +1158,7 @@ int somar_ccvel_upload_dev(somar_solver_t* s, const double* const* dev, const in
 {
     API_BEGIN
     SOMAR_CHECK(dev && ghost, "null pointer");
-    s->ps->upload_cc_vel_dev(dev, ghost);
+    s->ps->move_dev(s->ps->io_cc_vel(ghost, true), const_cast<double* const*>(dev), true);
     API_END
 }
 
@@ -1206,7 +1166,7 @@ int somar_ccvel_download_dev(somar_solver_t* s, double* const* dev, const int* g
 {
     API_BEGIN
     SOMAR_CHECK(dev && ghost, "null pointer");
-    s->ps->download_cc_vel_dev(dev, ghost);
+    s->ps->move_dev(s->ps->io_cc_vel(ghost, false), dev, false);
     API_END
 }
 
@@ -1216,7 +1176,7 @@ int somar_solver_solve_dev(somar_solver_t* s, double* const* phi, const int* phi
     API_BEGIN
     SOMAR_CHECK(phi && rhs && phi_ghost && rhs_ghost, "null pointer");
     SolveStats st;
-    s->ps->solve_dev(phi, phi_ghost, rhs, rhs_ghost, zero_phi != 0, force_homogeneous != 0, st);
+    s->ps->solve_on(PressureSolver::Mem::Device, phi, phi_ghost, rhs, rhs_ghost, zero_phi != 0, force_homogeneous != 0, st);
     fill_stats(st, stats);
     API_END
 }
@@ -1227,7 +1187,7 @@ int somar_amr_solve_dev(somar_amr_t* a, double* const* const* phi, const int* ph
 {
     API_BEGIN
     SolveStats st;
-    a->amr->solve_dev(phi, phi_ghost, rhs, rhs_ghost, l_max, l_base, zero_phi != 0, force_homogeneous != 0, st);
+    a->amr->solve_on(PressureSolver::Mem::Device, phi, phi_ghost, rhs, rhs_ghost, l_max, l_base, zero_phi != 0, force_homogeneous != 0, st);
     fill_stats(st, stats);
     API_END
 }
@@ -1238,7 +1198,7 @@ int somar_mac_project_dev(somar_solver_t* s, double* const* u0, double* const* u
     API_BEGIN
     double* const* const u[3] = {u0, u1, u2};
     SolveStats st;
-    s->ps->mac_project_dev(u, dt, zero_pressure != 0, force_homogeneous != 0, st);
+    s->ps->mac_project_on(PressureSolver::Mem::Device, u, dt, zero_pressure != 0, force_homogeneous != 0, st);
     fill_stats(st, stats);
     API_END
 }
@@ -1249,7 +1209,7 @@ int somar_cc_project_dev(somar_solver_t* s, double* const* vel, const int* ghost
     API_BEGIN
     SOMAR_CHECK(vel && ghost, "null pointer");
     SolveStats st;
-    s->ps->cc_project_dev(vel, ghost, dt, zero_pressure != 0, force_homogeneous != 0, wall_bc != 0, st);
+    s->ps->cc_project_on(PressureSolver::Mem::Device, vel, ghost, dt, zero_pressure != 0, force_homogeneous != 0, wall_bc != 0, st);
     fill_stats(st, stats);
     API_END
 }
@@ -1445,8 +1405,8 @@ int somar_solver_set_cc_j(somar_solver_t* s, int patch, const double* J, const d
 {
     API_BEGIN
     SOMAR_CHECK(J && Jinv && ghost, "null pointer");
-    s->ps->set_scale_cc(0, patch, J, ghost);
-    s->ps->set_scale_cc(1, patch, Jinv, ghost);
+    s->ps->upload(s->ps->io_scale_cc(0, ghost), patch, J);
+    s->ps->upload(s->ps->io_scale_cc(1, ghost), patch, Jinv);
     API_END
 }
 
@@ -1454,8 +1414,8 @@ int somar_solver_set_face_j(somar_solver_t* s, int dir, int patch, const double*
 {
     API_BEGIN
     SOMAR_CHECK(J && Jinv, "null pointer");
-    s->ps->set_scale_face(0, dir, patch, J);
-    s->ps->set_scale_face(1, dir, patch, Jinv);
+    s->ps->upload(s->ps->io_scale_face(0, dir), patch, J);
+    s->ps->upload(s->ps->io_scale_face(1, dir), patch, Jinv);
     API_END
 }
 
@@ -1719,7 +1679,7 @@ int somar_solver_metric_download(somar_solver_t* s, int depth, int which, int pa
 {
     API_BEGIN
     SOMAR_CHECK(s && s->ps && host, "null argument");
-    s->ps->metric_download(depth, which, patch, host);
+    s->ps->download(s->ps->io_metric(depth, which, false), patch, host);
     API_END
 }
 
@@ -1844,7 +1804,7 @@ int somar_heat_flux_download(somar_solver_t* s, int dir, int patch, double* host
 {
     API_BEGIN
     SOMAR_CHECK(s && host, "null pointer");
-    s->ps->download_heat_flux(dir, patch, host);
+    s->ps->download(s->ps->io_heat_flux(dir), patch, host);
     API_END
 }
 

@@ -1020,21 +1020,43 @@ void Level::download(const double* field, int patch, double* host, const IBox& h
            region.lo[2] - p.lo[2] + FRAME, n, hipMemcpyDeviceToHost, st);
 }
 
-// ---- caller arrays in device memory (box_io.hip) -------------------------------------------------------------------
-IBox Level::io_caller_box(int patch, const BoxIoShape& s) const
+// ---- caller arrays by shape: host memory (copy3d), device memory (box_io.hip) ----------------------------------------
+BoxIoBoxes Level::io_boxes(int patch, const BoxIoShape& s) const
 {
-    IBox b = boxes[local[patch]];
-    if (s.face >= 0) { b.hi[s.face] += 1; return b; }
-    return b.grow(s.ghost);
+    const IBox& valid = boxes[local[patch]];
+    BoxIoBoxes b;
+    if (s.face >= 0) {
+        b.caller = valid;
+        b.caller.hi[s.face] += 1;
+        b.region = b.caller;
+    } else {
+        b.caller = valid.grow(s.ghost);
+        b.region = valid.grow(s.grow);
+    }
+    return b;
 }
 
-static void check_shape(const BoxIoShape& s)
+void check_shape(const BoxIoShape& s)
 {
     SOMAR_CHECK(s.face >= -1 && s.face < 3 && s.ncomp >= 1 && s.ncomp <= 3, "box I/O: bad face direction / component count");
     for (int d = 0; d < 3; ++d) {
-        SOMAR_CHECK(s.ghost[d] >= 0 && s.ghost[d] <= FRAME, "ghost wider than device frame");
         SOMAR_CHECK(s.grow[d] >= 0 && s.grow[d] <= s.ghost[d], "box I/O: region outside the caller's box");
+        SOMAR_CHECK(s.grow[d] <= FRAME, "ghost wider than device frame");
         SOMAR_CHECK(s.face < 0 || s.ghost[d] == 0, "box I/O: face arrays carry no ghosts");
+    }
+}
+
+void Level::move_host(double* const field[3], int patch, double* host, const BoxIoShape& s, bool to_level, hipStream_t st) const
+{
+    check_shape(s);
+    SOMAR_CHECK(patch >= 0 && patch < npatches(), "bad patch index: patch out of range");
+    SOMAR_CHECK(host != nullptr, "null pointer");
+    const BoxIoBoxes b = io_boxes(patch, s);
+    for (int c = 0; c < s.ncomp; ++c) {
+        SOMAR_CHECK(field[c] != nullptr, "box I/O: no such level array");
+        double* h = host + (long long)c * b.caller.numPts();
+        if (to_level) upload(field[c], patch, h, b.caller, b.region, st);
+        else download(field[c], patch, h, b.caller, b.region, st);
     }
 }
 
@@ -1058,7 +1080,7 @@ void Level::check_dev_ptrs(const double* const* dev, const BoxIoShape& s, const 
         void* base = nullptr;
         size_t size = 0;
         if (hipMemGetAddressRange(&base, &size, const_cast<double*>(dev[p])) != hipSuccess) { (void)hipGetLastError(); continue; }
-        const size_t need = (size_t)io_caller_box(p, s).numPts() * s.ncomp * sizeof(double);
+        const size_t need = (size_t)io_boxes(p, s).caller.numPts() * s.ncomp * sizeof(double);
         const size_t at = (size_t)(reinterpret_cast<const char*>(dev[p]) - static_cast<const char*>(base));
         if (at > size || need > size - at)
             throw Error(-1, std::string(what) + "[" + std::to_string(p) + "]: the allocation ends before the array of local patch " +
@@ -1075,8 +1097,8 @@ Level::BoxIoTable& Level::io_table(const BoxIoShape& s)
     long long ntiles = 0;
     for (int p = 0; p < npatches(); ++p) {
         const PatchDesc& pd = hpatches[p];
-        const IBox cb = io_caller_box(p, s);
-        const IBox region = s.face >= 0 ? cb : boxes[local[p]].grow(s.grow);
+        const BoxIoBoxes b = io_boxes(p, s);
+        const IBox &cb = b.caller, &region = b.region;
         if (region.empty()) continue;
         for (int d = 0; d < 3; ++d)
             SOMAR_CHECK(region.lo[d] - pd.lo[d] >= -FRAME && region.hi[d] - pd.lo[d] < pd.n[d] + FRAME &&

@@ -92,10 +92,13 @@ struct ExchangePlan {
 ExchangePlan build_exchange_plan(const IBox& domain, const bool periodic[3], const int ghost[3],
                                  const std::vector<IBox>& boxes, const std::vector<int>& owner, int myrank);
 
-// What one device-pointer transfer moves, per local patch (Level::upload_dev / download_dev).  The caller's array is defined
-// on valid.grow(ghost) -- or, face >= 0, on faces(valid, face) without ghosts -- with ncomp components, component slowest;
-// the region moved is valid.grow(grow) resp. the whole face box.  The host calls' regions: a field transfer grow = ghost,
-// a solve's phi / rhs upload grow = 0, the cell-centred velocity up grow = 1 in the space directions and down grow = 0.
+// What a transfer between a caller's array and a level array moves, per local patch -- the one description both movers
+// read (Level::move_host for host memory, upload_dev / download_dev for device memory).  The caller's array is defined on
+// valid.grow(ghost) -- or, face >= 0, on faces(valid, face) without ghosts -- with ncomp components, component slowest;
+// the region moved is valid.grow(grow) resp. the whole face box.  A field transfer has grow = ghost, a solve's phi / rhs
+// upload grow = 0, the cell-centred velocity up grow = 1 in the space directions and down grow = 0.
+// check_shape: 0 <= grow <= ghost, grow <= FRAME (the region has to fit the device frame; ghost itself is unbounded, the
+// caller box only sets the pitch), face arrays carry no ghosts.
 struct BoxIoShape {
     int ghost[3] = {0, 0, 0};
     int grow[3] = {0, 0, 0};
@@ -114,6 +117,8 @@ struct BoxIoShape {
     }
     static BoxIoShape faces(int dir) { BoxIoShape s; s.face = dir; return s; }
 };
+void check_shape(const BoxIoShape& s);   // throws "ghost wider than device frame" etc.
+struct BoxIoBoxes { IBox caller, region; };
 
 class Level {
 public:
@@ -238,15 +243,17 @@ public:
     // payload bytes this rank has put on the wire in the exchanges above: [0] fp64 fields, [1] fp32 fields
     mutable long long sent_bytes[2] = {0, 0};
 
-    // host<->device transfer of one patch in Chombo FRA layout.  `hostbox` is the box the host
-    // array is defined on (valid grown by the caller's ghosts, or a face box); `region` is
-    // what to move.  comp selects a component of a multi-comp host FAB.
+    // host<->device transfer of one patch in Chombo FRA layout, in box form: `hostbox` is the box the host array is
+    // defined on, `region` is what to move.  The primitive under move_host, and what callers with arbitrary FABs use.
     void upload(double* field, int patch, const double* host, const IBox& hostbox, const IBox& region,
                 hipStream_t st) const;
     void download(const double* field, int patch, double* host, const IBox& hostbox, const IBox& region,
                   hipStream_t st) const;
 
-    // The same transfers for caller arrays in DEVICE memory, every local patch (and component) in one launch (box_io.hip).
+    // Caller arrays in HOST memory: patch `patch` of the level arrays field[0 .. ncomp) from (to_level) or to `host`, by
+    // shape.  Checks the shape and the patch index, refuses a null host pointer; enqueues on st and does not drain it.
+    void move_host(double* const field[3], int patch, double* host, const BoxIoShape& shape, bool to_level, hipStream_t st) const;
+    // Caller arrays in DEVICE memory, every local patch (and component) in one launch (box_io.hip).
     // dev: HOST array of npatches() device pointers in local-patch order, a null entry skips its patch; field[c]: the level
     // array component c goes to / comes from.  Every pointer is checked before the launch (check_dev_ptrs); the item table
     // is built on the first call with a given shape and reused, only its pointer column is written per call.  The calls
@@ -269,7 +276,7 @@ private:
     };
     std::vector<std::unique_ptr<BoxIoTable>> io_tables_;
     BoxIoTable& io_table(const BoxIoShape& shape);
-    IBox io_caller_box(int patch, const BoxIoShape& shape) const;
+    BoxIoBoxes io_boxes(int patch, const BoxIoShape& shape) const;   // the one derivation of (caller box, region moved)
     void run_box_io(double* const field[3], double* const* dev, const BoxIoShape& shape, hipStream_t st, bool to_level,
                     bool checked);
 };

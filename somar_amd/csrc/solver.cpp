@@ -225,17 +225,13 @@ void PressureSolver::set_metric_ortho(int patch, const double* jg0, const double
                                       const double* jinv)
 {
     metric_written("ortho");
-    Level& L = *lev[0];
-    SOMAR_CHECK(patch >= 0 && patch < L.npatches(), "bad patch index");
-    const IBox valid = L.boxes[L.local[patch]];
-    const double* jg[3] = {jg0, jg1, jg2};
-    for (int d = 0; d < prm.spaceDim; ++d) {
-        SOMAR_CHECK(jg[d] != nullptr, "null metric array");
-        IBox fb = valid;
-        fb.hi[d] += 1;
-        L.upload(L.dev.jg[d], patch, jg[d], fb, fb, st_);
+    const double* jg[4] = {jg0, jg1, jg2, jinv};
+    for (int w = 0; w < 4; ++w) {
+        if (w < 3 && w >= prm.spaceDim) continue;
+        SOMAR_CHECK(jg[w] != nullptr, "null metric array");
+        const CallerArray a = io_metric(0, w, true);
+        a.L->move_host(a.f, patch, const_cast<double*>(jg[w]), a.shape, true, st_);
     }
-    L.upload(L.dev.jinv, patch, jinv, valid, valid, st_);
     sync();
 }
 
@@ -786,138 +782,132 @@ void PressureSolver::refresh_metric()
                 std::chrono::duration<double>(t2 - t1).count(), std::chrono::duration<double>(now() - t2).count());
 }
 
-void PressureSolver::metric_download(int depth, int which, int patch, double* host)
+// ------------------------------------------------------------------------------------
+// boundary transfers: what each resident array moves (one description), the two movers, the calls on caller arrays
+// ------------------------------------------------------------------------------------
+PressureSolver::CallerArray PressureSolver::io_metric(int depth, int which, bool up)
 {
-    SOMAR_CHECK(finalized && depth >= 0 && depth < this->depth(), "metric_download: depth out of range / not finalized");
+    SOMAR_CHECK(up ? depth == 0 : finalized && depth >= 0 && depth < this->depth(), "metric_download: depth out of range / not finalized");
     Level& L = level(depth);
-    SOMAR_CHECK(patch >= 0 && patch < L.npatches(), "metric_download: patch out of range");
-    const IBox valid = L.boxes[L.local[patch]];
-    const double* f = nullptr;
+    double* f = nullptr;
     int dir = -1;
     if (which >= 0 && which < 3) { f = L.dev.jg[which]; dir = which; }
     else if (which == 3) f = L.dev.jinv;
     else if (which == 4) f = L.dev.lapdiag;
     else if (which >= 16 && which < 25) { dir = (which - 16) / 3; f = L.dev.jgf[dir][(which - 16) % 3]; }
     SOMAR_CHECK(f && (dir < 0 || dir < prm.spaceDim), "metric_download: no such array (which 0..4, or 16 + 3a + b of a non-diagonal metric)");
-    IBox b = valid;
-    if (dir >= 0) b.hi[dir] += 1;
-    L.download(f, patch, host, b, b, st_);
-    sync();
+    return {&L, {f, nullptr, nullptr}, dir >= 0 ? BoxIoShape::faces(dir) : BoxIoShape()};
 }
 
-// ------------------------------------------------------------------------------------
-// boundary transfers
-// ------------------------------------------------------------------------------------
-void PressureSolver::upload_phi(int patch, const double* host, const int ghost[3])
+PressureSolver::CallerArray PressureSolver::io_field(double* field, int depth, const int ghost[3], bool with_ghosts)
 {
-    Level& L = *lev[0];
-    const IBox valid = L.boxes[L.local[patch]];
-    L.upload(f_phi, patch, host, valid.grow(ghost), valid, st_);
-}
-void PressureSolver::upload_rhs(int patch, const double* host, const int ghost[3])
-{
-    Level& L = *lev[0];
-    const IBox valid = L.boxes[L.local[patch]];
-    L.upload(f_rhs, patch, host, valid.grow(ghost), valid, st_);
-}
-void PressureSolver::download_phi(int patch, double* host, const int ghost[3])
-{
-    download_field(f_phi, 0, patch, host, ghost);
-}
-void PressureSolver::download_field(const double* field, int depth, int patch, double* host, const int ghost[3])
-{
-    Level& L = *lev[depth];
-    const IBox valid = L.boxes[L.local[patch]];
-    int g[3];
-    for (int d = 0; d < 3; ++d) {
-        SOMAR_CHECK(ghost[d] >= 0 && ghost[d] <= FRAME, "host ghost wider than the device frame");
-        g[d] = ghost[d];
-    }
-    const IBox hb = valid.grow(g);
-    L.download(field, patch, host, hb, hb, st_);
-    sync();
+    SOMAR_CHECK(field && ghost, "no such field / null ghost");
+    return {&level(depth), {field, nullptr, nullptr}, BoxIoShape::cells(ghost, with_ghosts)};
 }
 
-// ---- caller arrays in device memory: one launch per call for all local patches (box_io.hip) ----
-void PressureSolver::upload_field_dev(double* field, int depth, const double* const* dev, const int ghost[3], bool with_ghosts,
-                                      bool checked)
+PressureSolver::CallerArray PressureSolver::io_vel(int dir)
 {
-    SOMAR_CHECK(field && ghost, "upload_field_dev: no such field / null ghost");
-    double* const f[3] = {field, nullptr, nullptr};
-    level(depth).upload_dev(f, dev, BoxIoShape::cells(ghost, with_ghosts), st_, checked);
+    return {lev[0].get(), {vel(dir), nullptr, nullptr}, BoxIoShape::faces(dir)};
 }
-void PressureSolver::download_field_dev(double* field, int depth, double* const* dev, const int ghost[3], bool checked)
-{
-    SOMAR_CHECK(field && ghost, "download_field_dev: no such field / null ghost");
-    double* const f[3] = {field, nullptr, nullptr};
-    level(depth).download_dev(f, dev, BoxIoShape::cells(ghost, true), st_, checked);
-}
-void PressureSolver::upload_vel_dev(int dir, const double* const* dev, bool checked)
-{
-    double* const f[3] = {vel(dir), nullptr, nullptr};
-    lev[0]->upload_dev(f, dev, BoxIoShape::faces(dir), st_, checked);
-}
-void PressureSolver::download_vel_dev(int dir, double* const* dev, bool checked)
-{
-    double* const f[3] = {vel(dir), nullptr, nullptr};
-    lev[0]->download_dev(f, dev, BoxIoShape::faces(dir), st_, checked);
-}
-BoxIoShape PressureSolver::cc_vel_shape(const int ghost[3], bool up) const
+
+PressureSolver::CallerArray PressureSolver::io_cc_vel(const int ghost[3], bool up)
 {
     SOMAR_CHECK(ghost, "null ghost");
     BoxIoShape s = BoxIoShape::cells(ghost, false);
     s.ncomp = prm.spaceDim;
-    for (int d = 0; d < prm.spaceDim; ++d) {
+    for (int d = 0; d < prm.spaceDim && up; ++d) {
         SOMAR_CHECK(ghost[d] >= 1, "the cell-centred velocity needs one ghost layer (CellToEdge reads it)");
-        if (up) s.grow[d] = 1;
+        s.grow[d] = 1;
     }
-    return s;
-}
-void PressureSolver::upload_cc_vel_dev(const double* const* dev, const int ghost[3], bool checked)
-{
-    const BoxIoShape s = cc_vel_shape(ghost, true);
-    double* const f[3] = {cc_vel(0), cc_vel(1), prm.spaceDim > 2 ? cc_vel(2) : nullptr};
-    lev[0]->upload_dev(f, dev, s, st_, checked);
-}
-void PressureSolver::download_cc_vel_dev(double* const* dev, const int ghost[3], bool checked)
-{
-    const BoxIoShape s = cc_vel_shape(ghost, false);
-    double* const f[3] = {cc_vel(0), cc_vel(1), prm.spaceDim > 2 ? cc_vel(2) : nullptr};
-    lev[0]->download_dev(f, dev, s, st_, checked);
+    return {lev[0].get(), {cc_vel(0), cc_vel(1), prm.spaceDim > 2 ? cc_vel(2) : nullptr}, s};
 }
 
-void PressureSolver::solve_dev(double* const* phi, const int phi_ghost[3], const double* const* rhs, const int rhs_ghost[3],
-                               bool zeroPhi, bool forceHomogeneous, SolveStats& st)
+PressureSolver::CallerArray PressureSolver::io_scale_cc(int which, const int ghost[3])
 {
-    SOMAR_CHECK(finalized && phi_ghost && rhs_ghost, "solve_dev: solver not finalized / null ghost");
     Level& L = *lev[0];
-    L.check_dev_ptrs(phi, BoxIoShape::cells(phi_ghost, true), "phi");
-    L.check_dev_ptrs(rhs, BoxIoShape::cells(rhs_ghost, false), "rhs");
-    upload_field_dev(f_rhs, 0, rhs, rhs_ghost, false, true);
-    if (!zeroPhi) upload_field_dev(f_phi, 0, phi, phi_ghost, false, true);
+    SOMAR_CHECK(finalized && (which == 0 || which == 1) && ghost, "set_scale_cc: bad argument");
+    BoxIoShape s = BoxIoShape::cells(ghost, false);
+    for (int d = 0; d < prm.spaceDim; ++d) {
+        SOMAR_CHECK(ghost[d] >= 1, "the cell-centred scale needs the velocity's ghost layer");
+        s.grow[d] = 1;
+    }
+    if (!f_sc_cc[which]) f_sc_cc[which] = L.alloc_field();
+    return {&L, {f_sc_cc[which], nullptr, nullptr}, s};
+}
+
+PressureSolver::CallerArray PressureSolver::io_scale_face(int which, int dir)
+{
+    Level& L = *lev[0];
+    SOMAR_CHECK(finalized && (which == 0 || which == 1) && dir >= 0 && dir < prm.spaceDim, "set_scale_face: bad argument");
+    if (!f_sc_face[which][dir]) f_sc_face[which][dir] = L.alloc_field();
+    return {&L, {f_sc_face[which][dir], nullptr, nullptr}, BoxIoShape::faces(dir)};
+}
+
+PressureSolver::CallerArray PressureSolver::io_heat_flux(int dir)
+{
+    return {lev[0].get(), {heat_flux(dir), nullptr, nullptr}, BoxIoShape::faces(dir)};
+}
+
+void PressureSolver::move_host(const CallerArray& a, int patch, double* host, bool up)
+{
+    a.L->move_host(a.f, patch, host, a.shape, up, st_);
+    sync();
+}
+
+void PressureSolver::move_dev(const CallerArray& a, double* const* dev, bool up, bool checked)
+{
+    if (up) a.L->upload_dev(a.f, dev, a.shape, st_, checked);
+    else a.L->download_dev(a.f, dev, a.shape, st_, checked);
+}
+
+void PressureSolver::check_table(Mem where, const CallerArray& a, const double* const* table, const char* what)
+{
+    if (where == Mem::Device) return a.L->check_dev_ptrs(table, a.shape, what);
+    check_shape(a.shape);
+    SOMAR_CHECK(table != nullptr, std::string(what) + ": null pointer table");
+}
+
+void PressureSolver::move_table(Mem where, const CallerArray& a, double* const* table, bool up)
+{
+    if (where == Mem::Device) return move_dev(a, table, up, true);
+    for (int p = 0; p < a.L->npatches(); ++p)
+        if (table[p]) a.L->move_host(a.f, p, table[p], a.shape, up, st_);
+    sync();   // one drain after the last copy: the caller's arrays are free again / hold the result
+}
+
+void PressureSolver::solve_on(Mem where, double* const* phi, const int phi_ghost[3], const double* const* rhs, const int rhs_ghost[3],
+                              bool zeroPhi, bool forceHomogeneous, SolveStats& st)
+{
+    SOMAR_CHECK(finalized, "solve on caller arrays: solver not finalized");
+    const CallerArray P = io_field(f_phi, 0, phi_ghost, true), R = io_field(f_rhs, 0, rhs_ghost, false);
+    check_table(where, P, phi, "phi");
+    check_table(where, R, rhs, "rhs");
+    move_table(where, R, const_cast<double* const*>(rhs), true);
+    if (!zeroPhi) move_table(where, io_field(f_phi, 0, phi_ghost, false), phi, true);   // the valid cells
     solve(zeroPhi, forceHomogeneous, st);
-    download_field_dev(f_phi, 0, phi, phi_ghost, true);
+    move_table(where, P, phi, false);
 }
 
-void PressureSolver::mac_project_dev(double* const* const u[3], double dt, bool zeroPressure, bool forceHomogeneous, SolveStats& st)
+void PressureSolver::mac_project_on(Mem where, double* const* const u[3], double dt, bool zeroPressure, bool forceHomogeneous,
+                                    SolveStats& st)
 {
-    SOMAR_CHECK(finalized && u && u[0] && u[1] && u[2], "mac_project_dev: solver not finalized / null pointer table");
-    Level& L = *lev[0];
+    SOMAR_CHECK(finalized, "MAC projection on caller arrays: solver not finalized");
     static const char* const name[3] = {"u0", "u1", "u2"};
-    for (int d = 0; d < 3; ++d) L.check_dev_ptrs(u[d], BoxIoShape::faces(d), name[d]);
-    for (int d = 0; d < 3; ++d) upload_vel_dev(d, u[d], true);
+    for (int d = 0; d < 3; ++d) check_table(where, io_vel(d), u[d], name[d]);
+    for (int d = 0; d < 3; ++d) move_table(where, io_vel(d), u[d], true);
     mac_project(dt, zeroPressure, forceHomogeneous, st);
-    for (int d = 0; d < 3; ++d) download_vel_dev(d, u[d], true);
+    for (int d = 0; d < 3; ++d) move_table(where, io_vel(d), u[d], false);
 }
 
-void PressureSolver::cc_project_dev(double* const* vel, const int ghost[3], double dt, bool zeroPressure, bool forceHomogeneous,
-                                    bool wall, SolveStats& st)
+void PressureSolver::cc_project_on(Mem where, double* const* vel, const int ghost[3], double dt, bool zeroPressure,
+                                   bool forceHomogeneous, bool wall, SolveStats& st)
 {
-    SOMAR_CHECK(finalized, "cc_project_dev: solver not finalized");
-    lev[0]->check_dev_ptrs(vel, cc_vel_shape(ghost, true), "vel");
-    upload_cc_vel_dev(vel, ghost, true);
+    SOMAR_CHECK(finalized, "cell-centred projection on caller arrays: solver not finalized");
+    const CallerArray up = io_cc_vel(ghost, true);
+    check_table(where, up, vel, "vel");
+    move_table(where, up, vel, true);
     cc_project(dt, zeroPressure, forceHomogeneous, wall, st);
-    download_cc_vel_dev(vel, ghost, true);
+    move_table(where, io_cc_vel(ghost, false), vel, false);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1358,26 +1348,6 @@ double* PressureSolver::vel(int dir)
     return f_vel[dir];
 }
 
-void PressureSolver::upload_vel(int dir, int patch, const double* host)
-{
-    Level& L = *lev[0];
-    SOMAR_CHECK(patch >= 0 && patch < L.npatches(), "bad patch index");
-    IBox fb = L.boxes[L.local[patch]];
-    fb.hi[dir] += 1;
-    L.upload(vel(dir), patch, host, fb, fb, st_);
-    sync();
-}
-
-void PressureSolver::download_vel(int dir, int patch, double* host)
-{
-    Level& L = *lev[0];
-    SOMAR_CHECK(patch >= 0 && patch < L.npatches(), "bad patch index");
-    IBox fb = L.boxes[L.local[patch]];
-    fb.hi[dir] += 1;
-    L.download(vel(dir), patch, host, fb, fb, st_);
-    sync();
-}
-
 void PressureSolver::divergence_mac(double* out, double dt)
 {
     launch_div_mac(st_, lev[0]->dev, out, vel(0), vel(1), vel(2), dt);
@@ -1396,33 +1366,6 @@ void PressureSolver::mac_correct(double* phi, double dt)
         return;
     }
     launch_mac_correct(st_, L.dev, v, phi, dt == 0.0 ? -1.0 : -dt);
-}
-
-void PressureSolver::set_scale_cc(int which, int patch, const double* host, const int ghost[3])
-{
-    Level& L = *lev[0];
-    SOMAR_CHECK(finalized && (which == 0 || which == 1) && patch >= 0 && patch < L.npatches(), "set_scale_cc: bad argument");
-    if (!f_sc_cc[which]) f_sc_cc[which] = L.alloc_field();
-    const IBox valid = L.boxes[L.local[patch]];
-    int one[3] = {0, 0, 0};
-    for (int d = 0; d < prm.spaceDim; ++d) {
-        SOMAR_CHECK(ghost[d] >= 1, "the cell-centred scale needs the velocity's ghost layer");
-        one[d] = 1;
-    }
-    L.upload(f_sc_cc[which], patch, host, valid.grow(ghost), valid.grow(one), st_);
-    sync();
-}
-
-void PressureSolver::set_scale_face(int which, int dir, int patch, const double* host)
-{
-    Level& L = *lev[0];
-    SOMAR_CHECK(finalized && (which == 0 || which == 1) && dir >= 0 && dir < prm.spaceDim && patch >= 0 && patch < L.npatches(),
-                "set_scale_face: bad argument");
-    if (!f_sc_face[which][dir]) f_sc_face[which][dir] = L.alloc_field();
-    IBox fb = L.boxes[L.local[patch]];
-    fb.hi[dir] += 1;
-    L.upload(f_sc_face[which][dir], patch, host, fb, fb, st_);
-    sync();
 }
 
 void PressureSolver::scale_vel(int centring, int which)
@@ -1528,16 +1471,6 @@ double* PressureSolver::heat_flux(int dir)
     return f_heatflux[dir];
 }
 
-void PressureSolver::download_heat_flux(int dir, int patch, double* host)
-{
-    Level& L = *lev[0];
-    SOMAR_CHECK(patch >= 0 && patch < L.npatches(), "bad patch index");
-    IBox fb = L.boxes[L.local[patch]];
-    fb.hi[dir] += 1;
-    L.download(heat_flux(dir), patch, host, fb, fb, st_);
-    sync();
-}
-
 void PressureSolver::increment_heat_flux(double* phi, bool setToZero)
 {
     Level& L = *lev[0];
@@ -1614,31 +1547,6 @@ double* PressureSolver::cc_vel(int comp)
     SOMAR_CHECK(comp >= 0 && comp < prm.spaceDim && finalized, "bad velocity component / solver not finalized");
     if (!f_ccvel[comp]) f_ccvel[comp] = lev[0]->alloc_field();
     return f_ccvel[comp];
-}
-
-void PressureSolver::upload_cc_vel(int patch, const double* host, const int ghost[3])
-{
-    Level& L = *lev[0];
-    SOMAR_CHECK(patch >= 0 && patch < L.npatches(), "bad patch index");
-    const IBox valid = L.boxes[L.local[patch]];
-    int one[3] = {0, 0, 0};
-    for (int d = 0; d < prm.spaceDim; ++d) {
-        SOMAR_CHECK(ghost[d] >= 1, "the cell-centred velocity needs one ghost layer (CellToEdge reads it)");
-        one[d] = 1;
-    }
-    const IBox hb = valid.grow(ghost);
-    for (int c = 0; c < prm.spaceDim; ++c) L.upload(cc_vel(c), patch, host + (long long)c * hb.numPts(), hb, valid.grow(one), st_);
-    sync();
-}
-
-void PressureSolver::download_cc_vel(int patch, double* host, const int ghost[3])
-{
-    Level& L = *lev[0];
-    SOMAR_CHECK(patch >= 0 && patch < L.npatches(), "bad patch index");
-    const IBox valid = L.boxes[L.local[patch]];
-    const IBox hb = valid.grow(ghost);
-    for (int c = 0; c < prm.spaceDim; ++c) L.download(cc_vel(c), patch, host + (long long)c * hb.numPts(), hb, valid, st_);
-    sync();
 }
 
 void PressureSolver::divergence_cc(double* out, double dt, bool wall)

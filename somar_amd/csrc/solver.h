@@ -83,32 +83,45 @@ public:
     bool metric_update_end(bool only_if_written = false);
     bool metric_updating() const { return updating_; }
     void refresh_metric();   // the recomputation alone (no begin / end bookkeeping): leptic internal solvers
-    // which 0..2: J g^{aa} on faces(valid, a); 3: J^{-1}; 4: lapDiag (valid); 16 + 3a + b: J g^{ab} of the non-diagonal metric
-    void metric_download(int depth, int which, int patch, double* host);
     void check_idle(const char* what) const;   // refuses while a metric update is open
 
-    // ---- data movement across the boundary (host FABs, caller-owned) ---------------------
-    void upload_phi(int patch, const double* host, const int ghost[3]);
-    void upload_rhs(int patch, const double* host, const int ghost[3]);
-    void download_phi(int patch, double* host, const int ghost[3]);
-    void download_field(const double* field, int depth, int patch, double* host, const int ghost[3]);
-    // ---- the same for caller arrays in DEVICE memory: every local patch in one launch (Level::upload_dev / download_dev).
-    // dev: HOST array of one device pointer per local patch (null skips the patch); regions as in the host calls.  Every
-    // pointer of a call is checked before its first launch; the calls run on this solver's stream and drain it.
-    void upload_field_dev(double* field, int depth, const double* const* dev, const int ghost[3], bool with_ghosts,
-                          bool checked = false);
-    void download_field_dev(double* field, int depth, double* const* dev, const int ghost[3], bool checked = false);
-    void upload_vel_dev(int dir, const double* const* dev, bool checked = false);
-    void download_vel_dev(int dir, double* const* dev, bool checked = false);
-    void upload_cc_vel_dev(const double* const* dev, const int ghost[3], bool checked = false);
-    void download_cc_vel_dev(double* const* dev, const int ghost[3], bool checked = false);
-    BoxIoShape cc_vel_shape(const int ghost[3], bool up) const;
-    // the *_host solves and projections of the C ABI with the copies replaced
-    void solve_dev(double* const* phi, const int phi_ghost[3], const double* const* rhs, const int rhs_ghost[3], bool zeroPhi,
-                   bool forceHomogeneous, SolveStats& st);
-    void mac_project_dev(double* const* const u[3], double dt, bool zeroPressure, bool forceHomogeneous, SolveStats& st);
-    void cc_project_dev(double* const* vel, const int ghost[3], double dt, bool zeroPressure, bool forceHomogeneous, bool wall,
-                        SolveStats& st);
+    // ---- data movement across the boundary (caller-owned arrays, Chombo FRA layout) ---------------------
+    // One resident array that crosses the boundary: its level, its level arrays (one per component) and what moves
+    // (BoxIoShape).  Each array below has ONE description, whichever memory the caller's side lives in.
+    struct CallerArray {
+        Level* L;
+        double* f[3];
+        BoxIoShape shape;
+    };
+    CallerArray io_field(double* field, int depth, const int ghost[3], bool with_ghosts);   // a field at a depth; region valid.grow(ghost) or valid
+    CallerArray io_vel(int dir);                                // MAC velocity J*u^dir on faces(valid, dir)
+    CallerArray io_cc_vel(const int ghost[3], bool up);         // SpaceDim comps; up: one ghost layer in the space directions, down: valid cells
+    CallerArray io_scale_cc(int which, const int ghost[3]);     // cell-centred J (0) / Jinv (1): the region of io_cc_vel up
+    CallerArray io_scale_face(int which, int dir);
+    CallerArray io_heat_flux(int dir);
+    // which 0..2: J g^{aa} on faces(valid, a); 3: J^{-1}; 4: lapDiag (valid); 16 + 3a + b: J g^{ab} of the non-diagonal metric.
+    // up: a producer writes depth 0 (set_metric_*); down needs a finalized solver
+    CallerArray io_metric(int depth, int which, bool up);
+    // The two movers.  Host memory: one local patch and one pointer (a null pointer or a patch index out of range is an
+    // error); blocks until the caller's array is free / filled.  Device memory: a HOST table of one device pointer per local
+    // patch, all of them in one launch (a null entry skips its patch); every pointer is checked before the launch unless
+    // `checked` says a check_table did; drains the stream.
+    void upload(const CallerArray& a, int patch, const double* host) { move_host(a, patch, const_cast<double*>(host), true); }
+    void download(const CallerArray& a, int patch, double* host) { move_host(a, patch, host, false); }
+    void move_dev(const CallerArray& a, double* const* dev, bool up, bool checked = false);
+    // ---- calls on caller arrays: check every table, shape and (device memory) pointer; upload; run the resident call;
+    // download.  Written once, with where the caller's arrays live as an argument: a table is one pointer per local patch
+    // either way, and a null entry skips its patch.  Both memories follow the same rules: (1) nothing moves and nothing is
+    // solved before every argument passed its check; (2) the ghost width of an array of which only valid cells move (rhs,
+    // the velocity on its way down) is not bounded by the device frame; (3) null table entries skip.
+    enum class Mem { Host, Device };
+    void check_table(Mem where, const CallerArray& a, const double* const* table, const char* what);
+    void move_table(Mem where, const CallerArray& a, double* const* table, bool up);   // after check_table
+    void solve_on(Mem where, double* const* phi, const int phi_ghost[3], const double* const* rhs, const int rhs_ghost[3],
+                  bool zeroPhi, bool forceHomogeneous, SolveStats& st);
+    void mac_project_on(Mem where, double* const* const u[3], double dt, bool zeroPressure, bool forceHomogeneous, SolveStats& st);
+    void cc_project_on(Mem where, double* const* vel, const int ghost[3], double dt, bool zeroPressure, bool forceHomogeneous,
+                       bool wall, SolveStats& st);
 
     // ---- AMREllipticSolver::solve on the resident phi/rhs (AMREllipticSolver.H:33-48) -----
     void solve(bool zeroPhi, bool forceHomogeneous, SolveStats& st);
@@ -220,8 +233,6 @@ public:
     void fill_hash(int d, double* f, unsigned long long seed);
     // ---- MAC level projection pieces (LevelMACProjector / BaseProjector::project), depth 0 -------------
     double* vel(int dir);   // resident face field J*u^dir (allocated on first use)
-    void upload_vel(int dir, int patch, const double* host);     // host FAB over faces(valid, dir)
-    void download_vel(int dir, int patch, double* host);
     void divergence_mac(double* out, double dt);                 // out = div(vel) [/ dt]
     void mac_correct(double* phi, double dt);                    // vel -= dt * G(phi)
     void mac_project(double dt, bool zeroPressure, bool forceHomogeneous, SolveStats& st);
@@ -236,21 +247,17 @@ public:
     // as the last operation left them
     void increment_heat_flux(double* phi, bool setToZero);
     double* heat_flux(int dir);
-    void download_heat_flux(int dir, int patch, double* host);   // host: faces(valid, dir), Fortran order   // MappedAMRPoissonOp::setAlphaAndBeta on every depth: alpha = a*aCoef, beta = b*bCoef
     double* heat_field(int which);             // 0: phiOld, 1: src (depth 0, allocated on first use)
     void heat_step(int scheme, double dt, bool zeroPhi, SolveStats& st);   // 0 backward Euler, 1 Crank-Nicolson, 2 TGA
     // cell-centred level projection (LevelCCProjector): velocity J*u, SpaceDim comps, resident with one ghost layer
     double* cc_vel(int comp);
-    void upload_cc_vel(int patch, const double* host, const int ghost[3]);   // host FAB: SpaceDim comps, comp slowest
-    void download_cc_vel(int patch, double* host, const int ghost[3]);       // valid cells only are written
     void divergence_cc(double* out, double dt, bool wall);                   // CellToEdge [+ wall BC] -> vel(); div [/ dt]
     void cc_correct(double* phi, double dt);                                 // cc_vel -= dt * EdgeToCell(G(phi))
     void cc_project(double dt, bool zeroPressure, bool forceHomogeneous, bool wall, SolveStats& st);
     // LevelGeometry::multByJ / divByJ on the resident velocities (geometry/LevelGeometryUtil.cpp:287-339, 372-420, 456-...):
     // data *= J resp. data *= Jinv, the scale arrays being the caller's (getCCJ / getCCJinv over valid.grow(ghost), fill_J /
-    // fill_Jinv on the face boxes).  which: 0 = J, 1 = Jinv.  centring 0: the MAC velocity (set per direction), 1: cell-centred.
-    void set_scale_cc(int which, int patch, const double* host, const int ghost[3]);
-    void set_scale_face(int which, int dir, int patch, const double* host);
+    // fill_Jinv on the face boxes; they arrive through io_scale_cc / io_scale_face).  which: 0 = J, 1 = Jinv.  centring 0: the
+    // MAC velocity (set per direction), 1: cell-centred.
     void scale_vel(int centring, int which);
     void remove_mean(int d, double* f);
     void sync();
@@ -272,6 +279,7 @@ public:
     std::vector<std::array<int, 3>> mgRefRatios;
 
 private:
+    void move_host(const CallerArray& a, int patch, double* host, bool up);
     void cycle(int d, double* corr, const double* res, bool corr_zero = false);
     // residual_i (mode 0) and apply_op_i (mode 1) in one: mode 0 out = rhs - L[phi] (timed in a profiled pass), mode 1 out = L[phi] (rhs unused)
     void operator_i(int d, int mode, double* out, double* phi, const double* rhs, bool homogeneous);

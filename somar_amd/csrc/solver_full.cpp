@@ -675,20 +675,19 @@ void PressureSolver::set_metric_full(int patch, const double* jg0, const double*
 {
     metric_written("full");
     Level& L = *lev[0];
-    SOMAR_CHECK(patch >= 0 && patch < L.npatches(), "bad patch index");
     full_ = true;
     L.alloc_cross_metric();  // SpaceDim 2: the planes with a z index stay zero, the 3-D operator / ghost kernels see 0 * finite
-    const IBox valid = L.boxes[L.local[patch]];
     const double* jg[3] = {jg0, jg1, jg2};
     const int nd = prm.spaceDim;
     for (int d = 0; d < nd; ++d) {
         SOMAR_CHECK(jg[d] != nullptr, "null metric array");
-        IBox fb = valid;
-        fb.hi[d] += 1;
-        const long long plane = fb.numPts();
-        for (int c = 0; c < nd; ++c) L.upload(L.dev.jgf[d][c], patch, jg[d] + c * plane, fb, fb, st_);  // comp slowest
+        CallerArray a = io_metric(0, 16 + 3 * d, true);   // row d: J g^{d c}, c < nd, component slowest
+        a.shape.ncomp = nd;
+        for (int c = 1; c < nd; ++c) a.f[c] = L.dev.jgf[d][c];
+        L.move_host(a.f, patch, const_cast<double*>(jg[d]), a.shape, true, st_);
     }
-    L.upload(L.dev.jinv, patch, jinv, valid, valid, st_);
+    const CallerArray a = io_metric(0, 3, true);
+    L.move_host(a.f, patch, const_cast<double*>(jinv), a.shape, true, st_);
     sync();
 }
 

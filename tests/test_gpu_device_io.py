@@ -229,13 +229,18 @@ def test_solve_dev_equals_solve_host(oracle, torch):
         hrhs = [np.asfortranarray(rhs.fabs[gi].a[..., 0]) for gi in order]
         shp = [_shape(gpu, p, (1, 1, 1)) for p in range(len(order))]
         rng = np.random.default_rng(5)
-        for zero_phi in (True, False):
+        # an rhs with three ghost layers, wider than the device frame: only its valid cells move, on either path
+        rg = (3, 3, 3)
+        hrhs3 = [np.asfortranarray(np.pad(a, 3, constant_values=SENTINEL)) for a in hrhs]
+        for zero_phi, rhs_ghost in ((True, (0, 0, 0)), (False, (0, 0, 0)), (False, rg)):
+            if rhs_ghost == rg:
+                hrhs = hrhs3
             start = [np.asfortranarray(0.0 * rng.standard_normal(sh) if zero_phi else 0.01 * rng.standard_normal(sh)) for sh in shp]
             hphi = [a.copy(order="F") for a in start]
-            st_h = dict(gpu.solve(hphi, hrhs, 0, 0, zero_phi, False))
+            st_h = dict(gpu.solve(hphi, hrhs, 0, 0, zero_phi, False, rhs_ghost=rhs_ghost))
             dphi = [_to_dev(torch, a) for a in start]
             drhs = [_to_dev(torch, a) for a in hrhs]
-            st_d = dict(twin.solveDev(dphi, drhs, zero_phi, False))
+            st_d = dict(twin.solveDev(dphi, drhs, zero_phi, False, rhs_ghost=rhs_ghost))
             _same_stats(st_h, st_d)
             for p in range(len(order)):
                 assert hphi[p].any()

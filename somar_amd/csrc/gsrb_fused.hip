@@ -396,9 +396,10 @@ __device__ __forceinline__ void gsrb_fused_body(T* __restrict__ S, const Tile& t
 #undef Sx
 }
 
-// NARROW: the tile table holds narrow lane classes (uniform-metric depths, or SOMAR_NARROW_7PT=1); the instantiation without
-// them is the one-body kernel with 48 KB of LDS that the HBM-bound streaming sweep was tuned as.
-template <int FR_J, int INMODE, bool DIRI = false, bool UNI = false, bool NARROW = false, class T = double>
+// NARROW 1: the tile table holds narrow lane classes (uniform-metric depths, or SOMAR_NARROW_7PT=1); the instantiation without
+// them (0) is the one-body kernel with 48 KB of LDS that the HBM-bound streaming sweep was tuned as.  NARROW 2: every tile is
+// class 1 (tall tiles, march_plan.h): one body again, the same 48 KB, the region read as 32 rows of 64.
+template <int FR_J, int INMODE, bool DIRI = false, bool UNI = false, int NARROW = 0, class T = double>
 __global__ __launch_bounds__(64 * FR_J) void k_gsrb_fused(const Tile* __restrict__ tiles,
                                                      const PatchDesc* __restrict__ patches,
                                                      T* __restrict__ phi_out,
@@ -413,10 +414,10 @@ __global__ __launch_bounds__(64 * FR_J) void k_gsrb_fused(const Tile* __restrict
                                                      const T* __restrict__ crse, int r0, int r1, int r2, int lean_ok)
 {
     // one slot = the largest class's region: FR_J rows of 128, or 16 FR_J rows of 8 + 2
-    __shared__ __attribute__((aligned(16))) T S[3 * FR_J * (NARROW ? 160 : 128)];
+    __shared__ __attribute__((aligned(16))) T S[3 * FR_J * (NARROW == 1 ? 160 : 128)];
     const Tile t = tiles[blockIdx.x];
     const PatchDesc p = patches[t.patch];
-    const int cls = NARROW ? t.pad_[1] : 0;
+    const int cls = NARROW == 1 ? t.pad_[1] : (NARROW == 2 ? 1 : 0);
     bool lean = false;
     if (UNI && !DIRI) {
         // does the tile grown by its red ring stay clear of every domain face (periodic seams included: the boundary form of
@@ -430,7 +431,9 @@ __global__ __launch_bounds__(64 * FR_J) void k_gsrb_fused(const Tile* __restrict
 #define SOMAR_FUSED_BODY(INT_, CLS_)                                                                                          \
     gsrb_fused_body<FR_J, INMODE, DIRI, UNI, INT_, CLS_, T>(S, t, p, phi_out, phi_in, rhs, jgx, jgy, jgz, jinv, P, sums, cpatches, \
                                                         crse, r0, r1, r2)
-    if (!NARROW || cls == 0) {
+    if constexpr (NARROW == 2) {
+        SOMAR_FUSED_BODY(false, 1);   // (never with UNI: no lean form)
+    } else if (!NARROW || cls == 0) {
         if (lean) SOMAR_FUSED_BODY(UNI && !DIRI, 0);
         else SOMAR_FUSED_BODY(false, 0);
     } else if (cls == 1) {
@@ -457,7 +460,7 @@ static void launch_gsrb_fused_t(hipStream_t st, const Tile* tiles, int ntiles, c
         hipLaunchKernelGGL(kern, dim3(ntiles), dim3(64, rows, 1), 0, st, tiles, L.patches, phi_out, phi_in, rhs, M.jg[0], M.jg[1],
                            M.jg[2], M.jinv, L.P, sums, cpatches, crse, r0, r1, r2, L.lean_tiles);
     };
-    // (rows, mode, Dirichlet sides, uniform metric, narrow lane classes in the tile table)
+    // (rows, mode, Dirichlet sides, uniform metric, narrow lane classes in the tile table: 0 none, 1 mixed, 2 all class 1)
 #define SOMAR_FUSED_MODES(ROWS, D, U, N, M0, M1, M2, M3, M4)                    \
     switch (in_mode) {                                                          \
         case 1: go(k_gsrb_fused<ROWS, M1, D, U, N, T>, ROWS); break;            \
@@ -468,12 +471,15 @@ static void launch_gsrb_fused_t(hipStream_t st, const Tile* tiles, int ntiles, c
     }
     const bool rows16 = L.fused_rows == 16;
     const bool narrow = L.narrow7 != 0 && rows16;   // Level::build_march_tiles hands the 8-row kernels class-0 tiles only
+    const bool tall = L.tall7 != 0;                 // ... and tall tiles to the 16-row kernels of a non-uniform metric only
+    SOMAR_CHECK(!tall || (rows16 && !L.P.uniform), "internal: tall tiles on a level whose fused sweep has no class-1 kernel");
     bool diri = false;
     for (int d = 0; d < 3; ++d) diri = diri || L.P.diri[d][0] || L.P.diri[d][1];
     if (diri) {
         // Dirichlet sides: no null space, hence never a mean removal (modes 2 / 4 fall back to 0 / 3 in the table below; checked)
         SOMAR_CHECK(in_mode == 0 || in_mode == 1 || in_mode == 3, "internal: mean removal on a level with Dirichlet sides");
         if (!rows16) { SOMAR_FUSED_MODES(8, true, false, false, 0, 1, 0, 3, 3) }
+        else if (tall) { SOMAR_FUSED_MODES(16, true, false, 2, 0, 1, 0, 3, 3) }
         else if (narrow) { SOMAR_FUSED_MODES(16, true, false, true, 0, 1, 0, 3, 3) }
         else { SOMAR_FUSED_MODES(16, true, false, false, 0, 1, 0, 3, 3) }
         return;
@@ -485,6 +491,7 @@ static void launch_gsrb_fused_t(hipStream_t st, const Tile* tiles, int ntiles, c
         return;
     }
     if (!rows16) { SOMAR_FUSED_MODES(8, false, false, false, 0, 1, 2, 3, 4) }
+    else if (tall) { SOMAR_FUSED_MODES(16, false, false, 2, 0, 1, 2, 3, 4) }
     else if (narrow) { SOMAR_FUSED_MODES(16, false, false, true, 0, 1, 2, 3, 4) }
     else { SOMAR_FUSED_MODES(16, false, false, false, 0, 1, 2, 3, 4) }
 #undef SOMAR_FUSED_MODES

@@ -26,6 +26,7 @@ struct LevelDev {
     // (PressureSolver::build_face_slices); the address never changes after finalize
     const double* bc_face = nullptr;
     int narrow7 = 0;                    // the 7-point marching kernels' tile tables hold narrow lane classes (Level::build_march_tiles)
+    int tall7 = 0;                      // every tile of the fused sweep's table is class 1 (march_plan.h: tall tiles)
     int narrowq = 0;                    // the 19-point marching kernels' tile table does
     // what the launchers take from the solver's Tuning (Level::define copies it here)
     int fused_rows = 16;                // region rows per workgroup of the fused 7-point sweep (tile rows = rows - 4): 16 or 8

@@ -1,5 +1,6 @@
 // somar_amd/csrc/level.cpp -- layout tables, HBM allocation, ghost-exchange plan.
 #include "level.h"
+#include "march_plan.h"
 
 #include <algorithm>
 #include <array>
@@ -486,72 +487,39 @@ void Copier::run(const double* s, double* d, hipStream_t st) const
 // classes for remainder columns.  That pays where the kernels are latency-bound -- a uniform metric, two or three streams
 // (C4: 158 -> 112 ms per AMR V-cycle, c2_cartesian 134 -> 159 V-cycles/s) -- and costs where six streams are HBM-bound
 // (512^3 stretched: residual 1.52 -> 2.00 ms: 64-byte row segments of six arrays), so PressureSolver::finalize asks for it
-// on the depths whose metric it found uniform; the 19-point tables always use the classes.
-void Level::build_march_tiles(bool narrow7)
+// on the depths whose metric it found uniform; the 19-point tables always use the classes.  tall7: finalize found the metric
+// not uniform: the fused sweep's table takes tall tiles (march_plan.h) where the boxes are wide enough.
+void Level::build_march_tiles(bool narrow7, bool tall7)
 {
     for (DevBuf<Tile>* q : {&d_ftiles, &d_ftiles_own, &d_ftiles_rem, &d_rtiles, &d_rtiles_own, &d_rtiles_rem, &d_qtiles, &d_gtiles, &d_stiles})
         q->reset();
     nftiles_own = nftiles_rem = nrtiles_own = nrtiles_rem = 0;
     narrow7_ = narrow7;
+    tall7_ = tall7;
     // ---- tiles of the k-marching kernels: (FT_I x FT_J) columns, k split into chunks so that the launch
     // fills the 256 CUs evenly (one 1024-thread workgroup per CU at a time); `halo` = planes a chunk reads
-    // beyond its own (fused red-black sweep: 3, marching residual: 2) ----------------------------------
-    // Tile columns and their lane class (Tile::pad_[1], see full19_march.hip): class 0 = 124 output columns, one region row
-    // per wavefront; class 1 = 60 columns, two rows per wavefront; class 4 = 4 columns, sixteen rows per wavefront.  A box
-    // is cut into 124-wide columns and its remainder into the narrow classes (128 -> 124 + 4, 64 -> 60 + 4, 512 -> 4 x 124 +
-    // 4 x 4), so that a remainder column costs a sixteenth (a half) of a workgroup-march instead of a whole one.
-    // `classes` off (Tuning::no_narrow_tiles, the 6-/8-row A/B variants): columns of equal width, all class 0 (128 -> 2 x 64,
-    // 512 -> 5 x 104).  region_rows = blockDim.y of the kernel, hrows = region rows that are halo.
-    struct ColSpec { int i0, w, cls; };
+    // beyond its own (fused red-black sweep: 3, marching residual: 2).  march_plan.h holds the rule: tile columns and their
+    // lane classes, tile rows, k-chunks.  `classes` off (Tuning::no_narrow_tiles, the 6-/8-row A/B variants): columns of equal
+    // width, all class 0.  `tall`: every tile is class 1 (the fused sweep's table on streamed levels of wide boxes). ----------
+    using march_plan::ColSpec;
     const int fused_rows = dev.fused_rows, full_rows = dev.full_rows;
-    auto march_tiles = [&](int FT_I, int region_rows, int hrows, double halo, int slots, bool classes, double min_gain = 1.0) {
-        classes = classes && !tune.no_narrow_tiles;
-        const bool balanced = !tune.no_balanced_tiles;
-        // min_gain: the narrow decomposition is taken only where it costs at most that fraction of the equal columns' workgroup-
-        // marches (a class-4 workgroup counted as a quarter: it runs long; a class-1 one as a half).  1.0 = always.
-        auto columns = [&](int n0) {
-            std::vector<ColSpec> eq, v;
-            {
-                int w = FT_I;
-                if (balanced) {
-                    const int ncol = (n0 + FT_I - 1) / FT_I;
-                    w = (n0 + ncol - 1) / ncol;
-                    w += w & 1;
-                    w = std::min(w, FT_I);
-                }
-                for (int i0 = 0; i0 < n0; i0 += w) eq.push_back({i0, w, 0});
-            }
-            if (!classes || (n0 & 1)) return eq;
-            int i0 = 0, rem = n0;
-            double cost = 0.0;
-            while (rem >= FT_I) { v.push_back({i0, FT_I, 0}); i0 += FT_I; rem -= FT_I; cost += 1.0; }
-            if (rem > 76) { v.push_back({i0, rem, 0}); rem = 0; cost += 1.0; }
-            if (rem > 16) { const int w = std::min(rem, 60); v.push_back({i0, w, 1}); i0 += w; rem -= w; cost += 0.5; }
-            while (rem > 0) { const int w = std::min(rem, 4); v.push_back({i0, w, 4}); i0 += w; rem -= w; cost += 0.25; }
-            return cost <= min_gain * (double)eq.size() ? v : eq;
-        };
-        auto rows_of = [&](int cls) { return (region_rows << cls) - hrows; };
-        long long cols = 0;
-        int maxn2 = 1;
-        for (const PatchDesc& p : hpatches) {
-            for (const ColSpec& c : columns(p.n[0])) cols += (p.n[1] + rows_of(c.cls) - 1) / rows_of(c.cls);
-            maxn2 = std::max(maxn2, p.n[2]);
-        }
-        int best = 1;
-        double best_eff = -1.0;
-        for (int nch = 1; nch <= 64 && (nch == 1 || maxn2 / nch >= 4); ++nch) {  // small levels: short chunks, more workgroups
-            const long long blocks = cols * nch;
-            const long long rounds = (blocks + slots - 1) / slots;
-            const double nk = (double)maxn2 / nch;
-            const double eff = (double)blocks / (double)(rounds * slots) * nk / (nk + halo);
-            if (eff > best_eff + 1e-9) { best_eff = eff; best = nch; }
-        }
+    std::vector<march_plan::BoxSize> sizes;
+    for (const PatchDesc& p : hpatches) sizes.push_back({p.n[0], p.n[1], p.n[2]});
+    auto march_tiles = [&](int FT_I, int region_rows, int hrows, double halo, int slots, bool classes, double min_gain = 1.0,
+                           bool tall = false) {
+        march_plan::Shape shape;
+        shape.FT_I = FT_I; shape.region_rows = region_rows; shape.hrows = hrows; shape.halo = halo; shape.slots = slots;
+        shape.classes = classes && !tune.no_narrow_tiles;
+        shape.balanced = !tune.no_balanced_tiles;
+        shape.min_gain = min_gain;
+        const march_plan::Plan plan = march_plan::plan(shape, sizes, tall);
+        auto rows_of = [&](int cls) { return march_plan::rows_of(shape, cls); };
         std::vector<Tile> fnat;
         for (int pi = 0; pi < (int)hpatches.size(); ++pi) {
             const PatchDesc& p = hpatches[pi];
-            int nk = (p.n[2] + best - 1) / best;
-            nk += nk & 1;  // even chunks: a chunk never splits the two planes of a coarse cell (fused restriction)
-            const std::vector<ColSpec> cs = columns(p.n[0]);
+            const int nk = march_plan::chunk_planes(p.n[2], plan.nch);
+            const std::vector<ColSpec> cs = plan.extra >= 0 ? march_plan::tall_columns(p.n[0], plan.extra)
+                                                            : march_plan::columns(shape, p.n[0]);
             auto add = [&](const ColSpec& c, int j0, int k0) {
                 Tile t;
                 std::memset(&t, 0, sizeof(t));
@@ -581,7 +549,12 @@ void Level::build_march_tiles(bool narrow7)
         for (int b = 0; b < NF; ++b) perm[b] = fnat[start[b % NX] + b / NX];
         return perm;
     };
-    hftiles = march_tiles(124, fused_rows, 4, 3.0, 256, narrow7 && fused_rows == 16, 0.85);
+    // tall tiles: the caller asks for them where the fused sweep can run at all (7-point operator, three active directions);
+    // march_plan.h's rule sees the boxes, the kernel family and the metric flag; the switches that restore the equal columns
+    // turn them off
+    const bool tall = tall7 && !tune.no_narrow_tiles && tune.narrow_7pt != 0 &&
+                      march_plan::tall_eligible(sizes, fused_rows, dev.P.uniform != 0);
+    hftiles = march_tiles(124, fused_rows, 4, 3.0, 256, narrow7 && fused_rows == 16, 0.85, tall);
     d_ftiles = DevBuf<Tile>::from(hftiles);
     nftiles = (int)hftiles.size();
     hrtiles = march_tiles(124, 16, 2, 2.0, 256, narrow7, 0.85);
@@ -590,8 +563,10 @@ void Level::build_march_tiles(bool narrow7)
     nrtiles = (int)hrtiles.size();
     // the three-body instantiation of the fused sweep only where the table really holds a narrow tile (on class-0 tiles alone it
     // is the slower kernel: c2_cartesian 151 -> 140 V-cycles/s)
+    // and the one-body class-1 instantiation where every tile is class 1 (tall tiles)
     dev.narrow7 = 0;
     for (const Tile& t : hftiles) if (t.pad_[1]) dev.narrow7 = 1;
+    dev.tall7 = tall ? 1 : 0;
     // every table: narrow classes where they save at least 15 % of the workgroup-marches (64-wide boxes: C5 62.8 -> 53.1 ms per
     // AMR V-cycle; 128-wide: C4 136.8 -> 111.6).  One 512-wide box, 5 equal columns against 4 + 4 narrow, is a wash or worse:
     // 19-point colour pass 3.02 -> 3.07 ms, residual 3.17 -> 3.42; c2_cartesian 151 -> 149-158 V-cycles/s depending on tile order)
@@ -800,7 +775,7 @@ void Level::define(const IBox& dom, const bool per[3], const double dx_[3], cons
     d_recv_items = DevBuf<CopyItem>::from(plan.recv_items);
     d_send_off = DevBuf<long long>::from(plan.send_itemoff);
     d_recv_off = DevBuf<long long>::from(plan.recv_itemoff);
-    build_march_tiles(false);
+    build_march_tiles(false, false);
     d_sendbuf = plan.send_total ? DevBuf<double>(plan.send_total) : DevBuf<double>();
     d_recvbuf = plan.recv_total ? DevBuf<double>(plan.recv_total) : DevBuf<double>();
 

@@ -133,8 +133,10 @@ public:
     std::vector<int> local;    // global box index of each local patch
     std::vector<PatchDesc> hpatches;
     std::vector<Tile> htiles;
-    void build_march_tiles(bool narrow7);   // (re)builds the marching kernels' tile tables below
-    bool narrow7_ = false;
+    // (re)builds the marching kernels' tile tables below.  tall7: the metric is known not to be uniform, so the fused sweep's
+    // table may take tall (all class-1) tiles where march_plan.h's rule allows them
+    void build_march_tiles(bool narrow7, bool tall7);
+    bool narrow7_ = false, tall7_ = false;
     std::vector<Tile> hftiles;   // tiles of the fused red-black sweep (gsrb_fused.hip)
     DevBuf<Tile> d_ftiles;
     int nftiles = 0;

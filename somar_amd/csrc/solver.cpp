@@ -388,7 +388,7 @@ void PressureSolver::finalize()
             fused19_[d] = ok ? 1 : 0;
             if (ok != L.want_fused19_) {
                 L.want_fused19_ = ok;
-                L.build_march_tiles(L.narrow7_);
+                L.build_march_tiles(L.narrow7_, L.tall7_);
             }
         }
     }
@@ -671,13 +671,16 @@ void PressureSolver::detect_metric_flags()
 
 // Narrow lane classes for the 7-point marching kernels where the metric is uniform (Level::build_march_tiles says why);
 // Tuning::narrow_7pt = 0 | 1 forces never / always (A/B).  d_partials holds two doubles per tile of the largest table: sized at
-// finalize, again when a table was rebuilt.
+// finalize, again when a table was rebuilt.  Where the metric is not uniform the fused sweep's table may take tall tiles
+// (march_plan.h; Tuning::narrow_7pt = 0 and Tuning::no_narrow_tiles keep the equal columns).
 void PressureSolver::choose_narrow_tiles()
 {
     bool rebuilt = false;
     for (auto& Lp : lev) {
         const bool want = tune_.narrow_7pt >= 0 ? tune_.narrow_7pt != 0 : Lp->dev.P.uniform != 0;
-        if (want != Lp->narrow7_) { Lp->build_march_tiles(want); rebuilt = true; }
+        // (march_plan::tall_eligible holds the rule, the metric flag included; here only: can the fused sweep run on this level?)
+        const bool tall = !full_ && Lp->dev.P.uniform == 0 && Lp->active[0] && Lp->active[1] && Lp->active[2];
+        if (want != Lp->narrow7_ || tall != Lp->tall7_) { Lp->build_march_tiles(want, tall); rebuilt = true; }
     }
     if (d_partials && !rebuilt) return;
     int maxTiles = 1;

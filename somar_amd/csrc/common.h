@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 
+#include "march_plan.h"   // Tile: the work item of a sweep kernel
+
 namespace somar {
 
 // Error convention of the C ABI (include/somar_amd.h): 0 ok, <0 failure.  Inside the
@@ -51,13 +53,6 @@ struct PatchDesc {
     long long off;  // offset of local cell (0,0,0)
 };
 
-// Work item of a sweep kernel: a (128 x 4 x nk) brick of one patch.
-struct Tile {
-    int patch;
-    int i0, j0, k0;  // local start
-    int nk;
-    int pad_[3];
-};
 // a pair of cells of one field (the marching kernels hold one per lane), for either element type of a field: fp64, or fp32 on the
 // depths of an opt-in mixed-precision cycle (PressureSolver::set_precision)
 template <class T> struct Vec2;
@@ -102,13 +97,17 @@ struct GhostOp {
     int dir, sgn;    // EXTRAP / NEUM / DIRI: direction and side sign (+1 high, -1 low)
     int order;       // EXTRAP: 0, 1 or 2
     int dstf, srcf;  // 0 = phi, 1 = psi (the extrapolated copy)
-    int pad_;
+    // the op's stage in its ghost program.  In the box-sorted copy of a program (PressureSolver::upload_program, k_ghost_program)
+    // the upper half counts the ops of the same stage that follow: stage | following << 16 (ghost_stage / ghost_following)
+    int stage;
     union {
         double val;      // DIRI: the boundary value of that side
         long long voff;  // DIRI_FACE: start of this op's slice of the level's face-value buffer (LevelDev::bc_face), one
                          // value per cell of the region in the op's own loop order (i fastest)
     };
 };
+__host__ __device__ inline int ghost_stage(int packed) { return packed & 0xffff; }
+__host__ __device__ inline int ghost_following(int packed) { return packed >> 16; }
 // k_ghost_program stages GP_MAX_OPS of these in LDS with 16-byte copies
 static_assert(sizeof(GhostOp) == 64 && sizeof(GhostOp) % 16 == 0, "GhostOp must stay 64 bytes (LDS staging, int4 copy)");
 

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(64 * FF_J) void k_full_fused(const Tile* __restrict
     const int lane = threadIdx.x, row = threadIdx.y;
     const int ri = 2 * lane;
     const int li = t.i0 - 2 + ri;  // even: rows are 16-byte aligned
-    const int wi = t.pad_[0] > 0 ? t.pad_[0] : FF_I - 4;
+    const int wi = t.w > 0 ? t.w : FF_I - 4;
     const int lj = t.j0 - 2 + row;
     const int gj = p.lo[1] + lj;
 
@@ -333,18 +333,18 @@ __global__ __launch_bounds__(64 * FF_J) void k_full_fused(const Tile* __restrict
     }
 }
 
-void launch_full_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* out, const double* phi,
+void launch_full_fused(hipStream_t st, TileSpan tiles, const LevelDev& L, double* out, const double* phi,
                        const double* psi, const double* rhs)
 {
-    if (ntiles == 0) return;
+    if (tiles.n == 0) return;
     JgFullF J;
     for (int d = 0; d < 3; ++d)
         for (int c = 0; c < 3; ++c) J.c[d][c] = L.jgf[d][c];
     if (L.P.zero_xy)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_full_fused<true>), dim3(ntiles), dim3(64, FF_J, 1), 0, st, tiles, L.patches, out, phi,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_full_fused<true>), dim3(tiles.n), dim3(64, FF_J, 1), 0, st, tiles.p, L.patches, out, phi,
                            psi, rhs, J, L.jinv, L.P);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_full_fused<false>), dim3(ntiles), dim3(64, FF_J, 1), 0, st, tiles, L.patches, out, phi,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_full_fused<false>), dim3(tiles.n), dim3(64, FF_J, 1), 0, st, tiles.p, L.patches, out, phi,
                            psi, rhs, J, L.jinv, L.P);
 }
 

@@ -56,7 +56,7 @@ __device__ __forceinline__ double fm_pick(const double2& v, int s) { return s ? 
 // ZXY: J g^{xy} on x-faces and J g^{yx} on y-faces are identically zero (StencilParams::zero_xy): those two planes are not
 // streamed -- three of the pass's thirteen coefficient loads per plane -- and zeros stand in for them; the products are the
 // zeros the stored planes would give (up to the sign of zero).
-// CLS: the tile's lane class (Tile::pad_[1], Level::define): a wavefront covers 2^CLS region rows of 128 >> CLS columns each.
+// CLS: the tile's lane class (Tile::cls, march_plan.h): a wavefront covers 2^CLS region rows of 128 >> CLS columns each.
 // CLS 0 = one 128-column row per wavefront (124 output columns); CLS 1 = two 64-column rows (60 output columns: a 64-wide
 // box is one such tile + a 4-wide one instead of a tile that leaves 30 of 64 lanes idle); CLS 4 = sixteen 8-column rows (the
 // 4-column remainder of a box, 128 -> 124 + 4).  Region rows of a wavefront have the same parity (row = 2^(CLS+1) (y / 2) +
@@ -80,7 +80,7 @@ __device__ __forceinline__ void full_march_body(double* __restrict__ SP, double*
                              : (int)(((threadIdx.y >> 1) << (CLS + 1)) + (threadIdx.y & 1) + 2 * (threadIdx.x >> (6 - CLS)));
     const int ri = 2 * lane;
     const int li = t.i0 - 2 + ri;  // even: rows are 16-byte aligned
-    const int wi = t.pad_[0] > 0 ? t.pad_[0] : 2 * LPR - 4;
+    const int wi = t.w > 0 ? t.w : 2 * LPR - 4;
     const int lj = t.j0 - 1 + row;
     const int gj = p.lo[1] + lj;
 
@@ -350,7 +350,7 @@ __global__ __launch_bounds__(64 * FM_J, (NARROW && !ZXY && MODE == 1) ? 3 : 1) v
     __shared__ __attribute__((aligned(16))) double SE[FM_S * FM_J * (NARROW ? 160 : 128)];  // E: phi inside the box, psi in its frame
     const Tile t = tiles[blockIdx.x];
     const PatchDesc p = patches[t.patch];
-    const int cls = NARROW ? t.pad_[1] : 0;
+    const int cls = NARROW ? t.cls : 0;
     if (!NARROW || cls == 0) full_march_body<MODE, FM_J, ZXY, 0>(SP, SE, t, p, out, phi, psi, rhs, J, jinv, P, color, phi2);
     else if (cls == 1) full_march_body<MODE, FM_J, ZXY, NARROW ? 1 : 0>(SP, SE, t, p, out, phi, psi, rhs, J, jinv, P, color, phi2);
     else full_march_body<MODE, FM_J, ZXY, NARROW ? 4 : 0>(SP, SE, t, p, out, phi, psi, rhs, J, jinv, P, color, phi2);
@@ -366,12 +366,12 @@ static JgFullM jgfullm(const LevelDev& L)
 
 // mode 0: out = rhs - L[phi], 1: out = L[phi], 2: one GSRB colour pass.  psi needs to be right only in the one-cell frame of every box.
 template <int MODE>
-static void launch_march(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* out, const double* phi,
-                         const double* psi, const double* rhs, int color, const double* phi2 = nullptr, bool narrow = false)
+static void launch_march(hipStream_t st, TileSpan tiles, const LevelDev& L, double* out, const double* phi,
+                         const double* psi, const double* rhs, int color, const double* phi2 = nullptr)
 {
-    const bool six = L.full_rows == 6, z = L.P.zero_xy != 0, nw = L.narrowq != 0 || narrow;   // (6-row tables never hold narrow classes)
+    const bool six = L.full_rows == 6, z = L.P.zero_xy != 0, nw = tiles.classes != 0;   // (6-row tables never hold narrow classes)
 #define SOMAR_FM(ROWS, Z, N)                                                                                                   \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_full_march<MODE, ROWS, Z, N>), dim3(ntiles), dim3(64, ROWS, 1), 0, st, tiles, L.patches, \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_full_march<MODE, ROWS, Z, N>), dim3(tiles.n), dim3(64, ROWS, 1), 0, st, tiles.p, L.patches, \
                        out, phi, psi, rhs, jgfullm(L), L.jinv, L.P, color, phi2)
     if (six) { if (z) SOMAR_FM(6, true, false); else SOMAR_FM(6, false, false); }
     else if (nw) { if (z) SOMAR_FM(8, true, true); else SOMAR_FM(8, false, true); }
@@ -379,32 +379,32 @@ static void launch_march(hipStream_t st, const Tile* tiles, int ntiles, const Le
 #undef SOMAR_FM
 }
 
-void launch_full_march(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* out, const double* phi,
+void launch_full_march(hipStream_t st, TileSpan tiles, const LevelDev& L, double* out, const double* phi,
                        const double* psi, const double* rhs, int mode)
 {
-    if (ntiles == 0) return;
-    if (mode == 0) launch_march<0>(st, tiles, ntiles, L, out, phi, psi, rhs, 0);
-    else launch_march<1>(st, tiles, ntiles, L, out, phi, psi, rhs, 0);
+    if (tiles.n == 0) return;
+    if (mode == 0) launch_march<0>(st, tiles, L, out, phi, psi, rhs, 0);
+    else launch_march<1>(st, tiles, L, out, phi, psi, rhs, 0);
 }
 
 // one colour pass of the 19-point GSRB: out = phi with the cells of `color` relaxed (out != phi)
-void launch_gsrb_full_march(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* out,
+void launch_gsrb_full_march(hipStream_t st, TileSpan tiles, const LevelDev& L, double* out,
                             const double* phi, const double* psi, const double* rhs, int color)
 {
-    if (ntiles == 0) return;
-    launch_march<2>(st, tiles, ntiles, L, out, phi, psi, rhs, color);
+    if (tiles.n == 0) return;
+    launch_march<2>(st, tiles, L, out, phi, psi, rhs, color);
 }
 
 }  // namespace somar
 
 namespace somar {
 // the black cells of the three outer layers of every box after k_full_fused (full19_fused.hip): in place on phi, their same-colour
-// neighbours from phi_in (the sweep's input); tiles = Level::d_stiles (box faces only, narrow classes on the x faces)
-void launch_gsrb_full_shell(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* phi, const double* phi_in,
+// neighbours from phi_in (the sweep's input); tiles = Level::stiles (box faces only, narrow classes on the x faces)
+void launch_gsrb_full_shell(hipStream_t st, TileSpan tiles, const LevelDev& L, double* phi, const double* phi_in,
                             const double* psi, const double* rhs)
 {
-    if (ntiles == 0) return;
+    if (tiles.n == 0) return;
     SOMAR_CHECK(L.full_rows == 8, "internal: the shell pass uses the 8-row marching kernels");
-    launch_march<3>(st, tiles, ntiles, L, phi, phi, psi, rhs, 1, phi_in, true);
+    launch_march<3>(st, tiles, L, phi, phi, psi, rhs, 1, phi_in);
 }
 }  // namespace somar

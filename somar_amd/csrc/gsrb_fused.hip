@@ -164,7 +164,7 @@ __device__ __forceinline__ void gsrb_fused_body(T* __restrict__ S, const Tile& t
     const int ri = 2 * lane;       // region column of the pair's first cell
     const int li = t.i0 - 2 + ri;  // local i of the pair's first cell (even: rows are 16-byte aligned)
     // output columns of this tile (even, <= region width - 4); the region beyond wi + 4 columns is neither loaded nor computed
-    const int wi = t.pad_[0] > 0 ? t.pad_[0] : 2 * LPR - 4;
+    const int wi = t.w > 0 ? t.w : 2 * LPR - 4;
     const int lj = t.j0 - 2 + row;
     // INMODE 3/4: where this pair's coarse parents live (floor division: ghosts map to coarse ghosts)
     long long cbase = 0, cpk = 0, coff = 0;
@@ -417,12 +417,12 @@ __global__ __launch_bounds__(64 * FR_J) void k_gsrb_fused(const Tile* __restrict
     __shared__ __attribute__((aligned(16))) T S[3 * FR_J * (NARROW == 1 ? 160 : 128)];
     const Tile t = tiles[blockIdx.x];
     const PatchDesc p = patches[t.patch];
-    const int cls = NARROW == 1 ? t.pad_[1] : (NARROW == 2 ? 1 : 0);
+    const int cls = NARROW == 1 ? t.cls : (NARROW == 2 ? 1 : 0);
     bool lean = false;
     if (UNI && !DIRI) {
         // does the tile grown by its red ring stay clear of every domain face (periodic seams included: the boundary form of
         // the update applies there too) and of every coarse-fine face, in x and y?  One scalar test per workgroup.
-        const int wi = t.pad_[0] > 0 ? t.pad_[0] : 124;
+        const int wi = t.w > 0 ? t.w : 124;
         const int ilo = t.i0 - 1, ihi = min(t.i0 + wi, p.n[0]), jlo = t.j0 - 1, jhi = min(t.j0 + (FR_J << cls) - 4, p.n[1]);
         lean = lean_ok && p.lo[0] + ilo > P.dom_lo[0] && p.lo[0] + ihi < P.dom_hi[0] && p.lo[1] + jlo > P.dom_lo[1] &&
                p.lo[1] + jhi < P.dom_hi[1] && !((p.cf & 1) && ilo < 0) && !((p.cf & 2) && ihi >= p.n[0]) &&
@@ -447,17 +447,17 @@ __global__ __launch_bounds__(64 * FR_J) void k_gsrb_fused(const Tile* __restrict
 
 // M: the level's coefficient arrays in T (L.jg / L.jinv, or their fp32 copies)
 template <class T>
-static void launch_gsrb_fused_t(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, const MetricPtrs<T>& M,
+static void launch_gsrb_fused_t(hipStream_t st, TileSpan tiles, const LevelDev& L, const MetricPtrs<T>& M,
                                 T* phi_out, const T* phi_in, const T* rhs, int in_mode, const double* sums,
                                 const LevelDev* C, const T* crse, const int* r)
 {
-    if (ntiles == 0) return;
+    if (tiles.n == 0) return;
     const PatchDesc* cpatches = C ? C->patches : nullptr;
     const int r0 = r ? r[0] : 1, r1 = r ? r[1] : 1, r2 = r ? r[2] : 1;
     SOMAR_CHECK(in_mode < 3 || ((r0 == 1 || r0 == 2) && (r1 == 1 || r1 == 2) && (r2 == 1 || r2 == 2)),
                 "internal: the prolongation folded into a sweep takes multigrid ratios of 1 or 2 per direction");
     auto go = [&](auto kern, int rows) {
-        hipLaunchKernelGGL(kern, dim3(ntiles), dim3(64, rows, 1), 0, st, tiles, L.patches, phi_out, phi_in, rhs, M.jg[0], M.jg[1],
+        hipLaunchKernelGGL(kern, dim3(tiles.n), dim3(64, rows, 1), 0, st, tiles.p, L.patches, phi_out, phi_in, rhs, M.jg[0], M.jg[1],
                            M.jg[2], M.jinv, L.P, sums, cpatches, crse, r0, r1, r2, L.lean_tiles);
     };
     // (rows, mode, Dirichlet sides, uniform metric, narrow lane classes in the tile table: 0 none, 1 mixed, 2 all class 1)
@@ -470,8 +470,8 @@ static void launch_gsrb_fused_t(hipStream_t st, const Tile* tiles, int ntiles, c
         default: go(k_gsrb_fused<ROWS, M0, D, U, N, T>, ROWS);                  \
     }
     const bool rows16 = L.fused_rows == 16;
-    const bool narrow = L.narrow7 != 0 && rows16;   // Level::build_march_tiles hands the 8-row kernels class-0 tiles only
-    const bool tall = L.tall7 != 0;                 // ... and tall tiles to the 16-row kernels of a non-uniform metric only
+    const bool narrow = tiles.classes != 0 && rows16;   // march_plan::fused_shape hands the 8-row kernels class-0 tiles only
+    const bool tall = tiles.classes == 2;               // ... and tall tiles to the 16-row kernels of a non-uniform metric only
     SOMAR_CHECK(!tall || (rows16 && !L.P.uniform), "internal: tall tiles on a level whose fused sweep has no class-1 kernel");
     bool diri = false;
     for (int d = 0; d < 3; ++d) diri = diri || L.P.diri[d][0] || L.P.diri[d][1];
@@ -497,21 +497,21 @@ static void launch_gsrb_fused_t(hipStream_t st, const Tile* tiles, int ntiles, c
 #undef SOMAR_FUSED_MODES
 }
 
-void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, const MetricPtrs<double>& M,
+void launch_gsrb_fused(hipStream_t st, TileSpan tiles, const LevelDev& L, const MetricPtrs<double>& M,
                        double* phi_out, const double* phi_in, const double* rhs, int in_mode, const double* sums,
                        const LevelDev* C, const double* crse, const int* r)
 {
-    launch_gsrb_fused_t<double>(st, tiles, ntiles, L, M, phi_out, phi_in, rhs, in_mode, sums, C, crse, r);
+    launch_gsrb_fused_t<double>(st, tiles, L, M, phi_out, phi_in, rhs, in_mode, sums, C, crse, r);
 }
 
-void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, const MetricPtrs<float>& M,
+void launch_gsrb_fused(hipStream_t st, TileSpan tiles, const LevelDev& L, const MetricPtrs<float>& M,
                        float* phi_out, const float* phi_in, const float* rhs, int in_mode, const double* sums,
                        const LevelDev* C, const float* crse, const int* r)
 {
     // the fp32 copies of a uniform depth are not made (PressureSolver::mp_convert_metric): only the UNI kernels may run without them
     SOMAR_CHECK(fused_uniform_kernel(L) || (M.jg[0] && M.jg[1] && M.jg[2] && M.jinv),
                 "internal: the fused sweep streams the metric of this depth, but its fp32 copies are missing");
-    launch_gsrb_fused_t<float>(st, tiles, ntiles, L, M, phi_out, phi_in, rhs, in_mode, sums, C, crse, r);
+    launch_gsrb_fused_t<float>(st, tiles, L, M, phi_out, phi_in, rhs, in_mode, sums, C, crse, r);
 }
 
 // the launcher's choice above: the uniform-metric kernels (coefficients from StencilParams::uc, no array read) run on a uniform

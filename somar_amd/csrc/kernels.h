@@ -4,6 +4,15 @@
 
 namespace somar {
 
+// A tile table on the device as a launcher takes it (TileTable::span, level.h).  classes is how the table was planned
+// (march_plan::Table): 0 every tile is class 0, 1 it holds narrow lane classes, 2 every tile is class 1 (tall tiles).  The
+// launchers pick the kernel instantiation from it: a table cannot reach a kernel that misreads its tiles.
+struct TileSpan {
+    const Tile* p = nullptr;
+    int n = 0;
+    int classes = 0;
+};
+
 // Device-side view of one (AMR level, MG depth): tables + coefficient planes in HBM.
 struct LevelDev {
     const Tile* tiles = nullptr;        // XCD-contiguous order
@@ -25,9 +34,6 @@ struct LevelDev {
     // position-dependent Dirichlet values of this level (depth 0 only): the slices GHOST_DIRI_FACE ops read at GhostOp::voff
     // (PressureSolver::build_face_slices); the address never changes after finalize
     const double* bc_face = nullptr;
-    int narrow7 = 0;                    // the 7-point marching kernels' tile tables hold narrow lane classes (Level::build_march_tiles)
-    int tall7 = 0;                      // every tile of the fused sweep's table is class 1 (march_plan.h: tall tiles)
-    int narrowq = 0;                    // the 19-point marching kernels' tile table does
     // what the launchers take from the solver's Tuning (Level::define copies it here)
     int fused_rows = 16;                // region rows per workgroup of the fused 7-point sweep (tile rows = rows - 4): 16 or 8
     int full_rows = 8;                  // ... of the 19-point marching kernels: 8 or 6
@@ -51,21 +57,21 @@ void launch_ghost_ops(hipStream_t st, const LevelDev& L, const GhostOp* ops, int
                       bool bc_homog = true, bool redirect = false);
 // homogeneous physical ghosts of an fp32 field (mixed-precision depths; ops without cross terms)
 void launch_ghost_ops(hipStream_t st, const LevelDev& L, const GhostOp* ops, int nops, float* phi);
-// a whole ghost program in one launch, one workgroup per box (ops sorted by box, then stage = GhostOp::pad_; box b owns
+// a whole ghost program in one launch, one workgroup per box (ops sorted by box, then GhostOp::stage; box b owns
 // box_ops[box_first[b] .. box_first[b + 1])); copy_all: psi := phi on every box grown by one cell first
 void launch_ghost_program(hipStream_t st, const LevelDev& L, const GhostOp* box_ops, const int* box_first, double* phi,
                           double* psi, bool bc_homog, bool redirect, bool copy_all);
 // k-marching 19-point operator / residual (mode 0: out = rhs - L[phi], 1: out = L[phi]) and one GSRB colour pass
 // (out = phi with the colour's cells relaxed; out != phi); psi valid in the one-cell frames only (full19_march.hip)
-void launch_full_march(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* out, const double* phi,
+void launch_full_march(hipStream_t st, TileSpan tiles, const LevelDev& L, double* out, const double* phi,
                        const double* psi, const double* rhs, int mode);
-void launch_gsrb_full_march(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* out,
+void launch_gsrb_full_march(hipStream_t st, TileSpan tiles, const LevelDev& L, double* out,
                             const double* phi, const double* psi, const double* rhs, int color);
 // red + black in one launch for the cells three layers inside their box (full19_fused.hip), then -- after the between-colour
 // ghost work on `out` -- the black cells of the outer layers in place (full19_march.hip, MODE 3)
-void launch_full_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* out, const double* phi,
+void launch_full_fused(hipStream_t st, TileSpan tiles, const LevelDev& L, double* out, const double* phi,
                        const double* psi, const double* rhs);
-void launch_gsrb_full_shell(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* phi, const double* phi_in,
+void launch_gsrb_full_shell(hipStream_t st, TileSpan tiles, const LevelDev& L, double* phi, const double* phi_in,
                             const double* psi, const double* rhs);
 void launch_flux_full(hipStream_t st, const LevelDev& L, double* const out[3], const double* phi, const double* psi);
 void launch_op_full(hipStream_t st, const LevelDev& L, double* out, const double* phi, const double* psi,
@@ -82,23 +88,23 @@ void launch_gsrb_ortho(hipStream_t st, const LevelDev& L, double* phi, const dou
 // (value - sums[0]/sums[1]) (deferred mean removal of the zero-average prolongation); 3: phi_in is read as
 // value + crse(i / r) (prolongation folded in; C = coarse level, crse exchanged one deep); 4: 3 and 2 together
 // M: the level's coefficient arrays in the fields' element type (metric_ptrs(L), or the fp32 copies)
-void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, const MetricPtrs<double>& M,
+void launch_gsrb_fused(hipStream_t st, TileSpan tiles, const LevelDev& L, const MetricPtrs<double>& M,
                        double* phi_out, const double* phi_in, const double* rhs, int in_mode, const double* sums,
                        const LevelDev* C, const double* crse, const int* r);
 // the same sweep on fp32 fields and coefficients (mixed-precision depths); sums stay fp64
-void launch_gsrb_fused(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, const MetricPtrs<float>& M,
+void launch_gsrb_fused(hipStream_t st, TileSpan tiles, const LevelDev& L, const MetricPtrs<float>& M,
                        float* phi_out, const float* phi_in, const float* rhs, int in_mode, const double* sums,
                        const LevelDev* C, const float* crse, const int* r);
 // whether launch_gsrb_fused takes a uniform-metric kernel on this level (it then reads none of the four coefficient arrays)
 bool fused_uniform_kernel(const LevelDev& L);
 // k-marching operator/residual of a large level (resid_march.hip); mode 0: out = rhs - L[phi], 1: out = L[phi]
-void launch_resid_march(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* out,
+void launch_resid_march(hipStream_t st, TileSpan tiles, const LevelDev& L, double* out,
                         const double* phi, const double* rhs, int mode);
-void launch_resid_restrict(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const MetricPtrs<double>& M,
+void launch_resid_restrict(hipStream_t st, TileSpan tiles, const LevelDev& F, const MetricPtrs<double>& M,
                            const LevelDev& C, double* crse, const double* phi, const double* rhs, const int r[3],
                            double dxProduct, double* volsum);
 // the same on fp32 fields and coefficients (mixed-precision depths); volsum is accumulated in fp64
-void launch_resid_restrict(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const MetricPtrs<float>& M,
+void launch_resid_restrict(hipStream_t st, TileSpan tiles, const LevelDev& F, const MetricPtrs<float>& M,
                            const LevelDev& C, float* crse, const float* phi, const float* rhs, const int r[3],
                            double dxProduct, double* volsum);
 // crse(ic) = sum over the children of ic of dxProduct / fjinv(child): the volume a coarse value is spread over
@@ -111,7 +117,7 @@ void launch_combine_sums(hipStream_t st, double* out, const double* a, const dou
 // LineGSRBIter2D (space_dim 2: lines along y); maxN0: the widest local box in x
 void launch_line_gsrb_2d(hipStream_t st, const LevelDev& L, int maxN0, double* phi, const double* rhs, double* dmod, int color,
                          const double* psi);
-void launch_line_gsrb_ortho(hipStream_t st, const Tile* ctiles, int nctiles, int tile_j, const LevelDev& L,
+void launch_line_gsrb_ortho(hipStream_t st, TileSpan ctiles, int tile_j, const LevelDev& L,
                             double* phi, const double* rhs, double* dmod, int color, const double* psi = nullptr);
 void launch_op_ortho(hipStream_t st, const LevelDev& L, double* out, const double* phi, const double* rhs, int mode,
                      bool pull = false);

@@ -204,10 +204,9 @@ void LepticSolver::finalize()
             flatOf[pi] = fp;
         }
         std::vector<Tile> st;
-        for (const Tile& t : V.hctiles)
+        for (const Tile& t : V.ctiles.host())
             if (flatPatch[V.local[t.patch]] >= 0) st.push_back(t);
-        nstiles = (int)st.size();
-        d_stiles = DevBuf<Tile>::from(st);
+        stiles_.assign(std::move(st), 0);
         d_flatOf = DevBuf<PatchDesc>::from(flatOf);
     } else {
         SOMAR_CHECK(V.npatches() == F.npatches(), "internal: layouts differ");
@@ -221,8 +220,8 @@ void LepticSolver::finalize()
     }
     launch_set(st_, V.dev.jinv, V.field_elems, 1.0);
     // metric of the flat problem: vertical average of the horizontal components, J^{-1} := 1
-    if (full_) launch_lep_avg_metric_full(st_, V.d_ctiles, V.nctiles, V.ctile_j, V.dev, F.dev);
-    else launch_lep_avg_metric(st_, span_tiles(), span_ntiles(), V.ctile_j, V.dev, flat_dev());
+    if (full_) launch_lep_avg_metric_full(st_, V.ctiles.span(), V.ctile_j, V.dev, F.dev);
+    else launch_lep_avg_metric(st_, span_tiles(), V.ctile_j, V.dev, flat_dev());
     launch_set(st_, F.dev.jinv, F.field_elems, 1.0);
     sync();
     vert_->finalize();
@@ -270,8 +269,8 @@ void LepticSolver::refresh_metric()
     launch_set(st_, V.dev.jinv, V.field_elems, 1.0);
     if (doHorizSolve_) {
         Level& F = horiz_->level(0);
-        if (full_) launch_lep_avg_metric_full(st_, V.d_ctiles, V.nctiles, V.ctile_j, V.dev, F.dev);
-        else launch_lep_avg_metric(st_, span_tiles(), span_ntiles(), V.ctile_j, V.dev, flat_dev());
+        if (full_) launch_lep_avg_metric_full(st_, V.ctiles.span(), V.ctile_j, V.dev, F.dev);
+        else launch_lep_avg_metric(st_, span_tiles(), V.ctile_j, V.dev, flat_dev());
         launch_set(st_, F.dev.jinv, F.field_elems, 1.0);
     }
     sync();
@@ -303,8 +302,8 @@ void LepticSolver::solve_fields_no_horiz(double* a_phi, const double* a_rhs, Lep
 {
     PressureSolver &Os = *orig_, &Vs = *vert_;
     Level& V = Vs.level(0);
-    const Tile* ct = V.d_ctiles;
-    const int nct = V.nctiles, tj = V.ctile_j;
+    const TileSpan ct = V.ctiles.span();
+    const int tj = V.ctile_j;
     const long long n = V.field_elems;
     const int maxOrder = prm.maxOrder;
     double* vertPhi = Vs.phi();
@@ -312,7 +311,7 @@ void LepticSolver::solve_fields_no_horiz(double* a_phi, const double* a_rhs, Lep
     double* tmpP = f_rhsB;
     S = LepticStats();
     Os.residual(0, rhsP, a_phi, a_rhs, homogeneous);
-    launch_lep_divide(st_, ct, nct, tj, V.dev, rhsP, rhsP, Os.level(0).dev.jinv);
+    launch_lep_divide(st_, ct, tj, V.dev, rhsP, rhsP, Os.level(0).dev.jinv);
     double resNorm = Vs.norm(0, rhsP, prm.normType);
     S.resNorms.push_back(resNorm);
     launch_set(st_, f_total, n, 0.0);
@@ -320,7 +319,7 @@ void LepticSolver::solve_fields_no_horiz(double* a_phi, const double* a_rhs, Lep
     for (int order = 0; order <= maxOrder; ++order) {
         S.orders = order + 1;
         // a Neumann end rolls in the boundary data, which stay zero without horizontal solves: rhs + 0
-        launch_lep_vsolve_lapack(st_, ct, nct, tj, V.dev, vertPhi, rhsP, f_gam, f_efac, d_vbc, dx_[2], dzCrse_, d_bad);
+        launch_lep_vsolve_lapack(st_, ct, tj, V.dev, vertPhi, rhsP, f_gam, f_efac, d_vbc, dx_[2], dzCrse_, d_bad);
         Vs.residual(0, tmpP, vertPhi, rhsP);
         resNorm = Vs.norm(0, tmpP, prm.normType);
         double relResNorm = resNorm / S.resNorms[0];
@@ -338,7 +337,7 @@ void LepticSolver::solve_fields_no_horiz(double* a_phi, const double* a_rhs, Lep
         S.resNorms.push_back(resNorm);
         redu = prevRelResNorm - relResNorm;
         if (redu > prm.hang || order < maxOrder) {
-            launch_lep_axpy(st_, ct, nct, tj, V.dev, f_total, vertPhi, 1.0);
+            launch_lep_axpy(st_, ct, tj, V.dev, f_total, vertPhi, 1.0);
             exitStatus = (order < maxOrder - 1) ? 0 : 1;
         } else if (-redu > prm.hang) {
             exitStatus = (order == 0) ? 4 : 3;
@@ -348,7 +347,7 @@ void LepticSolver::solve_fields_no_horiz(double* a_phi, const double* a_rhs, Lep
             break;
         }
     }
-    if (exitStatus != 4) launch_lep_axpy(st_, ct, nct, tj, V.dev, a_phi, f_total, 1.0);
+    if (exitStatus != 4) launch_lep_axpy(st_, ct, tj, V.dev, a_phi, f_total, 1.0);
     S.exitStatus = exitStatus;
     check_bad();
 }
@@ -374,11 +373,10 @@ void LepticSolver::solve_fields(double* a_phi, const double* a_rhs, LepticStats&
     PressureSolver &Os = *orig_, &Vs = *vert_, &Hs = *horiz_;
     Level& V = Vs.level(0);
     Level& F = Hs.level(0);
-    const Tile* ct = V.d_ctiles;
-    const int nct = V.nctiles, tj = V.ctile_j;
+    const TileSpan ct = V.ctiles.span();
+    const int tj = V.ctile_j;
     // the kernels that pair a column with its flat cell run on the spanning boxes: every box, unless the level is mixed
-    const Tile* sct = span_tiles();
-    const int nsct = span_ntiles();
+    const TileSpan sct = span_tiles();
     const LevelDev Fd = flat_dev();
     const long long n = V.field_elems, hn = F.field_elems;
     const int maxOrder = prm.maxOrder;
@@ -391,7 +389,7 @@ void LepticSolver::solve_fields(double* a_phi, const double* a_rhs, LepticStats&
 
     // J * residual of the level's own operator                                                   :697-715
     Os.residual(0, rhsP, a_phi, a_rhs, homogeneous);
-    launch_lep_divide(st_, ct, nct, tj, V.dev, rhsP, rhsP, Os.level(0).dev.jinv);
+    launch_lep_divide(st_, ct, tj, V.dev, rhsP, rhsP, Os.level(0).dev.jinv);
     double resNorm = Vs.norm(0, rhsP, prm.normType);
     S.resNorms.push_back(resNorm);
     launch_set(st_, f_total, n, 0.0);
@@ -406,20 +404,20 @@ void LepticSolver::solve_fields(double* a_phi, const double* a_rhs, LepticStats&
             launch_set(st_, h_bcHi, hn, 0.0);
             if (full_) {
                 Vs.run_aux_program(1, vertPhi);   // ExtrapolateFaceAndCopy in z, lo then hi, order 2, in place
-                launch_lep_vhgrad(st_, ct, nct, tj, V.dev, Fd, vertPhi, h_bcLo, h_bcHi, -1.0);
+                launch_lep_vhgrad(st_, ct, tj, V.dev, Fd, vertPhi, h_bcLo, h_bcHi, -1.0);
             }
         }
         if (order >= 1 && useExcess) launch_incr(st_, h_bcHi, h_excess, 1.0, hn);
         if (useExcess) {
-            launch_lep_excess(st_, sct, nsct, tj, V.dev, Fd, rhsP, h_bcLo, h_bcHi, h_excess, -1.0 * dz);
+            launch_lep_excess(st_, sct, tj, V.dev, Fd, rhsP, h_bcLo, h_bcHi, h_excess, -1.0 * dz);
             if (order == 1) useExcess = false;
         }
         if (order == 0 && useExcess) launch_incr(st_, h_bcHi, h_excess, -1.0, hn);
 
         // the complement's Neumann ends roll in boundary data that stay zero for a diagonal metric: rhs + 0
-        if (mixed_) launch_lep_vsolve_mixed(st_, ct, nct, tj, V.dev, d_flatOf, vertPhi, rhsP, f_gam, f_efac, h_bcLo, h_bcHi, d_vbc,
+        if (mixed_) launch_lep_vsolve_mixed(st_, ct, tj, V.dev, d_flatOf, vertPhi, rhsP, f_gam, f_efac, h_bcLo, h_bcHi, d_vbc,
                                             dz, dzCrse_, d_bad);
-        else launch_lep_vsolve(st_, ct, nct, tj, V.dev, Fd, vertPhi, rhsP, f_gam, h_bcLo, h_bcHi, dz);
+        else launch_lep_vsolve(st_, ct, tj, V.dev, Fd, vertPhi, rhsP, f_gam, h_bcLo, h_bcHi, dz);
 
         if (useHorizPhi) {
             if (full_) {
@@ -430,13 +428,13 @@ void LepticSolver::solve_fields(double* a_phi, const double* a_rhs, LepticStats&
                     Vs.cf_ev(0, vertPhi);
                     V.exchange(vertPhi, st_);
                 }
-                launch_lep_hgrad_full(st_, ct, nct, tj, V.dev, Fd, vertPhi, h_gx, h_gy);
+                launch_lep_hgrad_full(st_, ct, tj, V.dev, Fd, vertPhi, h_gx, h_gy);
             } else {
                 if (hasCF_) V.cf_homog(vertPhi, st_);
                 V.exchange(vertPhi, st_);
-                launch_lep_hgrad(st_, sct, nsct, tj, V.dev, Fd, vertPhi, h_gx, h_gy);
+                launch_lep_hgrad(st_, sct, tj, V.dev, Fd, vertPhi, h_gx, h_gy);
             }
-            launch_lep_hrhs(st_, sct, nsct, tj, V.dev, Fd, h_gx, h_gy, h_excess, Hs.rhs(), -1.0 / dx_[0],
+            launch_lep_hrhs(st_, sct, tj, V.dev, Fd, h_gx, h_gy, h_excess, Hs.rhs(), -1.0 / dx_[0],
                             -1.0 / dx_[1], -1.0 / H_, useExcess);
             const double horizRhsNorm = Hs.norm(0, Hs.rhs(), prm.normType);
             if (prm.horizRhsTol * S.resNorms[0] > horizRhsNorm) useHorizPhi = false;
@@ -444,7 +442,7 @@ void LepticSolver::solve_fields(double* a_phi, const double* a_rhs, LepticStats&
         if (useHorizPhi) {
             Hs.solve(true, true, S.horizStats);
             if (horizRemoveAvg_) set_zero_avg(Hs.phi());
-            launch_lep_extrude(st_, sct, nsct, tj, V.dev, Fd, vertPhi, Hs.phi());
+            launch_lep_extrude(st_, sct, tj, V.dev, Fd, vertPhi, Hs.phi());
             ++S.horizSolves;
         }
 
@@ -473,7 +471,7 @@ void LepticSolver::solve_fields(double* a_phi, const double* a_rhs, LepticStats&
 
         redu = prevRelResNorm - relResNorm;
         if (redu > prm.hang || order < maxOrder) {
-            launch_lep_axpy(st_, ct, nct, tj, V.dev, f_total, vertPhi, 1.0);
+            launch_lep_axpy(st_, ct, tj, V.dev, f_total, vertPhi, 1.0);
             exitStatus = (order < maxOrder - 1) ? 0 : 1;
         } else if (-redu > prm.hang) {
             exitStatus = (order == 0) ? 4 : 3;
@@ -485,7 +483,7 @@ void LepticSolver::solve_fields(double* a_phi, const double* a_rhs, LepticStats&
         if (!full_) useHorizPhi = false;  // LevelGeometry::isDiagonal()
     }
 
-    if (exitStatus != 4) launch_lep_axpy(st_, ct, nct, tj, V.dev, a_phi, f_total, 1.0);
+    if (exitStatus != 4) launch_lep_axpy(st_, ct, tj, V.dev, a_phi, f_total, 1.0);
     S.exitStatus = exitStatus;
     if (mixed_) check_bad();
     else sync();

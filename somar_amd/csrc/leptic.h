@@ -110,12 +110,10 @@ private:
     // flat patch of vertical patch p at d_flatOf[p] (complement patches: unused, zeroed)
     bool mixed_ = false;
     std::vector<int> flatDI_;          // global box indices of the spanning boxes, ascending
-    DevBuf<Tile> d_stiles;             // the whole-column tiles of the spanning patches
-    int nstiles = 0;
+    TileTable stiles_;                 // the whole-column tiles of the spanning patches
     DevBuf<PatchDesc> d_flatOf;
     // tiles / flat view for the kernels that pair a column with its flat cell: the level's own where nothing is mixed
-    const Tile* span_tiles() const { return mixed_ ? d_stiles : vert_->level(0).d_ctiles; }
-    int span_ntiles() const { return mixed_ ? nstiles : vert_->level(0).nctiles; }
+    TileSpan span_tiles() const { return mixed_ ? stiles_.span() : vert_->level(0).ctiles.span(); }
     LevelDev flat_dev() const
     {
         LevelDev H = horiz_->level(0).dev;
@@ -124,34 +122,34 @@ private:
     }
 };
 
-void launch_lep_avg_metric(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H);
+void launch_lep_avg_metric(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H);
 // non-diagonal metric: the horizontal block averaged, MAPPEDMACGRAD with cross terms, LEPTICVERTHORIZGRAD
-void launch_lep_avg_metric_full(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H);
-void launch_lep_hgrad_full(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
+void launch_lep_avg_metric_full(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H);
+void launch_lep_hgrad_full(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H,
                            const double* phi, double* gx, double* gy);
-void launch_lep_vhgrad(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
+void launch_lep_vhgrad(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H,
                        const double* phi, double* bcLo, double* bcHi, double scale);
-void launch_lep_excess(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
+void launch_lep_excess(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H,
                        const double* rhs, const double* bcLo, const double* bcHi, double* excess, double dzScale);
-void launch_lep_vsolve(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
+void launch_lep_vsolve(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H,
                        double* phi, double* rhs, double* gam, const double* bcLo, const double* bcHi, double dz);
-void launch_lep_vsolve_lapack(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, double* phi,
+void launch_lep_vsolve_lapack(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, double* phi,
                               const double* rhs, double* dfac, double* efac, const int* vbc, double dz, double dzCrse, int* bad);
 // a mixed level: per tile the Neumann-Neumann sweep or the dptsv restatement, by vbc; flatOf[patch]: the flat patch of a
 // spanning box
-void launch_lep_vsolve_mixed(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const PatchDesc* flatOf,
+void launch_lep_vsolve_mixed(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const PatchDesc* flatOf,
                              double* phi, double* rhs, double* dfac, double* efac, const double* bcLo, const double* bcHi,
                              const int* vbc, double dz, double dzCrse, int* bad);
-void launch_lep_hgrad(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
+void launch_lep_hgrad(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H,
                       const double* phi, double* gx, double* gy);
-void launch_lep_hrhs(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
+void launch_lep_hrhs(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H,
                      const double* gx, const double* gy, const double* excess, double* hrhs, double sx, double sy,
                      double negInvH, bool useExcess);
-void launch_lep_extrude(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
+void launch_lep_extrude(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H,
                         double* phi, const double* flat);
-void launch_lep_divide(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, double* y, const double* x,
+void launch_lep_divide(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, double* y, const double* x,
                        const double* b);
-void launch_lep_axpy(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, double* y, const double* x,
+void launch_lep_axpy(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, double* y, const double* x,
                      double a);
 
 }  // namespace somar

@@ -474,39 +474,39 @@ __global__ __launch_bounds__(512) void k_lep_valid(const Tile* __restrict__ tile
 }
 
 // ---- launchers (V: the 3-D level, ctiles: its whole-column tiles; H: the flat level) ----------------------------
-#define LEP_GRID(nct, tj) dim3(nct), dim3(64, tj, 1), 0, st
+#define LEP_GRID(ct, tj) dim3((ct).n), dim3(64, tj, 1), 0, st, (ct).p
 
-void launch_lep_avg_metric(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H)
+void launch_lep_avg_metric(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H)
 {
-    if (nct) hipLaunchKernelGGL(k_lep_avg_metric, LEP_GRID(nct, tj), ct, V.patches, H.patches, V.jg[0], V.jg[1], H.jg[0], H.jg[1]);
+    if (ct.n) hipLaunchKernelGGL(k_lep_avg_metric, LEP_GRID(ct, tj), V.patches, H.patches, V.jg[0], V.jg[1], H.jg[0], H.jg[1]);
 }
-void launch_lep_excess(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
+void launch_lep_excess(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H,
                        const double* rhs, const double* bcLo, const double* bcHi, double* excess, double dzScale)
 {
-    if (nct) hipLaunchKernelGGL(k_lep_excess, LEP_GRID(nct, tj), ct, V.patches, H.patches, rhs, bcLo, bcHi, excess, dzScale);
+    if (ct.n) hipLaunchKernelGGL(k_lep_excess, LEP_GRID(ct, tj), V.patches, H.patches, rhs, bcLo, bcHi, excess, dzScale);
 }
-void launch_lep_vsolve(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
+void launch_lep_vsolve(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H,
                        double* phi, double* rhs, double* gam, const double* bcLo, const double* bcHi, double dz)
 {
-    if (nct) hipLaunchKernelGGL(k_lep_vsolve, LEP_GRID(nct, tj), ct, V.patches, H.patches, phi, rhs, V.jg[2], gam, bcLo, bcHi, dz);
+    if (ct.n) hipLaunchKernelGGL(k_lep_vsolve, LEP_GRID(ct, tj), V.patches, H.patches, phi, rhs, V.jg[2], gam, bcLo, bcHi, dz);
 }
-void launch_lep_vsolve_lapack(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, double* phi,
+void launch_lep_vsolve_lapack(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, double* phi,
                               const double* rhs, double* dfac, double* efac, const int* vbc, double dz, double dzCrse, int* bad)
 {
-    if (nct) hipLaunchKernelGGL(k_lep_vsolve_lapack, LEP_GRID(nct, tj), ct, V.patches, phi, rhs, V.jg[2], dfac, efac, vbc, dz,
+    if (ct.n) hipLaunchKernelGGL(k_lep_vsolve_lapack, LEP_GRID(ct, tj), V.patches, phi, rhs, V.jg[2], dfac, efac, vbc, dz,
                                 dzCrse, bad);
 }
-void launch_lep_vsolve_mixed(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const PatchDesc* flatOf,
+void launch_lep_vsolve_mixed(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const PatchDesc* flatOf,
                              double* phi, double* rhs, double* dfac, double* efac, const double* bcLo, const double* bcHi,
                              const int* vbc, double dz, double dzCrse, int* bad)
 {
-    if (nct) hipLaunchKernelGGL(k_lep_vsolve_mixed, LEP_GRID(nct, tj), ct, V.patches, flatOf, phi, rhs, V.jg[2], dfac, efac, bcLo,
+    if (ct.n) hipLaunchKernelGGL(k_lep_vsolve_mixed, LEP_GRID(ct, tj), V.patches, flatOf, phi, rhs, V.jg[2], dfac, efac, bcLo,
                                 bcHi, vbc, dz, dzCrse, bad);
 }
-void launch_lep_hgrad(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
+void launch_lep_hgrad(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H,
                       const double* phi, double* gx, double* gy)
 {
-    if (nct) hipLaunchKernelGGL(k_lep_hgrad, LEP_GRID(nct, tj), ct, V.patches, H.patches, phi, V.jg[0], V.jg[1], gx, gy, V.P);
+    if (ct.n) hipLaunchKernelGGL(k_lep_hgrad, LEP_GRID(ct, tj), V.patches, H.patches, phi, V.jg[0], V.jg[1], gx, gy, V.P);
 }
 static LJ lj_of(const LevelDev& V)
 {
@@ -515,45 +515,45 @@ static LJ lj_of(const LevelDev& V)
         for (int b = 0; b < 3; ++b) J.c[a][b] = V.jgf[a][b];
     return J;
 }
-void launch_lep_avg_metric_full(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H)
+void launch_lep_avg_metric_full(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H)
 {
-    if (!nct) return;
+    if (!ct.n) return;
     HJ h;
     for (int a = 0; a < 2; ++a)
         for (int b = 0; b < 2; ++b) h.c[a][b] = H.jgf[a][b];
-    hipLaunchKernelGGL(k_lep_avg_metric_full, LEP_GRID(nct, tj), ct, V.patches, H.patches, lj_of(V), h);
+    hipLaunchKernelGGL(k_lep_avg_metric_full, LEP_GRID(ct, tj), V.patches, H.patches, lj_of(V), h);
 }
-void launch_lep_hgrad_full(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
+void launch_lep_hgrad_full(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H,
                            const double* phi, double* gx, double* gy)
 {
-    if (nct) hipLaunchKernelGGL(k_lep_hgrad_full, LEP_GRID(nct, tj), ct, V.patches, H.patches, phi, lj_of(V), gx, gy, V.P);
+    if (ct.n) hipLaunchKernelGGL(k_lep_hgrad_full, LEP_GRID(ct, tj), V.patches, H.patches, phi, lj_of(V), gx, gy, V.P);
 }
-void launch_lep_vhgrad(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
+void launch_lep_vhgrad(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H,
                        const double* phi, double* bcLo, double* bcHi, double scale)
 {
-    if (nct) hipLaunchKernelGGL(k_lep_vhgrad, LEP_GRID(nct, tj), ct, V.patches, H.patches, phi, V.jgf[2][0], V.jgf[2][1], bcLo,
+    if (ct.n) hipLaunchKernelGGL(k_lep_vhgrad, LEP_GRID(ct, tj), V.patches, H.patches, phi, V.jgf[2][0], V.jgf[2][1], bcLo,
                                 bcHi, V.P, scale);
 }
-void launch_lep_hrhs(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
+void launch_lep_hrhs(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H,
                      const double* gx, const double* gy, const double* excess, double* hrhs, double sx, double sy,
                      double negInvH, bool useExcess)
 {
-    if (nct) hipLaunchKernelGGL(k_lep_hrhs, LEP_GRID(nct, tj), ct, V.patches, H.patches, gx, gy, excess, hrhs, sx, sy, negInvH, useExcess ? 1 : 0);
+    if (ct.n) hipLaunchKernelGGL(k_lep_hrhs, LEP_GRID(ct, tj), V.patches, H.patches, gx, gy, excess, hrhs, sx, sy, negInvH, useExcess ? 1 : 0);
 }
-void launch_lep_extrude(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, const LevelDev& H,
+void launch_lep_extrude(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, const LevelDev& H,
                         double* phi, const double* flat)
 {
-    if (nct) hipLaunchKernelGGL(k_lep_extrude, LEP_GRID(nct, tj), ct, V.patches, H.patches, phi, flat);
+    if (ct.n) hipLaunchKernelGGL(k_lep_extrude, LEP_GRID(ct, tj), V.patches, H.patches, phi, flat);
 }
-void launch_lep_divide(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, double* y, const double* x,
+void launch_lep_divide(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, double* y, const double* x,
                        const double* b)
 {
-    if (nct) hipLaunchKernelGGL(k_lep_valid<0>, LEP_GRID(nct, tj), ct, V.patches, y, x, b, 0.0);
+    if (ct.n) hipLaunchKernelGGL(k_lep_valid<0>, LEP_GRID(ct, tj), V.patches, y, x, b, 0.0);
 }
-void launch_lep_axpy(hipStream_t st, const Tile* ct, int nct, int tj, const LevelDev& V, double* y, const double* x,
+void launch_lep_axpy(hipStream_t st, TileSpan ct, int tj, const LevelDev& V, double* y, const double* x,
                      double a)
 {
-    if (nct) hipLaunchKernelGGL(k_lep_valid<1>, LEP_GRID(nct, tj), ct, V.patches, y, x, nullptr, a);
+    if (ct.n) hipLaunchKernelGGL(k_lep_valid<1>, LEP_GRID(ct, tj), V.patches, y, x, nullptr, a);
 }
 
 }  // namespace somar

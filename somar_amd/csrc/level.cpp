@@ -483,174 +483,56 @@ void Copier::run(const double* s, double* d, hipStream_t st) const
 }
 
 // Tile tables of the k-marching kernels (fused 7-point sweep, 7-point operator / residual, 19-point kernels) and, on a sharded
-// level, their split into tiles that read no remote ghost cell and the rest.  narrow7: the 7-point tables use the narrow lane
-// classes for remainder columns.  That pays where the kernels are latency-bound -- a uniform metric, two or three streams
-// (C4: 158 -> 112 ms per AMR V-cycle, c2_cartesian 134 -> 159 V-cycles/s) -- and costs where six streams are HBM-bound
-// (512^3 stretched: residual 1.52 -> 2.00 ms: 64-byte row segments of six arrays), so PressureSolver::finalize asks for it
-// on the depths whose metric it found uniform; the 19-point tables always use the classes.  tall7: finalize found the metric
-// not uniform: the fused sweep's table takes tall tiles (march_plan.h) where the boxes are wide enough.
-void Level::build_march_tiles(bool narrow7, bool tall7)
+// level, their split into tiles that read no remote ghost cell and the rest; march_plan.h builds them.  narrow7: the 7-point
+// tables use the narrow lane classes for remainder columns.  That pays where the kernels are latency-bound -- a uniform metric,
+// two or three streams (C4: 158 -> 112 ms per AMR V-cycle, c2_cartesian 134 -> 159 V-cycles/s) -- and costs where six streams
+// are HBM-bound (512^3 stretched: residual 1.52 -> 2.00 ms: 64-byte row segments of six arrays), so PressureSolver::finalize asks
+// for it on the depths whose metric it found uniform; the 19-point tables always use the classes.  tall7: finalize found the
+// metric not uniform: the fused sweep's table takes tall tiles (march_plan.h) where the boxes are wide enough.
+void Level::build_march_tiles(const MarchRequest& req)
 {
-    for (DevBuf<Tile>* q : {&d_ftiles, &d_ftiles_own, &d_ftiles_rem, &d_rtiles, &d_rtiles_own, &d_rtiles_rem, &d_qtiles, &d_gtiles, &d_stiles})
-        q->reset();
-    nftiles_own = nftiles_rem = nrtiles_own = nrtiles_rem = 0;
-    narrow7_ = narrow7;
-    tall7_ = tall7;
-    // ---- tiles of the k-marching kernels: (FT_I x FT_J) columns, k split into chunks so that the launch
-    // fills the 256 CUs evenly (one 1024-thread workgroup per CU at a time); `halo` = planes a chunk reads
-    // beyond its own (fused red-black sweep: 3, marching residual: 2).  march_plan.h holds the rule: tile columns and their
-    // lane classes, tile rows, k-chunks.  `classes` off (Tuning::no_narrow_tiles, the 6-/8-row A/B variants): columns of equal
-    // width, all class 0.  `tall`: every tile is class 1 (the fused sweep's table on streamed levels of wide boxes). ----------
-    using march_plan::ColSpec;
-    const int fused_rows = dev.fused_rows, full_rows = dev.full_rows;
-    std::vector<march_plan::BoxSize> sizes;
+    namespace mp = march_plan;
+    march = req;
+    ftiles.clear(); rtiles.clear(); qtiles.clear(); gtiles.clear(); stiles.clear();
+    std::vector<mp::BoxSize> sizes;
     for (const PatchDesc& p : hpatches) sizes.push_back({p.n[0], p.n[1], p.n[2]});
-    auto march_tiles = [&](int FT_I, int region_rows, int hrows, double halo, int slots, bool classes, double min_gain = 1.0,
-                           bool tall = false) {
-        march_plan::Shape shape;
-        shape.FT_I = FT_I; shape.region_rows = region_rows; shape.hrows = hrows; shape.halo = halo; shape.slots = slots;
-        shape.classes = classes && !tune.no_narrow_tiles;
-        shape.balanced = !tune.no_balanced_tiles;
-        shape.min_gain = min_gain;
-        const march_plan::Plan plan = march_plan::plan(shape, sizes, tall);
-        auto rows_of = [&](int cls) { return march_plan::rows_of(shape, cls); };
-        std::vector<Tile> fnat;
-        for (int pi = 0; pi < (int)hpatches.size(); ++pi) {
-            const PatchDesc& p = hpatches[pi];
-            const int nk = march_plan::chunk_planes(p.n[2], plan.nch);
-            const std::vector<ColSpec> cs = plan.extra >= 0 ? march_plan::tall_columns(p.n[0], plan.extra)
-                                                            : march_plan::columns(shape, p.n[0]);
-            auto add = [&](const ColSpec& c, int j0, int k0) {
-                Tile t;
-                std::memset(&t, 0, sizeof(t));
-                t.patch = pi; t.i0 = c.i0; t.j0 = j0; t.k0 = k0;
-                t.nk = std::min(nk, p.n[2] - k0);
-                t.pad_[0] = c.w;
-                t.pad_[1] = c.cls;
-                fnat.push_back(t);
-            };
-            for (int k0 = 0; k0 < p.n[2]; k0 += nk) {
-                // rows outside, columns inside (the natural order: a 512-wide box's 19-point colour pass takes 3.07 ms so, 3.23 ms
-                // with the columns outside); a narrow column's tall tile goes where its first row is
-                const size_t first = fnat.size();
-                for (const ColSpec& c : cs)
-                    for (int j0 = 0; j0 < p.n[1]; j0 += rows_of(c.cls)) add(c, j0, k0);
-                std::stable_sort(fnat.begin() + first, fnat.end(), [](const Tile& a, const Tile& b) {
-                    return a.j0 != b.j0 ? a.j0 < b.j0 : a.i0 < b.i0;
-                });
-            }
-        }
-        const int NF = (int)fnat.size();
-        std::vector<Tile> perm(NF);
-        const int NX = 8;
-        int start[NX + 1];
-        start[0] = 0;
-        for (int x = 0; x < NX; ++x) start[x + 1] = start[x] + (NF - x + NX - 1) / NX;
-        for (int b = 0; b < NF; ++b) perm[b] = fnat[start[b % NX] + b / NX];
-        return perm;
+    // Tuning::no_narrow_tiles, no_balanced_tiles: columns of equal width, all class 0 / plain 124-wide columns
+    auto tuned = [&](mp::Shape s) {
+        s.classes = s.classes && !tune.no_narrow_tiles;
+        s.balanced = !tune.no_balanced_tiles;
+        return s;
     };
     // tall tiles: the caller asks for them where the fused sweep can run at all (7-point operator, three active directions);
     // march_plan.h's rule sees the boxes, the kernel family and the metric flag; the switches that restore the equal columns
     // turn them off
-    const bool tall = tall7 && !tune.no_narrow_tiles && tune.narrow_7pt != 0 &&
-                      march_plan::tall_eligible(sizes, fused_rows, dev.P.uniform != 0);
-    hftiles = march_tiles(124, fused_rows, 4, 3.0, 256, narrow7 && fused_rows == 16, 0.85, tall);
-    d_ftiles = DevBuf<Tile>::from(hftiles);
-    nftiles = (int)hftiles.size();
-    hrtiles = march_tiles(124, 16, 2, 2.0, 256, narrow7, 0.85);
-    for (size_t q = 0; q < hrtiles.size(); ++q) hrtiles[q].pad_[2] = (int)q;   // its slot in per-tile partial sums (k_resid_march<2>)
-    d_rtiles = DevBuf<Tile>::from(hrtiles);
-    nrtiles = (int)hrtiles.size();
-    // the three-body instantiation of the fused sweep only where the table really holds a narrow tile (on class-0 tiles alone it
-    // is the slower kernel: c2_cartesian 151 -> 140 V-cycles/s)
-    // and the one-body class-1 instantiation where every tile is class 1 (tall tiles)
-    dev.narrow7 = 0;
-    for (const Tile& t : hftiles) if (t.pad_[1]) dev.narrow7 = 1;
-    dev.tall7 = tall ? 1 : 0;
-    // every table: narrow classes where they save at least 15 % of the workgroup-marches (64-wide boxes: C5 62.8 -> 53.1 ms per
-    // AMR V-cycle; 128-wide: C4 136.8 -> 111.6).  One 512-wide box, 5 equal columns against 4 + 4 narrow, is a wash or worse:
-    // 19-point colour pass 3.02 -> 3.07 ms, residual 3.17 -> 3.42; c2_cartesian 151 -> 149-158 V-cycles/s depending on tile order)
-    hqtiles = march_tiles(124, full_rows, 2, 2.0, full_rows == 6 ? 512 : 256, full_rows == 8, 0.85);   // 6 rows: two workgroups per CU
-    d_qtiles = DevBuf<Tile>::from(hqtiles);
-    nqtiles = (int)hqtiles.size();
-    dev.narrowq = 0;
-    for (const Tile& t : hqtiles) if (t.pad_[1]) dev.narrowq = 1;
-    ngtiles = nstiles = 0;
-    if (want_fused19_) {
-        const std::vector<Tile> g = march_tiles(124, 8, 4, 3.0, 256, false);
-        d_gtiles = DevBuf<Tile>::from(g);
-        ngtiles = (int)g.size();
-        // shell pass: per box the two x faces (4-wide class-4 columns, 126 rows each), the two y faces (one 6-row band of class-0
-        // columns each) in k-chunks of 32 planes, and the two z faces (3 planes over every class-0 tile).  The sets overlap at
-        // the box edges: a cell relaxed twice gets the same value twice (its inputs are not written by the pass).
-        std::vector<Tile> sh;
-        const int KC = 32;
-        for (int pi = 0; pi < (int)hpatches.size(); ++pi) {
-            const PatchDesc& p = hpatches[pi];
-            auto add = [&](int i0, int w, int cls, int j0, int k0, int nk) {
-                Tile t;
-                std::memset(&t, 0, sizeof(t));
-                t.patch = pi; t.i0 = i0; t.j0 = j0; t.k0 = k0; t.nk = nk;
-                t.pad_[0] = w; t.pad_[1] = cls;
-                sh.push_back(t);
-            };
-            int wcol = 124;
-            {
-                const int ncol = (p.n[0] + 123) / 124;
-                wcol = (p.n[0] + ncol - 1) / ncol;
-                wcol += wcol & 1;
-                wcol = std::min(wcol, 124);
-            }
-            for (int k0 = 0; k0 < p.n[2]; k0 += KC) {
-                const int nk = std::min(KC, p.n[2] - k0);
-                for (int xi : {0, std::max(0, p.n[0] - 4)})
-                    for (int j0 = 0; j0 < p.n[1]; j0 += 126) add(xi, 4, 4, j0, k0, nk);
-                for (int yj : {0, std::max(0, p.n[1] - 6)})
-                    for (int i0 = 0; i0 < p.n[0]; i0 += wcol) add(i0, wcol, 0, yj, k0, nk);
-            }
-            for (int zk : {0, std::max(0, p.n[2] - 3)})
-                for (int j0 = 0; j0 < p.n[1]; j0 += 6)
-                    for (int i0 = 0; i0 < p.n[0]; i0 += wcol) add(i0, wcol, 0, j0, zk, std::min(3, p.n[2] - zk));
-        }
-        d_stiles = DevBuf<Tile>::from(sh);
-        nstiles = (int)sh.size();
-    }
-
+    const bool tall = req.tall7 && !tune.no_narrow_tiles && tune.narrow_7pt != 0 &&
+                      mp::tall_eligible(sizes, dev.fused_rows, dev.P.uniform != 0);
+    const mp::Shape fshape = tuned(mp::fused_shape(dev.fused_rows, req.narrow7)), rshape = tuned(mp::resid_shape(req.narrow7));
+    mp::Table f = mp::march_tiles(fshape, sizes, tall), r = mp::march_tiles(rshape, sizes);
+    mp::number_slots(r.tiles);
+    mp::Table q = mp::march_tiles(tuned(mp::full_shape(dev.full_rows)), sizes);
     if (!plan.peers.empty()) {
         // which marching tiles read a ghost cell that arrives from another rank?  The fused sweep reads phi two cells around
         // its columns and planes (the recomputed red ring) -- FRAME deep, as deep as the exchange fills; the operator one cell.
-        std::vector<std::vector<const CopyItem*>> byDst(hpatches.size());
-        for (const CopyItem& it : plan.recv_items) byDst[it.dst_patch].push_back(&it);
-        auto split = [&](const std::vector<Tile>& all, int region_rows, int hrows, int halo, std::vector<Tile>& own, std::vector<Tile>& rem) {
-            for (const Tile& t : all) {
-                const PatchDesc& p = hpatches[t.patch];
-                const int w = t.pad_[0] > 0 ? t.pad_[0] : 124;
-                const int rows = (region_rows << t.pad_[1]) - hrows;
-                const int lo[3] = {t.i0 - halo, t.j0 - halo, t.k0 - halo};
-                const int hi[3] = {std::min(t.i0 + w, p.n[0]) - 1 + halo, std::min(t.j0 + rows, p.n[1]) - 1 + halo, t.k0 + t.nk - 1 + halo};
-                bool hit = false;
-                for (const CopyItem* it : byDst[t.patch]) {
-                    bool ov = true;
-                    for (int d = 0; d < 3; ++d)
-                        ov = ov && std::max(lo[d], it->dst_lo[d]) <= std::min(hi[d], it->dst_lo[d] + it->n[d] - 1);
-                    if (ov) { hit = true; break; }
-                }
-                (hit ? rem : own).push_back(t);
-            }
+        std::vector<mp::Region> recv;
+        for (const CopyItem& it : plan.recv_items)
+            recv.push_back({it.dst_patch, {it.dst_lo[0], it.dst_lo[1], it.dst_lo[2]}, {it.n[0], it.n[1], it.n[2]}});
+        auto split = [&](SplitTileTable& t, const mp::Table& all, const mp::Shape& shape, int halo) {
+            std::vector<Tile> own, rem;
+            mp::split(all.tiles, shape, halo, sizes, recv, own, rem);
+            t.own.assign(std::move(own), all.classes);
+            t.rem.assign(std::move(rem), all.classes);
         };
-        std::vector<Tile> own, rem;
-        split(hftiles, fused_rows, 4, FRAME, own, rem);
-        nftiles_own = (int)own.size();
-        nftiles_rem = (int)rem.size();
-        d_ftiles_own = DevBuf<Tile>::from(own);
-        d_ftiles_rem = DevBuf<Tile>::from(rem);
-        own.clear();
-        rem.clear();
-        split(hrtiles, 16, 2, 1, own, rem);
-        nrtiles_own = (int)own.size();
-        nrtiles_rem = (int)rem.size();
-        d_rtiles_own = DevBuf<Tile>::from(own);
-        d_rtiles_rem = DevBuf<Tile>::from(rem);
+        split(ftiles, f, fshape, FRAME);
+        split(rtiles, r, rshape, 1);
+    }
+    ftiles.all.assign(std::move(f.tiles), f.classes);
+    rtiles.all.assign(std::move(r.tiles), r.classes);
+    qtiles.assign(std::move(q.tiles), q.classes);
+    if (req.fused19) {
+        mp::Table g = mp::march_tiles(tuned(mp::fused19_shape()), sizes), sh = mp::shell_tiles(sizes);
+        gtiles.assign(std::move(g.tiles), g.classes);
+        stiles.assign(std::move(sh.tiles), sh.classes);
     }
 }
 
@@ -698,9 +580,7 @@ void Level::define(const IBox& dom, const bool per[3], const double dx_[3], cons
     }
     field_elems = cursor;
 
-    // ---- tiles, XCD-contiguous: block b runs on XCD (b % 8) under round-robin dispatch, so
-    // give each XCD one contiguous slab of the natural (patch,k,j,i) tile order: neighbouring
-    // tiles then share their j/k halo rows through the same 4 MiB L2. ------------------
+    // ---- tiles, XCD-contiguous (march_plan::xcd_order) ------------------------------------------------
     // Tile shape per level: big bricks (8 rows x 32 planes) keep the j/k halo re-reads of a
     // stencil sweep at (8+2)/8 * (32+2)/32 of the ideal; shrink k then j until the level still
     // yields >= 1024 workgroups (4 per CU) so coarse levels keep the chip busy.
@@ -719,38 +599,20 @@ void Level::define(const IBox& dom, const bool per[3], const double dx_[3], cons
         const PatchDesc& p = hpatches[pi];
         for (int k0 = 0; k0 < p.n[2]; k0 += tk)
             for (int j0 = 0; j0 < p.n[1]; j0 += tj)
-                for (int i0 = 0; i0 < p.n[0]; i0 += TILE_I) {
-                    Tile t;
-                    std::memset(&t, 0, sizeof(t));
-                    t.patch = pi; t.i0 = i0; t.j0 = j0; t.k0 = k0;
-                    t.nk = std::min(tk, p.n[2] - k0);
-                    nat.push_back(t);
-                }
+                for (int i0 = 0; i0 < p.n[0]; i0 += TILE_I)
+                    nat.push_back(march_plan::make_tile(pi, i0, j0, k0, std::min(tk, p.n[2] - k0), 0, 0));
     }
     const int N = (int)nat.size();
-    htiles.assign(N, Tile());
-    {
-        const int NX = 8;
-        int start[NX + 1];
-        start[0] = 0;
-        for (int x = 0; x < NX; ++x) start[x + 1] = start[x] + (N - x + NX - 1) / NX;  // #b with b%8==x
-        for (int b = 0; b < N; ++b) htiles[b] = nat[start[b % NX] + b / NX];
-    }
 
     // ---- whole-column tiles for line relaxation (one lane per (i-pair, j) column) ---------------
     {
+        std::vector<Tile> ct;
         for (int pi = 0; pi < (int)hpatches.size(); ++pi) {
             const PatchDesc& p = hpatches[pi];
             for (int j0 = 0; j0 < p.n[1]; j0 += ctile_j)
-                for (int i0 = 0; i0 < p.n[0]; i0 += TILE_I) {
-                    Tile t;
-                    std::memset(&t, 0, sizeof(t));
-                    t.patch = pi; t.i0 = i0; t.j0 = j0; t.k0 = 0; t.nk = p.n[2];
-                    hctiles.push_back(t);
-                }
+                for (int i0 = 0; i0 < p.n[0]; i0 += TILE_I) ct.push_back(march_plan::make_tile(pi, i0, j0, 0, p.n[2], 0, 0));
         }
-        d_ctiles = DevBuf<Tile>::from(hctiles);
-        nctiles = (int)hctiles.size();
+        ctiles.assign(std::move(ct), 0);
     }
 
     // ---- exchange plan ----------------------------------------------------------------
@@ -769,17 +631,17 @@ void Level::define(const IBox& dom, const bool per[3], const double dx_[3], cons
 
     // ---- device tables ----------------------------------------------------------------
     d_patches = DevBuf<PatchDesc>::from(hpatches);
-    d_tiles = DevBuf<Tile>::from(htiles);
+    tiles.assign(march_plan::xcd_order(nat), 0);
     d_local_items = DevBuf<CopyItem>::from(plan.local);
     d_send_items = DevBuf<CopyItem>::from(plan.send_items);
     d_recv_items = DevBuf<CopyItem>::from(plan.recv_items);
     d_send_off = DevBuf<long long>::from(plan.send_itemoff);
     d_recv_off = DevBuf<long long>::from(plan.recv_itemoff);
-    build_march_tiles(false, false);
+    build_march_tiles(MarchRequest{false, false, march.fused19});
     d_sendbuf = plan.send_total ? DevBuf<double>(plan.send_total) : DevBuf<double>();
     d_recvbuf = plan.recv_total ? DevBuf<double>(plan.recv_total) : DevBuf<double>();
 
-    dev.tiles = d_tiles;
+    dev.tiles = tiles.span().p;
     dev.ntiles = N;
     dev.patches = d_patches;
     dev.npatches = (int)hpatches.size();
@@ -794,7 +656,7 @@ void Level::define(const IBox& dom, const bool per[3], const double dx_[3], cons
             std::vector<CopyItem> titems;
             std::vector<int> tstart(N + 1, 0);
             for (int b = 0; b < N; ++b) {
-                const Tile& t = htiles[b];
+                const Tile& t = tiles.host()[b];
                 const PatchDesc& p = hpatches[t.patch];
                 int lo[3] = {t.i0, t.j0, t.k0};
                 int hi[3] = {std::min(t.i0 + TILE_I, p.n[0]) - 1, std::min(t.j0 + dev.tile_j, p.n[1]) - 1, t.k0 + t.nk - 1};

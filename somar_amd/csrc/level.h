@@ -120,6 +120,39 @@ struct BoxIoShape {
 void check_shape(const BoxIoShape& s);   // throws "ghost wider than device frame" etc.
 struct BoxIoBoxes { IBox caller, region; };
 
+// A tile table: its host copy and its device copy, and how it was planned (TileSpan::classes).
+class TileTable {
+public:
+    void assign(std::vector<Tile> t, int classes)
+    {
+        dev_.reset();
+        host_ = std::move(t);
+        dev_ = DevBuf<Tile>::from(host_);
+        classes_ = classes;
+    }
+    void clear() { assign({}, 0); }
+    TileSpan span() const { return TileSpan{dev_.get(), size(), classes_}; }
+    int size() const { return (int)host_.size(); }
+    bool empty() const { return host_.empty(); }
+    const std::vector<Tile>& host() const { return host_; }
+
+private:
+    std::vector<Tile> host_;
+    DevBuf<Tile> dev_;
+    int classes_ = 0;
+};
+// a marching table and its split on a sharded level; own and rem keep the order and the classes of `all`
+struct SplitTileTable {
+    TileTable all, own, rem;
+    void clear() { all.clear(); own.clear(); rem.clear(); }
+};
+// How PressureSolver asks for the marching tables.  narrow7: the 7-point tables use the narrow lane classes (depths whose
+// metric is uniform); tall7: the metric is known not to be uniform, so the fused sweep's table may take tall (all class-1)
+// tiles where march_plan::tall_eligible allows them; fused19: build the fused 19-point sweep's tables too.
+struct MarchRequest {
+    bool narrow7 = false, tall7 = false, fused19 = false;
+};
+
 class Level {
 public:
     // layout
@@ -132,34 +165,20 @@ public:
     std::vector<int> owner;    // rank of each box
     std::vector<int> local;    // global box index of each local patch
     std::vector<PatchDesc> hpatches;
-    std::vector<Tile> htiles;
-    // (re)builds the marching kernels' tile tables below.  tall7: the metric is known not to be uniform, so the fused sweep's
-    // table may take tall (all class-1) tiles where march_plan.h's rule allows them
-    void build_march_tiles(bool narrow7, bool tall7);
-    bool narrow7_ = false, tall7_ = false;
-    std::vector<Tile> hftiles;   // tiles of the fused red-black sweep (gsrb_fused.hip)
-    DevBuf<Tile> d_ftiles;
-    int nftiles = 0;
-    // sharded levels: hftiles split into the tiles that read no ghost cell another rank fills (they may run while the
-    // messages are in flight) and the rest (fused_overlap in solver.cpp); both lists keep the XCD-contiguous order
-    DevBuf<Tile> d_ftiles_own, d_ftiles_rem;
-    int nftiles_own = 0, nftiles_rem = 0;
-    DevBuf<Tile> d_rtiles_own, d_rtiles_rem;   // the same split of the marching operator / residual's tiles (they read phi one cell around)
-    int nrtiles_own = 0, nrtiles_rem = 0;
-    std::vector<Tile> hrtiles;   // tiles of the k-marching operator/residual (resid_march.hip): 124 x 14 columns
-    DevBuf<Tile> d_rtiles;
-    int nrtiles = 0;
-    std::vector<Tile> hqtiles;   // tiles of the k-marching 19-point kernels (full19_march.hip): 124 x (rows - 2) columns
-    DevBuf<Tile> d_qtiles;
-    int nqtiles = 0;
-    // fused red+black 19-point sweep (full19_fused.hip), built when PressureSolver asks (want_fused19_): its 124 x 4 column tiles
+    TileTable tiles;             // base table (dev.tiles): 128 x tile_j x tk bricks, XCD-contiguous order
+    // (re)builds the marching kernels' tile tables below from march_plan.h; the request is kept in `march`
+    void build_march_tiles(const MarchRequest& req);
+    MarchRequest march;
+    // fused red-black sweep (gsrb_fused.hip).  Sharded levels: own = the tiles that read no ghost cell another rank fills (they
+    // may run while the messages are in flight), rem = the rest (fused_overlap in solver.cpp)
+    SplitTileTable ftiles;
+    SplitTileTable rtiles;       // k-marching operator / residual (resid_march.hip); it reads phi one cell around
+    TileTable qtiles;            // k-marching 19-point kernels (full19_march.hip)
+    // fused red+black 19-point sweep (full19_fused.hip), built when PressureSolver asks (MarchRequest::fused19): its column tiles
     // and the tiles of the shell pass that follows it (the three outer cell layers of every box)
-    bool want_fused19_ = false;
-    DevBuf<Tile> d_gtiles, d_stiles;
-    int ngtiles = 0, nstiles = 0;
-    std::vector<Tile> hctiles;   // whole-column tiles (line relaxation): 128 x ctile_j columns, all of k
-    DevBuf<Tile> d_ctiles;
-    int nctiles = 0, ctile_j = 2;
+    TileTable gtiles, stiles;
+    TileTable ctiles;            // whole-column tiles (line relaxation): 128 x ctile_j columns, all of k
+    int ctile_j = 2;
     long long field_elems = 0;
     long long valid_cells_global = 0;
     ExchangePlan plan;
@@ -168,7 +187,6 @@ public:
 
     // device tables
     DevBuf<PatchDesc> d_patches;
-    DevBuf<Tile> d_tiles;
     DevBuf<CopyItem> d_local_items;
     // pull exchange tables (LevelDev::tile_items): built for single-rank levels of at most Tuning::pull_max_cells cells
     DevBuf<CopyItem> d_tile_items;

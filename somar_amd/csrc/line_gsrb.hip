@@ -126,18 +126,18 @@ __global__ __launch_bounds__(256) void k_line_gsrb_ortho(const Tile* __restrict_
     }
 }
 
-void launch_line_gsrb_ortho(hipStream_t st, const Tile* ctiles, int nctiles, int tile_j, const LevelDev& L,
+void launch_line_gsrb_ortho(hipStream_t st, TileSpan ctiles, int tile_j, const LevelDev& L,
                             double* phi, const double* rhs, double* dmod, int color, const double* psi)
 {
-    if (nctiles == 0) return;
+    if (ctiles.n == 0) return;
     LJ9 J;
     for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 3; ++b) J.c[a][b] = L.jgf[a][b];
     if (psi)
-        hipLaunchKernelGGL(k_line_gsrb_ortho<true>, dim3(nctiles), dim3(64, tile_j, 1), 0, st, ctiles, L.patches, phi, rhs,
+        hipLaunchKernelGGL(k_line_gsrb_ortho<true>, dim3(ctiles.n), dim3(64, tile_j, 1), 0, st, ctiles.p, L.patches, phi, rhs,
                            L.jg[0], L.jg[1], L.jg[2], L.jinv, dmod, L.P, color, J, psi);
     else
-        hipLaunchKernelGGL(k_line_gsrb_ortho<false>, dim3(nctiles), dim3(64, tile_j, 1), 0, st, ctiles, L.patches, phi, rhs,
+        hipLaunchKernelGGL(k_line_gsrb_ortho<false>, dim3(ctiles.n), dim3(64, tile_j, 1), 0, st, ctiles.p, L.patches, phi, rhs,
                            L.jg[0], L.jg[1], L.jg[2], L.jinv, dmod, L.P, color, J, psi);
 }
 

@@ -65,7 +65,7 @@ __device__ __forceinline__ void resid_march_body(E* __restrict__ S, E* __restric
                              : (int)(((threadIdx.y >> 1) << (CLS + 1)) + (threadIdx.y & 1) + 2 * (threadIdx.x >> (6 - CLS)));
     const int ri = 2 * lane;
     const int li = t.i0 - 2 + ri;  // even: rows are 16-byte aligned
-    const int wi = t.pad_[0] > 0 ? t.pad_[0] : 2 * LPR - 4;  // output columns of this tile (see gsrb_fused.hip)
+    const int wi = t.w > 0 ? t.w : 2 * LPR - 4;  // output columns of this tile (see gsrb_fused.hip)
     const int lj = t.j0 - 1 + row;
     const int gj = p.lo[1] + lj;
     const E sx = E(1.0) / E(P.dx[0]), sy = E(1.0) / E(P.dx[1]), sz = E(1.0) / E(P.dx[2]);
@@ -238,7 +238,7 @@ __device__ __forceinline__ void resid_march_body(E* __restrict__ S, E* __restric
             if (threadIdx.x == 0 && threadIdx.y == 0) {
                 double tot = red[0];
                 for (int q = 1; q < RM_J; ++q) tot = tot + red[q];
-                volsum[t.pad_[2]] = tot;   // the tile's place in the level's full tile list: split launches (overlap) keep the order of the sum
+                volsum[t.slot] = tot;   // the tile's place in the level's full tile list: split launches (overlap) keep the order of the sum
             }
         }
     }
@@ -265,65 +265,65 @@ __global__ __launch_bounds__(64 * RM_J, (UNI && MODE != 2) ? 8 : 4) void k_resid
     __shared__ __attribute__((aligned(16))) E T[MODE == 2 ? 2 * RM_J * 64 * 4 : 4];
     const Tile t = tiles[blockIdx.x];
     const PatchDesc p = patches[t.patch];
-    const int cls = t.pad_[1];
+    const int cls = t.cls;
     if (cls == 0) resid_march_body<MODE, UNI, 0, E>(S, T, t, p, out, phi, rhs, jgx, jgy, jgz, jinv, P, cpatches, r0, r1, r2, dxProduct, volsum);
     else if (cls == 1) resid_march_body<MODE, UNI, 1, E>(S, T, t, p, out, phi, rhs, jgx, jgy, jgz, jinv, P, cpatches, r0, r1, r2, dxProduct, volsum);
     else resid_march_body<MODE, UNI, 4, E>(S, T, t, p, out, phi, rhs, jgx, jgy, jgz, jinv, P, cpatches, r0, r1, r2, dxProduct, volsum);
 }
 
-void launch_resid_march(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& L, double* out,
+void launch_resid_march(hipStream_t st, TileSpan tiles, const LevelDev& L, double* out,
                         const double* phi, const double* rhs, int mode)
 {
-    if (ntiles == 0) return;
+    if (tiles.n == 0) return;
     if (L.P.uniform) {
         if (mode == 0)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resid_march<0, true>), dim3(ntiles), dim3(64, RM_J, 1), 0, st, tiles, L.patches, out,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resid_march<0, true>), dim3(tiles.n), dim3(64, RM_J, 1), 0, st, tiles.p, L.patches, out,
                                phi, rhs, L.jg[0], L.jg[1], L.jg[2], L.jinv, L.P, nullptr, 1, 1, 1, 0.0, nullptr);
         else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resid_march<1, true>), dim3(ntiles), dim3(64, RM_J, 1), 0, st, tiles, L.patches, out,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resid_march<1, true>), dim3(tiles.n), dim3(64, RM_J, 1), 0, st, tiles.p, L.patches, out,
                                phi, rhs, L.jg[0], L.jg[1], L.jg[2], L.jinv, L.P, nullptr, 1, 1, 1, 0.0, nullptr);
         return;
     }
     if (mode == 0)
-        hipLaunchKernelGGL(k_resid_march<0>, dim3(ntiles), dim3(64, RM_J, 1), 0, st, tiles, L.patches, out, phi, rhs,
+        hipLaunchKernelGGL(k_resid_march<0>, dim3(tiles.n), dim3(64, RM_J, 1), 0, st, tiles.p, L.patches, out, phi, rhs,
                            L.jg[0], L.jg[1], L.jg[2], L.jinv, L.P, nullptr, 1, 1, 1, 0.0, nullptr);
     else
-        hipLaunchKernelGGL(k_resid_march<1>, dim3(ntiles), dim3(64, RM_J, 1), 0, st, tiles, L.patches, out, phi, rhs,
+        hipLaunchKernelGGL(k_resid_march<1>, dim3(tiles.n), dim3(64, RM_J, 1), 0, st, tiles.p, L.patches, out, phi, rhs,
                            L.jg[0], L.jg[1], L.jg[2], L.jinv, L.P, nullptr, 1, 1, 1, 0.0, nullptr);
 }
 
 // restrictResidual in one pass: crse = J-weighted average (MAPPEDAVERAGE2) of rhs - L[phi]; the fine residual is
-// never written.  Needs tiles whose k-extent is even (Level::hrtiles are) and a coarsenable layout.
+// never written.  Needs tiles whose k-extent is even (Level::rtiles are) and a coarsenable layout.
 // volsum (optional, ntiles doubles): per-block sums of (dxProduct / Jinv) * phi over the block's cells
 template <class E>
-static void launch_resid_restrict_t(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const MetricPtrs<E>& M,
+static void launch_resid_restrict_t(hipStream_t st, TileSpan tiles, const LevelDev& F, const MetricPtrs<E>& M,
                                     const LevelDev& C, E* crse, const E* phi, const E* rhs, const int r[3], double dxProduct,
                                     double* volsum)
 {
-    if (ntiles == 0) return;
+    if (tiles.n == 0) return;
     if (F.P.uniform) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resid_march<2, true, E>), dim3(ntiles), dim3(64, RM_J, 1), 0, st, tiles, F.patches, crse, phi,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resid_march<2, true, E>), dim3(tiles.n), dim3(64, RM_J, 1), 0, st, tiles.p, F.patches, crse, phi,
                            rhs, M.jg[0], M.jg[1], M.jg[2], M.jinv, F.P, C.patches, r[0], r[1], r[2], dxProduct, volsum);
         return;
     }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resid_march<2, false, E>), dim3(ntiles), dim3(64, RM_J, 1), 0, st, tiles, F.patches, crse, phi, rhs,
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_resid_march<2, false, E>), dim3(tiles.n), dim3(64, RM_J, 1), 0, st, tiles.p, F.patches, crse, phi, rhs,
                        M.jg[0], M.jg[1], M.jg[2], M.jinv, F.P, C.patches, r[0], r[1], r[2], dxProduct, volsum);
 }
 
-void launch_resid_restrict(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const MetricPtrs<double>& M,
+void launch_resid_restrict(hipStream_t st, TileSpan tiles, const LevelDev& F, const MetricPtrs<double>& M,
                            const LevelDev& C, double* crse, const double* phi, const double* rhs, const int r[3],
                            double dxProduct, double* volsum)
 {
-    launch_resid_restrict_t<double>(st, tiles, ntiles, F, M, C, crse, phi, rhs, r, dxProduct, volsum);
+    launch_resid_restrict_t<double>(st, tiles, F, M, C, crse, phi, rhs, r, dxProduct, volsum);
 }
 
-void launch_resid_restrict(hipStream_t st, const Tile* tiles, int ntiles, const LevelDev& F, const MetricPtrs<float>& M,
+void launch_resid_restrict(hipStream_t st, TileSpan tiles, const LevelDev& F, const MetricPtrs<float>& M,
                            const LevelDev& C, float* crse, const float* phi, const float* rhs, const int r[3],
                            double dxProduct, double* volsum)
 {
     SOMAR_CHECK(F.P.uniform || (M.jg[0] && M.jg[1] && M.jg[2] && M.jinv),
                 "internal: the residual restriction streams the metric of this depth, but its fp32 copies are missing");
-    launch_resid_restrict_t<float>(st, tiles, ntiles, F, M, C, crse, phi, rhs, r, dxProduct, volsum);
+    launch_resid_restrict_t<float>(st, tiles, F, M, C, crse, phi, rhs, r, dxProduct, volsum);
 }
 
 }  // namespace somar

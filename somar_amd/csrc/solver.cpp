@@ -386,10 +386,7 @@ void PressureSolver::finalize()
             for (const IBox& b : L.boxes)
                 for (int a = 0; a < 3; ++a) ok = ok && b.size(a) >= std::max(min_box, 8) && (a != 0 || b.size(a) % 2 == 0);
             fused19_[d] = ok ? 1 : 0;
-            if (ok != L.want_fused19_) {
-                L.want_fused19_ = ok;
-                L.build_march_tiles(L.narrow7_, L.tall7_);
-            }
+            if (ok != L.march.fused19) L.build_march_tiles(MarchRequest{L.march.narrow7, L.march.tall7, ok});
         }
     }
     choose_narrow_tiles();
@@ -680,11 +677,11 @@ void PressureSolver::choose_narrow_tiles()
         const bool want = tune_.narrow_7pt >= 0 ? tune_.narrow_7pt != 0 : Lp->dev.P.uniform != 0;
         // (march_plan::tall_eligible holds the rule, the metric flag included; here only: can the fused sweep run on this level?)
         const bool tall = !full_ && Lp->dev.P.uniform == 0 && Lp->active[0] && Lp->active[1] && Lp->active[2];
-        if (want != Lp->narrow7_ || tall != Lp->tall7_) { Lp->build_march_tiles(want, tall); rebuilt = true; }
+        if (want != Lp->march.narrow7 || tall != Lp->march.tall7) { Lp->build_march_tiles(MarchRequest{want, tall, Lp->march.fused19}); rebuilt = true; }
     }
     if (d_partials && !rebuilt) return;
     int maxTiles = 1;
-    for (auto& L : lev) maxTiles = std::max(std::max(maxTiles, L->dev.ntiles), std::max(L->nrtiles, L->nftiles));
+    for (auto& L : lev) maxTiles = std::max(std::max(maxTiles, L->dev.ntiles), std::max(L->rtiles.all.size(), L->ftiles.all.size()));
     SOMAR_HIP(hipStreamSynchronize(st_));
     d_partials.reset();
     d_partials = DevBuf<double>((size_t)maxTiles * 2);
@@ -957,22 +954,22 @@ void PressureSolver::fused_sweeps(int d, T* e, const T* res, int iters, bool e_z
         if (zin) mode = 1;
         else if (it == 0 && e_plus) mode = e_shift ? 4 : 3;
         else if (it == 0 && e_shift) mode = 2;
-        auto sweep = [&](Tile* tl, int nt) {
-            launch_gsrb_fused(st_, tl, nt, L.dev, metric<T>(d), alt, cur, res, mode, e_shift,
+        auto sweep = [&](TileSpan tl) {
+            launch_gsrb_fused(st_, tl, L.dev, metric<T>(d), alt, cur, res, mode, e_shift,
                               e_plus_level ? &e_plus_level->dev : nullptr, e_plus, L.mgCrseRefRatio);
         };
         if (!zin && fused_overlap(L)) {
             // the sweep's one exchange in flight on the second stream while the tiles that read none of its cells are swept
             // (the CF ghosts are other cells, computed from this rank's valid cells: filled before the first tiles run)
             cf_fill(L, cur, true);
-            overlapped(L, cur, L.d_ftiles_own, L.nftiles_own, L.d_ftiles_rem, L.nftiles_rem, sweep);
+            overlapped(L, cur, L.ftiles, sweep);
         } else {
             if (!zin) {
                 xchg(L, cur);
                 cf_fill(L, cur, true);  // CF ghosts (faces + the edge ghosts the red ring reads), pre-sweep values
             }
             ProfScope timed(*this, d, 0);
-            sweep(L.d_ftiles, L.nftiles);
+            sweep(L.ftiles.all.span());
         }
         std::swap(cur, alt);
     }
@@ -987,8 +984,8 @@ void PressureSolver::march_restrict(int d, T* resCoarse, T* phiFine, const T* rh
     Level& F = *lev[d];
     cf_fill(F, phiFine, false);
     const bool want = F.zeroAvg && !ordered(d);  // the fine half of the folded prolongation's mean
-    auto pass = [&](Tile* tl, int nt) {
-        launch_resid_restrict(st_, tl, nt, F.dev, metric<T>(d), lev[d + 1]->dev, resCoarse, phiFine, rhsFine, F.mgCrseRefRatio,
+    auto pass = [&](TileSpan tl) {
+        launch_resid_restrict(st_, tl, F.dev, metric<T>(d), lev[d + 1]->dev, resCoarse, phiFine, rhsFine, F.mgCrseRefRatio,
                               F.dxProduct, want ? d_partials : nullptr);
     };
     const bool overlap = resid_overlap(F);  // (never with Dirichlet sides, never in a profiled pass)
@@ -997,9 +994,9 @@ void PressureSolver::march_restrict(int d, T* resCoarse, T* phiFine, const T* rh
         if (diri_) diri_homog(d, phiFine);  // homogeneous Dirichlet ghosts, as residual() fills them
     }
     ProfScope timed(*this, d, 1);
-    if (overlap) overlapped(F, phiFine, F.d_rtiles_own, F.nrtiles_own, F.d_rtiles_rem, F.nrtiles_rem, pass);
-    else pass(F.d_rtiles, F.nrtiles);
-    if (want) launch_sum_partials(st_, d_partials, F.nrtiles, d_fold + 8 * d);
+    if (overlap) overlapped(F, phiFine, F.rtiles, pass);
+    else pass(F.rtiles.all.span());
+    if (want) launch_sum_partials(st_, d_partials, F.rtiles.all.size(), d_fold + 8 * d);
     sf_valid_[d] = want ? 1 : 0;
 }
 
@@ -1050,14 +1047,14 @@ void PressureSolver::relax(int d, double* e, const double* res, int iters, bool 
             copy_frames(d, cur, alt);
             {
                 ProfScope timed(*this, d, 0);
-                launch_full_fused(st_, L.d_gtiles, L.ngtiles, L.dev, alt, cur, f_psi[d], res);
+                launch_full_fused(st_, L.gtiles.span(), L.dev, alt, cur, f_psi[d], res);
             }
             L.cf_homog(alt, st_);
             xchg(L, alt);
             run_full_program_frames(d, 1, alt);
             {
                 ProfScope timed(*this, d, 0);   // (slot 0 then holds two launches per sweep, as in the two-pass form)
-                launch_gsrb_full_shell(st_, L.d_stiles, L.nstiles, L.dev, alt, cur, f_psi[d], res);
+                launch_gsrb_full_shell(st_, L.stiles.span(), L.dev, alt, cur, f_psi[d], res);
             }
             ++counters[4];
             std::swap(cur, alt);
@@ -1080,7 +1077,7 @@ void PressureSolver::relax(int d, double* e, const double* res, int iters, bool 
                 // coarse-fine corners keep whatever the last ExtrapolateCFEV left there, as in the reference's in-place sweep)
                 copy_frames(d, cur, alt);
                 ProfScope timed(*this, d, 0);
-                launch_gsrb_full_march(st_, L.d_qtiles, L.nqtiles, L.dev, alt, cur, f_psi[d], res, pass);
+                launch_gsrb_full_march(st_, L.qtiles.span(), L.dev, alt, cur, f_psi[d], res, pass);
                 std::swap(cur, alt);
             }
         // an even number of passes: the result is back in e
@@ -1140,7 +1137,7 @@ void PressureSolver::line_relax(int d, double* e, const double* res)
             launch_line_gsrb_2d(st_, L.dev, maxN0, e, res, f_pp[d], pass, full_ ? f_psi[d] : nullptr);
             continue;
         }
-        launch_line_gsrb_ortho(st_, L.d_ctiles, L.nctiles, L.ctile_j, L.dev, e, res, f_pp[d], pass, full_ ? f_psi[d] : nullptr);
+        launch_line_gsrb_ortho(st_, L.ctiles.span(), L.ctile_j, L.dev, e, res, f_pp[d], pass, full_ ? f_psi[d] : nullptr);
     }
 }
 
@@ -1168,12 +1165,12 @@ void PressureSolver::operator_i(int d, int mode, double* out, double* phi, const
     ProfScope timed(*this, d, 1, mode == 0);
     if (full_march(d)) {
         run_full_program_frames(d, 0, phi, homogeneous);
-        launch_full_march(st_, L.d_qtiles, L.nqtiles, L.dev, out, phi, f_psi[d], rhs, mode);
+        launch_full_march(st_, L.qtiles.span(), L.dev, out, phi, f_psi[d], rhs, mode);
     } else if (full_) {
         // exchangeComplete, fillExtrap (order 2), physical ghosts (Neumann with cross terms / Dirichlet), then the 19-point fluxes
         run_full_program(d, 0, phi, homogeneous);
         launch_op_full(st_, L.dev, out, phi, f_psi[d], rhs, mode);
-    } else if (ortho_march(d)) launch_resid_march(st_, L.d_rtiles, L.nrtiles, L.dev, out, phi, rhs, mode);  // Dirichlet sides: their ghosts were just written, the kernel only zeroes NEUMANN fluxes
+    } else if (ortho_march(d)) launch_resid_march(st_, L.rtiles.all.span(), L.dev, out, phi, rhs, mode);  // Dirichlet sides: their ghosts were just written, the kernel only zeroes NEUMANN fluxes
     else launch_op_ortho(st_, L.dev, out, phi, rhs, mode, pull);
 }
 
@@ -1219,7 +1216,7 @@ bool PressureSolver::residual_restrict_i(const LevelDev& C, double* crse, double
     if (!ortho_march(0)) return false;
     xchg(F, phi);  // exchangeComplete, as residual_i
     if (diri_) apply_diri(0, phi, true);
-    launch_resid_restrict(st_, F.d_rtiles, F.nrtiles, F.dev, metric<double>(0), C, crse, phi, rhs, r, F.dxProduct, nullptr);
+    launch_resid_restrict(st_, F.rtiles.all.span(), F.dev, metric<double>(0), C, crse, phi, rhs, r, F.dxProduct, nullptr);
     return true;
 }
 
@@ -2252,7 +2249,7 @@ void PressureSolver::build_box_tables(int d)
                 const int o0 = Pg.h_box_first.empty() ? 0 : Pg.h_box_first[b], o1 = Pg.h_box_first.empty() ? 0 : Pg.h_box_first[b + 1];
                 for (int o = o0; o < o1; ++o) {
                     const GhostOp& op = Pg.h_box_ops[o];
-                    const int stage = op.pad_ & 0xffff;
+                    const int stage = ghost_stage(op.stage);
                     if (stage != cur) { stg.push_back((int)ent.size() - efirst[b]); cur = stage; }
                     SOMAR_CHECK(!ghost_is_diri(op.type), "k_box_bicgstab: Dirichlet ghosts are not compiled (levels with Dirichlet sides take the launch path)");
                     for (int k = 0; k < op.n[2]; ++k)

@@ -434,7 +434,7 @@ private:
     bool fold_prolong(int d) const;
     // ---- non-diagonal metric (19-point) path, solver_full.cpp ----
     // d_ops: the ops stage by stage (first / count per stage) for the staged form, one launch per stage; d_box_ops / d_box_first:
-    // the same ops sorted by box, then stage (GhostOp::pad_), for the one-launch form (k_ghost_program, small levels)
+    // the same ops sorted by box, then GhostOp::stage, for the one-launch form (k_ghost_program, small levels)
     struct FullProgram { DevBuf<GhostOp> d_ops; std::vector<int> first, count; DevBuf<GhostOp> d_box_ops; DevBuf<int> d_box_first; int max_box_ops = 0;
                          std::vector<GhostOp> h_box_ops; std::vector<int> h_box_first;   // host copy of the box-sorted list (k_box_bicgstab's tables)
                          std::vector<GhostOp> h_ops; };                                   // ... and of d_ops (refresh_diri_ops)
@@ -531,12 +531,12 @@ private:
     hipEvent_t ev_ready_ = nullptr, ev_done_ = nullptr;
     bool resid_overlap(const Level& L) const
     {
-        return !tune_.no_overlap && !L.plan.peers.empty() && L.nrtiles_own > 0 && !capturing_ && !profiling_ && !diri_;
+        return !tune_.no_overlap && !L.plan.peers.empty() && !L.rtiles.own.empty() && !capturing_ && !profiling_ && !diri_;
     }
-    // exchange of f with its remote half on the second stream; run(tiles, n) is issued for the tiles that read no remote ghost
+    // exchange of f with its remote half on the second stream; run(tiles) is issued for the tiles that read no remote ghost
     // first, for the others once the messages have landed.  T: double, or float on the fp32 depths of a mixed cycle.
     template <class T, class Run>
-    void overlapped(const Level& L, T* f, Tile* own, int nown, Tile* rem, int nrem, Run run)
+    void overlapped(const Level& L, T* f, const SplitTileTable& table, Run run)
     {
         if (!st_comm_) {
             SOMAR_HIP(hipStreamCreateWithFlags(&st_comm_, hipStreamNonBlocking));
@@ -546,16 +546,16 @@ private:
         SOMAR_HIP(hipEventRecord(ev_ready_, st_));
         SOMAR_HIP(hipStreamWaitEvent(st_comm_, ev_ready_, 0));
         L.exchange_local(f, st_);
-        run(own, nown);
+        run(table.own.span());
         L.exchange_remote(f, st_comm_);   // (a host-staged transport may block here: the tiles above are already queued)
         SOMAR_HIP(hipEventRecord(ev_done_, st_comm_));
         SOMAR_HIP(hipStreamWaitEvent(st_, ev_done_, 0));
-        run(rem, nrem);
+        run(table.rem.span());
         ++counters[0];
     }
     bool fused_overlap(const Level& L) const
     {
-        return !tune_.no_overlap && !L.plan.peers.empty() && L.nftiles_own > 0 && !capturing_ && !profiling_;
+        return !tune_.no_overlap && !L.plan.peers.empty() && !L.ftiles.own.empty() && !capturing_ && !profiling_;
     }
     bool profiling_ = false;
     void prof_begin(int k);

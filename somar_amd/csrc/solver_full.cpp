@@ -454,7 +454,7 @@ void PressureSolver::upload_program(FullProgram& P, const std::vector<std::vecto
         P.first.push_back((int)flat.size());
         P.count.push_back((int)stages[s].size());
         for (GhostOp op : stages[s]) {
-            op.pad_ = (int)s;
+            op.stage = (int)s;
             flat.push_back(op);
             byBox[op.patch].push_back(op);
         }
@@ -473,15 +473,15 @@ void PressureSolver::upload_program(FullProgram& P, const std::vector<std::vecto
     std::vector<int> first(npatches + 1, 0);
     for (int b = 0; b < npatches; ++b) {
         first[b] = (int)sorted.size();
-        // stage order is kept (stages were walked in order).  pad_ of the box-sorted copy = stage | (how many ops of the same
+        // stage order is kept (stages were walked in order).  GhostOp::stage of the box-sorted copy = stage | (how many ops of the same
         // stage FOLLOW this one in the box's list) << 16: a kernel finds the end of a stage without walking the list
         std::vector<GhostOp>& v = byBox[b];
         for (size_t q = 0; q < v.size(); ++q) {
             size_t e = q + 1;
-            while (e < v.size() && v[e].pad_ == v[q].pad_) ++e;
-            SOMAR_CHECK(v[q].pad_ < 65536 && e - q - 1 < 32768, "ghost program too long for its stage encoding");
-            const int st = v[q].pad_;
-            for (size_t r = q; r < e; ++r) v[r].pad_ = st | (int)((e - r - 1) << 16);
+            while (e < v.size() && v[e].stage == v[q].stage) ++e;
+            SOMAR_CHECK(v[q].stage < 65536 && e - q - 1 < 32768, "ghost program too long for its stage encoding");
+            const int st = v[q].stage;
+            for (size_t r = q; r < e; ++r) v[r].stage = st | (int)((e - r - 1) << 16);
             q = e - 1;
         }
         sorted.insert(sorted.end(), v.begin(), v.end());

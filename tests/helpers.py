@@ -146,8 +146,9 @@ def smooth_cc_velocity(so, dom, grids, ghost, ncomp=3):
 
 
 def march_columns(n0, classes):
-    """The tile columns [(width, lane class)] of one box n0 cells wide in Level::build_march_tiles' marching tables
-    (somar_amd/csrc/level.cpp:563-582, `columns`, with FT_I = 124 and min_gain = 0.85), restated.  Class 0: 124 output
+    """The tile columns [(width, lane class)] of one box n0 cells wide in the marching tables
+    (somar_amd/csrc/march_plan.h, `columns`, with FT_I = 124 and min_gain = 0.85), restated;
+    tests/test_march_plan.py holds it against the header itself.  Class 0: 124 output
     columns, one region row per wavefront; class 1: 60 columns, two rows; class 4: 4 columns, sixteen rows.  classes off
     (or an odd n0): balanced columns of equal (even) width, all class 0.  With classes on, a box is cut into 124-wide
     columns and its remainder into the narrow classes, taken where that costs at most 0.85 of the equal columns'

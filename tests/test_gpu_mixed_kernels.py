@@ -41,7 +41,7 @@ STRETCHED_POISSON_BOUND = 2e-6
 
 
 def test_march_columns_restatement():
-    """the decompositions the comments of level.cpp name"""
+    """the decompositions the comments of march_plan.h name"""
     assert march_columns(128, True) == [(124, 0), (4, 4)]
     assert march_columns(64, True) == [(60, 1), (4, 4)]
     assert march_columns(512, True) == [(104, 0)] * 5   # 4 x 124 + 4 x 4 costs 5 workgroup-marches > 0.85 x 5

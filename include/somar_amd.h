@@ -739,6 +739,55 @@ int somar_solver_metric_download(somar_solver_t* s, int depth, int which, int pa
  * somar_solver_get_precision: the mode and K, the number of leading depths that run in fp32 (0 before finalize). */
 int somar_solver_set_precision(somar_solver_t* s, int mode, long long min_cells);
 int somar_solver_get_precision(const somar_solver_t* s, int* mode, int* fp32_depths);
+/* Several right-hand sides in one level solve: ONE handle that carries ncomp (1..4) components on one operator.
+ *  The reference keeps one MappedLevelTGA / BackwardEuler solver per velocity component and per scalar
+ *  (NavierStokes/AMRNavierStokesInit.cpp:887-1010, m_viscSolverPtrs[idir]); bound one to one, that is SpaceDim (and more) handles
+ *  on the same geometry, each with its own copy of the metric hierarchy, tile tables and ghost programs, each streaming the
+ *  coefficients again for its one field.  Here every component owns its depth-0 fields (SOMAR_F_PHI, RHS, RES, CORR, BEST,
+ *  HEAT_OLD, HEAT_SRC) and all share the metric, alpha / beta (somar_solver_set_alpha_beta), the BC types and the Dirichlet
+ *  values.  Component 0 is the handle's own fields: every other call keeps addressing it and behaves as without this call.
+ *  somar_solver_set_components: after finalize.  ncomp = 1 is always accepted and releases everything the other components
+ *    held.  min_cells: a multigrid depth is BATCHED -- its sweeps and its residual + restriction are launches that carry
+ *    several active components and read the coefficient arrays once -- when it has at least min_cells valid cells (min_cells
+ *    <= 0: the library's threshold, which is the fused sweep's own) and, as for the fp32 depths of somar_solver_set_precision, the
+ *    fused sweep and the marching restriction run there, the prolongation folds, the depth lies before the graph-replayed
+ *    legs and its MG ratios are 1 or 2; in addition the depth has no zero-average prolongation (a Helmholtz operator with
+ *    alpha != 0, or a Dirichlet side, has no null space), its metric is not uniform (the uniform-metric kernels stream no
+ *    coefficient array, so there is nothing to share) and its sweep is the 16-row form.  The batched depths form a prefix
+ *    0 .. K-1; below it the components go through the single-field cycle one after the other.  With K == 0 the calls below are
+ *    loops over the single-field ones, and the handle still saves ncomp - 1 metric hierarchies.
+ *    Launch shapes, as measured on one MI355X at 512^3 (profiles/r08_multi.md; time per field against the single-field
+ *    launch): the plain sweep carries TWO fields (-11 %; three go as 2 + 1, four as 2 + 2), the sweep from zero and the
+ *    residual up to three (-32 % / -27 % and -30 % / -44 %), the residual + restriction two (-35 %).  The first post-smoothing
+ *    sweep, which has the prolongation folded in, stays sequential (one single-field launch per component): its two- and
+ *    three-field forms, and the plain sweep on three fields, spilled registers and measured SLOWER than the single-field
+ *    launches (+20 % to +74 %), so they are not part of the library.  A 2/2/2 V-cycle of 2, 3, 4 components then takes 0.90,
+ *    0.93, 0.91 of the single-field cycles; the larger gain is memory, one metric hierarchy (an extra component costs 7 GB at
+ *    512^3, not a second solver).
+ *  Semantics, in one sentence: somar_solver_solve_multi leaves every component -- fields, stats[comp], residual history --
+ *    exactly as ncomp successive somar_solver_solve calls on the same handle would, bit for bit.  Each component has its own
+ *    outer-loop state; the components cycle in lock step; one whose loop condition fails leaves the active set and is neither
+ *    read nor written afterwards.  stats: ncomp entries (may be NULL).
+ *  somar_vcycle_multi: per component SOMAR_F_CORR := one V-cycle of SOMAR_F_RES, as somar_vcycle (from_zero = 0) or
+ *    somar_vcycle_from_zero.
+ *  somar_heat_step_multi: somar_heat_step's sequence (schemes 0, 1, 2) on every component with one dt; its solves are
+ *    somar_solver_solve_multi's.
+ *  somar_comp_upload / somar_comp_download: somar_field_upload / somar_field_download on a component's field (depth 0).
+ *  somar_comp_history: the complete residual history of component comp in the last multi solve, as somar_last_history.
+ *  somar_solver_get_components: ncomp, K and the number of N-field launches issued so far (any pointer may be NULL).
+ *  Refused, with the reason in somar_last_error: ncomp > 1 on a level of an AMR hierarchy, on the handles of a leptic solver,
+ *  with a non-diagonal (19-point) metric, relax_mode other than LevelGSRB, num_mg != 1, coarse-fine faces, more than one rank,
+ *  and with somar_solver_set_precision mode 1 -- in either order: mode 1 is refused on a handle of more than one component.
+ *  Not offered (yet): per-component Dirichlet values; per-component BC types (free-slip walls, where the normal and the
+ *  tangential components differ); _dev twins of the component I/O; levels sharded over ranks; the 19-point operator. */
+int somar_solver_set_components(somar_solver_t* s, int ncomp, long long min_cells);
+int somar_solver_get_components(somar_solver_t* s, int* ncomp, int* batched_depths, long long* batched_launches);
+int somar_comp_upload(somar_solver_t* s, int comp, int field, int patch, const double* host, const int* ghost);
+int somar_comp_download(somar_solver_t* s, int comp, int field, int patch, double* host, const int* ghost);
+int somar_solver_solve_multi(somar_solver_t* s, int zero_phi, int force_homogeneous, somar_stats_t* stats);
+int somar_vcycle_multi(somar_solver_t* s, int from_zero);
+int somar_heat_step_multi(somar_solver_t* s, int scheme, double dt, int zero_phi, somar_stats_t* stats);
+int somar_comp_history(somar_solver_t* s, int comp, double* out, int capacity, int* n);
 /* The nodal "depth" of the reference's analytic bathymetric maps, for SOMAR_MAP_BATHYMETRIC (host arithmetic, no GPU; x, y: the
  * Cartesian coordinates of the nodes, for these maps x = dXi0 * i, y = dXi1 * j):
  *   LedgeMap::fill_bathymetry            geometry/maps/LedgeMap.cpp:38-60, 98-164   order 1 / 3: h_l left of x_l, h_r right of x_r,

@@ -198,6 +198,15 @@ _SIGS = {
     "somar_solver_metric_download": [_H, C.c_int, C.c_int, C.c_int, _PD],
     "somar_solver_set_precision": [_H, C.c_int, C.c_longlong],
     "somar_solver_get_precision": [_H, _PI, _PI],
+    # several components on one operator
+    "somar_solver_set_components": [_H, C.c_int, C.c_longlong],
+    "somar_solver_get_components": [_H, _PI, _PI, C.POINTER(C.c_longlong)],
+    "somar_comp_upload": [_H, C.c_int, C.c_int, C.c_int, _PD, _PI],
+    "somar_comp_download": [_H, C.c_int, C.c_int, C.c_int, _PD, _PI],
+    "somar_solver_solve_multi": [_H, C.c_int, C.c_int, C.POINTER(Stats)],
+    "somar_vcycle_multi": [_H, C.c_int],
+    "somar_heat_step_multi": [_H, C.c_int, C.c_double, C.c_int, C.POINTER(Stats)],
+    "somar_comp_history": [_H, C.c_int, _PD, C.c_int, _PI],
     # caller arrays in device memory: HOST tables of device addresses, one per local patch
     "somar_field_upload_dev": [_H, C.c_int, _PV, _PI],
     "somar_field_download_dev": [_H, C.c_int, _PV, _PI],
@@ -835,6 +844,59 @@ class AMRPressureSolver:
         st = Stats()
         _ck(lib().somar_heat_step(self._h, int(scheme), float(dt), int(zeroPhi), C.byref(st)))
         return self._stats(st)
+
+    # -- several components on one operator (somar_solver_set_components) ---------------------------------
+    def setComponents(self, ncomp, min_cells=0):
+        """ncomp (1..4) components on this handle's operator: each owns PHI, RHS, RES, CORR, BEST, HEAT_OLD, HEAT_SRC of
+        depth 0; metric, alpha / beta and BCs are shared.  Component 0 is the handle's own fields.  After finalize; 1 releases
+        the others.  min_cells: depths with at least that many cells are batched (0: the library's threshold)."""
+        _ck(lib().somar_solver_set_components(self._h, int(ncomp), int(min_cells)))
+
+    def getComponents(self):
+        """(ncomp, batched depths K, N-field launches issued so far)"""
+        n, k, m = C.c_int(), C.c_int(), C.c_longlong()
+        _ck(lib().somar_solver_get_components(self._h, C.byref(n), C.byref(k), C.byref(m)))
+        return n.value, k.value, m.value
+
+    def uploadComp(self, comp, field, patch, host, ghost):
+        _ck(lib().somar_comp_upload(self._h, int(comp), field, patch, _dp(host), _ia(ghost)))
+
+    def downloadComp(self, comp, field, patch, ghost):
+        lo, hi, _ = self.patch_box(patch, 0)
+        shape = tuple(h - l + 1 + 2 * g for l, h, g in zip(lo, hi, ghost))
+        out = np.zeros(shape, dtype=np.float64, order="F")
+        _ck(lib().somar_comp_download(self._h, int(comp), field, patch, _dp(out), _ia(ghost)))
+        return out
+
+    def _stats_multi(self, arr):
+        """one dict per component (as solveResident's); raises on the first component whose solve blew up"""
+        return [dict(self._stats(st)) for st in arr]
+
+    def solveMulti(self, zeroPhi=True, forceHomogeneous=False):
+        """every component's F_PHI := the solution for its F_RHS, exactly as successive solveResident calls would leave it"""
+        n = self.getComponents()[0]
+        arr = (Stats * n)()
+        _ck(lib().somar_solver_solve_multi(self._h, int(zeroPhi), int(forceHomogeneous), arr))
+        return self._stats_multi(arr)
+
+    def vcycleMulti(self, from_zero=True):
+        """per component F_CORR := one V-cycle of F_RES (vcycleFromZero, or vcycle with from_zero=False)"""
+        _ck(lib().somar_vcycle_multi(self._h, int(from_zero)))
+
+    def heatStepMulti(self, scheme, dt, zeroPhi=True):
+        """heatStep on every component with one dt; the solves go through solveMulti"""
+        n = self.getComponents()[0]
+        arr = (Stats * n)()
+        _ck(lib().somar_heat_step_multi(self._h, int(scheme), float(dt), int(zeroPhi), arr))
+        return self._stats_multi(arr)
+
+    def compHistory(self, comp):
+        """the complete residual history of component comp in the last multi solve"""
+        n = C.c_int()
+        _ck(lib().somar_comp_history(self._h, int(comp), None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1))
+        _ck(lib().somar_comp_history(self._h, int(comp), out.ctypes.data_as(_PD), n.value, C.byref(n)))
+        return [float(v) for v in out[:n.value]]
 
     # -- cell-centred level projection (LevelCCProjector, velocity in flux form, SpaceDim comps + ghosts) --
     def uploadCCVel(self, patch, host, ghost):

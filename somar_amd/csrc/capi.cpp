@@ -1659,6 +1659,97 @@ int somar_solver_get_precision(const somar_solver_t* s, int* mode, int* fp32_dep
     API_END
 }
 
+// ---- several components on one operator (PressureSolver::set_components) ----
+int somar_solver_set_components(somar_solver_t* s, int ncomp, long long min_cells)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps, "null argument");
+    SOMAR_CHECK(ncomp <= 1 || (!s->lep && (s->owned || s->ps->amr_member())),
+                "set_components: more than one component is not available for the handles of a leptic solver");
+    s->ps->set_components(ncomp, min_cells);
+    API_END
+}
+
+int somar_solver_get_components(somar_solver_t* s, int* ncomp, int* batched_depths, long long* batched_launches)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps, "null argument");
+    if (ncomp) *ncomp = s->ps->components();
+    if (batched_depths) *batched_depths = s->ps->batched_depths();
+    if (batched_launches) *batched_launches = s->ps->batched_launches();
+    API_END
+}
+
+static double* comp_field_ptr(somar_solver* s, int comp, int field)
+{
+    SOMAR_CHECK(s && s->ps, "null argument");
+    SOMAR_CHECK((field >> 8) == 0, "a component's fields live at depth 0");
+    double* p = s->ps->comp_field(comp, field & 0xff);
+    SOMAR_CHECK(p != nullptr, "no such field of a component (PHI, RHS, RES, CORR, BEST, HEAT_OLD, HEAT_SRC)");
+    return p;
+}
+
+int somar_comp_upload(somar_solver_t* s, int comp, int field, int patch, const double* host, const int* ghost)
+{
+    API_BEGIN
+    double* f = comp_field_ptr(s, comp, field);
+    SOMAR_CHECK(host && ghost, "null pointer");
+    s->ps->upload(s->ps->io_field(f, 0, ghost, true), patch, host);
+    API_END
+}
+
+int somar_comp_download(somar_solver_t* s, int comp, int field, int patch, double* host, const int* ghost)
+{
+    API_BEGIN
+    double* f = comp_field_ptr(s, comp, field);
+    SOMAR_CHECK(host && ghost, "null pointer");
+    s->ps->download(s->ps->io_field(f, 0, ghost, true), patch, host);
+    API_END
+}
+
+static void fill_stats_multi(const std::vector<SolveStats>& st, somar_stats_t* stats)
+{
+    for (size_t c = 0; c < st.size(); ++c) fill_stats(st[c], stats ? stats + c : nullptr);   // (somar_last_history: the last component's)
+}
+
+int somar_solver_solve_multi(somar_solver_t* s, int zero_phi, int force_homogeneous, somar_stats_t* stats)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps, "null argument");
+    std::vector<SolveStats> st;
+    s->ps->solve_multi(zero_phi != 0, force_homogeneous != 0, st);
+    fill_stats_multi(st, stats);
+    API_END
+}
+
+int somar_vcycle_multi(somar_solver_t* s, int from_zero)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps, "null argument");
+    s->ps->vcycle_multi(from_zero != 0);
+    API_END
+}
+
+int somar_heat_step_multi(somar_solver_t* s, int scheme, double dt, int zero_phi, somar_stats_t* stats)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps, "null argument");
+    std::vector<SolveStats> st;
+    s->ps->heat_step_multi(scheme, dt, zero_phi != 0, st);
+    fill_stats_multi(st, stats);
+    API_END
+}
+
+int somar_comp_history(somar_solver_t* s, int comp, double* out, int capacity, int* n)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps && n && capacity >= 0 && (out || capacity == 0), "somar_comp_history: bad arguments");
+    const std::vector<double>& h = s->ps->comp_history(comp);
+    *n = (int)h.size();
+    for (int i = 0; i < capacity && i < *n; ++i) out[i] = h[i];
+    API_END
+}
+
 int somar_amr_metric_update_begin(somar_amr_t* a)
 {
     API_BEGIN

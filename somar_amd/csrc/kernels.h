@@ -107,6 +107,20 @@ void launch_resid_restrict(hipStream_t st, TileSpan tiles, const LevelDev& F, co
 void launch_resid_restrict(hipStream_t st, TileSpan tiles, const LevelDev& F, const MetricPtrs<float>& M,
                            const LevelDev& C, float* crse, const float* phi, const float* rhs, const int r[3],
                            double dxProduct, double* volsum);
+// The same three launches on NF = 2 or 3 fields that share the level's operator (multi_march.hip; PressureSolver::
+// set_components): the coefficient arrays are streamed once per launch, each field's arithmetic is the single-field kernel's.
+// Class-0 tiles of the 16-row forms on a streamed (non-uniform) diagonal metric without coarse-fine faces; fp64.
+// in_mode 0 (plain; NF = 2 only) or 1 (from zero) as above; the folded prolongation (3) stays with launch_gsrb_fused.
+template <int NF>
+struct SweepFields { double* out[NF]; const double* in[NF]; const double* rhs[NF]; };
+template <int NF>
+void launch_gsrb_fused_nf(hipStream_t st, TileSpan tiles, const LevelDev& L, const SweepFields<NF>& F, int in_mode);
+// C null: out[f] = rhs[f] - L[phi[f]] on the level; else out[f] on C = the J-weighted average of it (ratio r)
+template <int NF>
+struct ResidFields { double* out[NF]; const double* phi[NF]; const double* rhs[NF]; };
+template <int NF>
+void launch_resid_nf(hipStream_t st, TileSpan tiles, const LevelDev& F, const ResidFields<NF>& fields, const LevelDev* C,
+                     const int* r);
 // crse(ic) = sum over the children of ic of dxProduct / fjinv(child): the volume a coarse value is spread over
 void launch_child_volume(hipStream_t st, const LevelDev& C, const LevelDev& F, double* crse, const int r[3],
                          double dxProduct);

@@ -13,32 +13,16 @@
 // MODE 0: out = rhs - L[phi]   MODE 1: out = L[phi]
 #include "common.h"
 #include "kernels.h"
+#include "stencil_point.h"   // ld2, op_point: shared with the fused sweep and the N-field kernels (multi_march.hip)
 
 namespace somar {
 
 constexpr int RM_J = 16;   // region rows = 14-row tile + 1 low + 1 high
 
-// T: the element type of the fields and coefficient arrays -- double, or float on the depths of the opt-in mixed-precision
-// cycle (PressureSolver::set_precision), whose arithmetic then stays in float; only the volume sum is accumulated in double
-template <class T>
-__device__ __forceinline__ typename Vec2<T>::type rm_ld2(const T* __restrict__ a, long long idx, bool ok0, bool ok1,
-                                                         long long safe)
-{
-    // branch-free: always one aligned 16-byte load (from `safe`, any valid aligned element of the patch, when
-    // neither element may be touched), then selects.  Straight-line loads let the compiler count outstanding
-    // loads exactly (s_waitcnt vmcnt(N)) instead of draining everything at every predicated branch.
-#ifdef SOMAR_NT_LOADS
-    // streamed once per launch: keep the coefficient / right-hand-side lines out of the way of the phi halo reuse in L2
-    typedef T v2d_ __attribute__((ext_vector_type(2)));
-    const v2d_ w = __builtin_nontemporal_load(reinterpret_cast<const v2d_*>(a + ((ok0 || ok1) ? idx : safe)));
-    const typename Vec2<T>::type v = mk2<T>(w.x, w.y);
-#else
-    const typename Vec2<T>::type v = *reinterpret_cast<const typename Vec2<T>::type*>(a + ((ok0 || ok1) ? idx : safe));
-#endif
-    return mk2<T>(ok0 ? v.x : T(0), ok1 ? v.y : T(0));
-}
-
-// unconditional: the zeros rm_ld2 returns under a false predicate only reach cells that are not written (see gsrb_fused.hip)
+// E: the element type of the fields and coefficient arrays -- double, or float on the depths of the opt-in mixed-precision
+// cycle (PressureSolver::set_precision), whose arithmetic then stays in float; only the volume sum is accumulated in double.
+// ld2 (stencil_point.h): the branch-free predicated pair load
+// unconditional: the zeros ld2 returns under a false predicate only reach cells that are not written (see gsrb_fused.hip)
 template <class T>
 __device__ __forceinline__ typename Vec2<T>::type rm_uni2(double c, bool, bool) { return mk2<T>(T(c), T(c)); }
 
@@ -145,22 +129,22 @@ __device__ __forceinline__ void resid_march_body(E* __restrict__ S, E* __restric
     double vsum = 0.0;
 
     int k = t.k0;
-    E2 Pm = rm_ld2(phi, base + sk * (k - 1), o[0], o[1], p.off);
-    E2 Pc = rm_ld2(phi, base + sk * k, f0, f1, p.off);
-    E2 Gzc = UNI ? rm_uni2<E>(P.uc[2], o[0], o[1]) : rm_ld2(jgz, base + sk * k, o[0], o[1], p.off);
+    E2 Pm = ld2(phi, base + sk * (k - 1), o[0], o[1], p.off);
+    E2 Pc = ld2(phi, base + sk * k, f0, f1, p.off);
+    E2 Gzc = UNI ? rm_uni2<E>(P.uc[2], o[0], o[1]) : ld2(jgz, base + sk * k, o[0], o[1], p.off);
     const int kend = t.k0 + t.nk;
     for (; k < kend; ++k) {
         const int gk = p.lo[2] + k;
         const bool more = (k + 1 < kend);
         // ---- this step's loads ----
-        const E2 Pp = rm_ld2(phi, base + sk * (k + 1), more ? f0 : o[0], more ? f1 : o[1], p.off);
-        const E2 Gzp = UNI ? rm_uni2<E>(P.uc[2], o[0], o[1]) : rm_ld2(jgz, base + sk * (k + 1), o[0], o[1], p.off);
+        const E2 Pp = ld2(phi, base + sk * (k + 1), more ? f0 : o[0], more ? f1 : o[1], p.off);
+        const E2 Gzp = UNI ? rm_uni2<E>(P.uc[2], o[0], o[1]) : ld2(jgz, base + sk * (k + 1), o[0], o[1], p.off);
         E2 Rh = mk2<E>(E(0), E(0));
-        if (MODE != 1) Rh = rm_ld2(rhs, base + sk * k, o[0], o[1], p.off);
-        const E2 Ji = UNI ? rm_uni2<E>(P.uc[3], o[0], o[1]) : rm_ld2(jinv, base + sk * k, o[0], o[1], p.off);
-        const E2 Gx = UNI ? rm_uni2<E>(P.uc[0], gxo0, o[0] || o[1]) : rm_ld2(jgx, base + sk * k, gxo0, o[0] || o[1], p.off);
-        const E2 Gy = UNI ? rm_uni2<E>(P.uc[1], o[0], o[1]) : rm_ld2(jgy, base + sk * k, o[0], o[1], p.off);
-        const E2 Gyh = UNI ? rm_uni2<E>(P.uc[1], o[0], o[1]) : rm_ld2(jgy, base + sk * k + sj, o[0], o[1], p.off);
+        if (MODE != 1) Rh = ld2(rhs, base + sk * k, o[0], o[1], p.off);
+        const E2 Ji = UNI ? rm_uni2<E>(P.uc[3], o[0], o[1]) : ld2(jinv, base + sk * k, o[0], o[1], p.off);
+        const E2 Gx = UNI ? rm_uni2<E>(P.uc[0], gxo0, o[0] || o[1]) : ld2(jgx, base + sk * k, gxo0, o[0] || o[1], p.off);
+        const E2 Gy = UNI ? rm_uni2<E>(P.uc[1], o[0], o[1]) : ld2(jgy, base + sk * k, o[0], o[1], p.off);
+        const E2 Gyh = UNI ? rm_uni2<E>(P.uc[1], o[0], o[1]) : ld2(jgy, base + sk * k + sj, o[0], o[1], p.off);
         const E gx_next = __shfl_down(Gx.x, 1, 64);
 
         // ---- stage plane k; slot k&1 was last read two steps ago, one barrier per plane suffices ----
@@ -182,22 +166,9 @@ __device__ __forceinline__ void resid_march_body(E* __restrict__ S, E* __restric
                 const E pxh = s ? Sx(slot, row, rc + 1) : Pc.y;
                 const E pyl = Sx(slot, row - 1, rc), pyh = Sx(slot, row + 1, rc);
                 const E gxl = s ? Gx.y : Gx.x, gxh = s ? gx_next : Gx.y;
-                E fxl = gxl * sx * (pc - pxl);
-                E fxh = gxh * sx * (pxh - pc);
-                E fyl = (s ? Gy.y : Gy.x) * sy * (pc - pyl);
-                E fyh = (s ? Gyh.y : Gyh.x) * sy * (pyh - pc);
-                E fzl = (s ? Gzc.y : Gzc.x) * sz * (pc - (s ? Pm.y : Pm.x));
-                E fzh = (s ? Gzp.y : Gzp.x) * sz * ((s ? Pp.y : Pp.x) - pc);
-                if (zxl[s]) fxl = 0;
-                if (zxh[s]) fxh = 0;
-                if (zyl) fyl = 0;
-                if (zyh) fyh = 0;
-                if (zzl) fzl = 0;
-                if (zzh) fzh = 0;
-                const E beta = E(P.beta);
-                fxl *= beta; fxh *= beta; fyl *= beta; fyh *= beta; fzl *= beta; fzh *= beta;
-                E l = (s ? Ji.y : Ji.x) * ((fxh - fxl) * sx + (fyh - fyl) * sy + (fzh - fzl) * sz);
-                if (P.alpha != 0.0) l = E(P.alpha) * pc + E(1.0) * l;
+                const E l = op_point<E>(P, sx, sy, sz, pc, pxl, pxh, pyl, pyh, s ? Pm.y : Pm.x, s ? Pp.y : Pp.x, gxl, gxh,
+                                        s ? Gy.y : Gy.x, s ? Gyh.y : Gyh.x, s ? Gzc.y : Gzc.x, s ? Gzp.y : Gzp.x,
+                                        s ? Ji.y : Ji.x, zxl[s], zxh[s], zyl, zyh, zzl, zzh);
                 res[s] = (MODE != 1) ? ((s ? Rh.y : Rh.x) - l) : l;
             }
             if (MODE == 2) {

@@ -28,6 +28,7 @@ PressureSolver::~PressureSolver()
 {
     drop_graphs();
     mp_free();
+    mc_free();
     if (st_) hipStreamSynchronize(st_);
     if (st_comm_) { hipStreamSynchronize(st_comm_); hipStreamDestroy(st_comm_); }
     if (ev_ready_) hipEventDestroy(ev_ready_);
@@ -94,6 +95,7 @@ void PressureSolver::xchg(const Level& L, T* f)
     L.exchange(f, st_);
     if (timed) prof_end(2);
 }
+template void PressureSolver::xchg<double>(const Level&, double*);   // (solver_multi.cpp calls it too)
 
 double PressureSolver::fetch_scalar(int slot)
 {
@@ -775,6 +777,7 @@ void PressureSolver::refresh_metric()
         }
     drop_graphs();   // captured launches carry the old StencilParams and tile tables in their arguments
     if (mp_K_ > 0) mp_convert_metric();   // the fp32 copies of a mixed-precision cycle (the uniform flags may have changed)
+    if (ncomp_ > 1) mc_setup();           // the batched depths of a multi-component solver (likewise)
     sync();
     if (timing)
         fprintf(stderr, "[somar timing] metric refresh %lld cells: coarse depths %.3f s, flags + tiles %.3f s, volumes + probes %.3f s\n",
@@ -1971,6 +1974,8 @@ void PressureSolver::set_precision(int mode, long long min_cells)
     if (mode == 1) {
         const std::string why = mixed_refusal();
         SOMAR_CHECK(why.empty(), "set_precision: mixed precision is not available for " + why);
+        SOMAR_CHECK(ncomp_ == 1, "set_precision: mixed precision is not available for a solver of more than one component "
+                                 "(set_components: the fp32 cycle carries one field)");
     }
     mp_mode_ = mode;
     mp_min_cells_ = min_cells;

@@ -223,6 +223,27 @@ public:
     void exchange_bytes(long long out2[2]) const;
     int precision_mode() const { return mp_mode_; }
     int fp32_depths() const { return mp_K_; }
+    // ---- several components on ONE operator (solver_multi.cpp) -----------------------------------------------------------
+    // The viscous / diffusive solves of a time step run the same Helmholtz operator on SpaceDim (and more) fields; the reference
+    // keeps one solver per velocity component (m_viscSolverPtrs[idir], NavierStokes/AMRNavierStokesInit.cpp:887-1010).  Here one
+    // solver carries ncomp (1..4) components: each owns its depth-0 fields, all share the metric hierarchy, alpha / beta, the BC
+    // types and Dirichlet values.  Component 0 is the solver's own fields, which every other call keeps addressing.  After
+    // finalize; ncomp = 1 releases what the others held.  min_cells: a depth is BATCHED -- its sweeps and its residual +
+    // restriction are launches that carry several active components and read the coefficient arrays once (multi_march.hip)
+    // -- when it has at least that many cells (<= 0: the fused sweep's own threshold) and runs the fold path of the cycle on a
+    // streamed metric (mc_setup); the depths below go through the single-field cycle, one component after the other.  Either way solve_multi
+    // leaves every component as ncomp successive solve() calls would, bit for bit.  Refused where that does not reach
+    // (multi_refusal).
+    void set_components(int ncomp, long long min_cells);
+    int components() const { return ncomp_; }
+    int batched_depths() const { return mc_K_; }
+    long long batched_launches() const { return mc_launches_; }   // N-field launches so far (tests: a case reached its kernels)
+    // which: SOMAR_F_PHI (0), RHS (1), RES (2), CORR (3), BEST (4), HEAT_OLD (8), HEAT_SRC (9), depth 0; nullptr: no such field
+    double* comp_field(int comp, int which);
+    void solve_multi(bool zeroPhi, bool forceHomogeneous, std::vector<SolveStats>& st);
+    void vcycle_multi(bool from_zero);   // per component: F_CORR := one V-cycle of F_RES, as vcycle(e, res, from_zero)
+    void heat_step_multi(int scheme, double dt, bool zeroPhi, std::vector<SolveStats>& st);
+    const std::vector<double>& comp_history(int comp) const;   // residual history of the component's last multi solve
     // MG ratios imposed on the first depths (set before finalize): the coarsening pattern of the mini V-cycle of a
     // level refined by more than 2 (MappedAMRMultiGrid.H:1455-1482), and that mini V-cycle itself (:742-754)
     std::vector<std::array<int, 3>> forcedRatios;
@@ -328,6 +349,48 @@ private:
         else L.cf_homog(f, st_);
     }
     void cf_fill(const Level& L, float*, bool) { SOMAR_CHECK(L.ncf == 0, "internal: an fp32 depth with coarse-fine faces"); }
+    // ---- several components (solver_multi.cpp) ----
+    enum { MC_MAX = 4 };
+    struct Component { DevBuf<double> phi, rhs, res, corr, best, heat[3]; };   // depth 0 of a component beyond 0
+    struct CompDepth { DevBuf<double> corr, res, pp; };
+    int ncomp_ = 1;
+    long long mc_min_cells_ = 0, mc_launches_ = 0;
+    int mc_K_ = 0;                                   // depths 0 .. mc_K_ - 1 are batched
+    std::vector<Component> comps_;                   // [comp - 1]
+    // [comp][depth 0 .. K]: component 0 takes the solver's own arrays on the batched depths and owns depth K's pair only (the
+    // seam: every component's restricted residual waits there for its turn in the single-field cycle); the others own corr / res
+    // of depths 1 .. K and a ping-pong buffer per batched depth
+    std::vector<std::vector<CompDepth>> mc_depth_;
+    std::vector<TileTable> mc_ftiles_, mc_rtiles_;   // per batched depth: class-0 tables of the N-field sweep / residual
+    std::vector<std::vector<double>> mc_history_;
+    std::string multi_refusal() const;               // why ncomp > 1 is not available here ("" = it is)
+    void mc_setup();                                 // K, the components' buffers, the tile tables (set_components, metric refresh)
+    void mc_free();
+    void swap_comp(int comp);                        // component comp's depth-0 fields <-> the solver's own (comp 0: nothing)
+    // runs f with component comp in the place of the solver's own fields: the single-field code on that component.  (Where the
+    // graph-replayed legs start at depth 0 -- a level of at most Tuning::graph_cells cells, so nothing is batched and every
+    // multi call comes here -- the graphs are keyed on depth 0's correction / residual arrays, which change with the
+    // component: graph_cycle drops and recaptures them per component and call.  Same results; such a handle pays a graph
+    // instantiation per component where a one-component handle replays.)
+    template <class Fn>
+    void on_comp(int comp, Fn f)
+    {
+        swap_comp(comp);
+        try { f(); } catch (...) { swap_comp(comp); throw; }
+        swap_comp(comp);
+    }
+    // the fields of the active components, by position in the active list
+    struct CompFields { int n = 0; int comp[MC_MAX]; double* corr[MC_MAX]; double* res[MC_MAX]; };
+    double* mc_corr(int comp, int d) const { return (comp == 0 && d < mc_K_) ? f_corr[d].get() : mc_depth_[comp][d].corr.get(); }
+    double* mc_res(int comp, int d) const { return (comp == 0 && d < mc_K_) ? f_res[d].get() : mc_depth_[comp][d].res.get(); }
+    double* mc_pp(int comp, int d) const { return comp == 0 ? f_pp[d].get() : mc_depth_[comp][d].pp.get(); }
+    // per active component: the bottom solver's convergence metric going in (null: as it stands), its counts coming out
+    struct CompBottom { const double* metric = nullptr; int iters[MC_MAX], exit[MC_MAX]; };
+    void multi_cycle(int d, const CompFields& F, bool corr_zero, CompBottom& B);
+    void multi_sweeps(int d, const CompFields& F, int iters, bool e_zero, double* const* e_plus);
+    void multi_restrict(int d, const CompFields& F, double* const* crse);
+    // out[i] = rhs[i] - L[phi[i]] on depth 0 with the physical BCs (homogeneous or not), as residual()
+    void multi_residual0(int n, double* const* out, double* const* phi, double* const* rhs, bool homogeneous);
     double fetch_scalar(int slot);
     void fetch_scalars(int slot, int n);
     unsigned long long fetch_seq_ = 0;

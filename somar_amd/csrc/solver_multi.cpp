@@ -1,0 +1,517 @@
+// somar_amd/csrc/solver_multi.cpp -- several components on one operator (PressureSolver::set_components; see solver.h).
+//
+// The specification is one sentence: solve_multi leaves every component -- fields, statistics, residual history -- exactly
+// as ncomp successive solve() calls on the same handle would.  Everything here follows from it:
+//   * each component keeps its own outer-loop state (MappedAMRMultiGrid::solveNoInitResid, MappedAMRMultiGrid.H:979-1183);
+//     the components cycle in lock step, and one whose loop condition fails leaves the active set for good;
+//   * on the batched depths the fold path of the cycle (fused sweeps, residual + restriction, prolongation folded into the
+//     first post-smoothing sweep) runs as N-field launches (multi_march.hip) whose per-field arithmetic is the single-field
+//     kernels'; below the seam every component takes its turn in the single-field cycle(), through the solver's own arrays,
+//     so the captured graphs replay for all of them;
+//   * a component alone in the active set, and every component when no depth is batched, runs the single-field code.
+#include "solver.h"
+
+#include <cmath>
+
+namespace somar {
+
+std::string PressureSolver::multi_refusal() const
+{
+    if (amr_member_) return "a level of an AMR hierarchy (the composite cycle carries one field)";
+    if (full_) return "a non-diagonal metric (19-point operator)";
+    if (prm.relaxMode != RELAX_LEVEL_GSRB) return "a relax_mode other than LevelGSRB";
+    if (prm.numMG != 1) return "num_mg != 1 (W- and F-cycles run plain passes, no folding)";
+    if (hasCF_ || !forcedRatios.empty()) return "a level with coarse-fine boundaries";
+    if (comm_->size > 1 || coarse_) return "a level sharded over more than one rank";
+    if (mp_mode_ == 1) return "set_precision mode 1 (the fp32 cycle carries one field)";
+    return "";
+}
+
+void PressureSolver::set_components(int ncomp, long long min_cells)
+{
+    check_idle("set_components");
+    SOMAR_CHECK(ncomp >= 1 && ncomp <= MC_MAX, "set_components: 1 to 4 components");
+    if (ncomp > 1) {
+        const std::string why = multi_refusal();   // (before the finalize check: the reason is the better message)
+        SOMAR_CHECK(why.empty(), "set_components: more than one component is not available for " + why);
+    }
+    SOMAR_CHECK(finalized, "set_components before finalize");
+    sync();
+    ncomp_ = ncomp;
+    mc_min_cells_ = min_cells;
+    mc_setup();
+}
+
+void PressureSolver::mc_free()
+{
+    if (st_) hipStreamSynchronize(st_);
+    comps_.clear();
+    mc_depth_.clear();
+    mc_ftiles_.clear();
+    mc_rtiles_.clear();
+    mc_history_.clear();
+    mc_K_ = 0;
+}
+
+void PressureSolver::mc_setup()
+{
+    // the components' own fields outlive a metric refresh: only the batched depths are decided again
+    std::vector<Component> keep = std::move(comps_);
+    mc_free();
+    comps_ = std::move(keep);
+    if (ncomp_ == 1) {
+        comps_.clear();
+        return;
+    }
+    Level& L0 = *lev[0];
+    comps_.resize(ncomp_ - 1);
+    for (Component& c : comps_)
+        for (DevBuf<double>* f : {&c.phi, &c.rhs, &c.res, &c.corr, &c.best})
+            if (!*f) *f = L0.alloc_field();
+    mc_history_.assign(ncomp_, {});
+    // A depth is batched where the fp32 cycle's conditions hold (mp_setup) -- the fused sweep and the marching restriction run
+    // there, the prolongation folds, the depth lies before the graph-replayed legs, MG ratios of 1 or 2, tree-ordered sums --
+    // and, in addition: no zero-average prolongation (sweep modes 2 / 4 and the fold sums stay single-field: a Helmholtz
+    // operator or a Dirichlet side has no null space), a streamed metric (the uniform-metric kernels read no coefficient
+    // array, so there is nothing to share) and the 16-row sweep (the 8-row form re-reads half its region as halo).
+    const long long minc = mc_min_cells_ > 0 ? mc_min_cells_ : tune_.fused_min_cells;
+    const int D = (int)lev.size();
+    int K = 0;
+    for (int d = 0; d + 1 < D && !tune_.no_fold_prolong; ++d) {
+        const Level& L = *lev[d];
+        if (graph_from_ >= 0 && d >= graph_from_) break;
+        if (!fused_relax(d, prm.num_smooth_down) || !fused_relax(d, prm.num_smooth_up)) break;
+        if (L.valid_cells_global < minc || L.valid_cells_global < tune_.march_min_cells || ordered(d)) break;
+        if (L.zeroAvg || L.dev.P.uniform || L.dev.fused_rows != 16 || L.ncf != 0) break;
+        bool ok = true;
+        for (int q = 0; q < 3; ++q) ok = ok && (L.mgCrseRefRatio[q] == 1 || L.mgCrseRefRatio[q] == 2);
+        for (const PatchDesc& p : L.hpatches) ok = ok && !(p.n[0] & 1);   // pairs of cells per lane
+        if (!ok) break;
+        K = d + 1;
+    }
+    mc_depth_.resize(ncomp_);
+    for (int c = 0; c < ncomp_; ++c) {
+        mc_depth_[c].resize(K + 1);
+        for (int d = 0; d <= K && K > 0; ++d) {
+            CompDepth& z = mc_depth_[c][d];
+            if (d == K || (c > 0 && d > 0)) { z.corr = lev[d]->alloc_field(); z.res = lev[d]->alloc_field(); }
+            if (c > 0 && d < K) z.pp = lev[d]->alloc_field();
+        }
+    }
+    // class-0 tables of the batched depths (march_plan.h): equal columns of at most 124 cells, whatever the level's own tables
+    // hold -- a cell's arithmetic does not depend on the tile that computes it
+    namespace mp = march_plan;
+    mc_ftiles_.resize(K);
+    mc_rtiles_.resize(K);
+    for (int d = 0; d < K; ++d) {
+        std::vector<mp::BoxSize> sizes;
+        for (const PatchDesc& p : lev[d]->hpatches) sizes.push_back({p.n[0], p.n[1], p.n[2]});
+        mp::Table f = mp::march_tiles(mp::fused_shape(16, false), sizes), r = mp::march_tiles(mp::resid_shape(false), sizes);
+        mp::number_slots(r.tiles);
+        SOMAR_CHECK(f.classes == 0 && r.classes == 0, "internal: the N-field kernels take class-0 tiles");
+        for (const Tile& t : r.tiles) SOMAR_CHECK(!(t.j0 & 1) && !(t.k0 & 1), "internal: restriction tiles start on even rows and planes");
+        mc_ftiles_[d].assign(std::move(f.tiles), 0);
+        mc_rtiles_[d].assign(std::move(r.tiles), 0);
+    }
+    mc_K_ = K;
+    sync();
+}
+
+void PressureSolver::swap_comp(int comp)
+{
+    if (comp == 0) return;
+    Component& c = comps_.at(comp - 1);
+    std::swap(f_phi, c.phi);
+    std::swap(f_rhs, c.rhs);
+    std::swap(f_uberRes, c.res);
+    std::swap(f_uberCorr, c.corr);
+    std::swap(f_best, c.best);
+    for (int q = 0; q < 3; ++q) std::swap(f_heat[q], c.heat[q]);
+}
+
+double* PressureSolver::comp_field(int comp, int which)
+{
+    SOMAR_CHECK(finalized && comp >= 0 && comp < ncomp_, "component out of range (somar_solver_set_components)");
+    if (comp == 0) return (which <= 4 || which == 8 || which == 9) ? field(0, which) : nullptr;
+    Component& c = comps_[comp - 1];
+    switch (which) {
+        case 0: return c.phi;
+        case 1: return c.rhs;
+        case 2: return c.res;
+        case 3: return c.corr;
+        case 4: return c.best;
+        case 8: case 9:
+            if (!c.heat[which - 8]) c.heat[which - 8] = lev[0]->alloc_field();
+            return c.heat[which - 8];
+        default: return nullptr;
+    }
+}
+
+const std::vector<double>& PressureSolver::comp_history(int comp) const
+{
+    SOMAR_CHECK(comp >= 0 && comp < ncomp_ && comp < (int)mc_history_.size(), "component out of range, or no multi solve yet");
+    return mc_history_[comp];
+}
+
+// ------------------------------------------------------------------------------------
+// the fold path of the cycle on the active components (fused_sweeps / march_restrict / fold_up on N fields)
+// ------------------------------------------------------------------------------------
+// how n fields go into launches of at most maxnf: 4 = 2 + 2 (three planes of four fields do not fit the LDS), 3 = 2 + 1
+static int launch_plan(int n, int maxnf, int* out)
+{
+    int m = 0;
+    while (n > 0) {
+        const int take = maxnf == 1 ? 1 : (n <= maxnf ? n : (n == 4 || maxnf == 2 ? 2 : maxnf));
+        out[m++] = take;
+        n -= take;
+    }
+    return m;
+}
+
+void PressureSolver::multi_sweeps(int d, const CompFields& F, int iters, bool e_zero, double* const* e_plus)
+{
+    Level& L = *lev[d];
+    const int n = F.n;
+    if (e_zero && tune_.no_zero_start) {
+        for (int i = 0; i < n; ++i) launch_set(st_, F.corr[i], L.field_elems, 0.0);
+        e_zero = false;
+    }
+    for (int i = 0; i < n; ++i) xchg(L, F.res[i]);   // rhs ghosts: constant over the sweeps
+    double *cur[MC_MAX], *alt[MC_MAX];
+    for (int i = 0; i < n; ++i) { cur[i] = F.corr[i]; alt[i] = mc_pp(F.comp[i], d); }
+    const LevelDev* C = e_plus ? &lev[d + 1]->dev : nullptr;
+    // Launch shapes, as measured at 512^3 per field against the single-field sweep (profiles/r08_multi.md): from zero, two
+    // fields -32 % and three -27 % (three beat 2 + 1); plain, two fields -11 %.  The plain sweep on three fields and the sweep
+    // with the prolongation folded in spilled registers and lost (multi_march.hip): three plain go as 2 + 1, and the folded
+    // sweep -- the first post-smoothing one -- runs field by field through the single-field kernel.
+    int plan[MC_MAX];
+    for (int it = 0; it < iters; ++it) {
+        const bool zin = e_zero && it == 0;
+        const int mode = zin ? 1 : (it == 0 && e_plus ? 3 : 0);
+        if (!zin)
+            for (int i = 0; i < n; ++i) xchg(L, cur[i]);
+        const int nl = launch_plan(n, mode == 1 ? 3 : (mode == 3 ? 1 : 2), plan);
+        for (int q = 0, i0 = 0; q < nl; i0 += plan[q], ++q) {
+            if (plan[q] == 1) {
+                launch_gsrb_fused(st_, L.ftiles.all.span(), L.dev, metric_ptrs(L.dev), alt[i0], cur[i0], F.res[i0], mode, nullptr, C,
+                                  mode == 3 ? e_plus[i0] : nullptr, L.mgCrseRefRatio);
+            } else if (plan[q] == 2) {
+                SweepFields<2> S;
+                for (int f = 0; f < 2; ++f) { S.out[f] = alt[i0 + f]; S.in[f] = cur[i0 + f]; S.rhs[f] = F.res[i0 + f]; }
+                launch_gsrb_fused_nf<2>(st_, mc_ftiles_[d].span(), L.dev, S, mode);
+                ++mc_launches_;
+            } else {
+                SweepFields<3> S;
+                for (int f = 0; f < 3; ++f) { S.out[f] = alt[i0 + f]; S.in[f] = cur[i0 + f]; S.rhs[f] = F.res[i0 + f]; }
+                launch_gsrb_fused_nf<3>(st_, mc_ftiles_[d].span(), L.dev, S, mode);
+                ++mc_launches_;
+            }
+        }
+        for (int i = 0; i < n; ++i) std::swap(cur[i], alt[i]);
+    }
+    for (int i = 0; i < n; ++i)
+        if (cur[i] != F.corr[i]) launch_copy(st_, F.corr[i], cur[i], L.field_elems);
+}
+
+void PressureSolver::multi_restrict(int d, const CompFields& F, double* const* crse)
+{
+    Level& L = *lev[d];
+    for (int i = 0; i < F.n; ++i) {
+        xchg(L, F.corr[i]);
+        if (diri_) diri_homog(d, F.corr[i]);   // homogeneous Dirichlet ghosts, as residual() fills them
+    }
+    int plan[MC_MAX];
+    const int nl = launch_plan(F.n, 2, plan);   // (the handed-over rows of three fields would fill the LDS to the last byte)
+    for (int q = 0, i0 = 0; q < nl; i0 += plan[q], ++q) {
+        if (plan[q] == 1) {
+            launch_resid_restrict(st_, L.rtiles.all.span(), L.dev, metric_ptrs(L.dev), lev[d + 1]->dev, crse[i0], F.corr[i0], F.res[i0],
+                                  L.mgCrseRefRatio, L.dxProduct, nullptr);
+        } else {
+            ResidFields<2> R;
+            for (int f = 0; f < 2; ++f) { R.out[f] = crse[i0 + f]; R.phi[f] = F.corr[i0 + f]; R.rhs[f] = F.res[i0 + f]; }
+            launch_resid_nf<2>(st_, mc_rtiles_[d].span(), L.dev, R, &lev[d + 1]->dev, L.mgCrseRefRatio);
+            ++mc_launches_;
+        }
+    }
+    sf_valid_[d] = 0;   // (as march_restrict leaves it on a depth without a zero-average prolongation)
+}
+
+void PressureSolver::multi_residual0(int n, double* const* out, double* const* phi, double* const* rhs, bool homogeneous)
+{
+    Level& L = *lev[0];
+    for (int i = 0; i < n; ++i) {
+        xchg(L, phi[i]);                              // exchangeComplete, as operator_i
+        if (diri_) apply_diri(0, phi[i], homogeneous);
+    }
+    int plan[MC_MAX];
+    const int nl = launch_plan(n, 3, plan);   // (per field against the single-field residual: two fields -30 %, three -44 %)
+    for (int q = 0, i0 = 0; q < nl; i0 += plan[q], ++q) {
+        if (plan[q] == 1) {
+            launch_resid_march(st_, L.rtiles.all.span(), L.dev, out[i0], phi[i0], rhs[i0], 0);
+        } else if (plan[q] == 2) {
+            ResidFields<2> R;
+            for (int f = 0; f < 2; ++f) { R.out[f] = out[i0 + f]; R.phi[f] = phi[i0 + f]; R.rhs[f] = rhs[i0 + f]; }
+            launch_resid_nf<2>(st_, mc_rtiles_[0].span(), L.dev, R, nullptr, nullptr);
+            ++mc_launches_;
+        } else {
+            ResidFields<3> R;
+            for (int f = 0; f < 3; ++f) { R.out[f] = out[i0 + f]; R.phi[f] = phi[i0 + f]; R.rhs[f] = rhs[i0 + f]; }
+            launch_resid_nf<3>(st_, mc_rtiles_[0].span(), L.dev, R, nullptr, nullptr);
+            ++mc_launches_;
+        }
+    }
+}
+
+// cycle(d, ...) on the active components; d is a batched depth
+void PressureSolver::multi_cycle(int d, const CompFields& F, bool corr_zero, CompBottom& B)
+{
+    const int n = F.n, K = mc_K_;
+    if (n == 1) {
+        // alone in the active set: the single-field cycle, on this component's arrays
+        if (B.metric) bottom_metric = B.metric[0];
+        cycle(d, F.corr[0], F.res[0], corr_zero);
+        B.iters[0] = bottom_iters;
+        B.exit[0] = bottom_exit;
+        return;
+    }
+    multi_sweeps(d, F, prm.num_smooth_down, corr_zero, nullptr);
+    CompFields N;
+    N.n = n;
+    for (int i = 0; i < n; ++i) {
+        N.comp[i] = F.comp[i];
+        N.corr[i] = mc_corr(F.comp[i], d + 1);
+        N.res[i] = mc_res(F.comp[i], d + 1);
+    }
+    multi_restrict(d, F, N.res);
+    if (d + 1 < K) {
+        multi_cycle(d + 1, N, true, B);
+        for (int i = 0; i < n; ++i) xchg(*lev[d + 1], N.corr[i]);
+    } else {
+        // the seam: every component takes its turn in the single-field cycle, through the solver's own arrays of depth K (the
+        // graphs are captured for those); its exchanged correction goes back to the component
+        const long long nK = lev[K]->field_elems;
+        for (int i = 0; i < n; ++i) {
+            launch_copy(st_, f_res[K], N.res[i], nK);
+            if (B.metric) bottom_metric = B.metric[i];
+            cycle(K, f_corr[K], f_res[K], true);
+            B.iters[i] = bottom_iters;
+            B.exit[i] = bottom_exit;
+            xchg(*lev[K], f_corr[K].get());
+            launch_copy(st_, N.corr[i], f_corr[K], nK);
+        }
+    }
+    multi_sweeps(d, F, prm.num_smooth_up, false, N.corr);
+}
+
+void PressureSolver::vcycle_multi(bool from_zero)
+{
+    SOMAR_CHECK(finalized, "vcycle_multi before finalize");
+    check_idle("vcycle_multi");
+    if (mc_K_ == 0 || ncomp_ == 1) {
+        for (int c = 0; c < ncomp_; ++c) on_comp(c, [&]() { vcycle(f_uberCorr, f_uberRes, from_zero); });
+        return;
+    }
+    CompFields F;
+    F.n = ncomp_;
+    for (int c = 0; c < ncomp_; ++c) { F.comp[c] = c; F.corr[c] = comp_field(c, 3); F.res[c] = comp_field(c, 2); }
+    CompBottom B;
+    multi_cycle(0, F, from_zero, B);
+}
+
+// ------------------------------------------------------------------------------------
+// MappedAMRMultiGrid::solveNoInitResid (PressureSolver::solve) on every component, in lock step
+// ------------------------------------------------------------------------------------
+void PressureSolver::solve_multi(bool zeroPhi, bool forceHomogeneous, std::vector<SolveStats>& out)
+{
+    SOMAR_CHECK(finalized, "solve_multi before finalize");
+    check_idle("solve_multi");
+    const int nc = ncomp_;
+    out.assign(nc, SolveStats());
+    mc_history_.assign(nc, {});
+    if (mc_K_ == 0 || nc == 1) {
+        for (int c = 0; c < nc; ++c) {
+            on_comp(c, [&]() { solve(zeroPhi, forceHomogeneous, out[c]); });
+            mc_history_[c] = out[c].history;
+        }
+        return;
+    }
+    Level& L = *lev[0];
+    const long long n = L.field_elems;
+    // the bottom solver's counts as they stand before the first component's solve: a solve that runs no cycle reports those
+    int carry_iters = bottom_iters, carry_exit = bottom_exit;
+    struct State {
+        double initial = 0, rnorm = 0, norm_last = 0, best = 0;
+        bool useBest = false, converged = false, goNorm = false, goRedu = false, goIter = false, goHang = false;
+        int iter = 0, b_iters = -1, b_exit = 0;
+        bool go() const { return goIter && goRedu && goHang && goNorm; }
+    } S[MC_MAX];
+    double *phi[MC_MAX], *rhs[MC_MAX], *res[MC_MAX], *corr[MC_MAX], *best[MC_MAX];
+    for (int c = 0; c < nc; ++c) {
+        phi[c] = comp_field(c, 0); rhs[c] = comp_field(c, 1); res[c] = comp_field(c, 2); corr[c] = comp_field(c, 3);
+        best[c] = comp_field(c, 4);
+        launch_set(st_, res[c], n, 0.0);
+        launch_set(st_, corr[c], n, 0.0);
+        if (zeroPhi) launch_set(st_, phi[c], n, 0.0);
+        launch_copy(st_, best[c], phi[c], n);
+    }
+    auto tests = [&](State& s) {
+        s.goNorm = s.rnorm > prm.normThresh;
+        s.goRedu = s.rnorm > prm.eps * s.initial;
+        s.goIter = s.iter < prm.imax;
+        s.goHang = s.iter < prm.imin || s.rnorm < (1 - prm.hang) * s.norm_last;
+    };
+    multi_residual0(nc, res, phi, rhs, forceHomogeneous);   // computeAMRResidual(..., a_forceHomogeneous), :1021
+    for (int c = 0; c < nc; ++c) {
+        State& s = S[c];
+        s.initial = s.rnorm = s.best = norm(0, res[c], 0);
+        s.norm_last = 2 * s.initial;
+        out[c].history.push_back(s.rnorm);
+        tests(s);
+    }
+    for (;;) {
+        CompFields F;
+        double metric[MC_MAX], *aphi[MC_MAX], *arhs[MC_MAX];
+        for (int c = 0; c < nc; ++c) {
+            if (!S[c].go()) continue;
+            const int i = F.n++;
+            F.comp[i] = c; F.corr[i] = corr[c]; F.res[i] = res[c];
+            metric[i] = S[c].initial;   // setConvergenceMetrics(initial_rnorm, cushion * eps), :1047
+            aphi[i] = phi[c]; arhs[i] = rhs[c];
+            S[c].norm_last = S[c].rnorm;
+        }
+        if (F.n == 0) break;
+        bottom_eps_eff = 1.0 * prm.eps;
+        CompBottom B;
+        B.metric = metric;
+        multi_cycle(0, F, true, B);   // uberCorrection is zero here (setToZero, :1203)
+        for (int i = 0; i < F.n; ++i) launch_incr(st_, aphi[i], F.corr[i], 1.0, n);   // postVCycleOps, :1189-1215
+        if (F.n == 1) residual(0, F.res[0], aphi[0], arhs[0], forceHomogeneous);
+        else multi_residual0(F.n, F.res, aphi, arhs, forceHomogeneous);
+        for (int i = 0; i < F.n; ++i) {
+            const int c = F.comp[i];
+            State& s = S[c];
+            s.b_iters = B.iters[i];
+            s.b_exit = B.exit[i];
+            s.rnorm = norm(0, res[c], 0);
+            ++s.iter;
+            out[c].history.push_back(s.rnorm);
+            if (s.rnorm <= s.best) {
+                s.best = s.rnorm;
+                launch_copy(st_, best[c], phi[c], n);
+                s.useBest = false;
+                s.converged = true;
+            } else {
+                s.useBest = true;
+            }
+            tests(s);
+        }
+    }
+    // The bottom solver's counts are the solver's, not a solve's: a solve without a cycle reports what the solve before it left
+    // -- component after component, starting from the counts on entry (the lock-step loop has long overwritten the members
+    // with cycles of later components).
+    for (int c = 0; c < nc; ++c) {
+        State& s = S[c];
+        SolveStats& o = out[c];
+        if (s.useBest) {
+            s.rnorm = s.best;
+            launch_copy(st_, phi[c], best[c], n);
+        }
+        o.status = 0;
+        if (s.rnorm > 10. * s.initial && s.rnorm > 10. * prm.eps) o.status = 1;                       // "kaboom" :1134
+        else if (!s.converged && s.rnorm >= s.initial && s.rnorm >= prm.eps) o.status = 2;            // :1141
+        o.exitStatus = int(!s.goRedu) + int(!s.goIter) * 2 + int(!s.goHang) * 4 + int(!s.goNorm) * 8;
+        o.iters = s.iter;
+        o.initial_rnorm = s.initial;
+        o.final_rnorm = s.rnorm;
+        if (s.b_iters >= 0) { carry_iters = s.b_iters; carry_exit = s.b_exit; }
+        o.bottom_iters_last = carry_iters;
+        o.bottom_exit_last = carry_exit;
+        bottom_metric = s.initial;
+        mc_history_[c] = o.history;
+    }
+    bottom_iters = carry_iters;
+    bottom_exit = carry_exit;
+    sync();
+}
+
+// heat_step (MappedLevelBackwardEuler / MappedLevelCrankNicolson / MappedLevelTGA ::updateSoln) on every component: one dt and
+// one alpha / beta serve all, so the stages that set the coefficients run component after component between them and the
+// solves go through solve_multi
+void PressureSolver::heat_step_multi(int scheme, double dt, bool zeroPhi, std::vector<SolveStats>& out)
+{
+    check_idle("heat_step_multi");
+    SOMAR_CHECK(scheme >= 0 && scheme <= 2, "heat scheme: 0 backward Euler, 1 Crank-Nicolson, 2 TGA");
+    SOMAR_CHECK(dt >= 0.0, "negative time step");
+    const int nc = ncomp_;
+    if (mc_K_ == 0 || nc == 1) {
+        out.assign(nc, SolveStats());
+        mc_history_.assign(nc, {});
+        for (int c = 0; c < nc; ++c) {
+            on_comp(c, [&]() { heat_step(scheme, dt, zeroPhi, out[c]); });
+            mc_history_[c] = out[c].history;
+        }
+        return;
+    }
+    const long long n = lev[0]->field_elems;
+    auto each = [&](auto f) {
+        for (int c = 0; c < nc; ++c) on_comp(c, f);
+    };
+    if (scheme == 0) {
+        each([&]() { launch_copy(st_, f_rhs, heat_field(0), n); });
+        set_alpha_beta(1.0, -dt * 1.0);
+    } else if (scheme == 1) {
+        set_alpha_beta(1.0, 0.5 * dt);
+        each([&]() {
+            apply_op(0, f_scratch[0], heat_field(0), false);
+            launch_copy(st_, f_rhs, heat_field(1), n);
+            launch_scale(st_, f_rhs, dt, n);
+            launch_incr(st_, f_rhs, f_scratch[0], 1.0, n);
+        });
+        set_alpha_beta(1.0, -dt * 0.5);
+    } else {
+        // MappedLevelTGA::updateSolnWithTimeIndependentOp; coefficients as heat_step
+        const double tgaEpsilon = 1.e-12;
+        const double a = 2.0 - std::sqrt(2.0) - tgaEpsilon;
+        const double discr = std::sqrt(a * a - 4.0 * a + 2.0);
+        const double mu1 = (a - discr) / 2.0, mu2 = (a + discr) / 2.0, mu3 = 1.0 - a, mu4 = 0.5 - a;
+        each([&]() {
+            launch_copy(st_, heat_field(2), heat_field(1), n);   // srct = dt * src
+            launch_scale(st_, heat_field(2), dt, n);
+        });
+        set_alpha_beta(1.0, mu4 * dt);
+        each([&]() { apply_op(0, f_rhs, heat_field(2), true); });   // rhst = (I + mu4 dt L) srct, homogeneous BCs
+        set_alpha_beta(1.0, mu3 * dt);
+        each([&]() {
+            apply_op(0, f_scratch[0], heat_field(0), false);         // (I + mu3 dt L) phiOld with the inhomogeneous BCs
+            launch_incr(st_, f_rhs, f_scratch[0], 1.0, n);
+            if (!zeroPhi) launch_copy(st_, heat_field(2), f_phi, n);
+        });
+        set_alpha_beta(1.0, -dt * mu2);
+        const int pre_iters = bottom_iters, pre_exit = bottom_exit;
+        std::vector<SolveStats> first;
+        solve_multi(zeroPhi, false, first);                          // (I - mu2 dt L) phi* = rhst
+        each([&]() {
+            launch_copy(st_, f_rhs, f_phi, n);                       // assign(rhst, phiNew)
+            if (!zeroPhi) launch_copy(st_, f_phi, heat_field(2), n);
+        });
+        set_alpha_beta(1.0, -dt * mu1);                              // (I - mu1 dt L) phiNew = phi*
+        solve_multi(zeroPhi, false, out);
+        // the bottom solver's counts a solve without a cycle reports are the ones the solve before it left: component after
+        // component that is this component's first solve, then the component before it
+        int bi = pre_iters, be = pre_exit;
+        for (int c = 0; c < nc; ++c) {
+            if (first[c].iters > 0) { bi = first[c].bottom_iters_last; be = first[c].bottom_exit_last; }
+            if (out[c].iters > 0) { bi = out[c].bottom_iters_last; be = out[c].bottom_exit_last; }
+            out[c].bottom_iters_last = bi;
+            out[c].bottom_exit_last = be;
+        }
+        bottom_iters = bi;
+        bottom_exit = be;
+        sync();
+        return;
+    }
+    solve_multi(zeroPhi, false, out);
+    sync();
+}
+
+}  // namespace somar

@@ -10,8 +10,37 @@ with narrow (124 + 4, 60 + 4) and equal columns in the level's own tables -- the
 their own, the odd component of a 2 + 1 restriction takes the level's -- and with six Dirichlet sides; the ragged four-box
 layout, periodic in x and y; the semicoarsened layout with ratios (1, 2, 2) then (2, 2, 2).
 
-Every case first proves it reaches its target: batched_depths equals the expected K and batched_launches grew.  A case that
-silently fell back to the single-field path fails instead of passing vacuously.
+Layouts chosen for the N-field path itself, where it differs from the single-field one:
+  * extra-wide, extra-wide-dirichlet (256 x 24 x 24, one box; each also as *-equal-tables with SOMAR_NO_NARROW_TILES=1): the
+    N-field launches of depth 0 run three class-0 columns 86 / 86 / 84 of their own table, the last one cut by the box and not
+    by the tile's width, while the level's own sweep table -- which the folded-prolongation sweep and the odd component of a
+    2 + 1 restriction take -- holds tall class-1 tiles (default) or the same equal columns (switch).  One V-cycle mixes the
+    two tilings of the same cells.  As in tests/test_gpu_tall_tiles.py the library exports no tile table: the default run
+    asserts the tall rule's inputs (assert_tall_rule), and tests/test_march_plan.py pins the N-field tables on the CPU.
+    Four batched depths, ratios (2, 1, 1) x 3 then (2, 2, 2).
+  * wide-mixed-sides: the 128-wide box with one Dirichlet and one Neumann side in every direction -- the boundary predicates
+    the N-field kernels restate (P.neum || (DIRI && P.diri) per side; the Neumann edge flags of the residual).
+  * ragged-mixed-sides: the four ragged boxes with Dirichlet and Neumann sides that run across the box seams in x and y, where
+    the tests on the global index (g < P.dom_lo) decide and the local one does not.
+  * ragged-periodic-dirichlet-z: periodic seams in x and y with a Dirichlet direction (DIRI instantiations, periodic wrap).
+  * ratio-212, ratio-221, ratio-112: the restriction ratios (2, 1, 2), (2, 2, 1) and (1, 1, 2), whose leader / hand-over /
+    first / last logic in accumulate() branches on each direction separately and had run only as (2, 1, 1), (2, 2, 2) and
+    (1, 2, 2).
+
+What the valid region cannot show, and what stands in for it:
+  * the cut of extra-wide's last column by the box: uncut, the sweep stores into the ghost columns 256 and 257, which every
+    reader refills or ignores.  test_vcycle_multi_leaves_the_ghost_cells_as_the_single_field_cycle compares the ghost layer.
+  * the `P.neum ||` / `DIRI && P.diri` terms of the sweep's ring predicate (comp_ij): they keep the red pass from updating a
+    ghost cell beyond a physical side.  gsrb_point never uses that cell's value -- a Neumann face contributes no flux, a
+    Dirichlet face's ghost is -own -- and the ring lives in LDS only, so with one term removed every field keeps every bit
+    (tried: all of this file passes).  What a wrong side or a local index in place of the global one does change is the
+    residual's Neumann flags and the classification inside gsrb_point, and there the mixed-sides layouts fail while the
+    symmetric ones pass (tried with the x-low flag taken from the x-high side).
+
+Every case first proves it reaches its target: batched_depths equals the expected K, batched_launches grew, the MG ratios are
+the oracle's and begin with the ratios the layout is there for, and the boxes of every batched depth have the stated widths.
+A case that silently fell back to the single-field path, or whose hierarchy coarsens otherwise, fails instead of passing
+vacuously.
 
 One refusal of the list cannot be reached from a one-level Python handle and is held by tests/test_multi_exports.py on the
 text of multi_refusal: coarse-fine faces exist only on the levels of a hierarchy, which are refused as such first."""
@@ -19,38 +48,81 @@ import numpy as np
 import pytest
 
 from tests.helpers import download_valid, make_problem, upload
-from tests.test_gpu_mixed_kernels import (RAGGED_BOXES, RAGGED_N, WIDE_BOX, WIDE_N, Case, gpu_solver, oracle_cycle, problem,
-                                          set_env)
+from tests.test_gpu_mixed_kernels import (RAGGED_BOXES, RAGGED_N, WIDE_BOX, WIDE_N, WIDE_RATIOS, Case, gpu_solver, oracle_cycle,
+                                          problem, set_env)
+from tests.test_gpu_tall_tiles import assert_tall_rule
 
 pytestmark = pytest.mark.gpu
 
-D = 1
+D, N = 1, 0
 ALPHA, BETA = 1.0, -0.01
 BC_VALUES = [0.25, -0.5, 0.75, 0.1, -0.3, 0.6]
 
 
-def _case(name, n, boxes, periodic, L, bc, narrow, K, variant="stretched", alpha=ALPHA, beta=BETA):
-    return Case(name, n, boxes, variant, periodic, L, bc, alpha, beta, narrow, K, None, None, None)
+def _case(name, n, boxes, periodic, L, bc, narrow, K, variant="stretched", alpha=ALPHA, beta=BETA, widths=None, ratios=None,
+          tables=None, ref=None):
+    """widths: the sorted box widths of every batched depth; ratios: the MG ratios the hierarchy must begin with; tables: None,
+    or "tall" / "equal" -- the level's own sweep table of a depth wider than 128 (SOMAR_NO_NARROW_TILES unset / 1); ref: the
+    layout whose references (_cycle_refs) serve this one -- the same problem under the other table, the same bits"""
+    c = Case(name, n, boxes, variant, periodic, L, bc, alpha, beta, narrow, K, widths, ratios, None)
+    c.tables, c.ref = tables, ref or name
+    return c
 
 
+WIDE_WIDTHS = [[128], [64], [32]]
+RAGGED_WIDTHS = [[32, 32, 48, 48], [16, 16, 24, 24]]
+XWIDE_N = (256, 24, 24)                       # 147456 cells; 128 x 24 x 24, 64 x 24 x 24, 32 x 24 x 24, then 16 x 12 x 12 replayed
+XWIDE_BOX = [((0, 0, 0), (255, 23, 23))]
+XWIDE_WIDTHS = [[256], [128], [64], [32]]
+XWIDE_RATIOS = [(2, 1, 1)] * 3 + [(2, 2, 2)]
 LAYOUTS = {c.name: c for c in [
-    _case("wide-narrow", WIDE_N, WIDE_BOX, (False,) * 3, (1.0, 1.0, 1.0), None, "1", 3),
-    _case("wide-equal", WIDE_N, WIDE_BOX, (False,) * 3, (1.0, 1.0, 1.0), None, "0", 3),
-    _case("wide-dirichlet", WIDE_N, WIDE_BOX, (False,) * 3, (1.0, 1.0, 1.0), [D] * 6, None, 3),
-    _case("ragged", RAGGED_N, RAGGED_BOXES, (True, True, False), (1.25, 1.0, 0.5), None, None, 2),
-    _case("anisotropic", (64, 32, 16), 32, (False, True, False), (4.0, 1.0, 0.5), None, None, 2),
+    _case("wide-narrow", WIDE_N, WIDE_BOX, (False,) * 3, (1.0, 1.0, 1.0), None, "1", 3, widths=WIDE_WIDTHS, ratios=WIDE_RATIOS),
+    _case("wide-equal", WIDE_N, WIDE_BOX, (False,) * 3, (1.0, 1.0, 1.0), None, "0", 3, widths=WIDE_WIDTHS, ratios=WIDE_RATIOS),
+    _case("wide-dirichlet", WIDE_N, WIDE_BOX, (False,) * 3, (1.0, 1.0, 1.0), [D] * 6, None, 3, widths=WIDE_WIDTHS,
+          ratios=WIDE_RATIOS),
+    _case("ragged", RAGGED_N, RAGGED_BOXES, (True, True, False), (1.25, 1.0, 0.5), None, None, 2, widths=RAGGED_WIDTHS,
+          ratios=[(2, 2, 2)] * 2),
+    _case("anisotropic", (64, 32, 16), 32, (False, True, False), (4.0, 1.0, 0.5), None, None, 2, widths=[[32, 32]] * 2,
+          ratios=[(1, 2, 2), (2, 2, 2)]),
+    # ---- the N-field path's own corners (module docstring) ----
+    _case("extra-wide", XWIDE_N, XWIDE_BOX, (False,) * 3, (1.0, 1.0, 1.0), None, None, 4, widths=XWIDE_WIDTHS,
+          ratios=XWIDE_RATIOS, tables="tall"),
+    _case("extra-wide-equal-tables", XWIDE_N, XWIDE_BOX, (False,) * 3, (1.0, 1.0, 1.0), None, None, 4, widths=XWIDE_WIDTHS,
+          ratios=XWIDE_RATIOS, tables="equal", ref="extra-wide"),
+    _case("extra-wide-dirichlet", XWIDE_N, XWIDE_BOX, (False,) * 3, (1.0, 1.0, 1.0), [D] * 6, None, 4, widths=XWIDE_WIDTHS,
+          ratios=XWIDE_RATIOS, tables="tall"),
+    _case("extra-wide-dirichlet-equal-tables", XWIDE_N, XWIDE_BOX, (False,) * 3, (1.0, 1.0, 1.0), [D] * 6, None, 4,
+          widths=XWIDE_WIDTHS, ratios=XWIDE_RATIOS, tables="equal", ref="extra-wide-dirichlet"),
+    _case("wide-mixed-sides", WIDE_N, WIDE_BOX, (False,) * 3, (1.0, 1.0, 1.0), [D, N, N, D, D, N], None, 3, widths=WIDE_WIDTHS,
+          ratios=WIDE_RATIOS),
+    _case("ragged-mixed-sides", RAGGED_N, RAGGED_BOXES, (False,) * 3, (1.25, 1.0, 0.5), [N, D, D, N, D, D], None, 2,
+          widths=RAGGED_WIDTHS, ratios=[(2, 2, 2)] * 2),
+    _case("ragged-periodic-dirichlet-z", RAGGED_N, RAGGED_BOXES, (True, True, False), (1.25, 1.0, 0.5), [N, N, N, N, D, D], None,
+          2, widths=RAGGED_WIDTHS, ratios=[(2, 2, 2)] * 2),
+    # 64 x 16 x 64 in four boxes 32 x 16 x 32: dx = 1/64, 1/16, 1/64 -> (2, 1, 2) twice, then 16^3 (4096 cells: replayed)
+    _case("ratio-212", (64, 16, 64), 32, (False,) * 3, (1.0, 1.0, 1.0), None, None, 2, widths=[[32] * 4, [16] * 4],
+          ratios=[(2, 1, 2), (2, 1, 2)]),
+    # 64 x 64 x 16 in four boxes 32 x 32 x 16: dx = 1/64, 1/64, 1/32 -> (2, 2, 1), then (2, 2, 2) to 16 x 16 x 8 (replayed)
+    _case("ratio-221", (64, 64, 16), 32, (False,) * 3, (1.0, 1.0, 0.5), None, None, 2, widths=[[32] * 4, [16] * 4],
+          ratios=[(2, 2, 1), (2, 2, 2)]),
+    # 32 x 32 x 64 in two boxes of 32^3: dx = 1/32, 1/32, 1/64 -> (1, 1, 2), then (2, 2, 2) to 16^3 (replayed)
+    _case("ratio-112", (32, 32, 64), 32, (False,) * 3, (1.0, 1.0, 1.0), None, None, 2, widths=[[32] * 2, [32] * 2],
+          ratios=[(1, 1, 2), (2, 2, 2)]),
 ]}
 
 
 @pytest.fixture(autouse=True)
 def _large_level_kernels(monkeypatch):
     set_env(monkeypatch.setenv)
-    monkeypatch.delenv("SOMAR_NARROW_7PT", raising=False)
+    for k in ("SOMAR_NARROW_7PT", "SOMAR_NO_NARROW_TILES", "SOMAR_FUSED_ROWS", "SOMAR_ORDERED_REDUCE_MAX"):
+        monkeypatch.delenv(k, raising=False)
 
 
 def _narrow_env(monkeypatch, case):
     if case.narrow is not None:
         monkeypatch.setenv("SOMAR_NARROW_7PT", case.narrow)
+    if case.tables == "equal":
+        monkeypatch.setenv("SOMAR_NO_NARROW_TILES", "1")
 
 
 def _up(s, comp, field, ld):
@@ -80,6 +152,21 @@ def _reaches(s, ncomp, K, before):
     return launches
 
 
+def _reaches_layout(s, case, K, oracle_ratios):
+    """the hierarchy is the one the layout is there for: the oracle's MG ratios, beginning with the case's; the box widths of
+    every batched depth; where the level's own sweep table matters, the inputs of the tall rule (the table itself is not
+    exported: tests/test_gpu_tall_tiles.py says what that leaves open, tests/test_march_plan.py pins the tables on the CPU)"""
+    assert s.mgRefRatios() == oracle_ratios, (s.mgRefRatios(), oracle_ratios)
+    assert s.mgRefRatios()[:len(case.ratios)] == case.ratios, s.mgRefRatios()
+    for d in range(K):
+        widths = sorted(s.patch_box(q, d)[1][0] - s.patch_box(q, d)[0][0] + 1 for q in range(s.num_local_patches))
+        assert widths == case.widths[d], (d, widths)
+    if case.tables == "tall":
+        assert_tall_rule(s, None)
+    elif case.tables == "equal":
+        assert s.tuning("NO_NARROW_TILES") == 1 and s.metricUniform(0) is None
+
+
 # ---- 1. the V-cycle kernels -------------------------------------------------------------------------------------------------
 _CYCLE_REFS = {}
 
@@ -88,7 +175,7 @@ def _cycle_refs(so, case, sweeps):
     """per component seed: the residual field and its single-field V-cycle from zero on a handle of one component; for
     component 1 the oracle's one_cycle too.  Computed once per (layout, sweeps) and left unchanged."""
     from somar_amd import api as F
-    key = (case.name, sweeps)
+    key = (case.ref, sweeps)
     if key not in _CYCLE_REFS:
         prob = problem(so, case)
         dom, grids = prob[0], prob[1]
@@ -104,8 +191,8 @@ def _cycle_refs(so, case, sweeps):
             assert s.getComponents()[2] == 0   # the single-field path issues no N-field launch
         finally:
             s.undefine()
-        ora, _ = oracle_cycle(so, case, prob, res[1], sweeps)
-        _CYCLE_REFS[key] = (prob, res, seq, ora)
+        ora, oratios = oracle_cycle(so, case, prob, res[1], sweeps)
+        _CYCLE_REFS[key] = (prob, res, seq, ora, oratios)
     return _CYCLE_REFS[key]
 
 
@@ -119,12 +206,13 @@ def test_vcycle_multi_is_the_single_field_cycle_per_component(oracle, monkeypatc
     # two (three: 2 + 1 with the level's own table), the folded prolongation sweep field by field; then the full K with 2/2/2
     # sweeps: plain two-field sweeps too (three: 2 + 1), and the batched depths below 0
     for sweeps, full_K in ((1, False), (2, True)):
-        prob, res, seq, ora = _cycle_refs(so, case, sweeps)
+        prob, res, seq, ora, oratios = _cycle_refs(so, case, sweeps)
         grids = prob[1]
         s = gpu_solver(case, prob, sweeps=sweeps)
         try:
             K = case.K if full_K else 1
             s.setComponents(ncomp, 0 if full_K else s.levelInfo(0)["cells"])   # depth 0 alone reaches min_cells
+            _reaches_layout(s, case, K, oratios)
             for c in range(ncomp):
                 _up(s, c, F.F_RES, res[c])
             s.vcycleMulti(True)
@@ -139,14 +227,21 @@ def test_vcycle_multi_is_the_single_field_cycle_per_component(oracle, monkeypatc
         _same(got[1], ora, "%s K=%d component 1 of %d vs the oracle's one_cycle" % (name, K, ncomp))
 
 
-def test_vcycle_multi_on_a_given_correction(oracle):
-    """from_zero = False: the first pre-smoothing sweep reads the correction (plain sweeps on depth 0), as somar_vcycle"""
+GHOST_MARK = 7.5   # what the caller leaves in the ghost cells of a given correction
+
+
+def _given_correction(so, case, ghost=(0, 0, 0)):
+    """ghost: how much of the ghost layer is compared too.  The caller's ghost cells hold GHOST_MARK + the component."""
     from somar_amd import api as F
-    so, case = oracle, LAYOUTS["wide-dirichlet"]
     prob = problem(so, case)
     dom, grids = prob[0], prob[1]
     res = [so.random_field(grids, 21 + c, (0, 0, 0), dom.box) for c in range(3)]
     cor = [so.random_field(grids, 31 + c, (1, 1, 1), dom.box) for c in range(3)]
+    for c in range(3):
+        for g, f in zip(grids, cor[c].fabs):
+            valid = np.array(f.view(g))
+            f.a[...] = GHOST_MARK + c
+            f.view(g)[...] = valid
     s = gpu_solver(case, prob)
     try:
         seq = []
@@ -154,17 +249,45 @@ def test_vcycle_multi_on_a_given_correction(oracle):
             upload(s, F.F_RES, res[c])
             upload(s, F.F_CORR, cor[c])
             s.vcycle(F.F_CORR, F.F_RES)
-            seq.append(download_valid(s, F.F_CORR, grids))
+            seq.append([s.download(F.F_CORR, q, ghost) for q in range(s.num_local_patches)])
         s.setComponents(3)
         for c in range(3):
             _up(s, c, F.F_RES, res[c])
             _up(s, c, F.F_CORR, cor[c])
         s.vcycleMulti(False)
         _reaches(s, 3, case.K, 0)
+        got = [[s.downloadComp(c, F.F_CORR, q, ghost) for q in range(s.num_local_patches)] for c in range(3)]
         for c in range(3):
-            _same(_down(s, c, F.F_CORR, grids), seq[c], "component %d" % c)
+            _same(got[c], seq[c], "%s, component %d" % (case.name, c))
+        return got
     finally:
         s.undefine()
+
+
+def test_vcycle_multi_on_a_given_correction(oracle):
+    """from_zero = False: the first pre-smoothing sweep reads the correction (plain sweeps on depth 0), as somar_vcycle"""
+    _given_correction(oracle, LAYOUTS["wide-dirichlet"])
+
+
+def test_vcycle_multi_on_a_given_correction_with_mixed_sides(oracle):
+    """the same with one Dirichlet and one Neumann side per direction: nothing fills the given correction's ghost cells on the
+    Neumann sides, they hold the caller's mark, which the sweeps must not read"""
+    _given_correction(oracle, LAYOUTS["wide-mixed-sides"])
+
+
+def test_vcycle_multi_leaves_the_ghost_cells_as_the_single_field_cycle(oracle):
+    """extra-wide, every side Neumann, the ghost layer compared too.  No exchange and no boundary condition writes the ghost
+    cells of this box, and an even number of sweeps per side (2/2/2) ends in the caller's array: the single-field cycle leaves
+    them as the caller uploaded them, and so must the N-field sweeps.  This is what the cut of the last of the three columns by
+    the box (l < n0; the tile's width 86 reaches two cells past it) is for: without it the sweep stores into the ghost columns
+    256 and 257, which no valid cell of a cycle ever reads back -- the valid region alone cannot show it."""
+    case = LAYOUTS["extra-wide"]
+    got = _given_correction(oracle, case, ghost=(1, 1, 1))
+    for c in range(3):
+        (a,) = got[c]
+        assert a.shape == tuple(n + 2 for n in case.n)
+        for face in (a[0], a[-1], a[:, 0], a[:, -1], a[:, :, 0], a[:, :, -1]):
+            np.testing.assert_array_equal(face, GHOST_MARK + c)
 
 
 # ---- 2. solves ----------------------------------------------------------------------------------------------------------------
@@ -214,7 +337,8 @@ def _solver(case, prob, eps, imax, bc_values=None, norm_thresh=None):
     return s
 
 
-def _solve_both_ways(so, case, zero_phi, force_homogeneous, bc_values=None, expect_K=None):
+def _solve_both_ways(so, case, zero_phi, force_homogeneous, bc_values=None, expect_K=None, face_values=None, phi_out=None):
+    """face_values: {(dir, side): plane} for setBCFaceValues; phi_out: a list that receives every component's phi"""
     from somar_amd import api as F
     prob = problem(so, case)
     dom, grids = prob[0], prob[1]
@@ -222,6 +346,8 @@ def _solve_both_ways(so, case, zero_phi, force_homogeneous, bc_values=None, expe
     guess = [so.random_field(grids, 51 + c, (1, 1, 1), dom.box) for c in range(3)]
     s = _solver(case, prob, EPS, IMAX, bc_values, NORM_THRESH)
     try:
+        for (d, side), plane in sorted((face_values or {}).items()):
+            s.setBCFaceValues(d, side, plane)
         seq = []
         for c in range(3):
             upload(s, F.F_RHS, rhs[c])
@@ -248,6 +374,8 @@ def _solve_both_ways(so, case, zero_phi, force_homogeneous, bc_values=None, expe
             for k in STAT_KEYS:
                 assert stats[c][k] == seq[c][1][k], (c, k, stats[c][k], seq[c][1][k])
             assert s.compHistory(c) == seq[c][2], c
+        if phi_out is not None:
+            phi_out.extend(seq[c][0] for c in range(3))
     finally:
         s.undefine()
     return stats
@@ -260,12 +388,15 @@ def _assert_active_set_shrinks(stats):
 
 
 @pytest.mark.parametrize("zero_phi", [True, False])
-@pytest.mark.parametrize("name", ["wide-narrow", "ragged"])
+@pytest.mark.parametrize("name", ["wide-narrow", "ragged", "extra-wide", "ragged-mixed-sides"])
 def test_solve_multi_is_three_solves(oracle, monkeypatch, name, zero_phi):
+    """(ragged-mixed-sides: with constant values on its Dirichlet sides -- those of the Neumann sides are ignored -- so the
+    right-hand side identically zero is no longer a solve without a cycle, and the active set is not asserted to shrink)"""
     case = LAYOUTS[name]
     _narrow_env(monkeypatch, case)
-    stats = _solve_both_ways(oracle, case, zero_phi, False)
-    if zero_phi:
+    values = BC_VALUES if case.bc is not None else None
+    stats = _solve_both_ways(oracle, case, zero_phi, False, bc_values=values)
+    if zero_phi and values is None:
         _assert_active_set_shrinks(stats)
 
 

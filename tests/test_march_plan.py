@@ -336,3 +336,43 @@ def test_split_without_regions(planner, table, halo):
     out = planner("split", table, halo, 0, 0, 0, 0, 0, 0)
     all_, own, rem = ([t[1:] for t in out if t[0] == sec] for sec in (0, 1, 2))
     assert rem == [] and own == all_ and all_
+
+
+# ---- the tables the N-field launches of a multi-component solver get (PressureSolver::mc_setup) --------------------------------
+# mc_setup builds, for every batched depth, march_tiles(fused_shape(16, false), sizes) and march_tiles(resid_shape(false), sizes)
+# + number_slots -- class-0 equal columns whatever the level's own tables hold.  The depth-0 boxes of three layouts of
+# tests/test_gpu_multi.py, with the columns (i0, w) per box width written out (not recomputed): 256 -> three columns of 86, the
+# last one 84 cells of box (the kernels cut it by the box, l < n0, not by w).
+NFIELD_BOXES = {
+    "extra-wide": [(256, 24, 24)],
+    "ragged-mixed-sides": [(48, 48, 32), (48, 16, 32), (32, 16, 32), (32, 48, 32)],
+    "ratio-112": [(32, 32, 32), (32, 32, 32)],
+}
+NFIELD_COLUMNS = {256: [(0, 86), (86, 86), (172, 86)], 48: [(0, 48)], 32: [(0, 32)]}
+
+
+@pytest.mark.parametrize("table, rows", [("fused", 12), ("resid", 14)])
+@pytest.mark.parametrize("layout", sorted(NFIELD_BOXES))
+def test_tables_of_the_n_field_launches(planner, layout, table, rows):
+    boxes = NFIELD_BOXES[layout]
+    (count, _, classes), tiles = planner("table", table, 0, 0, *[n for b in boxes for n in b])
+    assert classes == 0 and count == len(tiles) > 0
+    cover = [np.zeros(b, dtype=np.int32) for b in boxes]
+    for patch, i0, j0, k0, nk, w, cls, _slot in tiles:
+        n0, n1, n2 = boxes[patch]
+        assert cls == 0
+        assert (i0, w) in NFIELD_COLUMNS[n0], (patch, i0, w)
+        assert 0 <= i0 < n0 and 0 <= j0 < n1 and 0 <= k0 < n2 and nk > 0 and k0 + nk <= n2   # no empty tile, none past the box
+        assert w <= 124 and j0 % rows == 0
+        cover[patch][i0:min(i0 + w, n0), j0:min(j0 + rows, n1), k0:k0 + nk] += 1
+        if table == "resid":
+            # a coarse cell's two rows and two planes lie in one tile
+            assert j0 % 2 == 0 and k0 % 2 == 0 and (nk % 2 == 0 or k0 + nk == n2)
+    for patch, c in enumerate(cover):
+        assert c.min() == 1 and c.max() == 1, (patch, int(c.min()), int(c.max()))
+    for patch, (n0, _, _) in enumerate(boxes):
+        assert sorted({(t[1], t[5]) for t in tiles if t[0] == patch}) == NFIELD_COLUMNS[n0]   # every column is there
+    if table == "resid":
+        assert [t[7] for t in tiles] == list(range(len(tiles)))   # the per-tile sums' slots: the table's own order
+    else:
+        assert {t[7] for t in tiles} == {0}

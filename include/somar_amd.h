@@ -778,8 +778,10 @@ int somar_solver_get_precision(const somar_solver_t* s, int* mode, int* fp32_dep
  *  Refused, with the reason in somar_last_error: ncomp > 1 on a level of an AMR hierarchy, on the handles of a leptic solver,
  *  with a non-diagonal (19-point) metric, relax_mode other than LevelGSRB, num_mg != 1, coarse-fine faces, more than one rank,
  *  and with somar_solver_set_precision mode 1 -- in either order: mode 1 is refused on a handle of more than one component.
- *  Not offered (yet): per-component Dirichlet values; per-component BC types (free-slip walls, where the normal and the
- *  tangential components differ); _dev twins of the component I/O; levels sharded over ranks; the 19-point operator. */
+ *  Through somar_comp_set_op (below): per-component Dirichlet values; per-component BC types (free-slip walls, where the
+ *  normal and the tangential components differ); per-component alpha / beta.
+ *  Not offered (yet): face-valued Dirichlet sides per component; _dev twins of the component I/O; levels sharded over ranks;
+ *  the 19-point operator. */
 int somar_solver_set_components(somar_solver_t* s, int ncomp, long long min_cells);
 int somar_solver_get_components(somar_solver_t* s, int* ncomp, int* batched_depths, long long* batched_launches);
 int somar_comp_upload(somar_solver_t* s, int comp, int field, int patch, const double* host, const int* ghost);
@@ -788,6 +790,38 @@ int somar_solver_solve_multi(somar_solver_t* s, int zero_phi, int force_homogene
 int somar_vcycle_multi(somar_solver_t* s, int from_zero);
 int somar_heat_step_multi(somar_solver_t* s, int scheme, double dt, int zero_phi, somar_stats_t* stats);
 int somar_comp_history(somar_solver_t* s, int comp, double* out, int capacity, int* n);
+/* A component's own operator on the shared handle: its BC type and Dirichlet constant per side and its coefficient pair -- the
+ *  free-slip velocity components (normal Dirichlet, tangential Neumann), wall values that differ by component (a moving lid, an
+ *  inflow side), a scalar with another diffusivity and no-flux sides next to the velocities: the ordinary cases of the
+ *  reference's m_viscSolverPtrs[idir] and scalar diffusion solvers, on ONE metric hierarchy.
+ *  somar_comp_set_op: after somar_solver_set_components accepted ncomp > 1, for 1 <= comp < ncomp.  bc_type6 / bc_values6 in the
+ *    layout of somar_solver_create / somar_solver_set_bc_values ({loX, hiX, loY, hiY, loZ, hiZ}); a periodic direction keeps the
+ *    handle's own entries.  (alpha, beta) is the pair somar_solver_create takes: somar_solver_set_alpha_beta(a, b) applies
+ *    (a * alpha, b * beta) to this component and the handle's pair scaled alike to the others, so somar_heat_step_multi with one
+ *    dt advances every component with its own diffusivity.  Component 0 is the handle's create-time operator and is not settable
+ *    (create the handle with component 0's BCs).  A component without an operator of its own keeps the handle's, face-valued
+ *    Dirichlet sides included; one with its own has constants only.  Shrinking ncomp drops the operators of the components that
+ *    go away; a metric refresh keeps the others.  Memory: an operator keeps its Dirichlet ghost lists and, once used, its
+ *    captured graphs -- kilobytes; but this call, and every metric refresh once per operator, runs the null-space probe of
+ *    finalize, which holds three temporary fields per depth while it runs (3 GB at depth 0 of 512^3), freed before it returns.
+ *  Semantics: somar_solver_solve_multi, somar_vcycle_multi and somar_heat_step_multi leave component c -- fields, stats[c],
+ *    residual history -- exactly as the single-field call would on a SEPARATE one-component handle created with c's BC types,
+ *    values and coefficients on the same geometry and metric, bit for bit.  On the batched depths a launch whose fields agree in
+ *    operator is the shared-operator launch; one whose fields differ takes kernels that carry the sides and alpha / beta per
+ *    field and still read the coefficient arrays once (counted by somar_solver_get_op_launches; profiles/r12_multi_ops.md).
+ *    Below the batched depths every component runs the single-field cycle with its operator in place, graphs included (one
+ *    captured pair per operator).  After a multi call the handle holds component 0's operator again.
+ *  Refused, with the reason in somar_last_error and nothing changed: comp 0 or out of range; a type other than Neumann (0) or
+ *    Dirichlet (1) on a non-periodic side; an operator with a null space (the null-space probe of finalize, run at every depth
+ *    with the operator in place: the batched kernels carry no mean removal, such a component keeps a handle of its own); a call
+ *    during a metric update.
+ *  somar_comp_get_op: the operator component comp runs (0: the handle's); own = 1 if it was set here.  Any pointer may be NULL.
+ *  somar_comp_reset_op: back to the handle's operator.
+ *  somar_solver_get_op_launches: the N-field launches so far whose fields had different operators. */
+int somar_comp_set_op(somar_solver_t* s, int comp, const int* bc_type6, const double* bc_values6, double alpha, double beta);
+int somar_comp_get_op(somar_solver_t* s, int comp, int* bc_type6, double* bc_values6, double* alpha, double* beta, int* own);
+int somar_comp_reset_op(somar_solver_t* s, int comp);
+int somar_solver_get_op_launches(somar_solver_t* s, long long* launches);
 /* The nodal "depth" of the reference's analytic bathymetric maps, for SOMAR_MAP_BATHYMETRIC (host arithmetic, no GPU; x, y: the
  * Cartesian coordinates of the nodes, for these maps x = dXi0 * i, y = dXi1 * j):
  *   LedgeMap::fill_bathymetry            geometry/maps/LedgeMap.cpp:38-60, 98-164   order 1 / 3: h_l left of x_l, h_r right of x_r,

@@ -207,6 +207,11 @@ _SIGS = {
     "somar_vcycle_multi": [_H, C.c_int],
     "somar_heat_step_multi": [_H, C.c_int, C.c_double, C.c_int, C.POINTER(Stats)],
     "somar_comp_history": [_H, C.c_int, _PD, C.c_int, _PI],
+    # a component's own operator on the shared handle
+    "somar_comp_set_op": [_H, C.c_int, _PI, _PD, C.c_double, C.c_double],
+    "somar_comp_get_op": [_H, C.c_int, _PI, _PD, _PD, _PD, _PI],
+    "somar_comp_reset_op": [_H, C.c_int],
+    "somar_solver_get_op_launches": [_H, C.POINTER(C.c_longlong)],
     # caller arrays in device memory: HOST tables of device addresses, one per local patch
     "somar_field_upload_dev": [_H, C.c_int, _PV, _PI],
     "somar_field_download_dev": [_H, C.c_int, _PV, _PI],
@@ -897,6 +902,31 @@ class AMRPressureSolver:
         out = np.zeros(max(n.value, 1))
         _ck(lib().somar_comp_history(self._h, int(comp), out.ctypes.data_as(_PD), n.value, C.byref(n)))
         return [float(v) for v in out[:n.value]]
+
+    # -- a component's own operator on the shared handle (somar_comp_set_op) -------------------------------
+    def setCompOp(self, comp, bc_type6, bc_values6, alpha, beta):
+        """component comp (1 .. ncomp - 1) gets BC types and Dirichlet constants of its own ({loX, hiX, loY, hiY, loZ, hiZ}, as
+        define's bc_type and setBCValues) and its own (alpha, beta), the pair setAlphaBeta scales.  The multi calls then leave
+        it as the single-field call would on a separate handle created with that operator.  Refused for component 0, a type
+        other than Neumann / Dirichlet, an operator with a null space, and during a metric update."""
+        _ck(lib().somar_comp_set_op(self._h, int(comp), _ia(bc_type6), _da(bc_values6), float(alpha), float(beta)))
+
+    def getCompOp(self, comp):
+        """(bc_type6, bc_values6, alpha, beta, own) of the operator component comp runs; own: it was set by setCompOp"""
+        bc, val = (C.c_int * 6)(), (C.c_double * 6)()
+        a, b, own = C.c_double(), C.c_double(), C.c_int()
+        _ck(lib().somar_comp_get_op(self._h, int(comp), bc, val, C.byref(a), C.byref(b), C.byref(own)))
+        return list(bc), list(val), a.value, b.value, bool(own.value)
+
+    def resetCompOp(self, comp):
+        """component comp goes back to the handle's operator"""
+        _ck(lib().somar_comp_reset_op(self._h, int(comp)))
+
+    def opLaunches(self):
+        """the N-field launches issued so far whose fields had different operators"""
+        n = C.c_longlong()
+        _ck(lib().somar_solver_get_op_launches(self._h, C.byref(n)))
+        return n.value
 
     # -- cell-centred level projection (LevelCCProjector, velocity in flux form, SpaceDim comps + ghosts) --
     def uploadCCVel(self, patch, host, ghost):

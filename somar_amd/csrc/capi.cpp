@@ -1750,6 +1750,41 @@ int somar_comp_history(somar_solver_t* s, int comp, double* out, int capacity, i
     API_END
 }
 
+// ---- a component's own operator (PressureSolver::comp_set_op) ----
+int somar_comp_set_op(somar_solver_t* s, int comp, const int* bc_type6, const double* bc_values6, double alpha, double beta)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps && bc_type6 && bc_values6, "null argument");
+    s->ps->comp_set_op(comp, bc_type6, bc_values6, alpha, beta);
+    API_END
+}
+
+int somar_comp_get_op(somar_solver_t* s, int comp, int* bc_type6, double* bc_values6, double* alpha, double* beta, int* own)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps, "null argument");
+    bool o = false;
+    s->ps->comp_get_op(comp, bc_type6, bc_values6, alpha, beta, &o);
+    if (own) *own = o ? 1 : 0;
+    API_END
+}
+
+int somar_comp_reset_op(somar_solver_t* s, int comp)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps, "null argument");
+    s->ps->comp_reset_op(comp);
+    API_END
+}
+
+int somar_solver_get_op_launches(somar_solver_t* s, long long* launches)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps, "null argument");
+    if (launches) *launches = s->ps->op_launches();
+    API_END
+}
+
 int somar_amr_metric_update_begin(somar_amr_t* a)
 {
     API_BEGIN

@@ -121,6 +121,16 @@ struct ResidFields { double* out[NF]; const double* phi[NF]; const double* rhs[N
 template <int NF>
 void launch_resid_nf(hipStream_t st, TileSpan tiles, const LevelDev& F, const ResidFields<NF>& fields, const LevelDev* C,
                      const int* r);
+// The same launches on fields that differ in operator (PressureSolver::comp_set_op): P[f] is the level's StencilParams with
+// the sides (neum / diri) and alpha / beta of field f's operator; everything else in it is the level's and equal in all of them.
+template <int NF>
+struct FieldOps { StencilParams P[NF]; };
+template <int NF>
+void launch_gsrb_fused_nfo(hipStream_t st, TileSpan tiles, const LevelDev& L, const SweepFields<NF>& F, const FieldOps<NF>& O,
+                           int in_mode);
+template <int NF>
+void launch_resid_nfo(hipStream_t st, TileSpan tiles, const LevelDev& F, const ResidFields<NF>& fields, const FieldOps<NF>& O,
+                      const LevelDev* C, const int* r);
 // crse(ic) = sum over the children of ic of dxProduct / fjinv(child): the volume a coarse value is spread over
 void launch_child_volume(hipStream_t st, const LevelDev& C, const LevelDev& F, double* crse, const int r[3],
                          double dxProduct);

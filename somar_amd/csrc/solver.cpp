@@ -775,6 +775,9 @@ void PressureSolver::refresh_metric()
             lev[d]->beta = ab[d].second;
             lev[d]->refresh_params();
         }
+    // the components' own operators stay (comp_set_op); their probes run again, as a separate solver's refresh would run them
+    for (Component& c : comps_)
+        if (c.op) probe_op(*c.op, nullptr);
     drop_graphs();   // captured launches carry the old StencilParams and tile tables in their arguments
     if (mp_K_ > 0) mp_convert_metric();   // the fp32 copies of a mixed-precision cycle (the uniform flags may have changed)
     if (ncomp_ > 1) mc_setup();           // the batched depths of a multi-component solver (likewise)
@@ -1453,16 +1456,27 @@ void PressureSolver::set_alpha_beta(double a, double b, bool amr_member_ok)
     SOMAR_CHECK(finalized, "set_alpha_beta before finalize");
     SOMAR_CHECK(!amr_member_ || amr_member_ok,
                 "set_alpha_beta on a level of an AMR hierarchy goes through the hierarchy (somar_amr_set_alpha_beta)");
+    // in: a component's own operator is in place (comp_set_op; the single-field heat_step of that component comes here): the
+    // live pair is then that operator's, and the solver's own waits in its OpState
+    CompOp* in = comp_op(op_in_place_);
     if (!coefs_saved_) {
-        aCoef_ = lev[0]->alpha;
-        bCoef_ = lev[0]->beta;
+        aCoef_ = in ? in->st.alpha : lev[0]->alpha;
+        bCoef_ = in ? in->st.beta : lev[0]->beta;
         coefs_saved_ = true;
     }
     for (auto& L : lev) {
-        L->alpha = a * aCoef_;
-        L->beta = b * bCoef_;
+        L->alpha = a * (in ? in->alpha0 : aCoef_);
+        L->beta = b * (in ? in->beta0 : bCoef_);
         L->refresh_params();
     }
+    // every operator kept aside is scaled too, each like a separate solver created with its pair would be
+    ab_scale_[0] = a;
+    ab_scale_[1] = b;
+    for (Component& c : comps_)
+        if (c.op) {
+            c.op->st.alpha = a * (c.op.get() == in ? aCoef_ : c.op->alpha0);
+            c.op->st.beta = b * (c.op.get() == in ? bCoef_ : c.op->beta0);
+        }
     drop_graphs();  // captured launches carry the old coefficients in their kernel arguments
     if (coarse_) coarse_->set_alpha_beta(a, b);
 }
@@ -1719,14 +1733,24 @@ void PressureSolver::set_bc_values(const double v[6])
 // one GHOST_DIRI op per (patch, Dirichlet side it touches): the face-adjacent ghost layer, setSideDiriBC's destBox
 void PressureSolver::build_diri_ops(int d)
 {
-    Level& L = *lev[d];
+    std::vector<GhostOp> ops = make_diri_ops(d, lev[d]->bc_type, bc_value_, true);
+    if (d == 0) h_diri_ops0_ = ops;
+    n_diri_ops_[d] = (int)ops.size();
+    d_diri_ops_[d] = DevBuf<GhostOp>::from(ops);
+}
+
+// sides_of_solver: bc / val are the solver's own sides, which at depth 0 may be face-valued (set_diri_op); a component's
+// operator (comp_set_op) has constants only
+std::vector<GhostOp> PressureSolver::make_diri_ops(int d, const int bc[3][2], const double val[3][2], bool sides_of_solver) const
+{
+    const Level& L = *lev[d];
     std::vector<GhostOp> ops;
     for (int pi = 0; pi < L.npatches(); ++pi) {
         const IBox valid = L.boxes[L.local[pi]];
         for (int a = 0; a < 3; ++a) {
             if (!L.active[a] || L.periodic[a]) continue;
             for (int s = 0; s < 2; ++s) {
-                if (L.bc_type[a][s] != BC_DIRI) continue;
+                if (bc[a][s] != BC_DIRI) continue;
                 if ((s ? valid.hi[a] : valid.lo[a]) != (s ? L.domain.hi[a] : L.domain.lo[a])) continue;
                 GhostOp op;
                 std::memset(&op, 0, sizeof(op));
@@ -1737,15 +1761,13 @@ void PressureSolver::build_diri_ops(int d)
                 op.n[a] = 1;
                 op.dir = a;
                 op.sgn = s ? 1 : -1;
-                op.val = bc_value_[a][s];
-                if (d == 0) set_diri_op(op);
+                op.val = val[a][s];
+                if (d == 0 && sides_of_solver) set_diri_op(op);
                 ops.push_back(op);
             }
         }
     }
-    if (d == 0) h_diri_ops0_ = ops;
-    n_diri_ops_[d] = (int)ops.size();
-    d_diri_ops_[d] = DevBuf<GhostOp>::from(ops);
+    return ops;
 }
 
 void PressureSolver::apply_diri(int d, double* phi, bool homogeneous)
@@ -1874,11 +1896,19 @@ void PressureSolver::refresh_diri_ops()
         }
 }
 
+void PressureSolver::drop_graph(CoarseGraph& g)
+{
+    if (g.down) hipGraphExecDestroy(g.down);
+    if (g.up) hipGraphExecDestroy(g.up);
+    g = CoarseGraph();
+}
+
+// the graphs of the operator in place and of every operator kept aside (comp_set_op): one pair per operator
 void PressureSolver::drop_graphs()
 {
-    if (cg_.down) hipGraphExecDestroy(cg_.down);
-    if (cg_.up) hipGraphExecDestroy(cg_.up);
-    cg_ = CoarseGraph();
+    drop_graph(cg_);
+    for (Component& c : comps_)
+        if (c.op) drop_graph(c.op->st.cg);
 }
 
 // The V-cycle from depth d down to the bottom and back as two graph replays around the bottom solve.  Returns
@@ -1891,7 +1921,7 @@ bool PressureSolver::graph_cycle(int d, double* corr, const double* res, bool co
         return false;
     if (cg_.down && (cg_.d0 != d || cg_.corr != corr || cg_.res != res || cg_.pre != prm.num_smooth_down ||
                      cg_.post != prm.num_smooth_up || cg_.bottom != prm.num_smooth_bottom))
-        drop_graphs();
+        drop_graph(cg_);   // (the operator in place alone: the graphs of the others describe other calls)
     if (!cg_.down) {
         auto capture = [&](bool down) -> hipGraphExec_t {
             hipGraph_t g = nullptr;

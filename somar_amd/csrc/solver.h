@@ -244,6 +244,17 @@ public:
     void vcycle_multi(bool from_zero);   // per component: F_CORR := one V-cycle of F_RES, as vcycle(e, res, from_zero)
     void heat_step_multi(int scheme, double dt, bool zeroPhi, std::vector<SolveStats>& st);
     const std::vector<double>& comp_history(int comp) const;   // residual history of the component's last multi solve
+    // ---- a component's own operator (solver_multi.cpp): BC type and Dirichlet constant per side {loX,hiX,loY,hiY,loZ,hiZ} and
+    // the coefficient pair set_alpha_beta scales.  Component 0 is the solver's create-time operator and not settable; a
+    // component without an operator of its own keeps the solver's (face-valued sides included).  The multi calls then leave
+    // component c as the single-field call would on a separate one-component solver created with c's operator on the same
+    // metric.  Refused (nothing changed): comp 0 or out of range, a type other than Neumann / Dirichlet on a non-periodic
+    // side, an operator with a null space (the null-space probe run at every depth with the operator in place), an open
+    // metric update.  A periodic (or inactive) direction keeps the solver's entries.
+    void comp_set_op(int comp, const int bc_type6[6], const double bc_values6[6], double alpha, double beta);
+    void comp_get_op(int comp, int bc_type6[6], double bc_values6[6], double* alpha, double* beta, bool* own);
+    void comp_reset_op(int comp);
+    long long op_launches() const { return mc_op_launches_; }   // N-field launches whose fields had different operators
     // MG ratios imposed on the first depths (set before finalize): the coarsening pattern of the mini V-cycle of a
     // level refined by more than 2 (MappedAMRMultiGrid.H:1455-1482), and that mini V-cycle itself (:742-754)
     std::vector<std::array<int, 3>> forcedRatios;
@@ -351,10 +362,12 @@ private:
     void cf_fill(const Level& L, float*, bool) { SOMAR_CHECK(L.ncf == 0, "internal: an fp32 depth with coarse-fine faces"); }
     // ---- several components (solver_multi.cpp) ----
     enum { MC_MAX = 4 };
-    struct Component { DevBuf<double> phi, rhs, res, corr, best, heat[3]; };   // depth 0 of a component beyond 0
+    struct CompOp;   // a component's own operator (below, after CoarseGraph)
+    // depth 0 of a component beyond 0; op: its own operator, null while it shares the solver's
+    struct Component { DevBuf<double> phi, rhs, res, corr, best, heat[3]; std::unique_ptr<CompOp> op; };
     struct CompDepth { DevBuf<double> corr, res, pp; };
     int ncomp_ = 1;
-    long long mc_min_cells_ = 0, mc_launches_ = 0;
+    long long mc_min_cells_ = 0, mc_launches_ = 0, mc_op_launches_ = 0;
     int mc_K_ = 0;                                   // depths 0 .. mc_K_ - 1 are batched
     std::vector<Component> comps_;                   // [comp - 1]
     // [comp][depth 0 .. K]: component 0 takes the solver's own arrays on the batched depths and owns depth K's pair only (the
@@ -366,7 +379,8 @@ private:
     std::string multi_refusal() const;               // why ncomp > 1 is not available here ("" = it is)
     void mc_setup();                                 // K, the components' buffers, the tile tables (set_components, metric refresh)
     void mc_free();
-    void swap_comp(int comp);                        // component comp's depth-0 fields <-> the solver's own (comp 0: nothing)
+    // component comp's depth-0 fields <-> the solver's own, and its operator, if it has one, <-> the solver's (comp 0: nothing)
+    void swap_comp(int comp);
     // runs f with component comp in the place of the solver's own fields: the single-field code on that component.  (Where the
     // graph-replayed legs start at depth 0 -- a level of at most Tuning::graph_cells cells, so nothing is batched and every
     // multi call comes here -- the graphs are keyed on depth 0's correction / residual arrays, which change with the
@@ -390,7 +404,8 @@ private:
     void multi_sweeps(int d, const CompFields& F, int iters, bool e_zero, double* const* e_plus);
     void multi_restrict(int d, const CompFields& F, double* const* crse);
     // out[i] = rhs[i] - L[phi[i]] on depth 0 with the physical BCs (homogeneous or not), as residual()
-    void multi_residual0(int n, double* const* out, double* const* phi, double* const* rhs, bool homogeneous);
+    // (comp[i]: the component of position i, whose operator the physical ghosts and the launch take)
+    void multi_residual0(int n, const int* comp, double* const* out, double* const* phi, double* const* rhs, bool homogeneous);
     double fetch_scalar(int slot);
     void fetch_scalars(int slot, int n);
     unsigned long long fetch_seq_ = 0;
@@ -550,6 +565,61 @@ private:
         const double *corr = nullptr, *res = nullptr;
     };
     CoarseGraph cg_;
+    static void drop_graph(CoarseGraph& g);
+    // ---- a component's own operator (comp_set_op; solver_multi.cpp) ----
+    // What of the solver an operator decides, for the operator that is NOT in place: sides and coefficients (every depth
+    // carries the same ones), the Dirichlet values and op lists per depth, the null-space probe's verdict per depth, and the
+    // captured coarse legs, whose kernel arguments embed all of that.  exchange_op swaps it with the solver's live state, so a
+    // second call puts everything back; between the two the whole single-field code runs the component's operator.
+    struct OpState {
+        int bc[3][2] = {{0, 0}, {0, 0}, {0, 0}};
+        double val[3][2] = {{0, 0}, {0, 0}, {0, 0}};
+        double alpha = 0.0, beta = 1.0;   // as in force now (set_alpha_beta's scaling applied)
+        bool diri = false;
+        std::vector<DevBuf<GhostOp>> d_ops;
+        std::vector<int> n_ops;
+        std::vector<GhostOp> h_ops0;
+        std::vector<char> zeroAvg;
+        CoarseGraph cg;
+    };
+    struct CompOp {
+        double alpha0 = 0.0, beta0 = 1.0;   // the pair comp_set_op received (a separate solver's create-time alpha / beta)
+        OpState st;
+        ~CompOp() { drop_graph(st.cg); }
+    };
+    double ab_scale_[2] = {1.0, 1.0};   // set_alpha_beta's last (a, b)
+    int op_in_place_ = 0;               // the component whose operator is live (0: the solver's own)
+    CompOp* comp_op(int comp) const { return comp > 0 && comp <= (int)comps_.size() ? comps_[comp - 1].op.get() : nullptr; }
+    bool any_ops() const
+    {
+        for (const Component& c : comps_)
+            if (c.op) return true;
+        return false;
+    }
+    void exchange_op(OpState& o);
+    // runs f with component comp's operator in place (fields untouched); nothing to do for a component that shares the solver's
+    template <class Fn>
+    void on_op(int comp, Fn f)
+    {
+        CompOp* o = comp_op(comp);
+        if (!o) { f(); return; }
+        exchange_op(o->st);
+        op_in_place_ = comp;
+        try { f(); } catch (...) { exchange_op(o->st); op_in_place_ = 0; throw; }
+        exchange_op(o->st);
+        op_in_place_ = 0;
+    }
+    bool probe_op(CompOp& o, int* depth);                  // the null-space probe at every depth with o in place: any zeroAvg?
+    void ensure_face_copiers(const int bc[3][2]);          // Level::cf_faces for the operator's Dirichlet HIGH sides, every depth
+    StencilParams comp_params(int comp, int d) const;      // depth d's StencilParams under component comp's operator
+    void comp_diri(int comp, int d, double* phi, bool homogeneous);   // the Dirichlet ghosts of comp's operator (none: nothing)
+    // one N-field launch on the fields at positions i0 .. i0 + NF - 1 of the active list: the shared-operator kernel where
+    // their operators agree, the per-field form (and mc_op_launches_) where they differ
+    template <int NF>
+    void sweep_launch(int d, const int* comp, const SweepFields<NF>& S, int mode);
+    template <int NF>
+    void resid_launch(int d, const int* comp, const ResidFields<NF>& R, bool restrict);
+    std::vector<GhostOp> make_diri_ops(int d, const int bc[3][2], const double val[3][2], bool sides_of_solver) const;
     int graph_from_ = -1;
     bool capturing_ = false;
     bool diri_ = false;

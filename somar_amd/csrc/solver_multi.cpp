@@ -9,6 +9,10 @@
 //     kernels'; below the seam every component takes its turn in the single-field cycle(), through the solver's own arrays,
 //     so the captured graphs replay for all of them;
 //   * a component alone in the active set, and every component when no depth is batched, runs the single-field code.
+// A component may have an operator of its own (comp_set_op: BC types, Dirichlet constants, alpha / beta); the sentence then
+// reads "as the single-field call on a separate solver created with that operator would".  Wherever the single-field code
+// takes a component's turn its operator is swapped in first (exchange_op: sides, coefficients, Dirichlet op lists, probe
+// verdicts, captured graphs); the N-field launches take the per-field kernels where their fields differ in operator.
 #include "solver.h"
 
 #include <cmath>
@@ -84,6 +88,7 @@ void PressureSolver::mc_setup()
         if (L.valid_cells_global < minc || L.valid_cells_global < tune_.march_min_cells || ordered(d)) break;
         if (L.zeroAvg || L.dev.P.uniform || L.dev.fused_rows != 16 || L.ncf != 0) break;
         bool ok = true;
+        for (const Component& c : comps_) ok = ok && !(c.op && c.op->st.zeroAvg[d]);   // (comp_set_op refuses such an operator)
         for (int q = 0; q < 3; ++q) ok = ok && (L.mgCrseRefRatio[q] == 1 || L.mgCrseRefRatio[q] == 2);
         for (const PatchDesc& p : L.hpatches) ok = ok && !(p.n[0] & 1);   // pairs of cells per lane
         if (!ok) break;
@@ -127,6 +132,249 @@ void PressureSolver::swap_comp(int comp)
     std::swap(f_uberCorr, c.corr);
     std::swap(f_best, c.best);
     for (int q = 0; q < 3; ++q) std::swap(f_heat[q], c.heat[q]);
+    if (c.op) {
+        exchange_op(c.op->st);
+        op_in_place_ = op_in_place_ == comp ? 0 : comp;
+    }
+}
+
+// ------------------------------------------------------------------------------------
+// a component's own operator (comp_set_op)
+// ------------------------------------------------------------------------------------
+void PressureSolver::exchange_op(OpState& o)
+{
+    const Level& L0 = *lev[0];
+    OpState live;
+    for (int a = 0; a < 3; ++a)
+        for (int s = 0; s < 2; ++s) { live.bc[a][s] = L0.bc_type[a][s]; live.val[a][s] = bc_value_[a][s]; bc_value_[a][s] = o.val[a][s]; }
+    live.alpha = L0.alpha;
+    live.beta = L0.beta;
+    for (size_t d = 0; d < lev.size(); ++d) {
+        Level& L = *lev[d];
+        for (int a = 0; a < 3; ++a)
+            for (int s = 0; s < 2; ++s) L.bc_type[a][s] = o.bc[a][s];
+        L.alpha = o.alpha;
+        L.beta = o.beta;
+        const char z = L.zeroAvg ? 1 : 0;
+        L.zeroAvg = o.zeroAvg[d] != 0;
+        o.zeroAvg[d] = z;
+        L.refresh_params();
+    }
+    for (int a = 0; a < 3; ++a)
+        for (int s = 0; s < 2; ++s) { o.bc[a][s] = live.bc[a][s]; o.val[a][s] = live.val[a][s]; }
+    o.alpha = live.alpha;
+    o.beta = live.beta;
+    std::swap(o.diri, diri_);
+    o.d_ops.swap(d_diri_ops_);
+    o.n_ops.swap(n_diri_ops_);
+    o.h_ops0.swap(h_diri_ops0_);
+    std::swap(o.cg, cg_);
+}
+
+bool PressureSolver::probe_op(CompOp& o, int* depth)
+{
+    // with the pair the operator was given, as finalize probes a solver with its create-time alpha / beta (set_alpha_beta
+    // keeps the probe's choice)
+    const double a = o.st.alpha, b = o.st.beta;
+    o.st.alpha = o.alpha0;
+    o.st.beta = o.beta0;
+    exchange_op(o.st);
+    bool any = false;
+    try {
+        for (int d = 0; d < (int)lev.size(); ++d) {
+            probe_null_space(d);
+            if (lev[d]->zeroAvg && !any) { any = true; if (depth) *depth = d; }
+        }
+    } catch (...) {
+        exchange_op(o.st);
+        o.st.alpha = a;
+        o.st.beta = b;
+        throw;
+    }
+    exchange_op(o.st);   // (the verdicts go back into o with it)
+    o.st.alpha = a;
+    o.st.beta = b;
+    return any;
+}
+
+// A Dirichlet wall on the HIGH side of a direction: the fused sweep's recomputed red ring reads, in a neighbouring box's
+// frame, the coefficient of that box's top face, which only the face copier carries (Level::define).  A level whose own
+// sides needed none gets it here; an operator with a Neumann wall there never reads the value, so it is harmless to the rest.
+void PressureSolver::ensure_face_copiers(const int bc[3][2])
+{
+    for (auto& Lp : lev) {
+        Level& L = *Lp;
+        for (int a = 0; a < 3; ++a) {
+            if (!L.active[a] || L.periodic[a] || bc[a][1] != BC_DIRI || L.cf_faces[a]) continue;
+            int gh[3];
+            for (int e = 0; e < 3; ++e) gh[e] = L.active[e] ? FRAME : 0;
+            L.cf_faces[a].reset(new Copier);
+            L.cf_faces[a]->define_faces(L.domain, L.periodic, L, a, gh, comm_);
+            SOMAR_HIP(hipDeviceSynchronize());   // (its tables went up on the null stream)
+            L.cf_faces[a]->run(L.dev.jg[a], L.dev.jg[a], st_);   // as fill_metric_ghosts: the copier, then the exchange
+            xchg(L, L.dev.jg[a]);
+        }
+    }
+}
+
+void PressureSolver::comp_set_op(int comp, const int bc6[6], const double val6[6], double alpha, double beta)
+{
+    check_idle("comp_set_op");
+    SOMAR_CHECK(finalized && ncomp_ > 1, "comp_set_op: after set_components has accepted more than one component");
+    SOMAR_CHECK(comp != 0, "comp_set_op: component 0 is the solver's create-time operator and is not settable");
+    SOMAR_CHECK(comp > 0 && comp < ncomp_, "comp_set_op: component out of range (1 .. ncomp - 1)");
+    SOMAR_CHECK(bc6 && val6, "comp_set_op: null argument");
+    SOMAR_CHECK(op_in_place_ == 0, "internal: comp_set_op while a component's operator is in place");
+    const Level& L0 = *lev[0];
+    std::unique_ptr<CompOp> n(new CompOp);
+    OpState& st = n->st;
+    for (int a = 0; a < 3; ++a)
+        for (int s = 0; s < 2; ++s) {
+            const bool own = L0.active[a] && !L0.periodic[a];   // (a periodic or inactive direction keeps the solver's entries)
+            SOMAR_CHECK(!own || bc6[2 * a + s] == BC_NEUM || bc6[2 * a + s] == BC_DIRI,
+                        "comp_set_op: physical BCs are Neumann (0) or Dirichlet (1)");
+            st.bc[a][s] = own ? bc6[2 * a + s] : L0.bc_type[a][s];
+            st.val[a][s] = own ? val6[2 * a + s] : bc_value_[a][s];
+            st.diri = st.diri || (own && st.bc[a][s] == BC_DIRI);
+        }
+    n->alpha0 = alpha;
+    n->beta0 = beta;
+    st.alpha = ab_scale_[0] * alpha;
+    st.beta = ab_scale_[1] * beta;
+    sync();
+    const int D = (int)lev.size();
+    st.d_ops.resize(D);
+    st.n_ops.assign(D, 0);
+    st.zeroAvg.assign(D, 0);
+    if (st.diri) {
+        for (int d = 0; d < D; ++d) {
+            const std::vector<GhostOp> ops = make_diri_ops(d, st.bc, st.val, false);
+            if (d == 0) st.h_ops0 = ops;
+            st.n_ops[d] = (int)ops.size();
+            st.d_ops[d] = DevBuf<GhostOp>::from(ops);
+        }
+        SOMAR_HIP(hipDeviceSynchronize());   // null-stream copies vs the solver's non-blocking stream
+    }
+    int zd = -1;
+    const bool null_space = probe_op(*n, &zd);
+    sync();
+    SOMAR_CHECK(!null_space, "comp_set_op: the operator has a null space (the probe finds one at depth " + std::to_string(zd) +
+                                 "): the batched kernels carry no mean removal -- such a component keeps a solver of its own");
+    ensure_face_copiers(st.bc);
+    comps_[comp - 1].op = std::move(n);
+    sync();
+}
+
+void PressureSolver::comp_get_op(int comp, int bc6[6], double val6[6], double* alpha, double* beta, bool* own)
+{
+    SOMAR_CHECK(finalized && comp >= 0 && comp < ncomp_, "component out of range (somar_solver_set_components)");
+    SOMAR_CHECK(op_in_place_ == 0, "internal: comp_get_op while a component's operator is in place");
+    const CompOp* o = comp_op(comp);
+    const Level& L0 = *lev[0];
+    for (int a = 0; a < 3; ++a)
+        for (int s = 0; s < 2; ++s) {
+            if (bc6) bc6[2 * a + s] = o ? o->st.bc[a][s] : L0.bc_type[a][s];
+            if (val6) val6[2 * a + s] = o ? o->st.val[a][s] : bc_value_[a][s];
+        }
+    // the pair set_alpha_beta scales: the operator's own, or the solver's create-time one
+    if (alpha) *alpha = o ? o->alpha0 : (coefs_saved_ ? aCoef_ : L0.alpha);
+    if (beta) *beta = o ? o->beta0 : (coefs_saved_ ? bCoef_ : L0.beta);
+    if (own) *own = o != nullptr;
+}
+
+void PressureSolver::comp_reset_op(int comp)
+{
+    check_idle("comp_reset_op");
+    SOMAR_CHECK(finalized && comp > 0 && comp < ncomp_, "comp_reset_op: component out of range (1 .. ncomp - 1)");
+    SOMAR_CHECK(op_in_place_ == 0, "internal: comp_reset_op while a component's operator is in place");
+    sync();
+    comps_[comp - 1].op.reset();
+}
+
+StencilParams PressureSolver::comp_params(int comp, int d) const
+{
+    const Level& L = *lev[d];
+    StencilParams P = L.dev.P;
+    if (const CompOp* o = comp_op(comp)) {
+        for (int a = 0; a < 3; ++a)
+            for (int s = 0; s < 2; ++s) {   // as Level::refresh_params
+                P.neum[a][s] = (!L.periodic[a] && o->st.bc[a][s] == BC_NEUM) ? 1 : 0;
+                P.diri[a][s] = (!L.periodic[a] && o->st.bc[a][s] == BC_DIRI) ? 1 : 0;
+            }
+        P.alpha = o->st.alpha;
+        P.beta = o->st.beta;
+    }
+    return P;
+}
+
+void PressureSolver::comp_diri(int comp, int d, double* phi, bool homogeneous)
+{
+    const CompOp* o = comp_op(comp);
+    if (!o) {
+        if (diri_) apply_diri(d, phi, homogeneous);
+    } else if (o->st.diri) {
+        launch_ghost_ops(st_, lev[d]->dev, o->st.d_ops[d], o->st.n_ops[d], phi, phi, homogeneous);
+    }
+}
+
+static bool same_operator(const StencilParams& a, const StencilParams& b)
+{
+    bool same = a.alpha == b.alpha && a.beta == b.beta;
+    for (int d = 0; d < 3; ++d)
+        for (int s = 0; s < 2; ++s) same = same && a.neum[d][s] == b.neum[d][s] && a.diri[d][s] == b.diri[d][s];
+    return same;
+}
+
+template <int NF>
+void PressureSolver::sweep_launch(int d, const int* comp, const SweepFields<NF>& S, int mode)
+{
+    Level& L = *lev[d];
+    ++mc_launches_;
+    if (!any_ops()) {
+        launch_gsrb_fused_nf<NF>(st_, mc_ftiles_[d].span(), L.dev, S, mode);
+        return;
+    }
+    FieldOps<NF> O;
+    bool differ = false;
+    for (int f = 0; f < NF; ++f) {
+        O.P[f] = comp_params(comp[f], d);
+        differ = differ || !same_operator(O.P[f], O.P[0]);
+    }
+    if (differ) {
+        launch_gsrb_fused_nfo<NF>(st_, mc_ftiles_[d].span(), L.dev, S, O, mode);
+        ++mc_op_launches_;
+    } else {
+        LevelDev Ld = L.dev;   // one operator, possibly not the solver's
+        Ld.P = O.P[0];
+        launch_gsrb_fused_nf<NF>(st_, mc_ftiles_[d].span(), Ld, S, mode);
+    }
+}
+
+template <int NF>
+void PressureSolver::resid_launch(int d, const int* comp, const ResidFields<NF>& R, bool restrict)
+{
+    Level& L = *lev[d];
+    const LevelDev* C = restrict ? &lev[d + 1]->dev : nullptr;
+    const int* r = restrict ? L.mgCrseRefRatio : nullptr;
+    ++mc_launches_;
+    if (!any_ops()) {
+        launch_resid_nf<NF>(st_, mc_rtiles_[d].span(), L.dev, R, C, r);
+        return;
+    }
+    FieldOps<NF> O;
+    bool differ = false;
+    for (int f = 0; f < NF; ++f) {
+        O.P[f] = comp_params(comp[f], d);
+        differ = differ || !same_operator(O.P[f], O.P[0]);
+    }
+    if (differ) {
+        launch_resid_nfo<NF>(st_, mc_rtiles_[d].span(), L.dev, R, O, C, r);
+        ++mc_op_launches_;
+    } else {
+        LevelDev Ld = L.dev;
+        Ld.P = O.P[0];
+        launch_resid_nf<NF>(st_, mc_rtiles_[d].span(), Ld, R, C, r);
+    }
 }
 
 double* PressureSolver::comp_field(int comp, int which)
@@ -193,18 +441,18 @@ void PressureSolver::multi_sweeps(int d, const CompFields& F, int iters, bool e_
         const int nl = launch_plan(n, mode == 1 ? 3 : (mode == 3 ? 1 : 2), plan);
         for (int q = 0, i0 = 0; q < nl; i0 += plan[q], ++q) {
             if (plan[q] == 1) {
-                launch_gsrb_fused(st_, L.ftiles.all.span(), L.dev, metric_ptrs(L.dev), alt[i0], cur[i0], F.res[i0], mode, nullptr, C,
+                LevelDev Ld = L.dev;   // the single-field kernel under this component's operator
+                if (comp_op(F.comp[i0])) Ld.P = comp_params(F.comp[i0], d);
+                launch_gsrb_fused(st_, L.ftiles.all.span(), Ld, metric_ptrs(L.dev), alt[i0], cur[i0], F.res[i0], mode, nullptr, C,
                                   mode == 3 ? e_plus[i0] : nullptr, L.mgCrseRefRatio);
             } else if (plan[q] == 2) {
                 SweepFields<2> S;
                 for (int f = 0; f < 2; ++f) { S.out[f] = alt[i0 + f]; S.in[f] = cur[i0 + f]; S.rhs[f] = F.res[i0 + f]; }
-                launch_gsrb_fused_nf<2>(st_, mc_ftiles_[d].span(), L.dev, S, mode);
-                ++mc_launches_;
+                sweep_launch<2>(d, F.comp + i0, S, mode);
             } else {
                 SweepFields<3> S;
                 for (int f = 0; f < 3; ++f) { S.out[f] = alt[i0 + f]; S.in[f] = cur[i0 + f]; S.rhs[f] = F.res[i0 + f]; }
-                launch_gsrb_fused_nf<3>(st_, mc_ftiles_[d].span(), L.dev, S, mode);
-                ++mc_launches_;
+                sweep_launch<3>(d, F.comp + i0, S, mode);
             }
         }
         for (int i = 0; i < n; ++i) std::swap(cur[i], alt[i]);
@@ -218,46 +466,48 @@ void PressureSolver::multi_restrict(int d, const CompFields& F, double* const* c
     Level& L = *lev[d];
     for (int i = 0; i < F.n; ++i) {
         xchg(L, F.corr[i]);
-        if (diri_) diri_homog(d, F.corr[i]);   // homogeneous Dirichlet ghosts, as residual() fills them
+        comp_diri(F.comp[i], d, F.corr[i], true);   // homogeneous Dirichlet ghosts, as residual() fills them
     }
     int plan[MC_MAX];
     const int nl = launch_plan(F.n, 2, plan);   // (the handed-over rows of three fields would fill the LDS to the last byte)
     for (int q = 0, i0 = 0; q < nl; i0 += plan[q], ++q) {
         if (plan[q] == 1) {
-            launch_resid_restrict(st_, L.rtiles.all.span(), L.dev, metric_ptrs(L.dev), lev[d + 1]->dev, crse[i0], F.corr[i0], F.res[i0],
+            LevelDev Ld = L.dev;   // the single-field kernel under this component's operator
+            if (comp_op(F.comp[i0])) Ld.P = comp_params(F.comp[i0], d);
+            launch_resid_restrict(st_, L.rtiles.all.span(), Ld, metric_ptrs(L.dev), lev[d + 1]->dev, crse[i0], F.corr[i0], F.res[i0],
                                   L.mgCrseRefRatio, L.dxProduct, nullptr);
         } else {
             ResidFields<2> R;
             for (int f = 0; f < 2; ++f) { R.out[f] = crse[i0 + f]; R.phi[f] = F.corr[i0 + f]; R.rhs[f] = F.res[i0 + f]; }
-            launch_resid_nf<2>(st_, mc_rtiles_[d].span(), L.dev, R, &lev[d + 1]->dev, L.mgCrseRefRatio);
-            ++mc_launches_;
+            resid_launch<2>(d, F.comp + i0, R, true);
         }
     }
     sf_valid_[d] = 0;   // (as march_restrict leaves it on a depth without a zero-average prolongation)
 }
 
-void PressureSolver::multi_residual0(int n, double* const* out, double* const* phi, double* const* rhs, bool homogeneous)
+void PressureSolver::multi_residual0(int n, const int* comp, double* const* out, double* const* phi, double* const* rhs,
+                                     bool homogeneous)
 {
     Level& L = *lev[0];
     for (int i = 0; i < n; ++i) {
         xchg(L, phi[i]);                              // exchangeComplete, as operator_i
-        if (diri_) apply_diri(0, phi[i], homogeneous);
+        comp_diri(comp[i], 0, phi[i], homogeneous);
     }
     int plan[MC_MAX];
     const int nl = launch_plan(n, 3, plan);   // (per field against the single-field residual: two fields -30 %, three -44 %)
     for (int q = 0, i0 = 0; q < nl; i0 += plan[q], ++q) {
         if (plan[q] == 1) {
-            launch_resid_march(st_, L.rtiles.all.span(), L.dev, out[i0], phi[i0], rhs[i0], 0);
+            LevelDev Ld = L.dev;   // the single-field kernel under this component's operator
+            if (comp_op(comp[i0])) Ld.P = comp_params(comp[i0], 0);
+            launch_resid_march(st_, L.rtiles.all.span(), Ld, out[i0], phi[i0], rhs[i0], 0);
         } else if (plan[q] == 2) {
             ResidFields<2> R;
             for (int f = 0; f < 2; ++f) { R.out[f] = out[i0 + f]; R.phi[f] = phi[i0 + f]; R.rhs[f] = rhs[i0 + f]; }
-            launch_resid_nf<2>(st_, mc_rtiles_[0].span(), L.dev, R, nullptr, nullptr);
-            ++mc_launches_;
+            resid_launch<2>(0, comp + i0, R, false);
         } else {
             ResidFields<3> R;
             for (int f = 0; f < 3; ++f) { R.out[f] = out[i0 + f]; R.phi[f] = phi[i0 + f]; R.rhs[f] = rhs[i0 + f]; }
-            launch_resid_nf<3>(st_, mc_rtiles_[0].span(), L.dev, R, nullptr, nullptr);
-            ++mc_launches_;
+            resid_launch<3>(0, comp + i0, R, false);
         }
     }
 }
@@ -269,7 +519,7 @@ void PressureSolver::multi_cycle(int d, const CompFields& F, bool corr_zero, Com
     if (n == 1) {
         // alone in the active set: the single-field cycle, on this component's arrays
         if (B.metric) bottom_metric = B.metric[0];
-        cycle(d, F.corr[0], F.res[0], corr_zero);
+        on_op(F.comp[0], [&]() { cycle(d, F.corr[0], F.res[0], corr_zero); });
         B.iters[0] = bottom_iters;
         B.exit[0] = bottom_exit;
         return;
@@ -288,12 +538,12 @@ void PressureSolver::multi_cycle(int d, const CompFields& F, bool corr_zero, Com
         for (int i = 0; i < n; ++i) xchg(*lev[d + 1], N.corr[i]);
     } else {
         // the seam: every component takes its turn in the single-field cycle, through the solver's own arrays of depth K (the
-        // graphs are captured for those); its exchanged correction goes back to the component
+        // graphs are captured for those, one pair per operator); its exchanged correction goes back to the component
         const long long nK = lev[K]->field_elems;
         for (int i = 0; i < n; ++i) {
             launch_copy(st_, f_res[K], N.res[i], nK);
             if (B.metric) bottom_metric = B.metric[i];
-            cycle(K, f_corr[K], f_res[K], true);
+            on_op(F.comp[i], [&]() { cycle(K, f_corr[K], f_res[K], true); });
             B.iters[i] = bottom_iters;
             B.exit[i] = bottom_exit;
             xchg(*lev[K], f_corr[K].get());
@@ -360,7 +610,8 @@ void PressureSolver::solve_multi(bool zeroPhi, bool forceHomogeneous, std::vecto
         s.goIter = s.iter < prm.imax;
         s.goHang = s.iter < prm.imin || s.rnorm < (1 - prm.hang) * s.norm_last;
     };
-    multi_residual0(nc, res, phi, rhs, forceHomogeneous);   // computeAMRResidual(..., a_forceHomogeneous), :1021
+    const int every[MC_MAX] = {0, 1, 2, 3};
+    multi_residual0(nc, every, res, phi, rhs, forceHomogeneous);   // computeAMRResidual(..., a_forceHomogeneous), :1021
     for (int c = 0; c < nc; ++c) {
         State& s = S[c];
         s.initial = s.rnorm = s.best = norm(0, res[c], 0);
@@ -385,8 +636,8 @@ void PressureSolver::solve_multi(bool zeroPhi, bool forceHomogeneous, std::vecto
         B.metric = metric;
         multi_cycle(0, F, true, B);   // uberCorrection is zero here (setToZero, :1203)
         for (int i = 0; i < F.n; ++i) launch_incr(st_, aphi[i], F.corr[i], 1.0, n);   // postVCycleOps, :1189-1215
-        if (F.n == 1) residual(0, F.res[0], aphi[0], arhs[0], forceHomogeneous);
-        else multi_residual0(F.n, F.res, aphi, arhs, forceHomogeneous);
+        if (F.n == 1) on_op(F.comp[0], [&]() { residual(0, F.res[0], aphi[0], arhs[0], forceHomogeneous); });
+        else multi_residual0(F.n, F.comp, F.res, aphi, arhs, forceHomogeneous);
         for (int i = 0; i < F.n; ++i) {
             const int c = F.comp[i];
             State& s = S[c];
@@ -435,8 +686,8 @@ void PressureSolver::solve_multi(bool zeroPhi, bool forceHomogeneous, std::vecto
 }
 
 // heat_step (MappedLevelBackwardEuler / MappedLevelCrankNicolson / MappedLevelTGA ::updateSoln) on every component: one dt and
-// one alpha / beta serve all, so the stages that set the coefficients run component after component between them and the
-// solves go through solve_multi
+// one set_alpha_beta serve all (it scales every component's own pair), so the stages that set the coefficients run component
+// after component between them and the solves go through solve_multi
 void PressureSolver::heat_step_multi(int scheme, double dt, bool zeroPhi, std::vector<SolveStats>& out)
 {
     check_idle("heat_step_multi");

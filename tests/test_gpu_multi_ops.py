@@ -53,8 +53,8 @@ OPS_HIGH = [Op([N] * 6, [0] * 6),
             Op([N] * 6, [0] * 6, beta=BETA_SCALAR)]
 
 
-def _layout(name, n, boxes, L, K, widths, ratios, ops=OPS, tables=None):
-    c = _case(name, n, boxes, (False,) * 3, L, ops[0].bc, None, K, widths=widths, ratios=ratios, tables=tables)
+def _layout(name, n, boxes, L, K, widths, ratios, ops=OPS, tables=None, periodic=(False,) * 3):
+    c = _case(name, n, boxes, periodic, L, ops[0].bc, None, K, widths=widths, ratios=ratios, tables=tables)
     c.ops = ops
     return c
 
@@ -82,10 +82,12 @@ def _own(case, c):
                  beta=op.beta)
 
 
-def _set_ops(s, case, ncomp):
+def _set_ops(s, case, ncomp, passed=None):
+    """passed: None, or op -> the (BC types, values) handed to setCompOp in its place (what getCompOp reports stays the op's)"""
     for c in range(1, ncomp):
         op = case.ops[c]
-        s.setCompOp(c, op.bc, op.values, op.alpha, op.beta)
+        bc, values = passed(op) if passed else (op.bc, op.values)
+        s.setCompOp(c, bc, values, op.alpha, op.beta)
         assert s.getCompOp(c) == (op.bc, [float(v) for v in op.values], op.alpha, op.beta, True)
     assert s.getCompOp(0) == (case.ops[0].bc, s.getCompOp(0)[1], case.ops[0].alpha, case.ops[0].beta, False)
 
@@ -248,7 +250,8 @@ def _solve_rhs(so, case, prob):
 
 def _with_small_walls(case):
     ops = [Op(o.bc, [v * WALL for v in o.values], o.alpha, o.beta) for o in case.ops]
-    return _layout(case.name, case.n, case.boxes, case.L, case.K, case.widths, case.ratios, ops=ops, tables=case.tables)
+    return _layout(case.name, case.n, case.boxes, case.L, case.K, case.widths, case.ratios, ops=ops, tables=case.tables,
+                   periodic=case.periodic)
 
 
 def _multi_solver(case, prob, ncomp, eps=EPS, imax=IMAX, norm_thresh=NORM_THRESH):

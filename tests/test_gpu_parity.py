@@ -250,7 +250,9 @@ def test_bottom_solver_and_vcycle(oracle, case, F):
 def test_one_launch_bottom_solver_equals_the_launch_by_launch_one(oracle, case, F, monkeypatch):
     """k_tiny_bicgstab (the whole BiCGStab bottom solve in one single-workgroup launch, default on bottom levels of at most
     512 cells) against PressureSolver::bottom_solve's launch-by-launch path (SOMAR_FUSED_BOTTOM_MAX_CELLS=0, read when the
-    solver is created): same iteration count, same exit code, same bits -- bottom solves and whole V-cycles."""
+    solver is created): same iteration count, same exit code, same bits -- bottom solves and whole V-cycles.
+    These are converging solves at deck parameters (the 8 boxes of 4^3 under 32^3: 12 iterations, no restart); the other
+    ways out of the loop, the restart and the norm types are tests/test_gpu_bottom_branches.py's."""
     so = oracle
     n, boxsz, variant, periodic, L = case
     dom, grids, dx, Jgup, Jinv = make_problem(so, n, boxsz, variant, periodic, L)

@@ -107,30 +107,26 @@ void launch_resid_restrict(hipStream_t st, TileSpan tiles, const LevelDev& F, co
 void launch_resid_restrict(hipStream_t st, TileSpan tiles, const LevelDev& F, const MetricPtrs<float>& M,
                            const LevelDev& C, float* crse, const float* phi, const float* rhs, const int r[3],
                            double dxProduct, double* volsum);
-// The same three launches on NF = 2 or 3 fields that share the level's operator (multi_march.hip; PressureSolver::
-// set_components): the coefficient arrays are streamed once per launch, each field's arithmetic is the single-field kernel's.
+// The same three launches on NF = 2 or 3 fields of one level (multi_march.hip; PressureSolver::set_components): the
+// coefficient arrays are streamed once per launch, each field's arithmetic is the single-field kernel's.
 // Class-0 tiles of the 16-row forms on a streamed (non-uniform) diagonal metric without coarse-fine faces; fp64.
+// The operator is handed over explicitly (L.P is not read) in one of two carriers OPS:
+//   StencilParams   one operator for all fields;
+//   FieldOps<NF>    one per field (PressureSolver::comp_set_op): P[f] is the level's StencilParams with the sides (neum /
+//                   diri) and alpha / beta of field f's operator; everything else in it is the level's and equal in all of them.
 // in_mode 0 (plain; NF = 2 only) or 1 (from zero) as above; the folded prolongation (3) stays with launch_gsrb_fused.
 template <int NF>
 struct SweepFields { double* out[NF]; const double* in[NF]; const double* rhs[NF]; };
 template <int NF>
-void launch_gsrb_fused_nf(hipStream_t st, TileSpan tiles, const LevelDev& L, const SweepFields<NF>& F, int in_mode);
-// C null: out[f] = rhs[f] - L[phi[f]] on the level; else out[f] on C = the J-weighted average of it (ratio r)
+struct FieldOps { StencilParams P[NF]; };
+template <int NF, class OPS>
+void launch_gsrb_fused_nf(hipStream_t st, TileSpan tiles, const LevelDev& L, const SweepFields<NF>& F, const OPS& O, int in_mode);
+// C null: out[f] = rhs[f] - L[phi[f]] on the level; else out[f] on C = the J-weighted average of it (ratio r; NF = 2 only)
 template <int NF>
 struct ResidFields { double* out[NF]; const double* phi[NF]; const double* rhs[NF]; };
-template <int NF>
-void launch_resid_nf(hipStream_t st, TileSpan tiles, const LevelDev& F, const ResidFields<NF>& fields, const LevelDev* C,
-                     const int* r);
-// The same launches on fields that differ in operator (PressureSolver::comp_set_op): P[f] is the level's StencilParams with
-// the sides (neum / diri) and alpha / beta of field f's operator; everything else in it is the level's and equal in all of them.
-template <int NF>
-struct FieldOps { StencilParams P[NF]; };
-template <int NF>
-void launch_gsrb_fused_nfo(hipStream_t st, TileSpan tiles, const LevelDev& L, const SweepFields<NF>& F, const FieldOps<NF>& O,
-                           int in_mode);
-template <int NF>
-void launch_resid_nfo(hipStream_t st, TileSpan tiles, const LevelDev& F, const ResidFields<NF>& fields, const FieldOps<NF>& O,
-                      const LevelDev* C, const int* r);
+template <int NF, class OPS>
+void launch_resid_nf(hipStream_t st, TileSpan tiles, const LevelDev& F, const ResidFields<NF>& fields, const OPS& O,
+                     const LevelDev* C, const int* r);
 // crse(ic) = sum over the children of ic of dxProduct / fjinv(child): the volume a coarse value is spread over
 void launch_child_volume(hipStream_t st, const LevelDev& C, const LevelDev& F, double* crse, const int r[3],
                          double dxProduct);

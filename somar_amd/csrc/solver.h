@@ -590,12 +590,6 @@ private:
     double ab_scale_[2] = {1.0, 1.0};   // set_alpha_beta's last (a, b)
     int op_in_place_ = 0;               // the component whose operator is live (0: the solver's own)
     CompOp* comp_op(int comp) const { return comp > 0 && comp <= (int)comps_.size() ? comps_[comp - 1].op.get() : nullptr; }
-    bool any_ops() const
-    {
-        for (const Component& c : comps_)
-            if (c.op) return true;
-        return false;
-    }
     void exchange_op(OpState& o);
     // runs f with component comp's operator in place (fields untouched); nothing to do for a component that shares the solver's
     template <class Fn>
@@ -612,9 +606,13 @@ private:
     bool probe_op(CompOp& o, int* depth);                  // the null-space probe at every depth with o in place: any zeroAvg?
     void ensure_face_copiers(const int bc[3][2]);          // Level::cf_faces for the operator's Dirichlet HIGH sides, every depth
     StencilParams comp_params(int comp, int d) const;      // depth d's StencilParams under component comp's operator
+    LevelDev comp_level(int comp, int d) const;            // depth d's LevelDev with them as its P: what a single-field launch takes
     void comp_diri(int comp, int d, double* phi, bool homogeneous);   // the Dirichlet ghosts of comp's operator (none: nothing)
-    // one N-field launch on the fields at positions i0 .. i0 + NF - 1 of the active list: the shared-operator kernel where
-    // their operators agree, the per-field form (and mc_op_launches_) where they differ
+    // one N-field launch on the fields at positions i0 .. i0 + NF - 1 of the active list: with one StencilParams where their
+    // operators agree (the solver's or not), with one per field where they differ.  field_ops fills O with the fields'
+    // comp_params, COUNTS the launch (mc_launches_; mc_op_launches_ where they differ) and returns whether they differ.
+    template <int NF>
+    bool field_ops(int d, const int* comp, FieldOps<NF>& O);
     template <int NF>
     void sweep_launch(int d, const int* comp, const SweepFields<NF>& S, int mode);
     template <int NF>

@@ -12,7 +12,7 @@
 // A component may have an operator of its own (comp_set_op: BC types, Dirichlet constants, alpha / beta); the sentence then
 // reads "as the single-field call on a separate solver created with that operator would".  Wherever the single-field code
 // takes a component's turn its operator is swapped in first (exchange_op: sides, coefficients, Dirichlet op lists, probe
-// verdicts, captured graphs); the N-field launches take the per-field kernels where their fields differ in operator.
+// verdicts, captured graphs); the N-field launches are handed one operator per field where their fields differ in it.
 #include "solver.h"
 
 #include <cmath>
@@ -325,29 +325,32 @@ static bool same_operator(const StencilParams& a, const StencilParams& b)
     return same;
 }
 
-template <int NF>
-void PressureSolver::sweep_launch(int d, const int* comp, const SweepFields<NF>& S, int mode)
+LevelDev PressureSolver::comp_level(int comp, int d) const
 {
-    Level& L = *lev[d];
-    ++mc_launches_;
-    if (!any_ops()) {
-        launch_gsrb_fused_nf<NF>(st_, mc_ftiles_[d].span(), L.dev, S, mode);
-        return;
-    }
-    FieldOps<NF> O;
+    LevelDev Ld = lev[d]->dev;
+    Ld.P = comp_params(comp, d);
+    return Ld;
+}
+
+template <int NF>
+bool PressureSolver::field_ops(int d, const int* comp, FieldOps<NF>& O)
+{
     bool differ = false;
     for (int f = 0; f < NF; ++f) {
         O.P[f] = comp_params(comp[f], d);
         differ = differ || !same_operator(O.P[f], O.P[0]);
     }
-    if (differ) {
-        launch_gsrb_fused_nfo<NF>(st_, mc_ftiles_[d].span(), L.dev, S, O, mode);
-        ++mc_op_launches_;
-    } else {
-        LevelDev Ld = L.dev;   // one operator, possibly not the solver's
-        Ld.P = O.P[0];
-        launch_gsrb_fused_nf<NF>(st_, mc_ftiles_[d].span(), Ld, S, mode);
-    }
+    ++mc_launches_;
+    if (differ) ++mc_op_launches_;
+    return differ;
+}
+
+template <int NF>
+void PressureSolver::sweep_launch(int d, const int* comp, const SweepFields<NF>& S, int mode)
+{
+    FieldOps<NF> O;
+    if (field_ops<NF>(d, comp, O)) launch_gsrb_fused_nf<NF>(st_, mc_ftiles_[d].span(), lev[d]->dev, S, O, mode);
+    else launch_gsrb_fused_nf<NF>(st_, mc_ftiles_[d].span(), lev[d]->dev, S, O.P[0], mode);
 }
 
 template <int NF>
@@ -356,25 +359,9 @@ void PressureSolver::resid_launch(int d, const int* comp, const ResidFields<NF>&
     Level& L = *lev[d];
     const LevelDev* C = restrict ? &lev[d + 1]->dev : nullptr;
     const int* r = restrict ? L.mgCrseRefRatio : nullptr;
-    ++mc_launches_;
-    if (!any_ops()) {
-        launch_resid_nf<NF>(st_, mc_rtiles_[d].span(), L.dev, R, C, r);
-        return;
-    }
     FieldOps<NF> O;
-    bool differ = false;
-    for (int f = 0; f < NF; ++f) {
-        O.P[f] = comp_params(comp[f], d);
-        differ = differ || !same_operator(O.P[f], O.P[0]);
-    }
-    if (differ) {
-        launch_resid_nfo<NF>(st_, mc_rtiles_[d].span(), L.dev, R, O, C, r);
-        ++mc_op_launches_;
-    } else {
-        LevelDev Ld = L.dev;
-        Ld.P = O.P[0];
-        launch_resid_nf<NF>(st_, mc_rtiles_[d].span(), Ld, R, C, r);
-    }
+    if (field_ops<NF>(d, comp, O)) launch_resid_nf<NF>(st_, mc_rtiles_[d].span(), L.dev, R, O, C, r);
+    else launch_resid_nf<NF>(st_, mc_rtiles_[d].span(), L.dev, R, O.P[0], C, r);
 }
 
 double* PressureSolver::comp_field(int comp, int which)
@@ -441,8 +428,7 @@ void PressureSolver::multi_sweeps(int d, const CompFields& F, int iters, bool e_
         const int nl = launch_plan(n, mode == 1 ? 3 : (mode == 3 ? 1 : 2), plan);
         for (int q = 0, i0 = 0; q < nl; i0 += plan[q], ++q) {
             if (plan[q] == 1) {
-                LevelDev Ld = L.dev;   // the single-field kernel under this component's operator
-                if (comp_op(F.comp[i0])) Ld.P = comp_params(F.comp[i0], d);
+                const LevelDev Ld = comp_level(F.comp[i0], d);   // the single-field kernel under this component's operator
                 launch_gsrb_fused(st_, L.ftiles.all.span(), Ld, metric_ptrs(L.dev), alt[i0], cur[i0], F.res[i0], mode, nullptr, C,
                                   mode == 3 ? e_plus[i0] : nullptr, L.mgCrseRefRatio);
             } else if (plan[q] == 2) {
@@ -472,8 +458,7 @@ void PressureSolver::multi_restrict(int d, const CompFields& F, double* const* c
     const int nl = launch_plan(F.n, 2, plan);   // (the handed-over rows of three fields would fill the LDS to the last byte)
     for (int q = 0, i0 = 0; q < nl; i0 += plan[q], ++q) {
         if (plan[q] == 1) {
-            LevelDev Ld = L.dev;   // the single-field kernel under this component's operator
-            if (comp_op(F.comp[i0])) Ld.P = comp_params(F.comp[i0], d);
+            const LevelDev Ld = comp_level(F.comp[i0], d);   // the single-field kernel under this component's operator
             launch_resid_restrict(st_, L.rtiles.all.span(), Ld, metric_ptrs(L.dev), lev[d + 1]->dev, crse[i0], F.corr[i0], F.res[i0],
                                   L.mgCrseRefRatio, L.dxProduct, nullptr);
         } else {
@@ -497,8 +482,7 @@ void PressureSolver::multi_residual0(int n, const int* comp, double* const* out,
     const int nl = launch_plan(n, 3, plan);   // (per field against the single-field residual: two fields -30 %, three -44 %)
     for (int q = 0, i0 = 0; q < nl; i0 += plan[q], ++q) {
         if (plan[q] == 1) {
-            LevelDev Ld = L.dev;   // the single-field kernel under this component's operator
-            if (comp_op(comp[i0])) Ld.P = comp_params(comp[i0], 0);
+            const LevelDev Ld = comp_level(comp[i0], 0);   // the single-field kernel under this component's operator
             launch_resid_march(st_, L.rtiles.all.span(), Ld, out[i0], phi[i0], rhs[i0], 0);
         } else if (plan[q] == 2) {
             ResidFields<2> R;

@@ -5,13 +5,13 @@ on the same geometry and metric; every comparison is assert_array_equal (through
 oracle" one component is held to the oracle's one_cycle for its operator too, so that both GPU paths wrong alike cannot pass.
 
 Groups (layouts: those of tests/test_gpu_multi.py and tests/test_gpu_multi_ops.py, not grown):
-  1. no Dirichlet side anywhere, operators that differ in (alpha, beta) only: the DIRI = false forms k_gsrb_fused_nfo<0,false,2>,
-     <1,false,2>, <1,false,3>.  With two and three components every N-field launch carries different operators
+  1. no Dirichlet side anywhere, operators that differ in (alpha, beta) only: the DIRI = false forms of the sweep on one operator
+     per field, k_gsrb_fused_nf<0,false,2,FieldOps<2>>, <1,false,2,FieldOps<2>>, <1,false,3,FieldOps<3>>.  With two and three components every N-field launch carries different operators
      (opLaunches == batched launches), and no field of any launch has a Dirichlet side: they are those forms by construction.
   2. components that differ in alpha, a Poisson component with Dirichlet sides next to Helmholtz ones, and a heat step whose
      components were created with different aCoef (set_alpha_beta scales each by its own pair).
   3. two components with one own operator that is not the handle's: the `differ == false` branch of sweep_launch / resid_launch
-     under any_ops() (the shared-operator kernel with O.P[0] substituted) -- (a) next to a pair that differs, (b) an own operator
+     with an operator that is not the level's (the one-operator kernel handed O.P[0]) -- (a) next to a pair that differs, (b) an own operator
      equal to the handle's in every entry, (c) the pair left over once component 0 has left a solve.
   4. periodic directions: comp_set_op keeps the handle's entries there whatever is passed (7 / 99.0 here), comp_params masks the
      sides by L.periodic, make_diri_ops skips them.
@@ -46,10 +46,12 @@ Beyond the eight groups: heatStepMulti in the sequential fallback (K = 0) with c
 set_alpha_beta runs while a component's operator is in place.
 
 Mutations, each applied to a scratch copy of the library and run once on the MI355X against this file and
-tests/test_gpu_multi_ops.py (failed tests here / there):
+tests/test_gpu_multi_ops.py (failed tests here / there), when the per-operator kernels were a text of their own (k_*_nfo) and
+sweep_launch substituted the operator through a copy of the level (`Ld.P = O.P[0]`):
   * field 1 of k_gsrb_fused_nfo<*, false, *> reads O.P[0].beta: 24 / 0 -- every test of group 1.
   * comp_params without the !L.periodic[a] mask: 15 / 0 -- group 4 and the periodic ragged cases of group 1.
-  * sweep_launch without `Ld.P = O.P[0]`: 4 / 0 -- group 3 (a) and (c), both layouts.
+  * sweep_launch without `Ld.P = O.P[0]` (now: handing the launcher L.dev.P instead of O.P[0]): 4 / 0 -- group 3 (a) and (c),
+    both layouts.
   * drop_graphs skips the components' graphs: 1 / 0 -- group 6 (a) with graph legs.  (Without the second value of
     SOMAR_GRAPH_CELLS nothing failed: no graph existed.)
   * comp_set_op ignores ab_scale_: 1 / 0 -- group 6 (b).

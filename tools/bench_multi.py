@@ -14,7 +14,8 @@ Prints one JSON line.  Not the driver's bench (bench.py).
     --ops: 3 and 4 components that DIFFER in operator (somar_comp_set_op: free-slip walls on three, an all-Neumann scalar with
         another beta) on one handle against the same components on separate one-component handles: V-cycles and backward-Euler
         heat steps in interleaved rounds, the device memory of both arrangements; with --quick a few of each, for a kernel
-        trace that shows k_gsrb_fused_nfo / k_resid_march_nfo next to the separate handles' single-field launches
+        trace that shows k_gsrb_fused_nf / k_resid_march_nf on one operator per field (last template argument FieldOps<NF>)
+        next to the separate handles' single-field launches
 """
 import argparse
 import json

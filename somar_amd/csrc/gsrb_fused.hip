@@ -42,6 +42,38 @@ namespace somar {
 template <class T>
 __device__ __forceinline__ typename Vec2<T>::type uni2(double c, bool, bool) { return mk2<T>(T(c), T(c)); }
 
+// Staged coefficients (STG): the six coefficient pairs a step consumes -- rhs, 1/J, J g^xx, J g^yy at j and j + 1 of
+// plane k and J g^zz of plane k + 1 -- are fetched ONE STEP AHEAD by loads that write LDS directly (no register destination:
+// the streamed instantiations have no registers left to prefetch in), into a slot per (stream, lane) that only the lane itself
+// reads back.  The destination of such a load is wave base + 16 x lane, which is exactly that slot; no other wave touches it,
+// so the wait for the loads (vmcnt(0) ahead of the plane's barrier) is all the ordering the slots need, and the lane's own
+// lgkmcnt(0) after the read covers the write-after-read before the next plane is staged.
+constexpr int STG_STREAMS = 6;
+// Which sweeps are staged, by INMODE, from the register count of each instantiation (profiles/r14_staged_coefficients.md): the
+// folded prolongation (3, 4) would have to carry its coarse parents a step as well and spills, and so does the mixed-class
+// kernel (NARROW 1, three bodies) with a phi pair in flight (0, 2).  Those keep the loads into registers.
+constexpr bool STAGED_MODES[5] = {true, true, true, false, false};
+constexpr bool STAGED_MODES_MIXED[5] = {false, true, false, false, false};
+template <class T>
+__device__ __forceinline__ void stage2(const T* __restrict__ safe, long long rel, bool ok0, bool ok1, T* wave_slot)
+{
+    // ld2's address, written as safe + (rel or 0) (safe: the element ld2 reads when neither element of the pair may be touched, a
+    // scalar pointer; rel: the pair's distance from it); ld2's zero-select is applied when the slot is read
+    static_assert(sizeof(T) == 8, "a staged pair is one 16-byte load: fp64 only");
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(safe + ((ok0 || ok1) ? rel : 0LL)),
+                                     (__attribute__((address_space(3))) void*)wave_slot, 16, 0, 0);
+}
+// a value that is the same in every lane, moved to scalar registers (the staged form has no vector register to spare for it)
+__device__ __forceinline__ double wave_uniform(double x)
+{
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
+}
+template <class T>
+__device__ __forceinline__ typename Vec2<T>::type sel2(const typename Vec2<T>::type& v, bool ok0, bool ok1)
+{
+    return mk2<T>(ok0 ? v.x : T(0), ok1 ? v.y : T(0));
+}
+
 // blockDim = (64, FR_J): lane = i-pair of the region, threadIdx.y = region row (one wavefront each).
 // FR_J = 16: 124 x 12 output columns per 1024-thread workgroup (one per CU);
 // FR_J =  8: 124 x 4 per 512-thread workgroup, two resident per CU so one computes while the other waits.
@@ -58,8 +90,11 @@ __device__ __forceinline__ typename Vec2<T>::type uni2(double c, bool, bool) { r
 // CLS: the tile's lane class (see full19_march.hip): a wavefront covers 2^CLS region rows of 128 >> CLS columns, all of the
 // same parity, so the colour column c stays wave-uniform.
 // sums (modes 2, 4) are fp64 whatever T is: the mean is formed in double, then taken to T
-template <int FR_J, int INMODE, bool DIRI, bool UNI, bool INT, int CLS, class T>
-__device__ __forceinline__ void gsrb_fused_body(T* __restrict__ S, const Tile& t, const PatchDesc& p,
+// STG: the coefficients come through the staging slots G (above); phi of plane k + 2 is issued in step k like the UNI form's, and
+// nothing a plain load returns is touched before the next step's barrier -- a use in between would make the compiler wait for
+// every load in flight, the staged ones included, in the middle of the arithmetic.
+template <int FR_J, int INMODE, bool DIRI, bool UNI, bool INT, int CLS, bool STG, class T>
+__device__ __forceinline__ void gsrb_fused_body(T* __restrict__ S, T* __restrict__ G, const Tile& t, const PatchDesc& p,
                                                 T* __restrict__ phi_out,
                                                 const T* __restrict__ phi_in,
                                                 const T* __restrict__ rhs,
@@ -72,16 +107,21 @@ __device__ __forceinline__ void gsrb_fused_body(T* __restrict__ S, const Tile& t
                                                 const T* __restrict__ crse, int r0, int r1, int r2)
 {
     typedef typename Vec2<T>::type T2;
-    const T avg = (INMODE == 2 || INMODE == 4) ? T(sums[0] / sums[1]) : T(0);
+    T avg = (INMODE == 2 || INMODE == 4) ? T(sums[0] / sums[1]) : T(0);
+    if constexpr (STG) avg = wave_uniform(avg);
     constexpr int LPR = 64 >> CLS;                 // lanes per region row
     constexpr int NR = FR_J << CLS;                // region rows of the workgroup
     constexpr int PITCH = 2 * LPR + (CLS >= 2 ? 2 : 0);
-#define Sx(slot, r, c) S[((slot) * NR + (r)) * PITCH + (c)]
+    // (STG: the same element addressed from the lane's own cell Sp, so that every neighbour is that one register plus a
+    // constant instead of a register of its own)
+#define Sx(slot, r, c) \
+    (*(STG ? &Sp[(slot) * (NR * PITCH) + ((r) - row) * PITCH + ((c) - ri)] : &S[((slot) * NR + (r)) * PITCH + (c)]))
     // class 0: the region row is the wavefront's index, a scalar -- everything derived from it stays in scalar registers
     const int lane = CLS == 0 ? (int)threadIdx.x : (int)(threadIdx.x & (LPR - 1));
     const int row = CLS == 0 ? (int)threadIdx.y
                              : (int)(((threadIdx.y >> 1) << (CLS + 1)) + (threadIdx.y & 1) + 2 * (threadIdx.x >> (6 - CLS)));
     const int ri = 2 * lane;       // region column of the pair's first cell
+    T* const Sp = S + row * PITCH + ri;
     const int li = t.i0 - 2 + ri;  // local i of the pair's first cell (even: rows are 16-byte aligned)
     // output columns of this tile (even, <= region width - 4); the region beyond wi + 4 columns is neither loaded nor computed
     const int wi = t.w > 0 ? t.w : 2 * LPR - 4;
@@ -116,10 +156,40 @@ __device__ __forceinline__ void gsrb_fused_body(T* __restrict__ S, const Tile& t
         if (INMODE == 2 || INMODE == 4) { v.x = v.x - avg; v.y = v.y - avg; }
         return v;
     };
+    // STG: ldphi in two halves -- the loads now (raw: phi's pair and, INMODE 3/4, its coarse parents), everything that USES what
+    // they return (the zero-select, the parents, the mean) one step later, with the same predicates: the same values.
+    // (INMODE 3/4 are written out although STAGED_MODES leaves them off: it is the form whose spills the profile note records.)
+    struct RawPhi { T2 v; T c0, c1; };
+    auto ldphi_raw = [&](int kp, bool ok0, bool ok1) {
+        RawPhi w;
+        w.v = mk2<T>(T(0), T(0));
+        w.c0 = w.c1 = T(0);
+        if (INMODE == 1) return w;
+        const bool any = ok0 || ok1;
+        w.v = *reinterpret_cast<const T2*>(phi_in + (any ? p.off + li + (long long)p.pj * lj + p.pk * kp : p.off));
+        if (INMODE >= 3) {
+            const long long c = any ? cbase + cpk * (long long)(kp >> csh2) : coff;
+            const long long c2 = any ? c + cstep : coff;
+            w.c0 = crse[c];
+            w.c1 = crse[c2];
+        }
+        return w;
+    };
+    auto ldphi_use = [&](const RawPhi& w, bool ok0, bool ok1) {
+        if (INMODE == 1) return mk2<T>(T(0), T(0));
+        T2 v = sel2<T>(w.v, ok0, ok1);
+        if (INMODE >= 3) {
+            v.x = ok0 ? v.x + w.c0 : T(0);
+            v.y = ok1 ? v.y + w.c1 : T(0);
+        }
+        if (INMODE == 2 || INMODE == 4) { v.x = v.x - avg; v.y = v.y - avg; }
+        return v;
+    };
     const int gj = p.lo[1] + lj;
-    const T xxS = T(1.0) / (T(P.dx[0]) * T(P.dx[0]));
-    const T yyS = T(1.0) / (T(P.dx[1]) * T(P.dx[1]));
-    const T zzS = T(1.0) / (T(P.dx[2]) * T(P.dx[2]));
+    T xxS = T(1.0) / (T(P.dx[0]) * T(P.dx[0]));
+    T yyS = T(1.0) / (T(P.dx[1]) * T(P.dx[1]));
+    T zzS = T(1.0) / (T(P.dx[2]) * T(P.dx[2]));
+    if constexpr (STG) { xxS = wave_uniform(xxS); yyS = wave_uniform(yyS); zzS = wave_uniform(zzS); }
 
     // memory predicates: a cell may be touched only inside the patch's 2-cell frame
     const bool fj = (lj >= -FRAME) && (lj < p.n[1] + FRAME);
@@ -156,6 +226,7 @@ __device__ __forceinline__ void gsrb_fused_body(T* __restrict__ S, const Tile& t
     }
     const long long sj = p.pj, sk = p.pk;
     const long long base = p.off + li + sj * lj;
+    const int rel0 = li + p.pj * lj;   // base - p.off: a row of a patch's plane is far below 2^31 elements
 
     // ---- prologue: planes k0-2 and k0-1 ------------------------------------------------------------
     int k = t.k0 - 1;  // first red plane (the ring below the tile)
@@ -177,6 +248,33 @@ __device__ __forceinline__ void gsrb_fused_body(T* __restrict__ S, const Tile& t
         Pn = ldphi(k + 1, f0 && fkp0, f1 && fkp0);
         Rn = ld2(rhs, base + sk * k, c0 && fk, c1 && fk, p.off);
     }
+    // STG: stream s of this wavefront lands at GW(s), the lane's own pair at GL(s).  stage(kk) issues what step kk consumes.
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.y);   // a scalar: so are the loads' LDS bases
+#define GW(s) (G + (wave * STG_STREAMS + (s)) * 128)
+#define GL(s) (*reinterpret_cast<const T2*>(GW(s) + 2 * (int)threadIdx.x))
+    auto stage = [&](int kk) {
+        // (the last step stages for a step that does not come: every predicate off, and no branch -- one around these loads
+        // made the compiler wait for them where the paths join)
+        const bool gk0 = (kk >= -FRAME) && (kk < p.n[2] + FRAME) && (kk <= t.k0 + t.nk);
+        const bool gk1 = (kk + 1 >= -FRAME) && (kk + 1 < p.n[2] + FRAME) && (kk <= t.k0 + t.nk);
+        if constexpr (STG) {
+            const long long rel = rel0 + sk * kk;   // = base + sk * kk - p.off
+            stage2(rhs + p.off, rel, c0 && gk0, c1 && gk0, GW(0));
+            stage2(jinv + p.off, rel, c0 && gk0, c1 && gk0, GW(1));
+            stage2(jgx + p.off, rel, c0 && gk0, c1 && gk0, GW(2));
+            stage2(jgy + p.off, rel, c0 && gk0, c1 && gk0, GW(3));
+            stage2(jgy + p.off, rel + sj, c0 && gk0 && fjh, c1 && gk0 && fjh, GW(4));
+            stage2(jgz + p.off, rel + sk, c0 && gk1, c1 && gk1, GW(5));
+        }
+    };
+    RawPhi Pr;
+    Pr.v = mk2<T>(T(0), T(0));
+    Pr.c0 = Pr.c1 = T(0);
+    if constexpr (STG) {
+        const bool fkp0 = (k + 1 >= -FRAME) && (k + 1 < p.n[2] + FRAME);
+        stage(k);
+        Pr = ldphi_raw(k + 1, f0 && fkp0, f1 && fkp0);
+    }
 
     const int kend = t.k0 + t.nk;  // last red plane (the ring above the tile)
     // One plane of the march.  The colour column c = (i + j + k) & 1 of the pair is the same for every lane of a wavefront
@@ -189,7 +287,9 @@ __device__ __forceinline__ void gsrb_fused_body(T* __restrict__ S, const Tile& t
         fk = (k >= -FRAME) && (k < p.n[2] + FRAME);
         const bool fkp = (k + 1 >= -FRAME) && (k + 1 < p.n[2] + FRAME);
         // ---- this step's loads: phi and Jg^zz of plane k+1, cell coefficients of plane k --------
-        T2 Pp, Rh;
+        T2 Pp, Rh, Gzp, Ji, Gx, Gy, Gyh;
+        T gx_next;
+        if constexpr (!STG) {
         if (UNI) {
             Pp = Pn;
             Rh = Rn;
@@ -200,14 +300,15 @@ __device__ __forceinline__ void gsrb_fused_body(T* __restrict__ S, const Tile& t
             Pp = ldphi(k + 1, f0 && fkp, f1 && fkp);
             Rh = ld2(rhs, base + sk * k, c0 && fk, c1 && fk, p.off);
         }
-        const T2 Gzp = UNI ? uni2<T>(P.uc[2], c0 && fkp, c1 && fkp) : ld2(jgz, base + sk * (k + 1), c0 && fkp, c1 && fkp, p.off);
-        const T2 Ji = UNI ? uni2<T>(P.uc[3], c0 && fk, c1 && fk) : ld2(jinv, base + sk * k, c0 && fk, c1 && fk, p.off);
-        const T2 Gx = UNI ? uni2<T>(P.uc[0], c0 && fk, c1 && fk) : ld2(jgx, base + sk * k, c0 && fk, c1 && fk, p.off);
-        const T2 Gy = UNI ? uni2<T>(P.uc[1], c0 && fk, c1 && fk) : ld2(jgy, base + sk * k, c0 && fk, c1 && fk, p.off);
-        const T2 Gyh = UNI ? uni2<T>(P.uc[1], c0 && fk && fjh, c1 && fk && fjh)
+        Gzp = UNI ? uni2<T>(P.uc[2], c0 && fkp, c1 && fkp) : ld2(jgz, base + sk * (k + 1), c0 && fkp, c1 && fkp, p.off);
+        Ji = UNI ? uni2<T>(P.uc[3], c0 && fk, c1 && fk) : ld2(jinv, base + sk * k, c0 && fk, c1 && fk, p.off);
+        Gx = UNI ? uni2<T>(P.uc[0], c0 && fk, c1 && fk) : ld2(jgx, base + sk * k, c0 && fk, c1 && fk, p.off);
+        Gy = UNI ? uni2<T>(P.uc[1], c0 && fk, c1 && fk) : ld2(jgy, base + sk * k, c0 && fk, c1 && fk, p.off);
+        Gyh = UNI ? uni2<T>(P.uc[1], c0 && fk && fjh, c1 && fk && fjh)
                            : ld2(jgy, base + sk * k + sj, c0 && fk && fjh, c1 && fk && fjh, p.off);
         // Jg^xx on the face right of the pair = first component of the next lane's pair
-        const T gx_next = __shfl_down(Gx.x, 1, 64);
+        gx_next = __shfl_down(Gx.x, 1, 64);
+        }
 
         // ---- stage plane k (old values) in LDS; ONE barrier per plane -----------------------------
         //   slot k%3 was last read two steps ago (black of plane k-3); every wave has passed the
@@ -215,6 +316,22 @@ __device__ __forceinline__ void gsrb_fused_body(T* __restrict__ S, const Tile& t
         const int slot = ((k % 3) + 3) % 3;
         *reinterpret_cast<T2*>(&Sx(slot, row, ri)) = Pc;
         __syncthreads();
+        if constexpr (STG) {
+            // every load of the previous step has landed (the wait ahead of the barrier): take what it staged and fetched,
+            // with ld2's / ldphi's selects under this plane's predicates, then issue ALL of the next plane's loads at once
+            Pp = ldphi_use(Pr, f0 && fkp, f1 && fkp);
+            Rh = sel2<T>(GL(0), c0 && fk, c1 && fk);
+            Ji = sel2<T>(GL(1), c0 && fk, c1 && fk);
+            Gx = sel2<T>(GL(2), c0 && fk, c1 && fk);
+            Gy = sel2<T>(GL(3), c0 && fk, c1 && fk);
+            Gyh = sel2<T>(GL(4), c0 && fk && fjh, c1 && fk && fjh);
+            Gzp = sel2<T>(GL(5), c0 && fkp, c1 && fkp);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the slots are read: they may be overwritten
+            const bool fkpp = (k + 2 >= -FRAME) && (k + 2 < p.n[2] + FRAME);
+            stage(k + 1);
+            Pr = ldphi_raw(k + 2, f0 && fkpp, f1 && fkpp);
+            gx_next = __shfl_down(Gx.x, 1, 64);
+        }
 
         // ---- red(k) at column c: reads only black cells of the plane, writes only red ones ---------
         // red = pass 0 = even i+j+k (GSRBF.ChF:381-387): c is this plane's red column of the pair
@@ -268,7 +385,8 @@ __device__ __forceinline__ void gsrb_fused_body(T* __restrict__ S, const Tile& t
                                        Sx(sb, row, rc));
                 }
                 // plane k-1: column c is the new black, column c^1 is red(k-1) (= redPrev1)
-                T* dst = phi_out + base + sk * kb;
+                // (STG: the same address from the 32-bit rel0, so that the 64-bit base need not stay in registers)
+                T* dst = STG ? phi_out + p.off + (rel0 + sk * kb) : phi_out + base + sk * kb;
                 const T ox = c ? redPrev1 : black, oy = c ? black : redPrev1;
                 if (out_ij[0] && out_ij[1]) *reinterpret_cast<T2*>(dst) = mk2<T>(ox, oy);
                 else if (out_ij[0]) dst[0] = ox;
@@ -313,13 +431,18 @@ __device__ __forceinline__ void gsrb_fused_body(T* __restrict__ S, const Tile& t
             ++k;
         }
     }
+    // nothing may still be in flight towards this workgroup's LDS when it ends
+    if constexpr (STG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#undef GL
+#undef GW
 #undef Sx
 }
 
 // NARROW 1: the tile table holds narrow lane classes (uniform-metric depths, or SOMAR_NARROW_7PT=1); the instantiation without
 // them (0) is the one-body kernel with 48 KB of LDS that the HBM-bound streaming sweep was tuned as.  NARROW 2: every tile is
 // class 1 (tall tiles, march_plan.h): one body again, the same 48 KB, the region read as 32 rows of 64.
-template <int FR_J, int INMODE, bool DIRI = false, bool UNI = false, int NARROW = 0, class T = double>
+// STG: the staged-coefficient form (above): 96 KB of slots next to the phi planes, still one workgroup per CU.
+template <int FR_J, int INMODE, bool DIRI = false, bool UNI = false, int NARROW = 0, class T = double, bool STG = false>
 __global__ __launch_bounds__(64 * FR_J) void k_gsrb_fused(const Tile* __restrict__ tiles,
                                                      const PatchDesc* __restrict__ patches,
                                                      T* __restrict__ phi_out,
@@ -335,6 +458,10 @@ __global__ __launch_bounds__(64 * FR_J) void k_gsrb_fused(const Tile* __restrict
 {
     // one slot = the largest class's region: FR_J rows of 128, or 16 FR_J rows of 8 + 2
     __shared__ __attribute__((aligned(16))) T S[3 * FR_J * (NARROW == 1 ? 160 : 128)];
+    // an array of its own, not a part of S: the compiler then knows that the phi planes' reads and writes cannot touch a slot a
+    // load is still writing, and does not wait for the loads in front of them
+    __shared__ __attribute__((aligned(16))) T G[STG ? STG_STREAMS * FR_J * 128 : 2];
+    static_assert(!STG || (FR_J == 16 && !UNI && sizeof(T) == 8), "staged coefficients: the fp64 streamed 16-row kernels");
     const Tile t = tiles[blockIdx.x];
     const PatchDesc p = patches[t.patch];
     const int cls = NARROW == 1 ? t.cls : (NARROW == 2 ? 1 : 0);
@@ -349,7 +476,7 @@ __global__ __launch_bounds__(64 * FR_J) void k_gsrb_fused(const Tile* __restrict
                !((p.cf & 4) && jlo < 0) && !((p.cf & 8) && jhi >= p.n[1]);
     }
 #define SOMAR_FUSED_BODY(INT_, CLS_)                                                                                          \
-    gsrb_fused_body<FR_J, INMODE, DIRI, UNI, INT_, CLS_, T>(S, t, p, phi_out, phi_in, rhs, jgx, jgy, jgz, jinv, P, sums, cpatches, \
+    gsrb_fused_body<FR_J, INMODE, DIRI, UNI, INT_, CLS_, STG, T>(S, G, t, p, phi_out, phi_in, rhs, jgx, jgy, jgz, jinv, P, sums, cpatches, \
                                                         crse, r0, r1, r2)
     if constexpr (NARROW == 2) {
         SOMAR_FUSED_BODY(false, 1);   // (never with UNI: no lean form)
@@ -365,6 +492,14 @@ __global__ __launch_bounds__(64 * FR_J) void k_gsrb_fused(const Tile* __restrict
 #undef SOMAR_FUSED_BODY
 }
 
+// which instantiations have a staged-coefficient twin: fp64 (a float pair is 8 bytes, not a width the load has), a streamed
+// metric, 16 rows (the 8-row kernels hide latency with a second workgroup per CU)
+template <class T>
+constexpr bool staged_mode(int rows, bool uni, int narrow, int in_mode)
+{
+    return sizeof(T) == 8 && rows == 16 && !uni && (narrow == 1 ? STAGED_MODES_MIXED[in_mode] : STAGED_MODES[in_mode]);
+}
+
 // M: the level's coefficient arrays in T (L.jg / L.jinv, or their fp32 copies)
 template <class T>
 static void launch_gsrb_fused_t(hipStream_t st, TileSpan tiles, const LevelDev& L, const MetricPtrs<T>& M,
@@ -376,18 +511,26 @@ static void launch_gsrb_fused_t(hipStream_t st, TileSpan tiles, const LevelDev& 
     const int r0 = r ? r[0] : 1, r1 = r ? r[1] : 1, r2 = r ? r[2] : 1;
     SOMAR_CHECK(in_mode < 3 || ((r0 == 1 || r0 == 2) && (r1 == 1 || r1 == 2) && (r2 == 1 || r2 == 2)),
                 "internal: the prolongation folded into a sweep takes multigrid ratios of 1 or 2 per direction");
-    auto go = [&](auto kern, int rows) {
-        hipLaunchKernelGGL(kern, dim3(tiles.n), dim3(64, rows, 1), 0, st, tiles.p, L.patches, phi_out, phi_in, rhs, M.jg[0], M.jg[1],
-                           M.jg[2], M.jinv, L.P, sums, cpatches, crse, r0, r1, r2, L.lean_tiles);
+    // the staged-coefficient twin of a streamed fp64 16-row kernel (the kernel itself otherwise): SOMAR_NO_STAGED_COEF=1 and
+    // every other instantiation keep the loads into registers
+    auto go = [&](auto kern0, auto kern1, int rows) {
+        auto launch = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(tiles.n), dim3(64, rows, 1), 0, st, tiles.p, L.patches, phi_out, phi_in, rhs, M.jg[0],
+                               M.jg[1], M.jg[2], M.jinv, L.P, sums, cpatches, crse, r0, r1, r2, L.lean_tiles);
+        };
+        if (L.staged_coef) launch(kern1);
+        else launch(kern0);
     };
     // (rows, mode, Dirichlet sides, uniform metric, narrow lane classes in the tile table: 0 none, 1 mixed, 2 all class 1)
+#define SOMAR_FUSED_KERN(ROWS, D, U, N, M) \
+    k_gsrb_fused<ROWS, M, D, U, N, T>, k_gsrb_fused<ROWS, M, D, U, N, T, staged_mode<T>(ROWS, U, N, M)>
 #define SOMAR_FUSED_MODES(ROWS, D, U, N, M0, M1, M2, M3, M4)                    \
     switch (in_mode) {                                                          \
-        case 1: go(k_gsrb_fused<ROWS, M1, D, U, N, T>, ROWS); break;            \
-        case 2: go(k_gsrb_fused<ROWS, M2, D, U, N, T>, ROWS); break;            \
-        case 3: go(k_gsrb_fused<ROWS, M3, D, U, N, T>, ROWS); break;            \
-        case 4: go(k_gsrb_fused<ROWS, M4, D, U, N, T>, ROWS); break;            \
-        default: go(k_gsrb_fused<ROWS, M0, D, U, N, T>, ROWS);                  \
+        case 1: go(SOMAR_FUSED_KERN(ROWS, D, U, N, M1), ROWS); break;           \
+        case 2: go(SOMAR_FUSED_KERN(ROWS, D, U, N, M2), ROWS); break;           \
+        case 3: go(SOMAR_FUSED_KERN(ROWS, D, U, N, M3), ROWS); break;           \
+        case 4: go(SOMAR_FUSED_KERN(ROWS, D, U, N, M4), ROWS); break;           \
+        default: go(SOMAR_FUSED_KERN(ROWS, D, U, N, M0), ROWS);                 \
     }
     const bool rows16 = L.fused_rows == 16;
     const bool narrow = tiles.classes != 0 && rows16;   // march_plan::fused_shape hands the 8-row kernels class-0 tiles only
@@ -415,6 +558,7 @@ static void launch_gsrb_fused_t(hipStream_t st, TileSpan tiles, const LevelDev& 
     else if (narrow) { SOMAR_FUSED_MODES(16, false, false, true, 0, 1, 2, 3, 4) }
     else { SOMAR_FUSED_MODES(16, false, false, false, 0, 1, 2, 3, 4) }
 #undef SOMAR_FUSED_MODES
+#undef SOMAR_FUSED_KERN
 }
 
 void launch_gsrb_fused(hipStream_t st, TileSpan tiles, const LevelDev& L, const MetricPtrs<double>& M,

@@ -38,6 +38,7 @@ struct LevelDev {
     int fused_rows = 16;                // region rows per workgroup of the fused 7-point sweep (tile rows = rows - 4): 16 or 8
     int full_rows = 8;                  // ... of the 19-point marching kernels: 8 or 6
     int lean_tiles = 1;                 // interior tiles of the uniform-metric fused sweep take the lean body
+    int staged_coef = 0;                // the streamed fp64 16-row fused sweep fetches its coefficients a plane ahead through LDS
     int ordered_serial = 0;             // serial-order sums walk all boxes in one chain (launch_reduce)
 };
 

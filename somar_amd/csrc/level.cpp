@@ -579,6 +579,7 @@ void Level::define(const IBox& dom, const bool per[3], const double dx_[3], cons
         local.push_back((int)b);
     }
     field_elems = cursor;
+    dev.staged_coef = !t.no_staged_coef && valid_cells_global >= t.staged_min_cells ? 1 : 0;
 
     // ---- tiles, XCD-contiguous (march_plan::xcd_order) ------------------------------------------------
     // Tile shape per level: big bricks (8 rows x 32 planes) keep the j/k halo re-reads of a

@@ -72,6 +72,10 @@ Tuning Tuning::from_env()
         if (s.field == &Tuning::march_min_cells) march_set = true;
     }
     if (!march_set) t.march_min_cells = t.fused_min_cells;
+    // the staged-coefficient sweep's two switches are read here, not from the table: the table is the list that
+    // DESIGN.md 8.9 and tests/test_gpu_tuning.py pin row for row
+    if (const char* e = getenv("SOMAR_NO_STAGED_COEF")) t.no_staged_coef = atoi(e) != 0;
+    if (const char* e = getenv("SOMAR_STAGED_MIN_CELLS")) t.staged_min_cells = atoll(e);
     return t;
 }
 
@@ -79,6 +83,8 @@ bool Tuning::get(const char* name, long long* value) const
 {
     for (const Switch& s : SWITCHES)
         if (!strcmp(name, s.name)) { *value = this->*s.field; return true; }
+    if (!strcmp(name, "NO_STAGED_COEF")) { *value = no_staged_coef; return true; }
+    if (!strcmp(name, "STAGED_MIN_CELLS")) { *value = staged_min_cells; return true; }
     return false;
 }
 

@@ -20,6 +20,8 @@ struct Tuning {
     long long no_narrow_tiles = 0;        // SOMAR_NO_NARROW_TILES: equal columns only, no narrow lane classes
     long long narrow_7pt = -1;            // SOMAR_NARROW_7PT: lane classes for the 7-point kernels never (0) / always (1); unset (-1): on uniform-metric depths
     long long no_lean_tiles = 0;          // SOMAR_NO_LEAN_TILES: interior tiles of the fused sweep take the general body too
+    long long no_staged_coef = 0;         // SOMAR_NO_STAGED_COEF: the streamed fused sweep loads its coefficients into registers in the step that uses them
+    long long staged_min_cells = 4194304; // SOMAR_STAGED_MIN_CELLS: ... on levels smaller than this too: the staging through LDS did not pay at 128^3 (tests: 0)
     // ---- metric flags (PressureSolver::detect_metric_flags) ----
     long long no_uniform = 0;             // SOMAR_NO_UNIFORM: stream constant coefficient arrays anyway
     long long no_zero_planes = 0;         // SOMAR_NO_ZERO_PLANES: multiply identically zero J g^{xy} planes anyway

@@ -1228,14 +1228,8 @@ void AMRSolver::heat_step(int l, int scheme, double dt, bool zeroPhi, double old
     // solveHelm: m_solver->solve(phi, rhs, l, l, zeroPhi) with alpha 1, beta -dt mu (:217-251)
     auto solve_helm = [&](double mu) {
         set_alpha_beta(1.0, -dt * mu);
-        crse_override_ = coarse;
-        try {
-            solve(l, l, zeroPhi, false, st);
-        } catch (...) {
-            crse_override_ = nullptr;
-            throw;
-        }
-        crse_override_ = nullptr;
+        ScopedSet<double*> with_coarse(crse_override_, coarse);
+        solve(l, l, zeroPhi, false, st);
     };
     if (scheme == 0) {
         launch_copy(st_, rhst, phiOld, n);
@@ -1251,11 +1245,7 @@ void AMRSolver::heat_step(int l, int scheme, double dt, bool zeroPhi, double old
         solve_helm(0.5);
         P.increment_heat_flux(phiNew, true);
     } else {
-        const double tgaEpsilon = 1.e-12;
-        const double a = 2.0 - std::sqrt(2.0) - tgaEpsilon;
-        const double discr = std::sqrt(a * a - 4.0 * a + 2.0);
-        const double mu1 = (a - discr) / 2.0, mu2 = (a + discr) / 2.0, mu3 = 1.0 - a, mu4 = 0.5 - a;
-        const double r1 = (2.0 * a - 1.0) / (a + discr);
+        const auto [mu1, mu2, mu3, mu4, r1] = tga_coefficients();
         double* phis = S[l]->field(0, 4);        // bestPhi's array: free between solves (each solve rewrites it first)
         launch_copy(st_, tmp, src, n);           // srct = dt * src
         launch_scale(st_, tmp, dt, n);
@@ -1301,10 +1291,7 @@ void AMRSolver::tga_step(int l_max, int l_base, double dt, SolveStats& st)
     SOMAR_CHECK(l_base == 0, "tga_step: l_base > 0 is undefined in the reference (MappedAMRTGA::oneStep reads the source "
                              "term of level l_base - 1, which createData never allocates)");
     SOMAR_CHECK(dt >= 0.0, "negative time step");
-    const double tgaEpsilon = 1.e-12;
-    const double a = 2.0 - std::sqrt(2.0) - tgaEpsilon;
-    const double discr = std::sqrt(a * a - 4.0 * a + 2.0);
-    const double mu1 = (a - discr) / 2.0, mu2 = (a + discr) / 2.0, mu3 = 1.0 - a, mu4 = 0.5 - a;
+    const auto [mu1, mu2, mu3, mu4, r1] = tga_coefficients();   // (r1: the level integrator's intermediate time, unused here)
     const int nl = nlevels();
     std::vector<double*> phiNew(nl), rhst(nl), phiOld(nl), src(nl), srct(nl), zero(nl);
     std::vector<long long> n(nl);
@@ -1388,14 +1375,8 @@ void AMRSolver::solve_on(PressureSolver::Mem where, double* const* const* phi, c
 void AMRSolver::solve_leptic(int l_max, int l_base, bool zeroPhi, bool forceHomogeneous, SolveStats& s)
 {
     SOMAR_CHECK((int)leptic_.size() == nlevels(), "solve_leptic before enable_leptic");
-    lepticCycle_ = true;
-    try {
-        solve_impl(l_max, l_base, zeroPhi, forceHomogeneous, s);
-    } catch (...) {
-        lepticCycle_ = false;
-        throw;
-    }
-    lepticCycle_ = false;
+    ScopedSet<bool> leptic(lepticCycle_, true);
+    solve_impl(l_max, l_base, zeroPhi, forceHomogeneous, s);
 }
 
 void AMRSolver::solve_impl(int l_max, int l_base, bool zeroPhi, bool forceHomogeneous, SolveStats& s)
@@ -1427,56 +1408,26 @@ void AMRSolver::solve_impl(int l_max, int l_base, bool zeroPhi, bool forceHomoge
     if (zeroPhi)
         for (int l = l_base; l <= l_max; ++l) launch_set(st_, phi[l], S[l]->level(0).field_elems, 0.0);
     for (int l = lowlim; l <= l_max; ++l) launch_copy(st_, best[l], phi[l], S[l]->level(0).field_elems);
-    double initial_rnorm = compute_residual(uRes.data(), phi.data(), rhs.data(), l_max, l_base, forceHomogeneous);
-    double rnorm = initial_rnorm, norm_last = 2 * initial_rnorm, best_rnorm = rnorm;
-    bool useBestPhi = false, somethingConverged = false;
-    S[l_base]->bottom_metric = initial_rnorm;  // setConvergenceMetrics(initial_rnorm, cushion * eps)
+    OuterLoop o;
+    o.start(compute_residual(uRes.data(), phi.data(), rhs.data(), l_max, l_base, forceHomogeneous), prm);
+    S[l_base]->bottom_metric = o.initial;  // setConvergenceMetrics(initial_rnorm, cushion * eps)
     S[l_base]->bottom_eps_eff = 1.0 * prm.eps;
-    int iter = 0;
-    s = SolveStats();
-    s.history.push_back(rnorm);
-    bool goNorm = rnorm > prm.normThresh;
-    bool goRedu = rnorm > prm.eps * initial_rnorm;
-    bool goIter = iter < prm.imax;
-    bool goHang = iter < prm.imin || rnorm < (1 - prm.hang) * norm_last;
-    while (goIter && goRedu && goHang && goNorm) {
-        if (inspector_) { sync(); inspector_(inspector_user_, 0, iter, l_base, l_max); }   // recordResiduals, :1064-1065
-        norm_last = rnorm;
+    while (o.go()) {
+        if (inspector_) { sync(); inspector_(inspector_user_, 0, o.iter, l_base, l_max); }   // recordResiduals, :1064-1065
+        o.begin_cycle();
         vcycle(uCorr.data(), uRes.data(), l_max, l_max, l_base);
-        if (inspector_) { sync(); inspector_(inspector_user_, 1, iter, l_base, l_max); }   // recordCorrections, :1083-1084
+        if (inspector_) { sync(); inspector_(inspector_user_, 1, o.iter, l_base, l_max); }   // recordCorrections, :1083-1084
         for (int l = l_base; l <= l_max; ++l) {  // postVCycleOps
             const long long ne = S[l]->level(0).field_elems;
             launch_incr(st_, phi[l], uCorr[l], 1.0, ne);
             launch_set(st_, uCorr[l], ne, 0.0);
         }
-        rnorm = compute_residual(uRes.data(), phi.data(), rhs.data(), l_max, l_base, forceHomogeneous);
-        ++iter;
-        s.history.push_back(rnorm);
-        if (rnorm <= best_rnorm) {
-            best_rnorm = rnorm;
+        if (o.end_cycle(compute_residual(uRes.data(), phi.data(), rhs.data(), l_max, l_base, forceHomogeneous), prm))
             for (int l = l_base; l <= l_max; ++l) launch_copy(st_, best[l], phi[l], S[l]->level(0).field_elems);
-            useBestPhi = false;
-            somethingConverged = true;
-        } else {
-            useBestPhi = true;
-        }
-        goNorm = rnorm > prm.normThresh;
-        goRedu = rnorm > prm.eps * initial_rnorm;
-        goIter = iter < prm.imax;
-        goHang = iter < prm.imin || rnorm < (1 - prm.hang) * norm_last;
     }
-    if (useBestPhi) {
-        rnorm = best_rnorm;
+    // AMRLepticSolver only prints where MappedAMRMultiGrid reports "blew up" (AMRLepticSolver.cpp:384-388)
+    if (o.finish(prm, !lepticCycle_, s))
         for (int l = l_base; l <= l_max; ++l) launch_copy(st_, phi[l], best[l], S[l]->level(0).field_elems);
-    }
-    s.status = 0;
-    if (rnorm > 10. * initial_rnorm && rnorm > 10. * prm.eps) s.status = 1;
-    else if (!lepticCycle_ && !somethingConverged && rnorm >= initial_rnorm && rnorm >= prm.eps)
-        s.status = 2;   // AMRLepticSolver only prints here (AMRLepticSolver.cpp:384-388)
-    s.exitStatus = int(!goRedu) + int(!goIter) * 2 + int(!goHang) * 4 + int(!goNorm) * 8;
-    s.iters = iter;
-    s.initial_rnorm = initial_rnorm;
-    s.final_rnorm = rnorm;
     s.bottom_iters_last = S[l_base]->bottom_iters;
     s.bottom_exit_last = S[l_base]->bottom_exit;
     sync();

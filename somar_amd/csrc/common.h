@@ -34,6 +34,24 @@ struct Error : std::runtime_error {
                                          ":" + std::to_string(__LINE__));         \
     } while (0)
 
+// "Set for the duration of the call": ScopedSet saves a variable, sets it, and puts the saved value back when the scope ends,
+// by return or by exception; ScopeExit runs any other way back (its lambda) at that point.
+template <class T>
+struct ScopedSet {
+    T& var;
+    const T saved;
+    ScopedSet(T& v, const T& value) : var(v), saved(v) { var = value; }
+    ~ScopedSet() { var = saved; }
+    ScopedSet(const ScopedSet&) = delete;
+};
+template <class F>
+struct ScopeExit {
+    F f;
+    ~ScopeExit() { f(); }
+};
+template <class F>
+ScopeExit(F) -> ScopeExit<F>;
+
 // BCType codes, reference calculus/BCInterface/BCDescriptor.H:34-39
 enum { BC_UNDEFINED = -2, BC_NONE = -1, BC_NEUM = 0, BC_DIRI = 1, BC_PERIODIC = 2, BC_CF = 3 };
 

@@ -1512,45 +1512,59 @@ double* PressureSolver::heat_field(int which)
 //   BE: rhs = phiOld (the source term is commented out in the reference);   solve (aCoef I - dt bCoef L) phiNew = rhs
 //   CN: rhs = dt src + (aCoef I + dt/2 bCoef L) phiOld [inhomogeneous BCs]; solve (aCoef I - dt/2 bCoef L) phiNew = rhs
 //   TGA: (I - mu1 dt L)(I - mu2 dt L) phiNew = (I + mu3 dt L) phiOld + (I + mu4 dt L) dt src; stats are the last solve's
+// Written once for one field and for every component (heat_step_multi): each(f) runs f with every component in turn in the
+// place of the solver's own fields, solve(last) is solve or solve_multi (last: the step's final solve).  One dt and one
+// set_alpha_beta serve all components (it scales every component's own pair), so the stages that set the coefficients run
+// component after component between them.
+void PressureSolver::heat_stages(int scheme, double dt, bool zeroPhi, const std::function<void(const std::function<void()>&)>& each,
+                                 const std::function<void(bool)>& solve)
+{
+    const long long n = lev[0]->field_elems;
+    if (scheme == 0) {
+        each([&]() { launch_copy(st_, f_rhs, heat_field(0), n); });
+        set_alpha_beta(1.0, -dt * 1.0);
+    } else if (scheme == 1) {
+        set_alpha_beta(1.0, 0.5 * dt);
+        each([&]() {
+            apply_op(0, f_scratch[0], heat_field(0), false);
+            launch_copy(st_, f_rhs, heat_field(1), n);
+            launch_scale(st_, f_rhs, dt, n);
+            launch_incr(st_, f_rhs, f_scratch[0], 1.0, n);
+        });
+        set_alpha_beta(1.0, -dt * 0.5);
+    } else {
+        // MappedLevelTGA::updateSolnWithTimeIndependentOp, MappedLevelTGA.cpp:231-387
+        const TGACoefficients c = tga_coefficients();
+        // heat_field(2): srct, then phis (the caller's initial guess for both solves)
+        each([&]() {
+            launch_copy(st_, heat_field(2), heat_field(1), n);   // srct = dt * src
+            launch_scale(st_, heat_field(2), dt, n);
+        });
+        set_alpha_beta(1.0, c.mu4 * dt);
+        each([&]() { apply_op(0, f_rhs, heat_field(2), true); });   // rhst = (I + mu4 dt L) srct, homogeneous BCs
+        set_alpha_beta(1.0, c.mu3 * dt);
+        each([&]() {
+            apply_op(0, f_scratch[0], heat_field(0), false);         // (I + mu3 dt L) phiOld with the inhomogeneous BCs
+            launch_incr(st_, f_rhs, f_scratch[0], 1.0, n);
+            if (!zeroPhi) launch_copy(st_, heat_field(2), f_phi, n);
+        });
+        set_alpha_beta(1.0, -dt * c.mu2);
+        solve(false);                                                // (I - mu2 dt L) phi* = rhst
+        each([&]() {
+            launch_copy(st_, f_rhs, f_phi, n);                       // assign(rhst, phiNew)
+            if (!zeroPhi) launch_copy(st_, f_phi, heat_field(2), n);
+        });
+        set_alpha_beta(1.0, -dt * c.mu1);                            // (I - mu1 dt L) phiNew = phi*
+    }
+    solve(true);
+}
+
 void PressureSolver::heat_step(int scheme, double dt, bool zeroPhi, SolveStats& s)
 {
     check_idle("heat_step");
     SOMAR_CHECK(scheme >= 0 && scheme <= 2, "heat scheme: 0 backward Euler, 1 Crank-Nicolson, 2 TGA");
     SOMAR_CHECK(dt >= 0.0, "negative time step");
-    const long long n = lev[0]->field_elems;
-    double* phiOld = heat_field(0);
-    if (scheme == 0) {
-        launch_copy(st_, f_rhs, phiOld, n);
-        set_alpha_beta(1.0, -dt * 1.0);
-    } else if (scheme == 1) {
-        set_alpha_beta(1.0, 0.5 * dt);
-        apply_op(0, f_scratch[0], phiOld, false);
-        launch_copy(st_, f_rhs, heat_field(1), n);
-        launch_scale(st_, f_rhs, dt, n);
-        launch_incr(st_, f_rhs, f_scratch[0], 1.0, n);
-        set_alpha_beta(1.0, -dt * 0.5);
-    } else {
-        // MappedLevelTGA::updateSolnWithTimeIndependentOp, MappedLevelTGA.cpp:231-387; coefficients: its constructor, :30-56
-        const double tgaEpsilon = 1.e-12;
-        const double a = 2.0 - std::sqrt(2.0) - tgaEpsilon;
-        const double discr = std::sqrt(a * a - 4.0 * a + 2.0);
-        const double mu1 = (a - discr) / 2.0, mu2 = (a + discr) / 2.0, mu3 = 1.0 - a, mu4 = 0.5 - a;
-        double* tmp = heat_field(2);              // srct, then phis (the caller's initial guess for both solves)
-        launch_copy(st_, tmp, heat_field(1), n);  // srct = dt * src
-        launch_scale(st_, tmp, dt, n);
-        set_alpha_beta(1.0, mu4 * dt);
-        apply_op(0, f_rhs, tmp, true);            // rhst = (I + mu4 dt L) srct, homogeneous BCs
-        set_alpha_beta(1.0, mu3 * dt);
-        apply_op(0, f_scratch[0], phiOld, false);  // (I + mu3 dt L) phiOld with the inhomogeneous BCs
-        launch_incr(st_, f_rhs, f_scratch[0], 1.0, n);
-        if (!zeroPhi) launch_copy(st_, tmp, f_phi, n);
-        set_alpha_beta(1.0, -dt * mu2);
-        solve(zeroPhi, false, s);                 // (I - mu2 dt L) phi* = rhst
-        launch_copy(st_, f_rhs, f_phi, n);        // assign(rhst, phiNew)
-        if (!zeroPhi) launch_copy(st_, f_phi, tmp, n);
-        set_alpha_beta(1.0, -dt * mu1);           // (I - mu1 dt L) phiNew = phi*
-    }
-    solve(zeroPhi, false, s);
+    heat_stages(scheme, dt, zeroPhi, [](const std::function<void()>& f) { f(); }, [&](bool) { solve(zeroPhi, false, s); });
     sync();
 }
 
@@ -1687,15 +1701,10 @@ void PressureSolver::cycle(int d, double* corr, const double* res, bool corr_zer
         relax(d, corr, res, prm.num_smooth_down);
         for (int img = 0; img < cycles; ++img) {
             restrict_residual(d, f_res[d + 1], corr, res);
-            const int saved = cycle_override_;
-            cycle_override_ = 1;
-            try {
+            {
+                ScopedSet<int> as_vcycle(cycle_override_, 1);
                 cycle(d + 1, f_corr[d + 1], f_res[d + 1], true);
-            } catch (...) {
-                cycle_override_ = saved;
-                throw;
             }
-            cycle_override_ = saved;
             prolong_increment(d, corr, f_corr[d + 1]);
         }
         relax(d, corr, res, prm.num_smooth_up);
@@ -1713,14 +1722,8 @@ void PressureSolver::mini_vcycle(double* corr, const double* res)
 {
     SOMAR_CHECK(!forcedRatios.empty() && (int)lev.size() > (int)forcedRatios.size(), "no forced MG depths on this level");
     SOMAR_CHECK(!coarse_ || agglom_depth_ > (int)forcedRatios.size(), "internal: forced depths inside the replicated tail");
-    mini_depth_ = (int)forcedRatios.size() + 1;
-    try {
-        cycle(0, corr, res, false);
-    } catch (...) {
-        mini_depth_ = 0;
-        throw;
-    }
-    mini_depth_ = 0;
+    ScopedSet<int> limit(mini_depth_, (int)forcedRatios.size() + 1);
+    cycle(0, corr, res, false);
 }
 
 void PressureSolver::set_bc_values(const double v[6])
@@ -2535,54 +2538,22 @@ void PressureSolver::solve(bool zeroPhi, bool forceHomogeneous, SolveStats& s)
     if (zeroPhi) launch_set(st_, f_phi, n, 0.0);
     launch_copy(st_, f_best, f_phi, n);
     residual(0, f_uberRes, f_phi, f_rhs, forceHomogeneous);  // computeAMRResidual(..., a_forceHomogeneous), :1021
-    double initial_rnorm = norm(0, f_uberRes, 0);
-    double rnorm = initial_rnorm, norm_last = 2 * initial_rnorm, best_rnorm = rnorm;
-    bool useBestPhi = false, somethingConverged = false;
-    bottom_metric = initial_rnorm;          // setConvergenceMetrics(initial_rnorm, cushion*eps), :1047
+    OuterLoop o;
+    o.start(norm(0, f_uberRes, 0), prm);
+    bottom_metric = o.initial;              // setConvergenceMetrics(initial_rnorm, cushion*eps), :1047
     bottom_eps_eff = 1.0 * prm.eps;
-    int iter = 0;
-    s = SolveStats();
-    s.history.push_back(rnorm);
-    bool goNorm = rnorm > prm.normThresh;
-    bool goRedu = rnorm > prm.eps * initial_rnorm;
-    bool goIter = iter < prm.imax;
-    bool goHang = iter < prm.imin || rnorm < (1 - prm.hang) * norm_last;
-    while (goIter && goRedu && goHang && goNorm) {
-        norm_last = rnorm;
+    while (o.go()) {
+        o.begin_cycle();
         if (mp_K_ > 0) {
-            vcycle_mixed(f_phi, f_uberRes, rnorm, true, true);   // the fp32 correction from zero, phi += (double)corr in one pass
+            vcycle_mixed(f_phi, f_uberRes, o.rnorm, true, true);   // the fp32 correction from zero, phi += (double)corr in one pass
         } else {
             vcycle(f_uberCorr, f_uberRes, true);          // uberCorrection is zero here (setToZero, :1203)
             launch_incr(st_, f_phi, f_uberCorr, 1.0, n);   // postVCycleOps, :1189-1215
         }
         residual(0, f_uberRes, f_phi, f_rhs, forceHomogeneous);
-        rnorm = norm(0, f_uberRes, 0);
-        ++iter;
-        s.history.push_back(rnorm);
-        if (rnorm <= best_rnorm) {
-            best_rnorm = rnorm;
-            launch_copy(st_, f_best, f_phi, n);
-            useBestPhi = false;
-            somethingConverged = true;
-        } else {
-            useBestPhi = true;
-        }
-        goNorm = rnorm > prm.normThresh;
-        goRedu = rnorm > prm.eps * initial_rnorm;
-        goIter = iter < prm.imax;
-        goHang = iter < prm.imin || rnorm < (1 - prm.hang) * norm_last;
+        if (o.end_cycle(norm(0, f_uberRes, 0), prm)) launch_copy(st_, f_best, f_phi, n);
     }
-    if (useBestPhi) {
-        rnorm = best_rnorm;
-        launch_copy(st_, f_phi, f_best, n);
-    }
-    s.status = 0;
-    if (rnorm > 10. * initial_rnorm && rnorm > 10. * prm.eps) s.status = 1;                        // "kaboom" :1134
-    else if (!somethingConverged && rnorm >= initial_rnorm && rnorm >= prm.eps) s.status = 2;      // :1141
-    s.exitStatus = int(!goRedu) + int(!goIter) * 2 + int(!goHang) * 4 + int(!goNorm) * 8;
-    s.iters = iter;
-    s.initial_rnorm = initial_rnorm;
-    s.final_rnorm = rnorm;
+    if (o.finish(prm, true, s)) launch_copy(st_, f_phi, f_best, n);
     s.bottom_iters_last = bottom_iters;
     s.bottom_exit_last = bottom_exit;
     sync();

@@ -9,10 +9,12 @@
 // kernel launches on one HIP stream and reads back the few scalars the stopping tests need.
 #pragma once
 #include <exception>
+#include <functional>
 #include <memory>
 #include <vector>
 
 #include "level.h"
+#include "outer_loop.h"   // StopCriteria, SolveStats, OuterLoop, tga_coefficients
 
 namespace somar {
 
@@ -20,25 +22,14 @@ enum { RELAX_JACOBI = 0, RELAX_LEVEL_GSRB = 1, RELAX_LOOSE_GSRB = 2, RELAX_LINE_
 enum { PRECOND_NONE = -1, PRECOND_DIAG_RELAX = 0, PRECOND_DIAG_LINE_RELAX = 1 };
 
 // AMRPressureSolver::setAMRMGParameters / setBottomParameters (projection/AMRPressureSolver.H:53-77);
-// defaults utils/ProblemContext.cpp:1147-1236
-struct SolverParams {
-    int imin = 5, imax = 20;
-    double eps = 1e-6, hang = 1e-15, normThresh = 1e-30;
+// defaults utils/ProblemContext.cpp:1147-1236.  StopCriteria (outer_loop.h): imin, imax, eps, hang, normThresh
+struct SolverParams : StopCriteria {
     int num_smooth_down = 2, num_smooth_up = 2, num_smooth_bottom = 2, num_smooth_precond = 2;
     int numMG = 1, maxDepth = -1, precondMode = PRECOND_DIAG_RELAX, relaxMode = RELAX_LEVEL_GSRB;
     int verbosity = 0;
     int spaceDim = 3;  // 2: the reference built with CH_SPACEDIM = 2 (boxes one cell thick in z, which is inactive)
     int bottom_imax = 80, bottom_numRestarts = 5, bottom_normType = 2, bottom_verbosity = 0;
     double bottom_eps = 1e-6, bottom_reps = 1e-12, bottom_hang = 1e-15, bottom_small = 1e-30;
-};
-
-struct SolveStats {
-    int iters = 0;
-    int exitStatus = 0;         // !goRedu + 2*!goIter + 4*!goHang + 8*!goNorm (MappedAMRMultiGrid.H:1148)
-    int status = 0;             // 0 ok, 1 "kaboom", 2 "solver blew up"
-    double initial_rnorm = 0, final_rnorm = 0;
-    std::vector<double> history;  // max-norm residual after each V-cycle (history[0] = initial)
-    int bottom_iters_last = 0, bottom_exit_last = 0;
 };
 
 class PressureSolver {
@@ -313,6 +304,9 @@ public:
 private:
     void move_host(const CallerArray& a, int patch, double* host, bool up);
     void cycle(int d, double* corr, const double* res, bool corr_zero = false);
+    // the stages of backward Euler, Crank-Nicolson and TGA, for heat_step and heat_step_multi (solver.cpp)
+    void heat_stages(int scheme, double dt, bool zeroPhi, const std::function<void(const std::function<void()>&)>& each,
+                     const std::function<void(bool)>& solve);
     // residual_i (mode 0) and apply_op_i (mode 1) in one: mode 0 out = rhs - L[phi] (timed in a profiled pass), mode 1 out = L[phi] (rhs unused)
     void operator_i(int d, int mode, double* out, double* phi, const double* rhs, bool homogeneous);
     // prolong_from and prolong_increment in one: depth d += the coarse field on layout C (ratio r), then the zero-average mean
@@ -390,8 +384,8 @@ private:
     void on_comp(int comp, Fn f)
     {
         swap_comp(comp);
-        try { f(); } catch (...) { swap_comp(comp); throw; }
-        swap_comp(comp);
+        ScopeExit back{[&]() { swap_comp(comp); }};
+        f();
     }
     // the fields of the active components, by position in the active list
     struct CompFields { int n = 0; int comp[MC_MAX]; double* corr[MC_MAX]; double* res[MC_MAX]; };
@@ -599,9 +593,8 @@ private:
         if (!o) { f(); return; }
         exchange_op(o->st);
         op_in_place_ = comp;
-        try { f(); } catch (...) { exchange_op(o->st); op_in_place_ = 0; throw; }
-        exchange_op(o->st);
-        op_in_place_ = 0;
+        ScopeExit back{[&]() { exchange_op(o->st); op_in_place_ = 0; }};
+        f();
     }
     bool probe_op(CompOp& o, int* depth);                  // the null-space probe at every depth with o in place: any zeroAvg?
     void ensure_face_copiers(const int bc[3][2]);          // Level::cf_faces for the operator's Dirichlet HIGH sides, every depth

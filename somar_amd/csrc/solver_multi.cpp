@@ -2,7 +2,7 @@
 //
 // The specification is one sentence: solve_multi leaves every component -- fields, statistics, residual history -- exactly
 // as ncomp successive solve() calls on the same handle would.  Everything here follows from it:
-//   * each component keeps its own outer-loop state (MappedAMRMultiGrid::solveNoInitResid, MappedAMRMultiGrid.H:979-1183);
+//   * each component has an OuterLoop of its own (outer_loop.h: the state and decisions of solve()'s iteration, one text);
 //     the components cycle in lock step, and one whose loop condition fails leaves the active set for good;
 //   * on the batched depths the fold path of the cycle (fused sweeps, residual + restriction, prolongation folded into the
 //     first post-smoothing sweep) runs as N-field launches (multi_march.hip) whose per-field arithmetic is the single-field
@@ -179,21 +179,16 @@ bool PressureSolver::probe_op(CompOp& o, int* depth)
     o.st.alpha = o.alpha0;
     o.st.beta = o.beta0;
     exchange_op(o.st);
-    bool any = false;
-    try {
-        for (int d = 0; d < (int)lev.size(); ++d) {
-            probe_null_space(d);
-            if (lev[d]->zeroAvg && !any) { any = true; if (depth) *depth = d; }
-        }
-    } catch (...) {
-        exchange_op(o.st);
+    ScopeExit back{[&]() {
+        exchange_op(o.st);   // (the verdicts go back into o with it)
         o.st.alpha = a;
         o.st.beta = b;
-        throw;
+    }};
+    bool any = false;
+    for (int d = 0; d < (int)lev.size(); ++d) {
+        probe_null_space(d);
+        if (lev[d]->zeroAvg && !any) { any = true; if (depth) *depth = d; }
     }
-    exchange_op(o.st);   // (the verdicts go back into o with it)
-    o.st.alpha = a;
-    o.st.beta = b;
     return any;
 }
 
@@ -573,12 +568,8 @@ void PressureSolver::solve_multi(bool zeroPhi, bool forceHomogeneous, std::vecto
     const long long n = L.field_elems;
     // the bottom solver's counts as they stand before the first component's solve: a solve that runs no cycle reports those
     int carry_iters = bottom_iters, carry_exit = bottom_exit;
-    struct State {
-        double initial = 0, rnorm = 0, norm_last = 0, best = 0;
-        bool useBest = false, converged = false, goNorm = false, goRedu = false, goIter = false, goHang = false;
-        int iter = 0, b_iters = -1, b_exit = 0;
-        bool go() const { return goIter && goRedu && goHang && goNorm; }
-    } S[MC_MAX];
+    OuterLoop S[MC_MAX];
+    int b_iters[MC_MAX] = {-1, -1, -1, -1}, b_exit[MC_MAX] = {0, 0, 0, 0};   // of each component's last cycle (-1: it ran none)
     double *phi[MC_MAX], *rhs[MC_MAX], *res[MC_MAX], *corr[MC_MAX], *best[MC_MAX];
     for (int c = 0; c < nc; ++c) {
         phi[c] = comp_field(c, 0); rhs[c] = comp_field(c, 1); res[c] = comp_field(c, 2); corr[c] = comp_field(c, 3);
@@ -588,21 +579,9 @@ void PressureSolver::solve_multi(bool zeroPhi, bool forceHomogeneous, std::vecto
         if (zeroPhi) launch_set(st_, phi[c], n, 0.0);
         launch_copy(st_, best[c], phi[c], n);
     }
-    auto tests = [&](State& s) {
-        s.goNorm = s.rnorm > prm.normThresh;
-        s.goRedu = s.rnorm > prm.eps * s.initial;
-        s.goIter = s.iter < prm.imax;
-        s.goHang = s.iter < prm.imin || s.rnorm < (1 - prm.hang) * s.norm_last;
-    };
     const int every[MC_MAX] = {0, 1, 2, 3};
     multi_residual0(nc, every, res, phi, rhs, forceHomogeneous);   // computeAMRResidual(..., a_forceHomogeneous), :1021
-    for (int c = 0; c < nc; ++c) {
-        State& s = S[c];
-        s.initial = s.rnorm = s.best = norm(0, res[c], 0);
-        s.norm_last = 2 * s.initial;
-        out[c].history.push_back(s.rnorm);
-        tests(s);
-    }
+    for (int c = 0; c < nc; ++c) S[c].start(norm(0, res[c], 0), prm);
     for (;;) {
         CompFields F;
         double metric[MC_MAX], *aphi[MC_MAX], *arhs[MC_MAX];
@@ -612,7 +591,7 @@ void PressureSolver::solve_multi(bool zeroPhi, bool forceHomogeneous, std::vecto
             F.comp[i] = c; F.corr[i] = corr[c]; F.res[i] = res[c];
             metric[i] = S[c].initial;   // setConvergenceMetrics(initial_rnorm, cushion * eps), :1047
             aphi[i] = phi[c]; arhs[i] = rhs[c];
-            S[c].norm_last = S[c].rnorm;
+            S[c].begin_cycle();
         }
         if (F.n == 0) break;
         bottom_eps_eff = 1.0 * prm.eps;
@@ -624,44 +603,21 @@ void PressureSolver::solve_multi(bool zeroPhi, bool forceHomogeneous, std::vecto
         else multi_residual0(F.n, F.comp, F.res, aphi, arhs, forceHomogeneous);
         for (int i = 0; i < F.n; ++i) {
             const int c = F.comp[i];
-            State& s = S[c];
-            s.b_iters = B.iters[i];
-            s.b_exit = B.exit[i];
-            s.rnorm = norm(0, res[c], 0);
-            ++s.iter;
-            out[c].history.push_back(s.rnorm);
-            if (s.rnorm <= s.best) {
-                s.best = s.rnorm;
-                launch_copy(st_, best[c], phi[c], n);
-                s.useBest = false;
-                s.converged = true;
-            } else {
-                s.useBest = true;
-            }
-            tests(s);
+            b_iters[c] = B.iters[i];
+            b_exit[c] = B.exit[i];
+            if (S[c].end_cycle(norm(0, res[c], 0), prm)) launch_copy(st_, best[c], phi[c], n);
         }
     }
     // The bottom solver's counts are the solver's, not a solve's: a solve without a cycle reports what the solve before it left
     // -- component after component, starting from the counts on entry (the lock-step loop has long overwritten the members
     // with cycles of later components).
     for (int c = 0; c < nc; ++c) {
-        State& s = S[c];
         SolveStats& o = out[c];
-        if (s.useBest) {
-            s.rnorm = s.best;
-            launch_copy(st_, phi[c], best[c], n);
-        }
-        o.status = 0;
-        if (s.rnorm > 10. * s.initial && s.rnorm > 10. * prm.eps) o.status = 1;                       // "kaboom" :1134
-        else if (!s.converged && s.rnorm >= s.initial && s.rnorm >= prm.eps) o.status = 2;            // :1141
-        o.exitStatus = int(!s.goRedu) + int(!s.goIter) * 2 + int(!s.goHang) * 4 + int(!s.goNorm) * 8;
-        o.iters = s.iter;
-        o.initial_rnorm = s.initial;
-        o.final_rnorm = s.rnorm;
-        if (s.b_iters >= 0) { carry_iters = s.b_iters; carry_exit = s.b_exit; }
+        if (S[c].finish(prm, true, o)) launch_copy(st_, phi[c], best[c], n);
+        if (b_iters[c] >= 0) { carry_iters = b_iters[c]; carry_exit = b_exit[c]; }
         o.bottom_iters_last = carry_iters;
         o.bottom_exit_last = carry_exit;
-        bottom_metric = s.initial;
+        bottom_metric = S[c].initial;
         mc_history_[c] = o.history;
     }
     bottom_iters = carry_iters;
@@ -669,9 +625,8 @@ void PressureSolver::solve_multi(bool zeroPhi, bool forceHomogeneous, std::vecto
     sync();
 }
 
-// heat_step (MappedLevelBackwardEuler / MappedLevelCrankNicolson / MappedLevelTGA ::updateSoln) on every component: one dt and
-// one set_alpha_beta serve all (it scales every component's own pair), so the stages that set the coefficients run component
-// after component between them and the solves go through solve_multi
+// heat_step (MappedLevelBackwardEuler / MappedLevelCrankNicolson / MappedLevelTGA ::updateSoln) on every component: heat_stages
+// with every stage run component after component and the solves going through solve_multi
 void PressureSolver::heat_step_multi(int scheme, double dt, bool zeroPhi, std::vector<SolveStats>& out)
 {
     check_idle("heat_step_multi");
@@ -687,50 +642,12 @@ void PressureSolver::heat_step_multi(int scheme, double dt, bool zeroPhi, std::v
         }
         return;
     }
-    const long long n = lev[0]->field_elems;
-    auto each = [&](auto f) {
-        for (int c = 0; c < nc; ++c) on_comp(c, f);
-    };
-    if (scheme == 0) {
-        each([&]() { launch_copy(st_, f_rhs, heat_field(0), n); });
-        set_alpha_beta(1.0, -dt * 1.0);
-    } else if (scheme == 1) {
-        set_alpha_beta(1.0, 0.5 * dt);
-        each([&]() {
-            apply_op(0, f_scratch[0], heat_field(0), false);
-            launch_copy(st_, f_rhs, heat_field(1), n);
-            launch_scale(st_, f_rhs, dt, n);
-            launch_incr(st_, f_rhs, f_scratch[0], 1.0, n);
-        });
-        set_alpha_beta(1.0, -dt * 0.5);
-    } else {
-        // MappedLevelTGA::updateSolnWithTimeIndependentOp; coefficients as heat_step
-        const double tgaEpsilon = 1.e-12;
-        const double a = 2.0 - std::sqrt(2.0) - tgaEpsilon;
-        const double discr = std::sqrt(a * a - 4.0 * a + 2.0);
-        const double mu1 = (a - discr) / 2.0, mu2 = (a + discr) / 2.0, mu3 = 1.0 - a, mu4 = 0.5 - a;
-        each([&]() {
-            launch_copy(st_, heat_field(2), heat_field(1), n);   // srct = dt * src
-            launch_scale(st_, heat_field(2), dt, n);
-        });
-        set_alpha_beta(1.0, mu4 * dt);
-        each([&]() { apply_op(0, f_rhs, heat_field(2), true); });   // rhst = (I + mu4 dt L) srct, homogeneous BCs
-        set_alpha_beta(1.0, mu3 * dt);
-        each([&]() {
-            apply_op(0, f_scratch[0], heat_field(0), false);         // (I + mu3 dt L) phiOld with the inhomogeneous BCs
-            launch_incr(st_, f_rhs, f_scratch[0], 1.0, n);
-            if (!zeroPhi) launch_copy(st_, heat_field(2), f_phi, n);
-        });
-        set_alpha_beta(1.0, -dt * mu2);
-        const int pre_iters = bottom_iters, pre_exit = bottom_exit;
-        std::vector<SolveStats> first;
-        solve_multi(zeroPhi, false, first);                          // (I - mu2 dt L) phi* = rhst
-        each([&]() {
-            launch_copy(st_, f_rhs, f_phi, n);                       // assign(rhst, phiNew)
-            if (!zeroPhi) launch_copy(st_, f_phi, heat_field(2), n);
-        });
-        set_alpha_beta(1.0, -dt * mu1);                              // (I - mu1 dt L) phiNew = phi*
-        solve_multi(zeroPhi, false, out);
+    const int pre_iters = bottom_iters, pre_exit = bottom_exit;
+    std::vector<SolveStats> first;   // TGA: the statistics of its first solve
+    heat_stages(scheme, dt, zeroPhi,
+                [&](const std::function<void()>& f) { for (int c = 0; c < nc; ++c) on_comp(c, f); },
+                [&](bool last) { solve_multi(zeroPhi, false, last ? out : first); });
+    if (scheme == 2) {
         // the bottom solver's counts a solve without a cycle reports are the ones the solve before it left: component after
         // component that is this component's first solve, then the component before it
         int bi = pre_iters, be = pre_exit;
@@ -742,10 +659,7 @@ void PressureSolver::heat_step_multi(int scheme, double dt, bool zeroPhi, std::v
         }
         bottom_iters = bi;
         bottom_exit = be;
-        sync();
-        return;
     }
-    solve_multi(zeroPhi, false, out);
     sync();
 }
 

@@ -52,7 +52,8 @@ extern "C" {
  * 11: ... + somar_solver_set_bc_face_values (position-dependent Dirichlet values); additions only, so the number stays 11
  * 12: + somar_solver_tuning; the SOMAR_* execution-path variables are read when a solver is created and hold for its life
  * 13: + somar_device_bytes_live; additions only
- * 13: ... + the *_dev entry points (caller arrays in device memory); additions only, so the number stays 13 */
+ * 13: ... + the *_dev entry points (caller arrays in device memory); additions only, so the number stays 13
+ * 13: ... + somar_amr_vd_correction[_host|_dev] and its pieces (the volume-discrepancy correction); additions only */
 #define SOMAR_AMD_ABI_VERSION 13
 
 /* BCType codes, calculus/BCInterface/BCDescriptor.H:34-39 */
@@ -533,6 +534,57 @@ int somar_amr_cc_project(somar_amr_t* a, int l_min, int l_max, double dt, int ze
 int somar_amr_comp_divergence_cc(somar_amr_t* a, int level, int l_max, int out_field, int wall_bc);
 int somar_amr_comp_grad_correct_cc(somar_amr_t* a, int level, int l_max, int phi_field, double dt);
 int somar_amr_average_down_ccvel(somar_amr_t* a, int level);
+
+/* The volume-discrepancy correction (freestream preservation) over levels l_base..l_max -- the third caller of
+ * AMRPressureSolver, run after every sync, after every regrid and on restart when projection.etaLambda > 0:
+ *   AMRNavierStokes::computeVDCorrection                          NavierStokes/AMRNavierStokesSync.cpp:850-1060
+ *   Gradient::levelGradientMAC                                    calculus/DivCurlGrad/Gradient.cpp:85-206
+ *   MappedCoarseAverageFace::averageToCoarse                      MappedChombo/MappedCoarseAverage.cpp:400-520
+ *   UNMAPPEDAVERAGEFACE                                           MappedChombo/MappedCoarseAverageF.ChF:182-237
+ * `a` is the caller's VD hierarchy: a somar_amr_t of its own, created with the VD_AMRMG_* / VD_bottom_* parameters and
+ * Neumann on every non-periodic side (FreestreamCorrFuncBC, BCutil/PhysBCUtil.cpp:1083-1098).
+ * somar_amr_vd_correction, the resident call: the freestream-preservation scalar lambda is resident in SOMAR_F_RHS of levels
+ * l_base..l_max and is CONSUMED -- it is overwritten in place with (lambda - 1.0) * lambda_mult, in that operation order
+ * (:879-880); lambda_mult = etaLambda / dt is formed by the caller.  The reference's lossy restore of lambda (:1046-1055) is
+ * NOT reproduced: keep lambda in your own array.  SOMAR_F_PHI is set to 0 on l_base..l_max, and on l_base - 1 when
+ * l_base > 0 (:903-908); then somar_amr_solve(l_max, l_base, zero_phi = 0, force_homogeneous = 0) (:956) leaves eLambda
+ * in SOMAR_F_PHI; then, from l_max down to l_base (:1001-1044), the MAC gradient of eLambda -- coarse-fine values
+ * interpolated from level l - 1 whenever l > 0 (at l_base > 0: from the zeroed level below), order-2 extrapolation at the
+ * physical boundary -- is stored in the level's resident MAC velocity arrays, the ones somar_vel_download[_dev] reads, and
+ * the finer level's gradient is averaged onto the coarse faces it covers.  The ghost pass of :958-992 and the closing
+ * exchanges of :1032-1040 are not issued: the gradient repeats the first, the second fills ghost faces no download reads.
+ * The averaging: every VALID face of a coarse box that is a face of a coarsened fine box, or of a periodic image of one,
+ * receives (r[dir] / (r0 r1 r2)) * the sum of the fine faces lying on it -- a coarse box's boundary face included when the
+ * coarsened fine box lies wholly in the neighbouring coarse box, and the face at the far side of a periodic direction.
+ * Where two fine boxes supply the same coarse face (they share the fine faces under it), the box LATER in layout order
+ * wins, periodic images last.  This later-box-wins rule is UNPINNED against the reference: it restates the order of
+ * Chombo's Copier motion plan, which is not part of the reference's sources.  With a diagonal metric both boxes hold the
+ * same bits there and the rule cannot matter; with a non-diagonal metric the cross terms read each box's own extrapolated
+ * copy and the two values can differ in the last bits.
+ * The pieces, as the composite projector has them: somar_amr_vd_rhs overwrites SOMAR_F_RHS of one level (:879-880);
+ * somar_amr_comp_gradient_mac is the gradient loop (:1001-1044) on whatever SOMAR_F_PHI holds;
+ * somar_amr_average_down_faces averages level+1's MAC arrays onto level's (:1019-1030).
+ * somar_amr_vd_correction_host / _dev, the call on caller arrays in host / device memory (same rules as
+ * somar_amr_solve_host / _dev: every table, shape and device pointer is checked before anything moves; _dev results equal
+ * _host results bit for bit): lambda[l] / elambda[l] / gradD[l] = one pointer per LOCAL patch of level l, l_base..l_max
+ * (entries of other levels may be NULL).  lambda: over valid.grow(lambda_ghost), read-only, valid cells go up; elambda: over
+ * valid.grow(elambda_ghost), ghost 0..2, written; gradD: over faces(valid, D) without ghosts, written; grad2 may be NULL when
+ * space_dim is 2.
+ * Errors (non-zero return, message in somar_last_error): lambda_mult not finite or zero; a level range that is not
+ * 0 <= l_base <= l_max < levels; a hierarchy that is not finalized; l_base > 0 without level l_base - 1. */
+int somar_amr_vd_correction(somar_amr_t* a, int l_max, int l_base, double lambda_mult, somar_stats_t* stats);
+int somar_amr_vd_rhs(somar_amr_t* a, int level, double lambda_mult);
+int somar_amr_comp_gradient_mac(somar_amr_t* a, int l_max, int l_base);
+int somar_amr_average_down_faces(somar_amr_t* a, int level);
+int somar_amr_vd_correction_host(somar_amr_t* a, const double* const* const* lambda, const int* lambda_ghost,
+                                 double* const* const* elambda, const int* elambda_ghost, double* const* const* grad0,
+                                 double* const* const* grad1, double* const* const* grad2, int l_max, int l_base,
+                                 double lambda_mult, somar_stats_t* stats);
+int somar_amr_vd_correction_dev(somar_amr_t* a, const double* const* const* lambda, const int* lambda_ghost,
+                                double* const* const* elambda, const int* elambda_ghost, double* const* const* grad0,
+                                double* const* const* grad1, double* const* const* grad2, int l_max, int l_base,
+                                double lambda_mult, somar_stats_t* stats);
+
 int somar_amr_residual_level(somar_amr_t* a, int l_max, int l_base, int ilev, int res_field, int phi_field,
                              int rhs_field);
 int somar_amr_zero_covered(somar_amr_t* a, int level, int field);

@@ -166,6 +166,13 @@ _SIGS = {
     "somar_amr_comp_divergence_cc": [_H, C.c_int, C.c_int, C.c_int, C.c_int],
     "somar_amr_comp_grad_correct_cc": [_H, C.c_int, C.c_int, C.c_int, C.c_double],
     "somar_amr_average_down_ccvel": [_H, C.c_int],
+    "somar_amr_vd_correction": [_H, C.c_int, C.c_int, C.c_double, C.POINTER(Stats)],
+    "somar_amr_vd_rhs": [_H, C.c_int, C.c_double],
+    "somar_amr_comp_gradient_mac": [_H, C.c_int, C.c_int],
+    "somar_amr_average_down_faces": [_H, C.c_int],
+    "somar_amr_vd_correction_host": [_H, C.POINTER(C.POINTER(_PD)), _PI, C.POINTER(C.POINTER(_PD)), _PI,
+                                     C.POINTER(C.POINTER(_PD)), C.POINTER(C.POINTER(_PD)), C.POINTER(C.POINTER(_PD)),
+                                     C.c_int, C.c_int, C.c_double, C.POINTER(Stats)],
     "somar_amr_residual_level": [_H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     "somar_amr_zero_covered": [_H, C.c_int, C.c_int],
     "somar_amr_vcycle": [_H, C.c_int, C.c_int],
@@ -222,6 +229,8 @@ _SIGS = {
     "somar_solver_solve_dev": [_H, _PV, _PI, _PV, _PI, C.c_int, C.c_int, C.POINTER(Stats)],
     "somar_amr_solve_dev": [_H, C.POINTER(_PV), _PI, C.POINTER(_PV), _PI, C.c_int, C.c_int, C.c_int, C.c_int,
                             C.POINTER(Stats)],
+    "somar_amr_vd_correction_dev": [_H, C.POINTER(_PV), _PI, C.POINTER(_PV), _PI, C.POINTER(_PV), C.POINTER(_PV),
+                                    C.POINTER(_PV), C.c_int, C.c_int, C.c_double, C.POINTER(Stats)],
     "somar_mac_project_dev": [_H, _PV, _PV, _PV, C.c_double, C.c_int, C.c_int, C.POINTER(Stats)],
     "somar_cc_project_dev": [_H, _PV, _PI, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Stats)],
     "somar_comm_unique_id": [C.POINTER(C.c_ubyte)],
@@ -483,6 +492,54 @@ class AMRPressureSolver:
 
     def averageDownCCVel(self, level):
         _ck(lib().somar_amr_average_down_ccvel(self._amr, level))
+
+    # -- the volume-discrepancy correction: AMRNavierStokes::computeVDCorrection (AMRNavierStokesSync.cpp:850-1060) --------
+    def vdCorrection(self, lmax, lbase, lambdaMult):
+        """lambda resident in F_RHS of levels lbase..lmax (consumed: F_RHS := (lambda - 1.0) * lambdaMult); leaves eLambda in
+        F_PHI and its MAC gradient, averaged down from the finer levels, in the levels' MAC velocity arrays (downloadVel).
+        lambdaMult = etaLambda / dt.  This hierarchy is the caller's VD hierarchy (VD_AMRMG_* / VD_bottom_*, Neumann sides)."""
+        st = Stats()
+        _ck(lib().somar_amr_vd_correction(self._amr, lmax, lbase, float(lambdaMult), C.byref(st)))
+        return self._stats(st)
+
+    def vdRhs(self, level, lambdaMult):
+        _ck(lib().somar_amr_vd_rhs(self._amr, level, float(lambdaMult)))
+
+    def compGradientMAC(self, lmax, lbase):
+        """the gradient loop of vdCorrection on whatever F_PHI holds, lmax down to lbase"""
+        _ck(lib().somar_amr_comp_gradient_mac(self._amr, lmax, lbase))
+
+    def averageDownFaces(self, level):
+        """level's valid faces that are faces of a coarsened box of level + 1 := the average of level + 1's MAC arrays; where
+        two fine boxes supply one coarse face the box later in layout order wins, periodic images last (unpinned)"""
+        _ck(lib().somar_amr_average_down_faces(self._amr, level))
+
+    def vdCorrectionHost(self, lam, eLambda, grad, lmax, lbase, lambdaMult, lambda_ghost=(0, 0, 0), elambda_ghost=(1, 1, 1)):
+        """vdCorrection on host data: lam[l] (read-only) / eLambda[l] / grad[d][l] = list (one per local patch of level l) of
+        Fortran-ordered arrays, or None for levels outside [lbase, lmax]; grad = [g0, g1, g2], g2 None when space_dim is 2.
+        eLambda and grad are filled in place."""
+        nl = len(self.levels)
+        keep = []
+
+        def table(v):
+            if v is None:
+                return None
+            rows = (C.POINTER(_PD) * nl)()
+            for l in range(nl):
+                if v[l] is None:
+                    rows[l] = None
+                    continue
+                assert len(v[l]) == self.levels[l].num_local_patches
+                row = (_PD * max(len(v[l]), 1))(*[_dp(a) for a in v[l]])
+                keep.append(row)
+                rows[l] = row
+            return rows
+
+        st = Stats()
+        _ck(lib().somar_amr_vd_correction_host(self._amr, table(lam), _ia(lambda_ghost), table(eLambda), _ia(elambda_ghost),
+                                               table(grad[0]), table(grad[1]), table(grad[2]), lmax, lbase,
+                                               float(lambdaMult), C.byref(st)))
+        return self._stats(st)
 
     def interpCF(self, level, fine_field=F_PHI, coarse_field=F_PHI):
         _ck(lib().somar_amr_interp_cf(self._amr, level, fine_field, coarse_field))
@@ -1094,6 +1151,37 @@ class AMRPressureSolver:
         st = Stats()
         _ck(lib().somar_amr_solve_dev(self._amr, P, _ia(pg), R, _ia(rg), lmax, lmin, int(zeroPhi), int(forceHomogeneous),
                                       C.byref(st)))
+        return self._stats(st)
+
+    def vdCorrectionDev(self, lam, eLambda, grad, lmax, lbase, lambdaMult, lambda_ghost=(0, 0, 0), elambda_ghost=(1, 1, 1)):
+        """vdCorrectionHost() on device tensors: lam[l] / eLambda[l] / grad[d][l] = list of tensors of level l, or None for
+        levels outside [lbase, lmax]; eLambda and grad are filled in place"""
+        torch = self._dev_ready()
+        lg, eg = self._dev_ghost(lambda_ghost), self._dev_ghost(elambda_ghost)
+        nl = len(self.levels)
+        if len(lam) != nl or len(eLambda) != nl or len(grad) != 3:
+            raise SomarError("lam / eLambda: expected one entry per level (%d); grad: [g0, g1, g2]" % nl)
+        keep = []
+
+        def table(v, what, **shape):
+            if v is None:
+                return None
+            rows = (_PV * nl)()
+            for l in range(nl):
+                if v[l] is None:
+                    rows[l] = None
+                    continue
+                row = self.levels[l]._dev_table(torch, v[l], "%s[%d]" % (what, l), **shape)
+                keep.append(row)
+                rows[l] = C.cast(row, _PV)
+            return rows
+
+        Lm, E = table(lam, "lam", ghost=lg), table(eLambda, "eLambda", ghost=eg)
+        G = [table(grad[d], "grad%d" % d, face=d) for d in range(3)]
+        torch.cuda.current_stream().synchronize()
+        st = Stats()
+        _ck(lib().somar_amr_vd_correction_dev(self._amr, Lm, _ia(lg), E, _ia(eg), G[0], G[1], G[2], lmax, lbase,
+                                              float(lambdaMult), C.byref(st)))
         return self._stats(st)
 
     def levelProjectDev(self, vel, dt, zeroPressure=True, forceHomogeneous=False):

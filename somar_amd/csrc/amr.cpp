@@ -891,6 +891,133 @@ void AMRSolver::cc_project(int l_min, int l_max, double dt, bool zeroPressure, b
     sync();
 }
 
+// ------------------------------------------------------------------------------------
+// The volume-discrepancy correction (AMRNavierStokes::computeVDCorrection, AMRNavierStokesSync.cpp:850-1060)
+// ------------------------------------------------------------------------------------
+// MappedCoarseAverageFace(fineGrids, 1, nRef) across link l (MappedCoarseAverage.cpp:400-520): m_coarsenedFineData lives on
+// the coarsened-fine layout, one array per direction; copyTo onto the coarse level's faces is one Copier per direction.
+void AMRSolver::build_face_avg_tables(int l)
+{
+    AMRLink& K = *links_[l];
+    if (K.favg_built) return;
+    Level& C = S[l - 1]->level(0);
+    Level& cfl = *K.cfl;
+    std::vector<FaceAvgItem> items;
+    for (int d = 0; d < prm.spaceDim; ++d) {
+        K.faceC[d] = cfl.alloc_field();
+        for (int pi = 0; pi < cfl.npatches(); ++pi) {
+            FaceAvgItem it;
+            std::memset(&it, 0, sizeof(it));
+            it.patch = pi;
+            it.dir = d;
+            for (int a = 0; a < 3; ++a) it.n[a] = cfl.hpatches[pi].n[a] + (a == d ? 1 : 0);
+            items.push_back(it);
+        }
+        K.face_scatter[d].define_face_copy(C.domain, C.periodic, cfl, C, d, comm_);
+    }
+    K.nfavg = (int)items.size();
+    K.d_favg = DevBuf<FaceAvgItem>::from(items);
+    SOMAR_HIP(hipDeviceSynchronize());   // the table went up with a plain hipMemcpy (null stream)
+    K.favg_built = true;
+}
+
+void AMRSolver::average_down_faces(int l)
+{
+    SOMAR_CHECK(finalized_, "average_down_faces: the hierarchy is not finalized");
+    SOMAR_CHECK(l >= 0 && l + 1 < nlevels(), "average_down_faces: bad level range (the level has no finer level)");
+    build_face_avg_tables(l + 1);
+    AMRLink& K = *links_[l + 1];
+    const int nd = prm.spaceDim;
+    double* crse[3] = {nullptr, nullptr, nullptr};
+    const double* fine[3] = {nullptr, nullptr, nullptr};
+    for (int d = 0; d < nd; ++d) { crse[d] = K.faceC[d]; fine[d] = S[l + 1]->vel(d); }
+    launch_avg_face_unweighted(st_, K.d_favg, K.nfavg, K.cfl->dev.patches, S[l + 1]->level(0).dev.patches, crse, fine, K.r);
+    for (int d = 0; d < nd; ++d) K.face_scatter[d].run(K.faceC[d], S[l]->vel(d), st_);
+}
+
+void AMRSolver::vd_rhs(int l, double lambda_mult)
+{
+    SOMAR_CHECK(finalized_, "vd_rhs: the hierarchy is not finalized");
+    SOMAR_CHECK(l >= 0 && l < nlevels(), "vd_rhs: bad level range");
+    SOMAR_CHECK(std::isfinite(lambda_mult) && lambda_mult != 0.0, "vd_rhs: lambda_mult (etaLambda / dt) must be finite and non-zero");
+    launch_vd_rhs(st_, S[l]->rhs(), lambda_mult, S[l]->level(0).field_elems);   // frame cells carry no meaning
+}
+
+// The gradient loop of computeVDCorrection (:1001-1044) on the levels' resident PHI: per level, finest first,
+// Gradient::levelGradientMAC (coarse-fine interpolation from level l-1 whenever l > 0 -- also at l_base, :1006; exchange;
+// order-2 extrapolation BC, gradELambdaFuncBC; per-box MAC gradient) into the level's MAC velocity arrays, then the finer
+// level's gradient averaged onto this one (:1019-1030).
+// Not issued: the ghost pass of :958-992 (extrapolation BC + exchange of eLambda) -- the gradient repeats it, and the
+// extrapolated ghosts depend only on the box's own valid cells; the closing exchanges of m_gradELambda (:1032-1040) --
+// they fill ghost faces only, which no download reads.
+void AMRSolver::comp_gradient_mac(int l_max, int l_base)
+{
+    check_idle("comp_gradient_mac");
+    SOMAR_CHECK(finalized_, "comp_gradient_mac: the hierarchy is not finalized");
+    SOMAR_CHECK(0 <= l_base && l_base <= l_max && l_max < nlevels(), "comp_gradient_mac: bad level range");
+    for (int l = l_max; l >= l_base; --l) {
+        PressureSolver& P = *S[l];
+        Level& L = P.level(0);
+        double* phi = P.phi();
+        L.exchange(phi, st_);
+        if (l > 0) interp_cf(l, phi, S[l - 1]->phi());
+        double* const* g = P.mac_grad(phi);
+        for (int d = 0; d < prm.spaceDim; ++d) launch_copy(st_, P.vel(d), g[d], L.field_elems);
+        if (l < l_max) average_down_faces(l);
+    }
+}
+
+void AMRSolver::vd_correction(int l_max, int l_base, double lambda_mult, SolveStats& st)
+{
+    check_idle("vd_correction");
+    SOMAR_CHECK(finalized_, "vd_correction: the hierarchy is not finalized");
+    SOMAR_CHECK(0 <= l_base && l_base <= l_max && l_max < nlevels(), "vd_correction: bad level range");
+    // a hierarchy's levels are contiguous from 0, so level l_base - 1 (zeroed below, the solve's and the gradient's coarse
+    // data) exists whenever l_base > 0
+    SOMAR_CHECK(l_base == 0 || S[l_base - 1], "vd_correction: l_base > 0 needs level l_base - 1 present");
+    SOMAR_CHECK(std::isfinite(lambda_mult) && lambda_mult != 0.0,
+                "vd_correction: lambda_mult (etaLambda / dt) must be finite and non-zero");
+    for (int l = l_base; l <= l_max; ++l) vd_rhs(l, lambda_mult);
+    for (int l = l_base > 0 ? l_base - 1 : 0; l <= l_max; ++l) launch_set(st_, S[l]->phi(), S[l]->level(0).field_elems, 0.0);
+    solve(l_max, l_base, false, false, st);
+    comp_gradient_mac(l_max, l_base);
+    sync();
+}
+
+void AMRSolver::vd_correction_on(PressureSolver::Mem where, const double* const* const* lambda, const int lambda_ghost[3],
+                                 double* const* const* eLambda, const int elambda_ghost[3], double* const* const* const grad[3],
+                                 int l_max, int l_base, double lambda_mult, SolveStats& st)
+{
+    check_idle("vd_correction");
+    SOMAR_CHECK(finalized_, "vd_correction: the hierarchy is not finalized");
+    SOMAR_CHECK(lambda && eLambda && lambda_ghost && elambda_ghost && grad, "null pointer");
+    SOMAR_CHECK(0 <= l_base && l_base <= l_max && l_max < nlevels(), "vd_correction: bad level range");
+    SOMAR_CHECK(std::isfinite(lambda_mult) && lambda_mult != 0.0,
+                "vd_correction: lambda_mult (etaLambda / dt) must be finite and non-zero");
+    const int nd = prm.spaceDim;
+    static const char* const gname[3] = {"grad0", "grad1", "grad2"};
+    for (int d = 0; d < nd; ++d) SOMAR_CHECK(grad[d], std::string(gname[d]) + ": null pointer table");
+    for (int l = l_base; l <= l_max; ++l) {
+        SOMAR_CHECK(lambda[l] && eLambda[l], "lambda / eLambda of a solved level is null");
+        for (int d = 0; d < nd; ++d) SOMAR_CHECK(grad[d][l], std::string(gname[d]) + " of a solved level is null");
+    }
+    for (int l = l_base; l <= l_max; ++l) {   // every table, shape and pointer, before anything moves
+        PressureSolver& ps = level(l);
+        const std::string at = "[" + std::to_string(l) + "]";
+        ps.check_table(where, ps.io_field(ps.rhs(), 0, lambda_ghost, false), lambda[l], ("lambda" + at).c_str());
+        ps.check_table(where, ps.io_field(ps.phi(), 0, elambda_ghost, true), eLambda[l], ("eLambda" + at).c_str());
+        for (int d = 0; d < nd; ++d) ps.check_table(where, ps.io_vel(d), grad[d][l], (gname[d] + at).c_str());
+    }
+    for (int l = l_base; l <= l_max; ++l)
+        level(l).move_table(where, level(l).io_field(level(l).rhs(), 0, lambda_ghost, false), const_cast<double* const*>(lambda[l]), true);
+    vd_correction(l_max, l_base, lambda_mult, st);
+    for (int l = l_base; l <= l_max; ++l) {
+        PressureSolver& ps = level(l);
+        ps.move_table(where, ps.io_field(ps.phi(), 0, elambda_ghost, true), eLambda[l], false);
+        for (int d = 0; d < nd; ++d) ps.move_table(where, ps.io_vel(d), grad[d][l], false);
+    }
+}
+
 void AMRSolver::amr_operator(int l, double* LofPhi, double* phiFine, double* phi, const double* phiCoarse,
                              bool homogeneous)
 {

@@ -67,6 +67,12 @@ struct OneSided {     // one face of CRSEONESIDEGRAD: g[face] = 2 g[face + strid
     int stride;       // signed element stride pointing AWAY from the finer level
     int dirmode;      // dir | mode << 2
 };
+struct FaceAvgItem {  // the face box of one patch of a coarsened-fine layout in one direction (k_avg_face_unweighted)
+    int patch;
+    int dir;
+    int n[3];         // faces per direction: the patch's cells, + 1 along dir
+    int pad_[3];
+};
 struct FillItem {     // a region of one patch
     int patch;
     int lo[3];        // local start
@@ -77,6 +83,11 @@ struct FillItem {     // a region of one patch
 void launch_one_sided(hipStream_t st, const OneSided* e, int n, double* const grad[3]);
 // crse(ic) = (sum over the children of ic of fine) * (1 / prod r): UNMAPPEDAVERAGE (MappedCoarseAverageF.ChF:7-41)
 void launch_avg_unweighted(hipStream_t st, const LevelDev& C, const LevelDev& F, double* crse, const double* fine, const int r[3]);
+// crse[d](face) = (r[d] / prod r) * (sum of the fine d-faces on it), every direction with a non-null pair and every patch of
+// the coarsened-fine layout in one launch: UNMAPPEDAVERAGEFACE (MappedCoarseAverageF.ChF:182-237)
+void launch_avg_face_unweighted(hipStream_t st, const FaceAvgItem* items, int nitems, const PatchDesc* cpatches,
+                                const PatchDesc* fpatches, double* const crse[3], const double* const fine[3], const int r[3]);
+void launch_vd_rhs(hipStream_t st, double* a, double mult, long long n);   // a[i] = (a[i] - 1.0) * mult
 void launch_divide(hipStream_t st, double* a, double d, long long n);   // a[i] = a[i] / d
 void launch_fill_items(hipStream_t st, const PatchDesc* patches, const FillItem* items, int nitems, double* f, double v);
 void launch_cf_slopes(hipStream_t st, const QCoarse* cc, int ncc, const QPoint* pts, const double* buf, double* der,
@@ -139,6 +150,13 @@ struct AMRLink {
     bool osg_built = false;
     DevBuf<OneSided> d_osg;
     std::vector<int> osg_first, osg_count;
+    // MappedCoarseAverageFace across this link (build_face_avg_tables, on first use): the averaged faces of every coarsened
+    // fine box, one array per direction on cfl, and their copy onto the valid faces of the coarse level
+    bool favg_built = false;
+    int nfavg = 0;
+    DevBuf<FaceAvgItem> d_favg;
+    DevBuf<double> faceC[3];
+    Copier face_scatter[3];     // Copier::define_face_copy(cfl -> coarse level, dir)
 };
 
 class AMRSolver {
@@ -207,6 +225,32 @@ public:
     void comp_grad_correct_cc(int l, int l_max, double* phi, double dt);
     void average_down_ccvel(int l);
 
+    // ---- the volume-discrepancy correction (freestream preservation) ------------------------------------------------------
+    //   AMRNavierStokes::computeVDCorrection            NavierStokes/AMRNavierStokesSync.cpp:850-1060
+    //   MappedCoarseAverageFace::averageToCoarse        MappedChombo/MappedCoarseAverage.cpp:400-520
+    //   UNMAPPEDAVERAGEFACE                             MappedChombo/MappedCoarseAverageF.ChF:182-237
+    // lambda is resident in RHS of levels l_base..l_max and is CONSUMED: RHS := (lambda - 1.0) * lambda_mult (:879-880; the
+    // reference's lossy restore, :1046-1055, is not reproduced).  PHI := 0 on l_base..l_max and on l_base - 1 (:903-908);
+    // solve(l_max, l_base, zeroPhi = false, forceHomogeneous = false) (:956) leaves eLambda in PHI; the MAC gradient of eLambda
+    // (:1001-1044) is left in the levels' MAC velocity arrays vel(d), every level's covered faces averaged down from the
+    // finer level.  This hierarchy is the caller's VD hierarchy (VD_AMRMG_* / VD_bottom_* parameters, all-Neumann sides).
+    void vd_correction(int l_max, int l_base, double lambda_mult, SolveStats& st);
+    // the same on caller arrays in host or device memory (one sequence, as solve_on): lambda[l] (read-only; valid cells go up),
+    // eLambda[l] (comes back over valid.grow(elambda_ghost)) and grad[d][l] (faces(valid, d); grad[2] may be null when
+    // space_dim is 2) = HOST arrays of one pointer per local patch of level l, l_base..l_max.  Every table, shape and (device
+    // memory) pointer is checked before anything moves.
+    void vd_correction_on(PressureSolver::Mem where, const double* const* const* lambda, const int lambda_ghost[3],
+                          double* const* const* eLambda, const int elambda_ghost[3], double* const* const* const grad[3],
+                          int l_max, int l_base, double lambda_mult, SolveStats& st);
+    // pieces: RHS of level l := (RHS - 1.0) * lambda_mult; the gradient loop on whatever PHI holds, l_max down to l_base;
+    // the valid faces of level l that are faces of a coarsened box of level l+1 := the average of level l+1's MAC arrays.
+    // Where two fine boxes (or a box and a periodic image) supply the same coarse face, the box LATER in layout order wins,
+    // periodic images last -- UNPINNED against the reference (Chombo's Copier is not part of it); the candidates hold the
+    // same bits when the metric is diagonal.
+    void vd_rhs(int l, double lambda_mult);
+    void comp_gradient_mac(int l_max, int l_base);
+    void average_down_faces(int l);
+
     // pieces (parity tests)
     // interpCFGhosts(phi, &phiCoarse, false); ev = false: MappedQuadCFInterp::coarseFineInterp alone (no ExtrapolateCFEV)
     void interp_cf(int l, double* phiFine, const double* phiCoarse, bool ev = true);
@@ -256,6 +300,7 @@ private:
     void build_quad_tables(int l);
     void build_reflux_tables(int l);
     void build_one_sided_tables(int l);   // link l: the one-sided faces on level l-1
+    void build_face_avg_tables(int l);    // link l: the face average onto level l-1
     const Tuning tune_;
     Comm* comm_;
     Comm self_;

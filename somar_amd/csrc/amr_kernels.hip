@@ -9,6 +9,9 @@
 //   k_fine_register          MappedAMRPoissonOp::reflux (fine loop, MappedAMRPoissonOp.cpp:1676-1701) +
 //                            MAPPEDGETFLUXORTHO + MAPPEDINCREMENTFINE (MappedLevelFluxRegisterF.ChF:9-44)
 //   k_reflux                 incrementCoarse (MappedLevelFluxRegister.cpp:298-347) + reflux (:560-650)
+//   k_avg_face_unweighted    UNMAPPEDAVERAGEFACE (MappedCoarseAverageF.ChF:182-237) per fine box and direction, as
+//                            MappedCoarseAverageFace::averageToCoarse runs it (MappedCoarseAverage.cpp:400-520)
+//   k_vd_rhs                 computeVDCorrection's right-hand side (NavierStokes/AMRNavierStokesSync.cpp:879-880)
 #include "amr.h"
 
 namespace somar {
@@ -330,6 +333,61 @@ void launch_avg_unweighted(hipStream_t st, const LevelDev& C, const LevelDev& F,
     if (C.ntiles == 0) return;
     hipLaunchKernelGGL(k_avg_unweighted, dim3(C.ntiles), dim3(64, C.tile_j, 1), 0, st, C.tiles, C.patches, F.patches, crse,
                        fine, r[0], r[1], r[2]);
+}
+
+// UNMAPPEDAVERAGEFACE (MappedCoarseAverageF.ChF:182-237) as MappedCoarseAverageFace::averageToCoarse runs it per fine box
+// (MappedCoarseAverage.cpp:400-520): every coarse face of faces(coarsen(fineBox, r), dir) := refScale * the sum of the fine faces
+// lying ON it (the refinement box is flat in dir), summed ii0 fastest, then ii1, then ii2.  One item per (patch of the
+// coarsened-fine layout, direction): all directions and patches in one launch; a workgroup row per (j, k), lanes along i,
+// one 8-byte store per lane.  The high face of a box (local index n[dir]) lives in the frame of both layouts.
+__global__ void k_avg_face_unweighted(const FaceAvgItem* __restrict__ items, const PatchDesc* __restrict__ cpatches,
+                                      const PatchDesc* __restrict__ fpatches, G3 crse, JG3 fine, I3 r)
+{
+    const FaceAvgItem it = items[blockIdx.x];
+    const PatchDesc cp = cpatches[it.patch];
+    const PatchDesc fp = fpatches[it.patch];
+    const int d = it.dir;
+    const int r0 = r.v[0], r1 = r.v[1], r2 = r.v[2];
+    const int n0 = d == 0 ? 1 : r0, n1 = d == 1 ? 1 : r1, n2 = d == 2 ? 1 : r2;
+    const double refScale = (double)r.v[d] / (double)(r0 * r1 * r2);
+    double* __restrict__ c = crse.v[d];
+    const double* __restrict__ f = fine.v[d];
+    const int rows = it.n[1] * it.n[2];
+    for (int row = blockIdx.y * blockDim.y + threadIdx.y; row < rows; row += gridDim.y * blockDim.y) {
+        const int lj = row % it.n[1], lk = row / it.n[1];
+        for (int li = threadIdx.x; li < it.n[0]; li += blockDim.x) {
+            double sum = 0.0;
+            for (int o2 = 0; o2 < n2; ++o2)
+                for (int o1 = 0; o1 < n1; ++o1)
+                    for (int o0 = 0; o0 < n0; ++o0) sum = sum + f[pidx(fp, li * r0 + o0, lj * r1 + o1, lk * r2 + o2)];
+            c[pidx(cp, li, lj, lk)] = refScale * sum;
+        }
+    }
+}
+void launch_avg_face_unweighted(hipStream_t st, const FaceAvgItem* items, int nitems, const PatchDesc* cpatches,
+                                const PatchDesc* fpatches, double* const crse[3], const double* const fine[3], const int r[3])
+{
+    if (nitems == 0) return;
+    G3 c;
+    JG3 f;
+    for (int d = 0; d < 3; ++d) { c.v[d] = crse[d]; f.v[d] = fine[d]; }
+    hipLaunchKernelGGL(k_avg_face_unweighted, dim3(nitems, 8), dim3(64, 4), 0, st, items, cpatches, fpatches, c, f, i3(r));
+}
+
+// the volume-discrepancy right-hand side, AMRNavierStokes::computeVDCorrection (AMRNavierStokesSync.cpp:879-880):
+// rhsFAB -= 1.0; rhsFAB *= lambdaMult -- two rounded operations, in that order
+__global__ void k_vd_rhs(double* __restrict__ a, double mult, long long n)
+{
+    const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (i < n) {
+        const double t = a[i] - 1.0;
+        a[i] = t * mult;
+    }
+}
+void launch_vd_rhs(hipStream_t st, double* a, double mult, long long n)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_vd_rhs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, mult, n);
 }
 
 __global__ void k_divide(double* __restrict__ a, double d, long long n)

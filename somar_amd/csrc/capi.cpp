@@ -1482,6 +1482,68 @@ int somar_amr_average_down_ccvel(somar_amr_t* a, int level)
     API_END
 }
 
+// ---- the volume-discrepancy correction: AMRNavierStokes::computeVDCorrection (NavierStokes/AMRNavierStokesSync.cpp:850-1060) ----
+int somar_amr_vd_correction(somar_amr_t* a, int l_max, int l_base, double lambda_mult, somar_stats_t* stats)
+{
+    API_BEGIN
+    SolveStats st;
+    a->amr->vd_correction(l_max, l_base, lambda_mult, st);
+    fill_stats(st, stats);
+    API_END
+}
+
+int somar_amr_vd_rhs(somar_amr_t* a, int level, double lambda_mult)
+{
+    API_BEGIN
+    a->amr->vd_rhs(level, lambda_mult);
+    a->amr->sync();
+    API_END
+}
+
+int somar_amr_comp_gradient_mac(somar_amr_t* a, int l_max, int l_base)
+{
+    API_BEGIN
+    a->amr->comp_gradient_mac(l_max, l_base);
+    a->amr->sync();
+    API_END
+}
+
+int somar_amr_average_down_faces(somar_amr_t* a, int level)
+{
+    API_BEGIN
+    a->amr->average_down_faces(level);
+    a->amr->sync();
+    API_END
+}
+
+int somar_amr_vd_correction_host(somar_amr_t* a, const double* const* const* lambda, const int* lambda_ghost,
+                                 double* const* const* elambda, const int* elambda_ghost, double* const* const* grad0,
+                                 double* const* const* grad1, double* const* const* grad2, int l_max, int l_base,
+                                 double lambda_mult, somar_stats_t* stats)
+{
+    API_BEGIN
+    double* const* const* const grad[3] = {grad0, grad1, grad2};
+    SolveStats st;
+    a->amr->vd_correction_on(PressureSolver::Mem::Host, lambda, lambda_ghost, elambda, elambda_ghost, grad, l_max, l_base,
+                             lambda_mult, st);
+    fill_stats(st, stats);
+    API_END
+}
+
+int somar_amr_vd_correction_dev(somar_amr_t* a, const double* const* const* lambda, const int* lambda_ghost,
+                                double* const* const* elambda, const int* elambda_ghost, double* const* const* grad0,
+                                double* const* const* grad1, double* const* const* grad2, int l_max, int l_base,
+                                double lambda_mult, somar_stats_t* stats)
+{
+    API_BEGIN
+    double* const* const* const grad[3] = {grad0, grad1, grad2};
+    SolveStats st;
+    a->amr->vd_correction_on(PressureSolver::Mem::Device, lambda, lambda_ghost, elambda, elambda_ghost, grad, l_max, l_base,
+                             lambda_mult, st);
+    fill_stats(st, stats);
+    API_END
+}
+
 int somar_amr_level_project(somar_amr_t* a, int level, int centring, double dt, int zero_pressure, int force_homogeneous,
                             int wall_bc, somar_stats_t* stats)
 {

@@ -278,13 +278,42 @@ void Level::define_cf(const double dxCrse[3])
 // ------------------------------------------------------------------------------------
 // Pure host logic.  Items carry GLOBAL box indices; every rank enumerates (dst box, src box, shift) in the
 // same order, so the i-th item of a send message is the i-th item of the matching receive message.
+namespace {
+struct Remote { int peer; CopyItem it; };
+// peers in ascending order, one message per peer: its items in walk order, offsets in doubles
+void layout_messages(ExchangePlan& plan, const std::vector<Remote>& sends, const std::vector<Remote>& recvs)
+{
+    for (auto& r : sends) plan.peers.push_back(r.peer);
+    for (auto& r : recvs) plan.peers.push_back(r.peer);
+    std::sort(plan.peers.begin(), plan.peers.end());
+    plan.peers.erase(std::unique(plan.peers.begin(), plan.peers.end()), plan.peers.end());
+    for (int q : plan.peers) {
+        plan.soff.push_back(plan.send_total);
+        for (auto& r : sends)
+            if (r.peer == q) {
+                plan.send_items.push_back(r.it);
+                plan.send_itemoff.push_back(plan.send_total);
+                plan.send_total += (long long)r.it.n[0] * r.it.n[1] * r.it.n[2];
+            }
+        plan.scount.push_back(plan.send_total - plan.soff.back());
+        plan.roff.push_back(plan.recv_total);
+        for (auto& r : recvs)
+            if (r.peer == q) {
+                plan.recv_items.push_back(r.it);
+                plan.recv_itemoff.push_back(plan.recv_total);
+                plan.recv_total += (long long)r.it.n[0] * r.it.n[1] * r.it.n[2];
+            }
+        plan.rcount.push_back(plan.recv_total - plan.roff.back());
+    }
+}
+}  // namespace
+
 ExchangePlan build_copy_plan(const IBox& domain, const bool periodic[3], const std::vector<IBox>& srcBoxes,
                              const std::vector<int>& srcOwner, const std::vector<IBox>& dstBoxes,
                              const std::vector<int>& dstOwner, const int ghost[3], int myrank, bool ring_only)
 {
     ExchangePlan plan;
     const auto shifts = periodic_shifts(domain, periodic);
-    struct Remote { int peer; CopyItem it; };
     std::vector<Remote> sends, recvs;
     for (size_t di = 0; di < dstBoxes.size(); ++di) {
         const IBox gbox = dstBoxes[di].grow(ghost);
@@ -328,29 +357,76 @@ ExchangePlan build_copy_plan(const IBox& domain, const bool periodic[3], const s
             }
         }
     }
-    for (auto& r : sends) plan.peers.push_back(r.peer);
-    for (auto& r : recvs) plan.peers.push_back(r.peer);
-    std::sort(plan.peers.begin(), plan.peers.end());
-    plan.peers.erase(std::unique(plan.peers.begin(), plan.peers.end()), plan.peers.end());
-    for (int q : plan.peers) {
-        plan.soff.push_back(plan.send_total);
-        for (auto& r : sends)
-            if (r.peer == q) {
-                plan.send_items.push_back(r.it);
-                plan.send_itemoff.push_back(plan.send_total);
-                plan.send_total += (long long)r.it.n[0] * r.it.n[1] * r.it.n[2];
-            }
-        plan.scount.push_back(plan.send_total - plan.soff.back());
-        plan.roff.push_back(plan.recv_total);
-        for (auto& r : recvs)
-            if (r.peer == q) {
-                plan.recv_items.push_back(r.it);
-                plan.recv_itemoff.push_back(plan.recv_total);
-                plan.recv_total += (long long)r.it.n[0] * r.it.n[1] * r.it.n[2];
-            }
-        plan.rcount.push_back(plan.recv_total - plan.roff.back());
-    }
+    layout_messages(plan, sends, recvs);
     return plan;
+}
+
+// Face-centred data of direction `dir` between two layouts.  For one destination box the candidate sources are walked from
+// the LAST in priority order (periodic images after unshifted boxes, within each the layout order) to the first, and each
+// takes only what no later one has taken: every destination face is written by exactly one item -- the later box wins --
+// whatever order the items run in.
+ExchangePlan build_face_copy_plan(const IBox& domain, const bool periodic[3], const std::vector<IBox>& srcBoxes,
+                                  const std::vector<int>& srcOwner, const std::vector<IBox>& dstBoxes,
+                                  const std::vector<int>& dstOwner, int dir, int myrank)
+{
+    ExchangePlan plan;
+    const auto shifts = periodic_shifts(domain, periodic);   // the unshifted image first
+    std::vector<Remote> sends, recvs;
+    for (size_t di = 0; di < dstBoxes.size(); ++di) {
+        IBox dface = dstBoxes[di];
+        dface.hi[dir] += 1;
+        std::vector<IBox> taken;
+        for (size_t shi = shifts.size(); shi-- > 0;) {
+            const auto& sh = shifts[shi];
+            for (size_t si = srcBoxes.size(); si-- > 0;) {
+                IBox sface = srcBoxes[si];
+                sface.hi[dir] += 1;
+                const IBox r0 = dface & sface.shift(sh.data());
+                if (r0.empty()) continue;
+                std::vector<IBox> pieces{r0};
+                for (const IBox& t : taken) {
+                    std::vector<IBox> nxt;
+                    for (const IBox& c : pieces) box_subtract(c, t, nxt);
+                    pieces.swap(nxt);
+                }
+                taken.push_back(r0);
+                const bool dl = dstOwner[di] == myrank, sl = srcOwner[si] == myrank;
+                if (!dl && !sl) continue;
+                for (const IBox& r : pieces) {
+                    CopyItem it;
+                    std::memset(&it, 0, sizeof(it));
+                    it.src_patch = (int)si;
+                    it.dst_patch = (int)di;
+                    for (int d = 0; d < 3; ++d) {
+                        it.n[d] = r.size(d);
+                        it.dst_lo[d] = r.lo[d] - dstBoxes[di].lo[d];
+                        it.src_lo[d] = r.lo[d] - sh[d] - srcBoxes[si].lo[d];
+                    }
+                    if (dl && sl) plan.local.push_back(it);
+                    else if (sl) sends.push_back({dstOwner[di], it});
+                    else recvs.push_back({srcOwner[si], it});
+                }
+            }
+        }
+    }
+    layout_messages(plan, sends, recvs);
+    return plan;
+}
+
+void Copier::define_face_copy(const IBox& domain, const bool periodic[3], const Level& src, const Level& dst, int dir, Comm* comm)
+{
+    src_ = &src;
+    dst_ = &dst;
+    comm_ = comm;
+    SOMAR_CHECK(dir >= 0 && dir < 3, "face copy: bad direction");
+    plan = build_face_copy_plan(domain, periodic, src.boxes, src.owner, dst.boxes, dst.owner, dir, comm ? comm->rank : 0);
+    std::vector<int> sp(src.boxes.size(), -1), dp(dst.boxes.size(), -1);
+    for (int pi = 0; pi < (int)src.local.size(); ++pi) sp[src.local[pi]] = pi;
+    for (int pi = 0; pi < (int)dst.local.size(); ++pi) dp[dst.local[pi]] = pi;
+    for (CopyItem& it : plan.local) { it.src_patch = sp[it.src_patch]; it.dst_patch = dp[it.dst_patch]; }
+    for (CopyItem& it : plan.send_items) it.src_patch = sp[it.src_patch];
+    for (CopyItem& it : plan.recv_items) it.dst_patch = dp[it.dst_patch];
+    upload_tables();
 }
 
 void Copier::define(const IBox& domain, const bool periodic[3], const Level& src, const Level& dst, const int ghost[3],

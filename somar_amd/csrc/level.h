@@ -312,6 +312,11 @@ public:
     void define_allgather(const Level& src, const Level& dst, int grow, Comm* comm);
     void define_faces(const IBox& domain, const bool periodic[3], const Level& L, int dir, const int ghost[3],
                       Comm* comm);
+    // Face-centred data of direction `dir` from one layout onto another (LevelData<FluxBox>::copyTo, one direction): every
+    // face of faces(dst box, dir) that is a face of faces(src box, dir), or of a periodic image of it, receives that value.
+    // A face several sources supply is written ONCE, by the source box later in layout order, periodic images last; every
+    // rank derives the same pieces in the same order, so sends and receives pair up.
+    void define_face_copy(const IBox& domain, const bool periodic[3], const Level& src, const Level& dst, int dir, Comm* comm);
     void run(const double* s, double* d, hipStream_t st) const;
     ExchangePlan plan;
 
@@ -328,6 +333,9 @@ private:
 ExchangePlan build_copy_plan(const IBox& domain, const bool periodic[3], const std::vector<IBox>& srcBoxes,
                              const std::vector<int>& srcOwner, const std::vector<IBox>& dstBoxes,
                              const std::vector<int>& dstOwner, const int ghost[3], int myrank, bool ring_only = false);
+ExchangePlan build_face_copy_plan(const IBox& domain, const bool periodic[3], const std::vector<IBox>& srcBoxes,
+                                  const std::vector<int>& srcOwner, const std::vector<IBox>& dstBoxes,
+                                  const std::vector<int>& dstOwner, int dir, int myrank);
 // every rank gets every box (grown): items carry GLOBAL box indices on both sides
 ExchangePlan build_allgather_plan(const std::vector<IBox>& boxes, const std::vector<int>& owner, int grow, int myrank,
                                   int nranks);

@@ -53,7 +53,8 @@ extern "C" {
  * 12: + somar_solver_tuning; the SOMAR_* execution-path variables are read when a solver is created and hold for its life
  * 13: + somar_device_bytes_live; additions only
  * 13: ... + the *_dev entry points (caller arrays in device memory); additions only, so the number stays 13
- * 13: ... + somar_amr_vd_correction[_host|_dev] and its pieces (the volume-discrepancy correction); additions only */
+ * 13: ... + somar_amr_vd_correction[_host|_dev] and its pieces (the volume-discrepancy correction); additions only
+ * 13: ... + somar_solver_set_neum_face_values (position-dependent Neumann values, diagonal metric); additions only */
 #define SOMAR_AMD_ABI_VERSION 13
 
 /* BCType codes, calculus/BCInterface/BCDescriptor.H:34-39 */
@@ -168,6 +169,40 @@ int somar_solver_set_bc_values(somar_solver_t* s, const double* values6);
  * functors such as HorizConvBCUtil's topBCValueFunc); change them between steps.  somar_leptic_solve and
  * somar_amr_solve_leptic refuse a level with a face-valued side. */
 int somar_solver_set_bc_face_values(somar_solver_t* s, int dir, int side, const double* values);
+/* Position-dependent values of one Neumann side of a solver with a DIAGONAL metric: EllipticNeumBCGhostClass and
+ * EllipticNeumBCFluxClass (BCInterface/EllipticBCUtils.cpp:696-947), whose functor gives one value per boundary face.
+ *   values:  the layout of somar_solver_set_bc_face_values: one double per boundary face of side (dir, side) over the
+ *            level's WHOLE domain box, Fortran order over the two transverse directions in increasing order (space_dim 2:
+ *            a line); each entry is what the reference functor returns at pos[d] = (fc[d] + offset[d]) * dx[d],
+ *            offset[dir] = 0, else 0.5.
+ *   meaning: value = J g^{dd} dphi/dxi_d at the face, on BOTH sides.  It is not the outward-normal flux: a positive value
+ *            on the low side is a flux INTO the domain.
+ *   ghost:   near + ((sgn * dx[dir]) * value) / Jg^{dir,dir}(boundary face), sgn = +1 high, -1 low, evaluated in that order
+ *            (EllipticBCUtils.cpp:842-843 with the cross term zero, as it is on a diagonal metric); homogeneous: near, the
+ *            ghost of the folded "no flux" face.
+ *   flux:    the flux through the boundary face is the value itself (EllipticNeumBCFluxClass, :861-947): the operator takes
+ *            it as it stands, not the difference quotient of the ghost, which equals it only up to rounding.
+ *   NULL:    the side returns to zero Neumann.
+ * Refused (non-zero return, somar_last_error, nothing changed): a side that is not SOMAR_BC_NEUM, a periodic or inactive
+ * direction, dir not in 0..2, side not 0 / 1, a solver with a non-diagonal metric (somar_solver_set_metric_full and the
+ * non-diagonal maps; they in turn refuse a solver that already has such a side).  The reference's two Neumann ghost rules
+ * differ in the sign of the cross term on the high side, so a face-valued side there is not defined by them.
+ * May be called before or after somar_solver_finalize; after it the call only copies into the existing device buffers (no
+ * rebuild, no reallocation, addresses unchanged).  Each rank keeps the slices its own patches touch.  On AMR level handles
+ * (somar_amr_level) each level takes its own plane at its own resolution.
+ * The values enter where the position-dependent Dirichlet values do and nowhere else: the outer residuals of
+ * somar_solver_solve[_host|_dev] / somar_amr_solve[_host|_dev] unless force_homogeneous is set, somar_level_apply_op_bc /
+ * somar_level_residual_bc with homogeneous = 0, the explicit operator applications of somar_heat_step /
+ * somar_amr_heat_step / somar_amr_tga_step, and the boundary faces somar_heat_flux_download returns after
+ * somar_amr_heat_step.  somar_amr_residual_level is homogeneous in the physical boundary values, as it is for Dirichlet ones.
+ * Relaxation, corrections, every coarser depth and the bottom solver see zero.  With several components the planes belong
+ * to the solver's own sides (component 0 and every component without an operator of its own); somar_comp_set_op takes
+ * constants only.
+ * Limits: as for the Dirichlet values, one set serves every stage of a heat step (the reference evaluates the functor at
+ * a_time); change them between steps.  somar_leptic_solve and somar_amr_solve_leptic refuse a level with a face-valued side.
+ * A constant Neumann value other than zero (EllipticConstNeumBC*Class, whose setSideNeumBC ignores a_homogeneous and so
+ * enters corrections too, EllipticBCUtils.cpp:128-214) is not offered: pass a constant plane. */
+int somar_solver_set_neum_face_values(somar_solver_t* s, int dir, int side, const double* values);
 /* Non-diagonal metric (LevelGeometry::isDiagonal() == false): jgD holds J g^{Db}, b = 0..2, over faces(valid, D),
  * component slowest (the FluxBox layout of LevelGeometry::getFCJgupPtr).  Selects the 19-point kernels
  * (GSRBITER3D, GSRBBOUNDARYITER3D, MAPPEDGETFLUX, fillExtrap / ExtrapolateFaceAndCopy, the cross-term Neumann

@@ -77,6 +77,7 @@ _SIGS = {
     "somar_solver_set_metric_full": [_H, C.c_int, _PD, _PD, _PD, _PD],
     "somar_solver_set_bc_values": [_H, _PD],
     "somar_solver_set_bc_face_values": [_H, C.c_int, C.c_int, _PD],
+    "somar_solver_set_neum_face_values": [_H, C.c_int, C.c_int, _PD],
     "somar_solver_finalize": [_H],
     "somar_solver_depth": [_H, _PI],
     "somar_solver_mg_ref_ratio": [_H, C.c_int, _PI],
@@ -576,6 +577,16 @@ class AMRPressureSolver:
             return
         a = np.asfortranarray(np.asarray(values, dtype=np.float64))
         _ck(lib().somar_solver_set_bc_face_values(self._h, int(dir), int(side), _dp(a)))
+
+    def setNeumFaceValues(self, dir, side, values):
+        """position-dependent values of the Neumann side (dir, side) on a diagonal metric (EllipticNeumBCGhostClass /
+        EllipticNeumBCFluxClass): a plane laid out as setBCFaceValues', each value J g^{dd} dphi/dxi_d at its face (on both
+        sides: positive on the low side is a flux into the domain); None restores zero Neumann.  Before or after finalize."""
+        if values is None:
+            _ck(lib().somar_solver_set_neum_face_values(self._h, int(dir), int(side), None))
+            return
+        a = np.asfortranarray(np.asarray(values, dtype=np.float64))
+        _ck(lib().somar_solver_set_neum_face_values(self._h, int(dir), int(side), _dp(a)))
 
     def heatFlux(self, dir, patch):
         """a_flux of the last heat step(s) on faces(valid, dir) of one local patch"""

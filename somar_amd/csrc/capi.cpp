@@ -422,12 +422,20 @@ int somar_solver_set_bc_face_values(somar_solver_t* s, int dir, int side, const 
     API_END
 }
 
+int somar_solver_set_neum_face_values(somar_solver_t* s, int dir, int side, const double* values)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps, "null argument");
+    SOMAR_CHECK(dir >= 0 && dir < 3 && (side == 0 || side == 1), "somar_solver_set_neum_face_values: dir must be 0..2 and side 0 (low) or 1 (high)");
+    s->ps->set_neum_face_values(dir, side, values);
+    API_END
+}
+
 int somar_solver_set_metric_full(somar_solver_t* s, int patch, const double* jg0, const double* jg1, const double* jg2,
                                  const double* jinv)
 {
     API_BEGIN
-    SOMAR_CHECK(jg0 && jg1 && jinv && (jg2 || s->ps->prm.spaceDim == 2), "null metric pointer");
-    s->ps->set_metric_full(patch, jg0, jg1, jg2, jinv);
+    SOMAR_CHECK(jg0 && jg1 && jinv && (jg2 || s->ps->prm.spaceDim == 2), "null metric pointer");    s->ps->set_metric_full(patch, jg0, jg1, jg2, jinv);
     API_END
 }
 

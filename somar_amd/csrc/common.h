@@ -106,7 +106,8 @@ struct CFCell {
 
 // One step of a ghost "program" of the non-diagonal (19-point) path (full19.hip): a region of one patch.
 // GHOST_DIRI_FACE: a Dirichlet side with one value per boundary face (EllipticDiriBCGhostClass) instead of one per side
-enum { GHOST_COPY = 0, GHOST_EXTRAP = 1, GHOST_NEUM = 2, GHOST_DIRI = 3, GHOST_DIRI_FACE = 4 };
+// GHOST_NEUM_FACE: a Neumann side of a DIAGONAL-metric level with one value per boundary face (EllipticNeumBCGhostClass)
+enum { GHOST_COPY = 0, GHOST_EXTRAP = 1, GHOST_NEUM = 2, GHOST_DIRI = 3, GHOST_DIRI_FACE = 4, GHOST_NEUM_FACE = 5 };
 __host__ __device__ inline bool ghost_is_diri(int type) { return type == GHOST_DIRI || type == GHOST_DIRI_FACE; }
 struct GhostOp {
     int patch, type;
@@ -120,8 +121,8 @@ struct GhostOp {
     int stage;
     union {
         double val;      // DIRI: the boundary value of that side
-        long long voff;  // DIRI_FACE: start of this op's slice of the level's face-value buffer (LevelDev::bc_face), one
-                         // value per cell of the region in the op's own loop order (i fastest)
+        long long voff;  // DIRI_FACE / NEUM_FACE: start of this op's slice of the level's face-value buffer (LevelDev::bc_face),
+                         // one value per cell of the region in the op's own loop order (i fastest)
     };
 };
 __host__ __device__ inline int ghost_stage(int packed) { return packed & 0xffff; }

@@ -82,6 +82,19 @@ __device__ __forceinline__ void ghost_op_body(const GhostOp& op, const PatchDesc
             const long long s = op.sgn * st[op.dir];
             if (P.bc_homog) dst[c] = -src[c - s];
             else dst[c] = (-src[c - s]) + T(2.0) * T(bcf[op.voff + idx]);
+        } else if (op.type == GHOST_NEUM_FACE) {
+            // EllipticNeumBCGhostClass on a DIAGONAL metric (EllipticBCUtils.cpp:842-843, the cross term being zero):
+            // ghost = first valid + ((sgn dx) g(face)) / Jg^{dd}(boundary face), in that order.  Homogeneous: the first valid
+            // cell's value, the ghost of a zero flux.  The coefficient comes from the level's own array, or from
+            // StencilParams::uc on a uniform-metric depth.
+            const long long sd = st[op.dir];
+            const long long s = op.sgn * sd;
+            if (P.bc_homog) dst[c] = src[c - s];
+            else {
+                const long long f = (op.sgn < 0) ? c + sd : c;   // boundary face (index of the cell it is the low face of)
+                const double jg = P.uniform ? P.uc[op.dir] : J.c[op.dir][op.dir][f];
+                dst[c] = src[c - s] + T(((op.sgn * P.dx[op.dir]) * bcf[op.voff + idx]) / jg);
+            }
         } else {  // GHOST_NEUM: phi ghost such that the boundary flux (cross terms from psi included) equals bcval = 0
             const int a = op.dir, b = (a + 1) % 3, cc = (a + 2) % 3;
             const long long sa = st[a], sb = st[b], sc = st[cc];
@@ -376,6 +389,9 @@ static JgFull jgfull(const LevelDev& L)
     JgFull J;
     for (int d = 0; d < 3; ++d)
         for (int c = 0; c < 3; ++c) J.c[d][c] = L.jgf[d][c];
+    // a diagonal-metric level keeps no jgf: its GHOST_NEUM_FACE ops read J g^{dd} through the same table
+    for (int d = 0; d < 3; ++d)
+        if (!J.c[d][d]) J.c[d][d] = L.jg[d];
     return J;
 }
 

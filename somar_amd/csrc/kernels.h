@@ -31,8 +31,8 @@ struct LevelDev {
     // non-diagonal metric: all components J g^{ab} on a-faces, jgf[a][b]; jgf[a][a] aliases jg[a]
     double* jgf[3][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     StencilParams P;
-    // position-dependent Dirichlet values of this level (depth 0 only): the slices GHOST_DIRI_FACE ops read at GhostOp::voff
-    // (PressureSolver::build_face_slices); the address never changes after finalize
+    // position-dependent Dirichlet / Neumann values of this level (depth 0 only): the slices GHOST_DIRI_FACE / GHOST_NEUM_FACE
+    // ops read at GhostOp::voff (PressureSolver::build_face_slices); the address never changes after finalize
     const double* bc_face = nullptr;
     // what the launchers take from the solver's Tuning (Level::define copies it here)
     int fused_rows = 16;                // region rows per workgroup of the fused 7-point sweep (tile rows = rows - 4): 16 or 8
@@ -142,6 +142,13 @@ void launch_line_gsrb_ortho(hipStream_t st, TileSpan ctiles, int tile_j, const L
                             double* phi, const double* rhs, double* dmod, int color, const double* psi = nullptr);
 void launch_op_ortho(hipStream_t st, const LevelDev& L, double* out, const double* phi, const double* rhs, int mode,
                      bool pull = false);
+// Face-valued Neumann sides of a diagonal-metric level (ops: its GHOST_NEUM_FACE ops; foff[6 * patch + 2 * dir + side]: the
+// start of that patch's slice of L.bc_face, -1 where there is none).  The cells next to those sides evaluated again with the
+// planes' values as their boundary fluxes (mode as launch_op_ortho), over the result an operator launch left in out ...
+void launch_op_neum_face(hipStream_t st, const LevelDev& L, const GhostOp* ops, int nops, const long long* foff, double* out,
+                         const double* phi, const double* rhs, int mode);
+// ... and the planes' values into the boundary faces of a face-centred field (flux[a]: direction a, null: skipped)
+void launch_set_neum_faces(hipStream_t st, const LevelDev& L, const GhostOp* ops, int nops, double* const flux[3]);
 void launch_lapdiag(hipStream_t st, const LevelDev& L);
 void launch_diag(hipStream_t st, const LevelDev& L, double* phi, const double* r, int mode);
 void launch_restrict(hipStream_t st, const LevelDev& C, const LevelDev& F, double* crse, const double* fine,

@@ -296,6 +296,93 @@ __global__ __launch_bounds__(512) void k_op_ortho(const Tile* __restrict__ tiles
 }
 
 // ------------------------------------------------------------------------------------
+// Face-valued Neumann sides (EllipticNeumBCFluxClass, BCInterface/EllipticBCUtils.cpp:861-947): in the inhomogeneous operator
+// the flux through a boundary face of such a side is the plane's value ITSELF, not the difference quotient of the ghost
+// EllipticNeumBCGhostClass wrote (which equals it only up to rounding).  The operator kernels above keep folding every Neumann
+// face in as "no flux"; this kernel then evaluates the cells next to the face-valued sides again -- op_ortho_body's expression,
+// the same operations in the same order, with the plane's value in the place of the zero -- and overwrites their result.
+// One block row per GHOST_NEUM_FACE op (the ghost layer of one patch on one side); the cell a thread owns is the ghost cell's
+// first valid neighbour.  foff[6 * patch + 2 * dir + side]: where that patch's slice of bcf starts, -1 where the side is not
+// face-valued Neumann or the patch does not touch it; a cell in an edge or corner of the domain takes every such side it
+// touches, and is written by each of their ops with the same bits.
+// ------------------------------------------------------------------------------------
+template <int MODE>
+__global__ __launch_bounds__(256) void k_op_neum_face(const GhostOp* __restrict__ ops, const PatchDesc* __restrict__ patches,
+                                                      const long long* __restrict__ foff, const double* __restrict__ bcf,
+                                                      double* __restrict__ out, const double* __restrict__ phi,
+                                                      const double* __restrict__ rhs, const double* __restrict__ jgx,
+                                                      const double* __restrict__ jgy, const double* __restrict__ jgz,
+                                                      const double* __restrict__ jinv, StencilParams P)
+{
+    const GhostOp op = ops[blockIdx.x];
+    const PatchDesc p = patches[op.patch];
+    const long long* fo = foff + 6 * (long long)op.patch;
+    const int n0 = op.n[0], n01 = op.n[0] * op.n[1];
+    const int cells = n01 * op.n[2];
+    const double sx = 1.0 / P.dx[0], sy = 1.0 / P.dx[1], sz = 1.0 / P.dx[2];
+    const long long sj = p.pj, sk = p.pk;
+    for (int idx = blockIdx.y * blockDim.x + threadIdx.x; idx < cells; idx += gridDim.y * blockDim.x) {
+        const int k = idx / n01;
+        const int r = idx - k * n01;
+        const int j = r / n0, i = r - j * n0;
+        int l[3] = {op.lo[0] + i, op.lo[1] + j, op.lo[2] + k};
+        l[op.dir] -= op.sgn;   // from the ghost cell to the first valid one
+        const int gi = p.lo[0] + l[0], gj = p.lo[1] + l[1], gk = p.lo[2] + l[2];
+        const long long c = cidx(p, l[0], l[1], l[2]);
+        const double pc = phi[c];
+        double fxl = jgx[c] * sx * (pc - phi[c - 1]);
+        double fxh = jgx[c + 1] * sx * (phi[c + 1] - pc);
+        double fyl = jgy[c] * sy * (pc - phi[c - sj]);
+        double fyh = jgy[c + sj] * sy * (phi[c + sj] - pc);
+        double fzl = 0.0, fzh = 0.0;
+        if (P.active[2]) {
+            fzl = jgz[c] * sz * (pc - phi[c - sk]);
+            fzh = jgz[c + sk] * sz * (phi[c + sk] - pc);
+        }
+        if ((gi == P.dom_lo[0]) && P.neum[0][0]) fxl = 0.0;
+        if ((gi == P.dom_hi[0]) && P.neum[0][1]) fxh = 0.0;
+        if ((gj == P.dom_lo[1]) && P.neum[1][0]) fyl = 0.0;
+        if ((gj == P.dom_hi[1]) && P.neum[1][1]) fyh = 0.0;
+        if ((gk == P.dom_lo[2]) && P.neum[2][0]) fzl = 0.0;
+        if ((gk == P.dom_hi[2]) && P.neum[2][1]) fzh = 0.0;
+        // a slice holds its side's values over the patch's transverse extent, the lower transverse direction fastest
+        if (fo[0] >= 0 && l[0] == 0) fxl = bcf[fo[0] + l[1] + (long long)p.n[1] * l[2]];
+        if (fo[1] >= 0 && l[0] == p.n[0] - 1) fxh = bcf[fo[1] + l[1] + (long long)p.n[1] * l[2]];
+        if (fo[2] >= 0 && l[1] == 0) fyl = bcf[fo[2] + l[0] + (long long)p.n[0] * l[2]];
+        if (fo[3] >= 0 && l[1] == p.n[1] - 1) fyh = bcf[fo[3] + l[0] + (long long)p.n[0] * l[2]];
+        if (fo[4] >= 0 && l[2] == 0) fzl = bcf[fo[4] + l[0] + (long long)p.n[0] * l[1]];
+        if (fo[5] >= 0 && l[2] == p.n[2] - 1) fzh = bcf[fo[5] + l[0] + (long long)p.n[0] * l[1]];
+        fxl *= P.beta; fxh *= P.beta; fyl *= P.beta; fyh *= P.beta; fzl *= P.beta; fzh *= P.beta;
+        double lp = P.active[2] ? jinv[c] * ((fxh - fxl) * sx + (fyh - fyl) * sy + (fzh - fzl) * sz)
+                                : jinv[c] * ((fxh - fxl) * sx + (fyh - fyl) * sy);  // MAPPEDFLUXDIVERGENCE2D
+        if (P.alpha != 0.0) lp = P.alpha * pc + 1.0 * lp;
+        out[c] = (MODE == 0) ? (rhs[c] - lp) : lp;
+    }
+}
+
+// the boundary faces of the face-valued Neumann sides of a face-centred field := the planes' values (what
+// EllipticNeumBCFluxClass puts there); flux[a]: the field of direction a, cell c holding its low face
+struct FaceFields { double* v[3]; };
+__global__ __launch_bounds__(256) void k_set_neum_faces(const GhostOp* __restrict__ ops, const PatchDesc* __restrict__ patches,
+                                                        const double* __restrict__ bcf, FaceFields flux)
+{
+    const GhostOp op = ops[blockIdx.x];
+    const PatchDesc p = patches[op.patch];
+    double* f = flux.v[op.dir];
+    if (!f) return;
+    const int n0 = op.n[0], n01 = op.n[0] * op.n[1];
+    const int cells = n01 * op.n[2];
+    for (int idx = blockIdx.y * blockDim.x + threadIdx.x; idx < cells; idx += gridDim.y * blockDim.x) {
+        const int k = idx / n01;
+        const int r = idx - k * n01;
+        const int j = r / n0, i = r - j * n0;
+        int l[3] = {op.lo[0] + i, op.lo[1] + j, op.lo[2] + k};
+        if (op.sgn < 0) l[op.dir] += 1;   // the low side's boundary face is the low face of the first valid cell
+        f[cidx(p, l[0], l[1], l[2])] = bcf[op.voff + idx];
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // lapDiag fill (setup).  FILLMAPPEDLAPDIAG3D
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(512) void k_lapdiag(const Tile* __restrict__ tiles,
@@ -1060,6 +1147,24 @@ void launch_op_ortho(hipStream_t st, const LevelDev& L, double* out, const doubl
     else
         hipLaunchKernelGGL(k_op_ortho<1>, dim3(L.ntiles), tile_block(L), 0, st, L.tiles, L.patches, out, phi,
                            rhs, L.jg[0], L.jg[1], L.jg[2], L.jinv, L.P, ti, ts);
+}
+void launch_op_neum_face(hipStream_t st, const LevelDev& L, const GhostOp* ops, int nops, const long long* foff, double* out,
+                         const double* phi, const double* rhs, int mode)
+{
+    if (nops == 0) return;
+    if (mode == 0)
+        hipLaunchKernelGGL(k_op_neum_face<0>, dim3(nops, L.ghost_gy), dim3(256), 0, st, ops, L.patches, foff, L.bc_face, out, phi,
+                           rhs, L.jg[0], L.jg[1], L.jg[2], L.jinv, L.P);
+    else
+        hipLaunchKernelGGL(k_op_neum_face<1>, dim3(nops, L.ghost_gy), dim3(256), 0, st, ops, L.patches, foff, L.bc_face, out, phi,
+                           rhs, L.jg[0], L.jg[1], L.jg[2], L.jinv, L.P);
+}
+void launch_set_neum_faces(hipStream_t st, const LevelDev& L, const GhostOp* ops, int nops, double* const flux[3])
+{
+    if (nops == 0) return;
+    FaceFields F;
+    for (int a = 0; a < 3; ++a) F.v[a] = flux[a];
+    hipLaunchKernelGGL(k_set_neum_faces, dim3(nops, L.ghost_gy), dim3(256), 0, st, ops, L.patches, L.bc_face, F);
 }
 void launch_lapdiag(hipStream_t st, const LevelDev& L)
 {

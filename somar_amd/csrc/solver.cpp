@@ -410,7 +410,8 @@ void PressureSolver::finalize()
         v->clear();
         v->resize(D);
     }
-    if (diri_) build_face_slices();   // before the op lists of depth 0, which take their slices from it
+    if (full_) refuse_full_with_neum_faces("finalize");
+    build_face_slices();   // before the op lists of depth 0, which take their slices from it
     if (full_) {
         SOMAR_CHECK(prm.relaxMode == RELAX_LEVEL_GSRB || prm.relaxMode == RELAX_JACOBI || prm.relaxMode == RELAX_LINE_GSRB,
                     "the non-diagonal metric path offers LevelGSRB, LineGSRB and Jacobi");
@@ -428,6 +429,7 @@ void PressureSolver::finalize()
     n_diri_ops_.assign(D, 0);
     if (diri_)
         for (int d = 0; d < D; ++d) build_diri_ops(d);
+    build_neum_ops();
     for (int d = 0; d < D; ++d) {
         if (d > 0) { f_res[d] = lev[d]->alloc_field(); f_corr[d] = lev[d]->alloc_field(); }
         f_scratch[d] = lev[d]->alloc_field();
@@ -1168,6 +1170,10 @@ void PressureSolver::operator_i(int d, int mode, double* out, double* phi, const
     const bool pull = !full_ && L.pull_ready() && !ortho_march(d);
     if (!pull) xchg(L, phi);  // exchangeComplete, MappedAMRPoissonOp.cpp:2222-2238
     if (diri_ && !full_) apply_diri(d, phi, homogeneous);  // m_bc.setGhosts, :822 (non-diagonal: inside the program)
+    // face-valued Neumann sides (diagonal metric, depth 0): their ghosts with the Dirichlet ones, their boundary fluxes after
+    // the launch below, which is the one of a solver without such sides
+    const bool neum_faces = d == 0 && !homogeneous && neum_face_live();
+    if (neum_faces) neum_face_ghosts(phi);
     ProfScope timed(*this, d, 1, mode == 0);
     if (full_march(d)) {
         run_full_program_frames(d, 0, phi, homogeneous);
@@ -1178,6 +1184,7 @@ void PressureSolver::operator_i(int d, int mode, double* out, double* phi, const
         launch_op_full(st_, L.dev, out, phi, f_psi[d], rhs, mode);
     } else if (ortho_march(d)) launch_resid_march(st_, L.rtiles.all.span(), L.dev, out, phi, rhs, mode);  // Dirichlet sides: their ghosts were just written, the kernel only zeroes NEUMANN fluxes
     else launch_op_ortho(st_, L.dev, out, phi, rhs, mode, pull);
+    if (neum_faces) neum_face_cells(mode, out, phi, rhs);
 }
 
 void PressureSolver::prolong_from(const LevelDev& C, const double* crse, const int r[3], double* fine)
@@ -1497,6 +1504,12 @@ void PressureSolver::increment_heat_flux(double* phi, bool setToZero)
         if (setToZero) launch_set(st_, acc, L.field_elems, 0.0);
         launch_incr(st_, acc, G[d], 1.0, L.field_elems);   // thisFlux += tempFlux
     }
+    // EllipticNeumBCFluxClass: the flux through a boundary face of a face-valued Neumann side is the plane's value itself,
+    // whatever the stages of the step added up there
+    if (neum_face_live()) {
+        double* acc[3] = {heat_flux(0), heat_flux(1), prm.spaceDim == 3 ? heat_flux(2) : nullptr};
+        launch_set_neum_faces(st_, L.dev, d_neum_ops_, n_neum_face_ops_, acc);
+    }
 }
 
 double* PressureSolver::heat_field(int which)
@@ -1805,7 +1818,8 @@ void PressureSolver::set_bc_face_values(int dir, int side, const double* values)
 
 // One slice of d_bcface_ per (local patch of depth 0, Dirichlet side it touches), in patch order: the ghost layer over the
 // patch's transverse extent, as build_diri_ops and build_program cover it.  Allocated once, whether or not a side is
-// face-valued yet, so that a later set_bc_face_values only copies.
+// face-valued yet, so that a later set_bc_face_values only copies.  With a diagonal metric the Neumann sides have theirs too
+// (set_neum_face_values).
 void PressureSolver::build_face_slices()
 {
     const Level& L = *lev[0];
@@ -1816,7 +1830,7 @@ void PressureSolver::build_face_slices()
         for (int a = 0; a < 3; ++a) {
             if (!L.active[a] || L.periodic[a]) continue;
             for (int s = 0; s < 2; ++s) {
-                if (L.bc_type[a][s] != BC_DIRI) continue;
+                if (L.bc_type[a][s] != BC_DIRI && (L.bc_type[a][s] != BC_NEUM || full_)) continue;
                 if ((s ? valid.hi[a] : valid.lo[a]) != (s ? L.domain.hi[a] : L.domain.lo[a])) continue;
                 face_off_[6 * pi + 2 * a + s] = total;
                 total += valid.numPts() / valid.size(a);
@@ -1829,8 +1843,8 @@ void PressureSolver::build_face_slices()
     fill_face_values();
 }
 
-// host mirror of every slice (face-valued sides from their planes, constant sides their constant, which no op reads), then
-// one copy into the device buffer
+// host mirror of every slice (face-valued sides from their planes, constant sides their constant -- zero on a Neumann side --
+// which no op reads), then one copy into the device buffer
 void PressureSolver::fill_face_values()
 {
     const Level& L = *lev[0];
@@ -1847,29 +1861,37 @@ void PressureSolver::fill_face_values()
                 for (int g1 = valid.lo[t1]; g1 <= valid.hi[t1]; ++g1)
                     for (int g0 = valid.lo[t0]; g0 <= valid.hi[t0]; ++g0, ++q)
                         h_bcface_[q] = face_[a][s] ? face_plane_[a][s][(g0 - L.domain.lo[t0]) + nt0 * (g1 - L.domain.lo[t1])]
-                                                   : bc_value_[a][s];
+                                                   : (L.bc_type[a][s] == BC_DIRI ? bc_value_[a][s] : 0.0);
             }
     }
     SOMAR_HIP(hipMemcpy(d_bcface_, h_bcface_.data(), h_bcface_.size() * sizeof(double), hipMemcpyHostToDevice));
 }
 
-// A Dirichlet op of depth 0 as its side now is: GHOST_DIRI with the side's constant, or GHOST_DIRI_FACE reading its slice.
-// The op must cover exactly the (patch, side) ghost layer its slice was laid out for, so that bcf[voff + loop index] stays
-// inside the buffer -- checked here, on the host, for every op before any upload.
-void PressureSolver::set_diri_op(GhostOp& op) const
+// The slice of a physical-boundary op of depth 0.  The op must cover exactly the (patch, side) ghost layer its slice was laid
+// out for, so that bcf[voff + loop index] stays inside the buffer -- checked here, on the host, for every op before any upload.
+long long PressureSolver::face_slice_of(const GhostOp& op, const char* what) const
 {
     const Level& L = *lev[0];
+    const std::string w(what);
     SOMAR_CHECK(op.patch >= 0 && op.patch < L.npatches() && op.dir >= 0 && op.dir < 3 && (op.sgn == 1 || op.sgn == -1),
-                "Dirichlet ghost op: bad patch / direction / side");
+                w + " ghost op: bad patch / direction / side");
     const int a = op.dir, s = op.sgn > 0 ? 1 : 0;
     const IBox valid = L.boxes[L.local[op.patch]];
     for (int q = 0; q < 3; ++q) {
         const int lo = q == a ? (s ? valid.size(a) : -1) : 0, n = q == a ? 1 : valid.size(q);
-        SOMAR_CHECK(op.lo[q] == lo && op.n[q] == n, "Dirichlet ghost op does not cover its patch's ghost layer");
+        SOMAR_CHECK(op.lo[q] == lo && op.n[q] == n, w + " ghost op does not cover its patch's ghost layer");
     }
     const long long off = face_off_.at((size_t)6 * op.patch + 2 * a + s);
     const long long cells = (long long)op.n[0] * op.n[1] * op.n[2];
-    SOMAR_CHECK(off >= 0 && off + cells <= (long long)h_bcface_.size(), "Dirichlet ghost op: face-value slice out of range");
+    SOMAR_CHECK(off >= 0 && off + cells <= (long long)h_bcface_.size(), w + " ghost op: face-value slice out of range");
+    return off;
+}
+
+// A Dirichlet op of depth 0 as its side now is: GHOST_DIRI with the side's constant, or GHOST_DIRI_FACE reading its slice.
+void PressureSolver::set_diri_op(GhostOp& op) const
+{
+    const long long off = face_slice_of(op, "Dirichlet");
+    const int a = op.dir, s = op.sgn > 0 ? 1 : 0;
     if (face_[a][s]) {
         op.type = GHOST_DIRI_FACE;
         op.voff = off;
@@ -1897,6 +1919,110 @@ void PressureSolver::refresh_diri_ops()
             fix(P.h_ops, P.d_ops);
             fix(P.h_box_ops, P.d_box_ops);
         }
+}
+
+// ------------------------------------------------------------------------------------
+// Position-dependent Neumann values on a diagonal metric (EllipticNeumBCGhostClass / EllipticNeumBCFluxClass,
+// BCInterface/EllipticBCUtils.cpp:696-947).  Everything but the inhomogeneous operator of depth 0 sees zero, i.e. the folded
+// "no ghost, no flux" face of StencilParams::neum, and launches what it launched before.
+// ------------------------------------------------------------------------------------
+void PressureSolver::refuse_full_with_neum_faces(const char* who) const
+{
+    SOMAR_CHECK(!has_neum_face_values(), std::string(who) + ": this solver has position-dependent Neumann values "
+                    "(somar_solver_set_neum_face_values), which are defined for a diagonal metric only");
+}
+
+void PressureSolver::set_neum_face_values(int dir, int side, const double* values)
+{
+    SOMAR_CHECK(!lev.empty(), "set_neum_face_values before define");
+    SOMAR_CHECK(dir >= 0 && dir < 3 && (side == 0 || side == 1), "set_neum_face_values: dir must be 0..2, side 0 (low) or 1 (high)");
+    SOMAR_CHECK(op_in_place_ == 0, "internal: set_neum_face_values while a component's operator is in place");
+    const Level& L = *lev[0];
+    SOMAR_CHECK(L.active[dir], "set_neum_face_values: direction " + std::to_string(dir) + " is inactive (space_dim 2)");
+    SOMAR_CHECK(!L.periodic[dir], "set_neum_face_values: direction " + std::to_string(dir) + " is periodic");
+    SOMAR_CHECK(L.bc_type[dir][side] == BC_NEUM, "set_neum_face_values: side (" + std::to_string(dir) + ", " +
+                                                     std::to_string(side) + ") is not a Neumann side");
+    SOMAR_CHECK(!full_, "set_neum_face_values: this solver has a non-diagonal metric; position-dependent Neumann values are "
+                        "defined for a diagonal metric only (the reference's two Neumann ghost rules differ in the cross term)");
+    const bool was = neum_face_[dir][side];
+    if (values) {
+        const int t0 = (dir + 1) % 3 < (dir + 2) % 3 ? (dir + 1) % 3 : (dir + 2) % 3, t1 = 3 - dir - t0;
+        const size_t n = (size_t)L.domain.size(t0) * L.domain.size(t1);
+        face_plane_[dir][side].assign(values, values + n);
+    } else {
+        face_plane_[dir][side].clear();
+    }
+    face_[dir][side] = neum_face_[dir][side] = values != nullptr;
+    if (!finalized) return;   // finalize builds the ops and the buffers from these
+    sync();                   // nothing in flight reads the op list or the values while they are rewritten
+    if (was != neum_face_[dir][side]) refresh_neum_ops();
+    fill_face_values();
+}
+
+// room for one op per (local patch of depth 0, physical Neumann side it touches), and the offset table, at their final sizes
+void PressureSolver::build_neum_ops()
+{
+    const Level& L = *lev[0];
+    h_neum_ops_.clear();
+    h_neum_off_.assign((size_t)std::max(6 * L.npatches(), 1), -1);
+    n_neum_face_ops_ = 0;
+    if (full_) return;
+    for (int pi = 0; pi < L.npatches(); ++pi)
+        for (int a = 0; a < 3; ++a)
+            for (int s = 0; s < 2; ++s)
+                if (L.bc_type[a][s] == BC_NEUM && face_off_[6 * pi + 2 * a + s] >= 0) h_neum_ops_.push_back(GhostOp());
+    if (h_neum_ops_.empty()) return;
+    d_neum_ops_ = DevBuf<GhostOp>(h_neum_ops_.size());
+    d_neum_off_ = DevBuf<long long>(h_neum_off_.size());
+    refresh_neum_ops();
+}
+
+// the ops of the face-valued Neumann sides first (the rest of the list is never launched), each checked against its slice on
+// the host; then one copy of the list and one of the offset table into the buffers build_neum_ops made
+void PressureSolver::refresh_neum_ops()
+{
+    if (h_neum_ops_.empty()) return;   // no local patch touches a Neumann side (a rank of a sharded level)
+    const Level& L = *lev[0];
+    std::vector<GhostOp> ops;
+    std::fill(h_neum_off_.begin(), h_neum_off_.end(), -1);
+    for (int pi = 0; pi < L.npatches(); ++pi) {
+        const IBox valid = L.boxes[L.local[pi]];
+        for (int a = 0; a < 3; ++a)
+            for (int s = 0; s < 2; ++s) {
+                if (!neum_face_[a][s] || face_off_[6 * pi + 2 * a + s] < 0) continue;
+                GhostOp op;
+                std::memset(&op, 0, sizeof(op));
+                op.patch = pi;
+                op.type = GHOST_NEUM_FACE;
+                for (int q = 0; q < 3; ++q) { op.lo[q] = 0; op.n[q] = valid.size(q); }
+                op.lo[a] = s ? valid.size(a) : -1;
+                op.n[a] = 1;
+                op.dir = a;
+                op.sgn = s ? 1 : -1;
+                op.voff = face_slice_of(op, "Neumann");
+                h_neum_off_[6 * pi + 2 * a + s] = op.voff;
+                ops.push_back(op);
+            }
+    }
+    SOMAR_CHECK(ops.size() <= h_neum_ops_.size(), "internal: more face-valued Neumann ops than the list has room for");
+    n_neum_face_ops_ = (int)ops.size();
+    GhostOp idle;   // behind the launched ones: an empty region
+    std::memset(&idle, 0, sizeof(idle));
+    idle.type = GHOST_COPY;
+    ops.resize(h_neum_ops_.size(), idle);
+    h_neum_ops_ = ops;
+    SOMAR_HIP(hipMemcpy(d_neum_ops_, h_neum_ops_.data(), h_neum_ops_.size() * sizeof(GhostOp), hipMemcpyHostToDevice));
+    SOMAR_HIP(hipMemcpy(d_neum_off_, h_neum_off_.data(), h_neum_off_.size() * sizeof(long long), hipMemcpyHostToDevice));
+}
+
+void PressureSolver::neum_face_ghosts(double* phi)
+{
+    launch_ghost_ops(st_, lev[0]->dev, d_neum_ops_, n_neum_face_ops_, phi, phi, false);
+}
+
+void PressureSolver::neum_face_cells(int mode, double* out, const double* phi, const double* rhs)
+{
+    launch_op_neum_face(st_, lev[0]->dev, d_neum_ops_, n_neum_face_ops_, d_neum_off_, out, phi, rhs, mode);
 }
 
 void PressureSolver::drop_graph(CoarseGraph& g)

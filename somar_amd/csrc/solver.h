@@ -146,7 +146,7 @@ public:
     void relax(int d, double* e, const double* res, int iters, bool e_zero = false, const double* e_shift = nullptr,
                const Level* e_plus_level = nullptr, const double* e_plus = nullptr);
     bool fused_relax(int d, int iters) const;
-    // homogeneous: physical BC values taken as zero (only Dirichlet sides can carry a value here)
+    // homogeneous: physical BC values taken as zero (the values of Dirichlet sides and of face-valued Neumann sides)
     void residual(int d, double* out, double* phi, const double* rhs, bool homogeneous = true);   // homogeneous CF ghosts, then residual_i
     void apply_op(int d, double* out, double* phi, bool homogeneous = true);
     void residual_i(int d, double* out, double* phi, const double* rhs, bool homogeneous = true) // residualI: CF ghosts as they are
@@ -166,6 +166,21 @@ public:
     // directions in increasing order.  nullptr: back to the constant of set_bc_values.  Before or after finalize; after it
     // only copies into the existing device buffers (op lists and face values keep their addresses).
     void set_bc_face_values(int dir, int side, const double* values);
+    // Position-dependent values of the Neumann side (dir, side) of a DIAGONAL-metric solver (EllipticNeumBCGhostClass /
+    // EllipticNeumBCFluxClass, BCInterface/EllipticBCUtils.cpp:696-947): the layout of set_bc_face_values; a value is
+    // J g^{dd} dphi/dxi_d at the face on both sides.  nullptr: back to zero Neumann.  Before or after finalize; after it only
+    // copies into the existing device buffers.  The inhomogeneous operator of depth 0 takes them (operator_i), nothing else.
+    void set_neum_face_values(int dir, int side, const double* values);
+    bool has_neum_face_values() const
+    {
+        for (int d = 0; d < 3; ++d)
+            for (int s = 0; s < 2; ++s)
+                if (neum_face_[d][s]) return true;
+        return false;
+    }
+    // a non-diagonal metric on a solver with face-valued Neumann sides is refused (who: the call that would set it)
+    void refuse_full_with_neum_faces(const char* who) const;
+    // Dirichlet or Neumann
     bool has_face_values() const
     {
         for (int d = 0; d < 3; ++d)
@@ -633,8 +648,29 @@ private:
     std::vector<GhostOp> h_diri_ops0_;   // host copy of d_diri_ops_[0]
     void build_face_slices();
     void fill_face_values();
+    long long face_slice_of(const GhostOp& op, const char* what) const;   // the op covers its (patch, side) ghost layer: its slice
     void set_diri_op(GhostOp& op) const;   // depth-0 Dirichlet op: constant or face-valued, as its side is now
     void refresh_diri_ops();
+    // ---- position-dependent Neumann values (diagonal metric, depth 0, the solver's own operator) ----
+    // neum_face_[a][s]: the Neumann side (a, s) is face-valued (face_ / face_plane_ / its slices of d_bcface_ serve both kinds:
+    // a side is one or the other).  d_neum_ops_ has room for one op per (local patch, physical Neumann side it touches), built
+    // at finalize; the ops of the face-valued sides stand first (n_neum_face_ops_ of them: all that is ever launched) and are
+    // rewritten in place when a side changes kind.  d_neum_off_[6 * patch + 2 * a + s]: the slice of a face-valued Neumann
+    // side on that patch, -1 otherwise (k_op_neum_face).  No plane set: n_neum_face_ops_ == 0 and nothing is launched.
+    bool neum_face_[3][2] = {{false, false}, {false, false}, {false, false}};
+    std::vector<GhostOp> h_neum_ops_;
+    DevBuf<GhostOp> d_neum_ops_;
+    int n_neum_face_ops_ = 0;
+    std::vector<long long> h_neum_off_;
+    DevBuf<long long> d_neum_off_;
+    void build_neum_ops();     // finalize: the buffers at their final size
+    void refresh_neum_ops();   // the ops and the offsets as the sides are now; one copy each into the existing buffers
+    // the inhomogeneous operator of depth 0 takes face-valued Neumann sides now (not while a component's own operator is in place)
+    bool neum_face_live() const { return n_neum_face_ops_ > 0 && op_in_place_ == 0; }
+    // EllipticNeumBCGhostClass: the ghosts of those sides; EllipticNeumBCFluxClass: the cells next to them evaluated with the
+    // planes' values as boundary fluxes, over what the operator launch left in out (mode as operator_i)
+    void neum_face_ghosts(double* phi);
+    void neum_face_cells(int mode, double* out, const double* phi, const double* rhs);
     int mini_depth_ = 0;  // > 0 while a mini V-cycle runs: the depth count it is limited to
     int cycle_override_ = 0;  // != 0 inside an F-cycle's inner V-cycles: the effective numMG ("m_cycle = 1" hack, MappedMultiGrid.H:603-605)
     void cycle_down(int d, double* corr, const double* res, bool corr_zero);  // pre-smoothing + restriction

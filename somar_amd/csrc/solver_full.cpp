@@ -559,6 +559,7 @@ void PressureSolver::copy_frames(int d, const double* src, double* dst)
 void PressureSolver::make_full()
 {
     SOMAR_CHECK(!lev.empty() && !finalized, "make_full before define / after finalize");
+    refuse_full_with_neum_faces("make_full");
     full_ = true;
     lev[0]->alloc_cross_metric();
 }
@@ -673,6 +674,7 @@ void PressureSolver::mac_grad_full(double* phi)
 void PressureSolver::set_metric_full(int patch, const double* jg0, const double* jg1, const double* jg2,
                                      const double* jinv)
 {
+    refuse_full_with_neum_faces("set_metric_full");
     metric_written("full");
     Level& L = *lev[0];
     full_ = true;
@@ -699,6 +701,7 @@ void PressureSolver::set_metric_map(int kind, const double Lc[3], const double* 
     SOMAR_CHECK(!lev.empty() && (!finalized || updating_), "set_metric before define / after finalize");
     SOMAR_CHECK(prm.spaceDim == 3, "the map producers restate the CH_SPACEDIM = 3 algebra (GeoSourceInterface.cpp:236-291)");
     SOMAR_CHECK(kind >= 1 && kind <= 4, "map kind: 1 cylindrical, 2 bathymetric, 3 twisted (type 0), 4 twisted (type 1)");
+    if (kind != 1) refuse_full_with_neum_faces("set_metric_map (a non-diagonal map)");
     metric_written(kind == 1 ? "cylindrical" : "map");
     Level& L = *lev[0];
     SOMAR_CHECK(L.npatches() < 65536, "too many local patches for one launch");

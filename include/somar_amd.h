@@ -868,8 +868,34 @@ int somar_solver_get_precision(const somar_solver_t* s, int* mode, int* fp32_dep
  *  Through somar_comp_set_op (below): per-component Dirichlet values; per-component BC types (free-slip walls, where the
  *  normal and the tangential components differ); per-component alpha / beta.
  *  Not offered (yet): face-valued Dirichlet sides per component; _dev twins of the component I/O; levels sharded over ranks;
- *  the 19-point operator. */
+ *  the 19-point operator (it has a call of its own, below).
+ *  somar_solver_set_components_full: the counterpart for a handle finalized with a NON-diagonal metric
+ *    (somar_solver_set_metric_full, a non-diagonal map producer) -- the terrain-following decks, whose m_viscSolverPtrs[idir]
+ *    (NavierStokes/AMRNavierStokesInit.cpp:887-1010) otherwise each hold a copy of the nine J g^{ab} planes, Jinv, every coarse
+ *    metric, the tile tables and the ghost programs.  Same semantics: after finalize, 1 to 4 components, component 0 is the
+ *    handle's own fields, ncomp = 1 releases the others (through either call), min_cells <= 0 is the library's threshold (that
+ *    of the marching 19-point kernels).  Once it accepts ncomp > 1 every call of this group works unchanged and under the same
+ *    sentence: every component comes out exactly as ncomp successive single-field calls on the handle would leave it, bit for bit.
+ *    A depth is BATCHED -- its GSRB colour passes and its residuals are launches that carry two fields and stream the
+ *    coefficients once -- where the marching 19-point kernels run and the fused red+black 19-point sweep (off by default) does
+ *    not, before the serial-order sums and the graph-replayed legs, without coarse-fine faces or a zero-average prolongation,
+ *    with at least min_cells cells.  Three components go as 2 + 1 and four as 2 + 2: the three-field form measured slower than
+ *    the single-field kernel and is not built.  (A coarser depth below it is not required: where the boxes stop coarsening
+ *    while the level is still large -- a box width that is no multiple of 8 -- the bottom depth's sweeps are batched and its
+ *    bottom solve runs per component.)  The 19-point cycle folds nothing: the exchanges, the ghost programs (one psi frame
+ *    array per component and batched depth), the averaging and the prolongation stay per field.  Traffic of a colour pass or
+ *    residual per cell and field, COMPUTED from the accounting of the single-field kernel (about 106 B, of which 80 are
+ *    coefficients): (80 + 26 NF) / NF, 66 B for two fields; what was measured on one MI355X, and the launch shapes chosen
+ *    from it, are in profiles/r14_multi_full19.md.  With K == 0 -- every 2-D (9-point) handle, every level
+ *    below the marching threshold -- the multi calls are loops over the single-field ones and the gain is the shared metric alone.
+ *    Refused, with the reason in somar_last_error: a handle with a diagonal metric (it takes somar_solver_set_components); ncomp
+ *    > 1 where that call refuses it, in its words: a level of an AMR hierarchy, the handles of a leptic solver, relax_mode other
+ *    than LevelGSRB, num_mg != 1, coarse-fine faces, more than one rank, an open metric update.  somar_comp_set_op is refused on a
+ *    handle with a non-diagonal metric: the ghost programs of the 19-point path carry one operator's sides and values, so a
+ *    component with an operator of its own keeps a handle of its own there; fp32 (somar_solver_set_precision mode 1) is not
+ *    offered on a non-diagonal metric at all. */
 int somar_solver_set_components(somar_solver_t* s, int ncomp, long long min_cells);
+int somar_solver_set_components_full(somar_solver_t* s, int ncomp, long long min_cells);
 int somar_solver_get_components(somar_solver_t* s, int* ncomp, int* batched_depths, long long* batched_launches);
 int somar_comp_upload(somar_solver_t* s, int comp, int field, int patch, const double* host, const int* ghost);
 int somar_comp_download(somar_solver_t* s, int comp, int field, int patch, double* host, const int* ghost);
@@ -901,7 +927,8 @@ int somar_comp_history(somar_solver_t* s, int comp, double* out, int capacity, i
  *  Refused, with the reason in somar_last_error and nothing changed: comp 0 or out of range; a type other than Neumann (0) or
  *    Dirichlet (1) on a non-periodic side; an operator with a null space (the null-space probe of finalize, run at every depth
  *    with the operator in place: the batched kernels carry no mean removal, such a component keeps a handle of its own); a call
- *    during a metric update.
+ *    during a metric update; a handle with a non-diagonal metric (somar_solver_set_components_full: the ghost programs of the
+ *    19-point path carry one operator's sides and values -- out of scope for now).
  *  somar_comp_get_op: the operator component comp runs (0: the handle's); own = 1 if it was set here.  Any pointer may be NULL.
  *  somar_comp_reset_op: back to the handle's operator.
  *  somar_solver_get_op_launches: the N-field launches so far whose fields had different operators. */

@@ -208,6 +208,7 @@ _SIGS = {
     "somar_solver_get_precision": [_H, _PI, _PI],
     # several components on one operator
     "somar_solver_set_components": [_H, C.c_int, C.c_longlong],
+    "somar_solver_set_components_full": [_H, C.c_int, C.c_longlong],
     "somar_solver_get_components": [_H, _PI, _PI, C.POINTER(C.c_longlong)],
     "somar_comp_upload": [_H, C.c_int, C.c_int, C.c_int, _PD, _PI],
     "somar_comp_download": [_H, C.c_int, C.c_int, C.c_int, _PD, _PI],
@@ -924,6 +925,12 @@ class AMRPressureSolver:
         depth 0; metric, alpha / beta and BCs are shared.  Component 0 is the handle's own fields.  After finalize; 1 releases
         the others.  min_cells: depths with at least that many cells are batched (0: the library's threshold)."""
         _ck(lib().somar_solver_set_components(self._h, int(ncomp), int(min_cells)))
+
+    def setComponentsFull(self, ncomp, min_cells=0):
+        """setComponents for a handle finalized with a non-diagonal metric (setMetricFull, a non-diagonal map): the depths on
+        which the marching 19-point kernels run are batched.  Refused on a diagonal-metric handle; setCompOp is refused on
+        these handles."""
+        _ck(lib().somar_solver_set_components_full(self._h, int(ncomp), int(min_cells)))
 
     def getComponents(self):
         """(ncomp, batched depths K, N-field launches issued so far)"""

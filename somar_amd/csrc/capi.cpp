@@ -1740,6 +1740,16 @@ int somar_solver_set_components(somar_solver_t* s, int ncomp, long long min_cell
     API_END
 }
 
+int somar_solver_set_components_full(somar_solver_t* s, int ncomp, long long min_cells)
+{
+    API_BEGIN
+    SOMAR_CHECK(s && s->ps, "null argument");
+    SOMAR_CHECK(ncomp <= 1 || (!s->lep && (s->owned || s->ps->amr_member())),
+                "set_components_full: more than one component is not available for the handles of a leptic solver");
+    s->ps->set_components_full(ncomp, min_cells);
+    API_END
+}
+
 int somar_solver_get_components(somar_solver_t* s, int* ncomp, int* batched_depths, long long* batched_launches)
 {
     API_BEGIN

@@ -128,6 +128,17 @@ struct ResidFields { double* out[NF]; const double* phi[NF]; const double* rhs[N
 template <int NF, class OPS>
 void launch_resid_nf(hipStream_t st, TileSpan tiles, const LevelDev& F, const ResidFields<NF>& fields, const OPS& O,
                      const LevelDev* C, const int* r);
+// The 19-point marching residual (mode 0: out[f] = rhs[f] - L[phi[f]]) and colour pass (mode 2: out[f] = phi[f] with the cells
+// of `color` relaxed; out != phi) on NF = 2 fields of one level (full19_multi.hip; PressureSolver::set_components_full):
+// the nine J g^{ab} planes and Jinv are streamed once per launch, each field's arithmetic is launch_full_march's /
+// launch_gsrb_full_march's.  Every field has its own psi (right in the one-cell frames) and all share L.P.  Class-0 tiles of
+// full_march_nf_rows(NF) region rows (two fields: 8), whatever L.full_rows says.  The three-field form (6 rows) measured
+// slower than the single-field kernel and is not instantiated (profiles/r14_multi_full19.md).
+template <int NF>
+struct FullFields { double* out[NF]; const double* phi[NF]; const double* psi[NF]; const double* rhs[NF]; };
+template <int NF>
+void launch_full_march_nf(hipStream_t st, TileSpan tiles, const LevelDev& L, const FullFields<NF>& F, int mode, int color);
+int full_march_nf_rows(int nf);
 // crse(ic) = sum over the children of ic of dxProduct / fjinv(child): the volume a coarse value is spread over
 void launch_child_volume(hipStream_t st, const LevelDev& C, const LevelDev& F, double* crse, const int r[3],
                          double dxProduct);

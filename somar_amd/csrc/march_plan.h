@@ -177,6 +177,8 @@ inline Shape resid_shape(bool narrow) { return make_shape(16, 2, 2.0, 256, narro
 // marching 19-point kernels (full19_march.hip), 8 or 6 region rows: 124 x (rows - 2) columns; 6 rows: two workgroups per CU,
 // never narrow
 inline Shape full_shape(int rows) { return make_shape(rows, 2, 2.0, rows == 6 ? 512 : 256, rows == 8, 0.85); }
+// the same kernels on several fields (full19_multi.hip): class-0 columns only, one workgroup per CU at either row count
+inline Shape full_nf_shape(int rows) { return make_shape(rows, 2, 2.0, 256, false, 0.85); }
 // fused red+black 19-point sweep (full19_fused.hip): 124 x 4 column tiles
 inline Shape fused19_shape() { return make_shape(8, 4, 3.0, 256, false, 1.0); }
 

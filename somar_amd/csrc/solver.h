@@ -241,6 +241,15 @@ public:
     // leaves every component as ncomp successive solve() calls would, bit for bit.  Refused where that does not reach
     // (multi_refusal).
     void set_components(int ncomp, long long min_cells);
+    // The same on a handle with a NON-diagonal metric (19-point operator; refused on a diagonal one, which takes the call above).
+    // A depth is batched -- its colour passes and residuals are N-field launches of full19_multi.hip, which stream the nine
+    // J g^{ab} planes and Jinv once -- where the marching 19-point kernels run (full_march) and the fused red+black sweep does
+    // not, before the serial-order sums and the graph-replayed legs, without coarse-fine faces or a zero-average prolongation,
+    // with at least min_cells cells (<= 0: the marching kernels' own threshold).  The bottom depth of a hierarchy whose boxes
+    // stop coarsening while the level still marches is batched too: its bottom sweeps, the bottom solve stays per field.  The ghost
+    // programs stay per field (each component has a psi frame array of its own on the batched depths).  Components with an
+    // operator of their own are not offered here (comp_set_op): the ghost programs carry one operator's sides and values.
+    void set_components_full(int ncomp, long long min_cells);
     int components() const { return ncomp_; }
     int batched_depths() const { return mc_K_; }
     long long batched_launches() const { return mc_launches_; }   // N-field launches so far (tests: a case reached its kernels)
@@ -374,7 +383,7 @@ private:
     struct CompOp;   // a component's own operator (below, after CoarseGraph)
     // depth 0 of a component beyond 0; op: its own operator, null while it shares the solver's
     struct Component { DevBuf<double> phi, rhs, res, corr, best, heat[3]; std::unique_ptr<CompOp> op; };
-    struct CompDepth { DevBuf<double> corr, res, pp; };
+    struct CompDepth { DevBuf<double> corr, res, pp, psi; };   // psi: non-diagonal metric (the frame array of the ghost programs)
     int ncomp_ = 1;
     long long mc_min_cells_ = 0, mc_launches_ = 0, mc_op_launches_ = 0;
     int mc_K_ = 0;                                   // depths 0 .. mc_K_ - 1 are batched
@@ -383,7 +392,10 @@ private:
     // seam: every component's restricted residual waits there for its turn in the single-field cycle); the others own corr / res
     // of depths 1 .. K and a ping-pong buffer per batched depth
     std::vector<std::vector<CompDepth>> mc_depth_;
-    std::vector<TileTable> mc_ftiles_, mc_rtiles_;   // per batched depth: class-0 tables of the N-field sweep / residual
+    // per batched depth: class-0 tables of the N-field sweep / residual; non-diagonal metric: mc_ftiles_ alone, of the
+    // 19-point kernels' two-field (8-row) form
+    std::vector<TileTable> mc_ftiles_, mc_rtiles_;
+    bool mc_full_call_ = false;                      // set_components_full is asking (multi_refusal)
     std::vector<std::vector<double>> mc_history_;
     std::string multi_refusal() const;               // why ncomp > 1 is not available here ("" = it is)
     void mc_setup();                                 // K, the components' buffers, the tile tables (set_components, metric refresh)
@@ -407,11 +419,19 @@ private:
     double* mc_corr(int comp, int d) const { return (comp == 0 && d < mc_K_) ? f_corr[d].get() : mc_depth_[comp][d].corr.get(); }
     double* mc_res(int comp, int d) const { return (comp == 0 && d < mc_K_) ? f_res[d].get() : mc_depth_[comp][d].res.get(); }
     double* mc_pp(int comp, int d) const { return comp == 0 ? f_pp[d].get() : mc_depth_[comp][d].pp.get(); }
+    double* mc_psi(int comp, int d) const { return comp == 0 ? f_psi[d].get() : mc_depth_[comp][d].psi.get(); }
     // per active component: the bottom solver's convergence metric going in (null: as it stands), its counts coming out
     struct CompBottom { const double* metric = nullptr; int iters[MC_MAX], exit[MC_MAX]; };
     void multi_cycle(int d, const CompFields& F, bool corr_zero, CompBottom& B);
     void multi_sweeps(int d, const CompFields& F, int iters, bool e_zero, double* const* e_plus);
     void multi_restrict(int d, const CompFields& F, double* const* crse);
+    // the same three on a batched depth of a non-diagonal metric, as relax() / restrict_residual() / prolong_increment() run there
+    void multi_full_sweeps(int d, const CompFields& F, int iters, bool e_zero);
+    void multi_full_restrict(int d, const CompFields& F, double* const* crse);
+    // mode 0: out[i] = rhs[i] - L[phi[i]] (the frame programs of the operator have run), 2: the colour pass out[i] := phi[i] with
+    // `color` relaxed (those of the smoother have): N-field launches by the launch plan, a lone field through the level's own table
+    void multi_full_launches(int d, int n, const int* comp, double* const* out, double* const* phi, double* const* rhs, int mode,
+                             int color);
     // out[i] = rhs[i] - L[phi[i]] on depth 0 with the physical BCs (homogeneous or not), as residual()
     // (comp[i]: the component of position i, whose operator the physical ghosts and the launch take)
     void multi_residual0(int n, const int* comp, double* const* out, double* const* phi, double* const* rhs, bool homogeneous);

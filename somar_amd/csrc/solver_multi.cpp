@@ -22,7 +22,7 @@ namespace somar {
 std::string PressureSolver::multi_refusal() const
 {
     if (amr_member_) return "a level of an AMR hierarchy (the composite cycle carries one field)";
-    if (full_) return "a non-diagonal metric (19-point operator)";
+    if (full_ && !mc_full_call_) return "a non-diagonal metric (19-point operator)";   // (set_components_full is its call)
     if (prm.relaxMode != RELAX_LEVEL_GSRB) return "a relax_mode other than LevelGSRB";
     if (prm.numMG != 1) return "num_mg != 1 (W- and F-cycles run plain passes, no folding)";
     if (hasCF_ || !forcedRatios.empty()) return "a level with coarse-fine boundaries";
@@ -40,6 +40,23 @@ void PressureSolver::set_components(int ncomp, long long min_cells)
         SOMAR_CHECK(why.empty(), "set_components: more than one component is not available for " + why);
     }
     SOMAR_CHECK(finalized, "set_components before finalize");
+    sync();
+    ncomp_ = ncomp;
+    mc_min_cells_ = min_cells;
+    mc_setup();
+}
+
+void PressureSolver::set_components_full(int ncomp, long long min_cells)
+{
+    check_idle("set_components_full");
+    SOMAR_CHECK(ncomp >= 1 && ncomp <= MC_MAX, "set_components_full: 1 to 4 components");
+    SOMAR_CHECK(full_ || !finalized, "set_components_full: the handle has a diagonal metric, which takes somar_solver_set_components");
+    if (ncomp > 1) {
+        ScopedSet<bool> asking(mc_full_call_, true);
+        const std::string why = multi_refusal();   // the 7-point call's reasons, in its words
+        SOMAR_CHECK(why.empty(), "set_components_full: more than one component is not available for " + why);
+    }
+    SOMAR_CHECK(finalized, "set_components_full before finalize");
     sync();
     ncomp_ = ncomp;
     mc_min_cells_ = min_cells;
@@ -81,7 +98,20 @@ void PressureSolver::mc_setup()
     const long long minc = mc_min_cells_ > 0 ? mc_min_cells_ : tune_.fused_min_cells;
     const int D = (int)lev.size();
     int K = 0;
-    for (int d = 0; d + 1 < D && !tune_.no_fold_prolong; ++d) {
+    // Non-diagonal metric: the 19-point cycle folds nothing, so none of the fold path's conditions carries over.  A depth is
+    // batched where the two-pass marching kernels run (the fused red+black 19-point sweep stays single-field), before the
+    // serial-order sums and the graph-replayed legs, without coarse-fine faces or a zero-average prolongation (launch_prolong's
+    // mean removal stays single-field), where a sweep visits a cell at all, with min_cells cells (the marching kernels' own
+    // threshold is full_march's).  The bottom depth counts too (boxes that do not coarsen: a hierarchy of one large depth):
+    // its bottom sweeps are batched, the bottom solve stays per field.
+    for (int d = 0; d < D && full_; ++d) {
+        const Level& L = *lev[d];
+        if (graph_from_ >= 0 && d >= graph_from_) break;
+        if (!full_march(d) || fused19(d) || ordered(d) || unswept(d)) break;
+        if (L.valid_cells_global < mc_min_cells_ || L.zeroAvg || L.ncf != 0) break;
+        K = d + 1;
+    }
+    for (int d = 0; d + 1 < D && !tune_.no_fold_prolong && !full_; ++d) {
         const Level& L = *lev[d];
         if (graph_from_ >= 0 && d >= graph_from_) break;
         if (!fused_relax(d, prm.num_smooth_down) || !fused_relax(d, prm.num_smooth_up)) break;
@@ -97,10 +127,11 @@ void PressureSolver::mc_setup()
     mc_depth_.resize(ncomp_);
     for (int c = 0; c < ncomp_; ++c) {
         mc_depth_[c].resize(K + 1);
-        for (int d = 0; d <= K && K > 0; ++d) {
+        for (int d = 0; d <= K && d < D && K > 0; ++d) {   // (K == D, non-diagonal metric only: no seam, nothing below)
             CompDepth& z = mc_depth_[c][d];
             if (d == K || (c > 0 && d > 0)) { z.corr = lev[d]->alloc_field(); z.res = lev[d]->alloc_field(); }
             if (c > 0 && d < K) z.pp = lev[d]->alloc_field();
+            if (c > 0 && d < K && full_) z.psi = lev[d]->alloc_field();   // the frame array its ghost programs write
         }
     }
     // class-0 tables of the batched depths (march_plan.h): equal columns of at most 124 cells, whatever the level's own tables
@@ -111,6 +142,18 @@ void PressureSolver::mc_setup()
     for (int d = 0; d < K; ++d) {
         std::vector<mp::BoxSize> sizes;
         for (const PatchDesc& p : lev[d]->hpatches) sizes.push_back({p.n[0], p.n[1], p.n[2]});
+        if (full_) {
+            // the table of full19_multi.hip's form: two fields march 8 region rows
+            mp::Table two = mp::march_tiles(mp::full_nf_shape(full_march_nf_rows(2)), sizes);
+            SOMAR_CHECK(two.classes == 0, "internal: the N-field kernels take class-0 tiles");
+            mc_ftiles_[d].assign(std::move(two.tiles), 0);
+#ifdef SOMAR_FULL19_NF3
+            mp::Table three = mp::march_tiles(mp::full_nf_shape(full_march_nf_rows(3)), sizes);
+            SOMAR_CHECK(three.classes == 0, "internal: the N-field kernels take class-0 tiles");
+            mc_rtiles_[d].assign(std::move(three.tiles), 0);
+#endif
+            continue;
+        }
         mp::Table f = mp::march_tiles(mp::fused_shape(16, false), sizes), r = mp::march_tiles(mp::resid_shape(false), sizes);
         mp::number_slots(r.tiles);
         SOMAR_CHECK(f.classes == 0 && r.classes == 0, "internal: the N-field kernels take class-0 tiles");
@@ -216,6 +259,8 @@ void PressureSolver::comp_set_op(int comp, const int bc6[6], const double val6[6
 {
     check_idle("comp_set_op");
     SOMAR_CHECK(finalized && ncomp_ > 1, "comp_set_op: after set_components has accepted more than one component");
+    SOMAR_CHECK(!full_, "comp_set_op: not available on a non-diagonal metric (the ghost programs of the 19-point path carry one "
+                        "operator's sides and values): such a component keeps a handle of its own");
     SOMAR_CHECK(comp != 0, "comp_set_op: component 0 is the solver's create-time operator and is not settable");
     SOMAR_CHECK(comp > 0 && comp < ncomp_, "comp_set_op: component out of range (1 .. ncomp - 1)");
     SOMAR_CHECK(bc6 && val6, "comp_set_op: null argument");
@@ -465,10 +510,98 @@ void PressureSolver::multi_restrict(int d, const CompFields& F, double* const* c
     sf_valid_[d] = 0;   // (as march_restrict leaves it on a depth without a zero-average prolongation)
 }
 
+// ------------------------------------------------------------------------------------
+// the same on a non-diagonal metric: relax() / restrict_residual() / prolong_increment() for full_march on the active components
+// ------------------------------------------------------------------------------------
+// Fields per launch of the 19-point N-field forms (full19_multi.hip), as measured per field against the single-field kernels
+// at 512^3 (profiles/r14_multi_full19.md)
+// two fields -26 % (colour pass) and -29 % (residual); three fields at 6 rows +22 % and +0.7 %: dropped, three go as 2 + 1.
+// (-DSOMAR_FULL19_NF3 builds the three-field form and sends three fields through it: the build the note's figures came from.)
+#ifdef SOMAR_FULL19_NF3
+constexpr int FULL_MAXNF = 3;
+#else
+constexpr int FULL_MAXNF = 2;
+#endif
+
+void PressureSolver::multi_full_launches(int d, int n, const int* comp, double* const* out, double* const* phi,
+                                         double* const* rhs, int mode, int color)
+{
+    Level& L = *lev[d];
+    int plan[MC_MAX];
+    const int nl = launch_plan(n, FULL_MAXNF, plan);
+    ProfScope timed(*this, d, mode == 0 ? 1 : 0);   // the slots relax() and operator_i() time their launches into
+    for (int q = 0, i0 = 0; q < nl; i0 += plan[q], ++q) {
+        if (plan[q] == 1) {
+            const double* psi = mc_psi(comp[i0], d);
+            if (mode == 0) launch_full_march(st_, L.qtiles.span(), L.dev, out[i0], phi[i0], psi, rhs[i0], 0);
+            else launch_gsrb_full_march(st_, L.qtiles.span(), L.dev, out[i0], phi[i0], psi, rhs[i0], color);
+        } else if (plan[q] == 2) {
+            FullFields<2> F;
+            for (int f = 0; f < 2; ++f) { F.out[f] = out[i0 + f]; F.phi[f] = phi[i0 + f]; F.psi[f] = mc_psi(comp[i0 + f], d); F.rhs[f] = rhs[i0 + f]; }
+            launch_full_march_nf<2>(st_, mc_ftiles_[d].span(), L.dev, F, mode, color);
+            ++mc_launches_;
+#ifdef SOMAR_FULL19_NF3
+        } else {
+            FullFields<3> F;
+            for (int f = 0; f < 3; ++f) { F.out[f] = out[i0 + f]; F.phi[f] = phi[i0 + f]; F.psi[f] = mc_psi(comp[i0 + f], d); F.rhs[f] = rhs[i0 + f]; }
+            launch_full_march_nf<3>(st_, mc_rtiles_[d].span(), L.dev, F, mode, color);
+            ++mc_launches_;
+#endif
+        }
+    }
+}
+
+// LevelGSRB::relax on the marching 19-point kernels (relax(), the full_march branch): per colour and field the exchange and
+// the smoother's frame program into that field's psi, the frame of the other buffer; then the colour pass of all fields
+void PressureSolver::multi_full_sweeps(int d, const CompFields& F, int iters, bool e_zero)
+{
+    Level& L = *lev[d];
+    const int n = F.n;
+    if (e_zero)
+        for (int i = 0; i < n; ++i) launch_set(st_, F.corr[i], L.field_elems, 0.0);
+    double *cur[MC_MAX], *alt[MC_MAX];
+    for (int i = 0; i < n; ++i) { cur[i] = F.corr[i]; alt[i] = mc_pp(F.comp[i], d); }
+    for (int it = 0; it < iters; ++it)
+        for (int pass = 0; pass < 2; ++pass) {
+            for (int i = 0; i < n; ++i) {
+                xchg(L, cur[i]);
+                run_program(d, full_prog_[d][5], cur[i], mc_psi(F.comp[i], d), true, true, false);
+                copy_frames(d, cur[i], alt[i]);
+            }
+            multi_full_launches(d, n, F.comp, alt, cur, F.res, 2, pass);
+            for (int i = 0; i < n; ++i) std::swap(cur[i], alt[i]);
+        }
+    // an even number of passes: every result is back in its corr
+}
+
+// restrict_residual() off the marching path: the residual of every field (homogeneous BCs) into its ping-pong buffer, which
+// the sweeps have left free, then the single-field averaging
+void PressureSolver::multi_full_restrict(int d, const CompFields& F, double* const* crse)
+{
+    Level& L = *lev[d];
+    double* scratch[MC_MAX];
+    for (int i = 0; i < F.n; ++i) {
+        scratch[i] = mc_pp(F.comp[i], d);
+        xchg(L, F.corr[i]);
+        run_program(d, full_prog_[d][4], F.corr[i], mc_psi(F.comp[i], d), true, true, false);
+    }
+    multi_full_launches(d, F.n, F.comp, scratch, F.corr, F.res, 0, 0);
+    for (int i = 0; i < F.n; ++i) launch_restrict(st_, lev[d + 1]->dev, L.dev, crse[i], scratch[i], L.mgCrseRefRatio);
+}
+
 void PressureSolver::multi_residual0(int n, const int* comp, double* const* out, double* const* phi, double* const* rhs,
                                      bool homogeneous)
 {
     Level& L = *lev[0];
+    if (full_) {
+        // operator_i on the marching path: exchange, the operator's frame program with the caller's flag, the residual
+        for (int i = 0; i < n; ++i) {
+            xchg(L, phi[i]);
+            run_program(0, full_prog_[0][4], phi[i], mc_psi(comp[i], 0), homogeneous, true, false);
+        }
+        multi_full_launches(0, n, comp, out, phi, rhs, 0, 0);
+        return;
+    }
     for (int i = 0; i < n; ++i) {
         xchg(L, phi[i]);                              // exchangeComplete, as operator_i
         comp_diri(comp[i], 0, phi[i], homogeneous);
@@ -511,7 +644,19 @@ void PressureSolver::multi_cycle(int d, const CompFields& F, bool corr_zero, Com
         B.exit[0] = bottom_exit;
         return;
     }
-    multi_sweeps(d, F, prm.num_smooth_down, corr_zero, nullptr);
+    if (full_ && d == (int)lev.size() - 1) {
+        // cycle() on the bottom depth: the bottom sweeps on all fields, then every component's bottom solve in its turn
+        multi_full_sweeps(d, F, prm.num_smooth_bottom, corr_zero);
+        for (int i = 0; i < n; ++i) {
+            if (B.metric) bottom_metric = B.metric[i];
+            bottom_solve(F.corr[i], F.res[i]);
+            B.iters[i] = bottom_iters;
+            B.exit[i] = bottom_exit;
+        }
+        return;
+    }
+    if (full_) multi_full_sweeps(d, F, prm.num_smooth_down, corr_zero);
+    else multi_sweeps(d, F, prm.num_smooth_down, corr_zero, nullptr);
     CompFields N;
     N.n = n;
     for (int i = 0; i < n; ++i) {
@@ -519,10 +664,12 @@ void PressureSolver::multi_cycle(int d, const CompFields& F, bool corr_zero, Com
         N.corr[i] = mc_corr(F.comp[i], d + 1);
         N.res[i] = mc_res(F.comp[i], d + 1);
     }
-    multi_restrict(d, F, N.res);
+    if (full_) multi_full_restrict(d, F, N.res);
+    else multi_restrict(d, F, N.res);
     if (d + 1 < K) {
         multi_cycle(d + 1, N, true, B);
-        for (int i = 0; i < n; ++i) xchg(*lev[d + 1], N.corr[i]);
+        if (!full_)
+            for (int i = 0; i < n; ++i) xchg(*lev[d + 1], N.corr[i]);   // (the folded prolongation reads the coarse ghosts)
     } else {
         // the seam: every component takes its turn in the single-field cycle, through the solver's own arrays of depth K (the
         // graphs are captured for those, one pair per operator); its exchanged correction goes back to the component
@@ -536,6 +683,13 @@ void PressureSolver::multi_cycle(int d, const CompFields& F, bool corr_zero, Com
             xchg(*lev[K], f_corr[K].get());
             launch_copy(st_, N.corr[i], f_corr[K], nK);
         }
+    }
+    if (full_) {
+        // cycle_up off the fold path: the prolongation per field (no mean removal: a zero-average depth is not batched), then
+        // the post-smoothing passes
+        for (int i = 0; i < n; ++i) prolong_onto(d, lev[d + 1]->dev, N.corr[i], lev[d]->mgCrseRefRatio, F.corr[i], false);
+        multi_full_sweeps(d, F, prm.num_smooth_up, false);
+        return;
     }
     multi_sweeps(d, F, prm.num_smooth_up, false, N.corr);
 }

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libsomar_amd.so")
 SOURCES = ["kernels.hip", "box_bicgstab.hip", "gsrb_fused.hip", "resid_march.hip", "multi_march.hip", "full19.hip", "full19_march.hip", "full19_multi.hip", "full19_fused.hip", "projection.hip", "line_gsrb.hip", "amr_kernels.hip", "leptic_kernels.hip", "maps.hip", "metric_refresh.hip", "box_io.hip", "tuning.cpp", "level.cpp", "solver.cpp", "solver_full.cpp", "solver_multi.cpp", "amr.cpp", "leptic.cpp", "comm_rccl.cpp", "comm_shm.cpp", "capi.cpp"]
-HEADERS = ["common.h", "devbuf.h", "tuning.h", "kernels.h", "level.h", "march_plan.h", "outer_loop.h", "stencil_point.h", "solver.h", "amr.h", "leptic.h", os.path.join("..", "..", "include", "somar_amd.h")]
+HEADERS = ["common.h", "devbuf.h", "tuning.h", "kernels.h", "level.h", "march_plan.h", "outer_loop.h", "stencil_point.h", "full19_point.h", "full19_point.inc", "solver.h", "amr.h", "leptic.h", os.path.join("..", "..", "include", "somar_amd.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-result", "-Wno-unused-value", "-I/opt/rocm/include"]

@@ -328,6 +328,7 @@ __global__ __launch_bounds__(MAXT) void k_box_bicgstab(BoxBicg A)
         ++tk[5];
     };
     // one GSRB point update, 19-point: GSRBITER3D / GSRBBOUNDARYITER3D in k_gsrb_full's expression order, operands from the LDS copy
+    // (a copy of full19_point.h's text kept on purpose: it works from a precomputed diagonal and a flag mask, within this kernel's register budget)
     auto relax_cell_full = [&](int q, double rhsv) {
         const int f0 = fc[q];
 #define PN(di, dj, dk) Fp[f0 + (di) + m0 * (dj) + m01 * (dk)]

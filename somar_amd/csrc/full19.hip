@@ -4,8 +4,8 @@
 // Reference kernels restated here (arithmetic in the Fortran's order; -ffp-contract=off => bit-identical to
 // oracle/kernels.c):
 //   MAPPEDGETFLUX                 calculus/AMRElliptic/MappedAMRPoissonOpF.ChF:335-427
-//   GSRBITER3D                    calculus/AMRElliptic/RelaxationMethods/GSRBF.ChF:36-282
-//   GSRBBOUNDARYITER3D            .../GSRBF.ChF:1024-1253
+//   GSRBITER2D / GSRBBOUNDARYITER2D   calculus/AMRElliptic/RelaxationMethods/GSRBF.ChF:155-281 (the 3-D forms, and the
+//                                 operator's per-cell sequence: full19_point.h, which k_op_full and k_gsrb_full call)
 //   EXTRAPOLATEFACENOEV           calculus/extrapolation/ExtrapolationUtilsF.ChF:35-138
 //   ELLIPTICCONSTNEUMBCGHOST      calculus/BCInterface/EllipticBCUtilsF.ChF (cross-term Neumann ghost)
 // and the call sequences of fillExtrap (MappedAMRPoissonOp.cpp:2244-2270), RelaxationMethod::
@@ -18,6 +18,7 @@
 // colour pass, i.e. the cross terms lag -- reproduced as is.
 #include "common.h"
 #include "kernels.h"
+#include "full19_point.h"
 
 namespace somar {
 
@@ -25,8 +26,6 @@ __device__ __forceinline__ long long fidx(const PatchDesc& p, int i, int j, int 
 {
     return p.off + i + (long long)p.pj * j + p.pk * k;
 }
-
-struct JgFull { const double* c[3][3]; };  // c[faceDir][component]
 
 // ------------------------------------------------------------------------------------
 // ghost programs
@@ -219,6 +218,25 @@ __global__ __launch_bounds__(512) void k_flux_full(const Tile* __restrict__ tile
     }
 }
 
+// the coefficients of cell c from global memory (full19_point.h).  flat (SpaceDim 2): there are no z faces, their entries are
+// never used and not loaded
+__device__ __forceinline__ Full19Coef coef_at(const JgFull& J, const double* __restrict__ jinv, long long c, long long sj,
+                                              long long sk, bool flat)
+{
+    Full19Coef C;
+    C.x0l = J.c[0][0][c]; C.x0h = J.c[0][0][c + 1];
+    C.x1l = J.c[0][1][c]; C.x1h = J.c[0][1][c + 1];
+    C.x2l = J.c[0][2][c]; C.x2h = J.c[0][2][c + 1];
+    C.y0l = J.c[1][0][c]; C.y0h = J.c[1][0][c + sj];
+    C.y1l = J.c[1][1][c]; C.y1h = J.c[1][1][c + sj];
+    C.y2l = J.c[1][2][c]; C.y2h = J.c[1][2][c + sj];
+    C.z0l = flat ? 0.0 : J.c[2][0][c]; C.z0h = flat ? 0.0 : J.c[2][0][c + sk];
+    C.z1l = flat ? 0.0 : J.c[2][1][c]; C.z1h = flat ? 0.0 : J.c[2][1][c + sk];
+    C.z2l = flat ? 0.0 : J.c[2][2][c]; C.z2h = flat ? 0.0 : J.c[2][2][c + sk];
+    C.ji = jinv[c];
+    return C;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(512) void k_op_full(const Tile* __restrict__ tiles, const PatchDesc* __restrict__ patches,
                                                  double* __restrict__ out, const double* __restrict__ phi,
@@ -230,10 +248,8 @@ __global__ __launch_bounds__(512) void k_op_full(const Tile* __restrict__ tiles,
     const int lj = t.j0 + threadIdx.y;
     const int li0 = t.i0 + 2 * threadIdx.x;
     if (lj >= p.n[1] || li0 >= p.n[0]) return;
-    // aScale = beta / dx with beta = 1: the Fortran divides, it does not multiply by a reciprocal
-    const double dxi[3] = {1.0 / P.dx[0], 1.0 / P.dx[1], 1.0 / P.dx[2]};
-    const double dxinv[3] = {1.0 / P.dx[0], 1.0 / P.dx[1], 1.0 / P.dx[2]};
-    const long long st[3] = {1, (long long)p.pj, p.pk};
+    const Full19Scales S = full19_scales(P.dx[0], P.dx[1], P.dx[2]);
+    const long long sj = p.pj, sk = p.pk;
     const int gj = p.lo[1] + lj;
     const int npair = (li0 + 1 < p.n[0]) ? 2 : 1;
     for (int kk = 0; kk < t.nk; ++kk) {
@@ -243,20 +259,11 @@ __global__ __launch_bounds__(512) void k_op_full(const Tile* __restrict__ tiles,
             const int li = li0 + q;
             const int gi = p.lo[0] + li;
             const long long c = fidx(p, li, lj, lk);
-            double fl[3], fh[3];
-            const int g[3] = {gi, gj, gk};
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                fl[a] = flux19(phi, psi, J, c, a, st, dxi);
-                fh[a] = flux19(phi, psi, J, c + st[a], a, st, dxi);
-                // EllipticConstNeumBCFluxClass: boundary faces := 0 (homogeneous)
-                if (g[a] == P.dom_lo[a] && P.neum[a][0]) fl[a] = 0.0;
-                if (g[a] == P.dom_hi[a] && P.neum[a][1]) fh[a] = 0.0;
-                fl[a] *= P.beta;
-                fh[a] *= P.beta;
-            }
-            double l = jinv[c] * ((fh[0] - fl[0]) * dxinv[0] + (fh[1] - fl[1]) * dxinv[1] + (fh[2] - fl[2]) * dxinv[2]);
-            if (P.alpha != 0.0) l = P.alpha * phi[c] + 1.0 * l;
+            const auto Pn = [=](int di, int dj, int dk) { return phi[c + di + sj * dj + sk * dk]; };
+            const auto En = [=](int di, int dj, int dk) { return psi[c + di + sj * dj + sk * dk]; };
+            const Full19Coef C = coef_at(J, jinv, c, sj, sk, false);
+            const double l = full19_op(C, S, P.alpha, P.beta, phi[c], Pn, En, FULL19_NF(xl), FULL19_NF(xh), FULL19_NF(yl),
+                                       FULL19_NF(yh), FULL19_NF(zl), FULL19_NF(zh));
             out[c] = (MODE == 0) ? (rhs[c] - l) : l;
         }
     }
@@ -276,17 +283,11 @@ __global__ __launch_bounds__(512) void k_gsrb_full(const Tile* __restrict__ tile
     const int lj = t.j0 + threadIdx.y;
     const int li0 = t.i0 + 2 * threadIdx.x;
     if (lj >= p.n[1] || li0 >= p.n[0]) return;
-    const double xxScale = 1.0 / (P.dx[0] * P.dx[0]);
-    const double yyScale = 1.0 / (P.dx[1] * P.dx[1]);
-    const double zzScale = 1.0 / (P.dx[2] * P.dx[2]);
-    const double xyScale = 0.25 / (P.dx[0] * P.dx[1]);
-    const double yzScale = 0.25 / (P.dx[1] * P.dx[2]);
-    const double zxScale = 0.25 / (P.dx[2] * P.dx[0]);
+    const Full19Scales S = full19_scales(P.dx[0], P.dx[1], P.dx[2]);
     const long long sj = p.pj, sk = p.pk;
     const int gj = p.lo[1] + lj;
-    const double* Jx0 = J.c[0][0]; const double* Jx1 = J.c[0][1]; const double* Jx2 = J.c[0][2];
-    const double* Jy0 = J.c[1][0]; const double* Jy1 = J.c[1][1]; const double* Jy2 = J.c[1][2];
-    const double* Jz0 = J.c[2][0]; const double* Jz1 = J.c[2][1]; const double* Jz2 = J.c[2][2];
+    const double* Jx0 = J.c[0][0]; const double* Jx1 = J.c[0][1];
+    const double* Jy0 = J.c[1][0]; const double* Jy1 = J.c[1][1];
     for (int kk = 0; kk < t.nk; ++kk) {
         const int lk = t.k0 + kk;
         const int gk = p.lo[2] + lk;
@@ -308,73 +309,16 @@ __global__ __launch_bounds__(512) void k_gsrb_full(const Tile* __restrict__ tile
             const double JDyx = Jy0[c + sj] * (EE(1, 1, 0) - EE(-1, 1, 0) + EE(1, 0, 0) - EE(-1, 0, 0)) -
                                 Jy0[c] * (EE(1, 0, 0) - EE(-1, 0, 0) + EE(1, -1, 0) - EE(-1, -1, 0));
             const double JDyy = Jy1[c + sj] * phi[c + sj] + Jy1[c] * phi[c - sj];
-            const double lphi = P.beta * jinv[c] * (JDxx * xxScale + JDyy * yyScale + (JDxy + JDyx) * xyScale);
-            out = (rhs[c] - lphi) / (P.alpha + P.beta * lapd[c]);
-        } else if (!onb) {
-            const double pdx = EE(1, 0, 0) - EE(-1, 0, 0);
-            const double pdy = EE(0, 1, 0) - EE(0, -1, 0);
-            const double pdz = EE(0, 0, 1) - EE(0, 0, -1);
-            const double JDxx = Jx0[c + 1] * phi[c + 1] + Jx0[c] * phi[c - 1];
-            const double JDxy = Jx1[c + 1] * (EE(1, 1, 0) - EE(1, -1, 0) + pdy) - Jx1[c] * (pdy + EE(-1, 1, 0) - EE(-1, -1, 0));
-            const double JDxz = Jx2[c + 1] * (EE(1, 0, 1) - EE(1, 0, -1) + pdz) - Jx2[c] * (pdz + EE(-1, 0, 1) - EE(-1, 0, -1));
-            const double JDyx = Jy0[c + sj] * (EE(1, 1, 0) - EE(-1, 1, 0) + pdx) - Jy0[c] * (pdx + EE(1, -1, 0) - EE(-1, -1, 0));
-            const double JDyy = Jy1[c + sj] * phi[c + sj] + Jy1[c] * phi[c - sj];
-            const double JDyz = Jy2[c + sj] * (EE(0, 1, 1) - EE(0, 1, -1) + pdz) - Jy2[c] * (pdz + EE(0, -1, 1) - EE(0, -1, -1));
-            const double JDzx = Jz0[c + sk] * (EE(1, 0, 1) - EE(-1, 0, 1) + pdx) - Jz0[c] * (pdx + EE(1, 0, -1) - EE(-1, 0, -1));
-            const double JDzy = Jz1[c + sk] * (EE(0, 1, 1) - EE(0, -1, 1) + pdy) - Jz1[c] * (pdy + EE(0, 1, -1) - EE(0, -1, -1));
-            const double JDzz = Jz2[c + sk] * phi[c + sk] + Jz2[c] * phi[c - sk];
-            const double lphi = P.beta * jinv[c] *
-                                (JDxx * xxScale + JDyy * yyScale + JDzz * zzScale + (JDxy + JDyx) * xyScale +
-                                 (JDyz + JDzy) * yzScale + (JDzx + JDxz) * zxScale);
+            const double lphi = P.beta * jinv[c] * (JDxx * S.xx + JDyy * S.yy + (JDxy + JDyx) * S.xy);
             out = (rhs[c] - lphi) / (P.alpha + P.beta * lapd[c]);
         } else {
-            const bool nxl = (gi == P.dom_lo[0]) && P.neum[0][0];
-            const bool nxh = (gi == P.dom_hi[0]) && P.neum[0][1];
-            const bool nyl = (gj == P.dom_lo[1]) && P.neum[1][0];
-            const bool nyh = (gj == P.dom_hi[1]) && P.neum[1][1];
-            // flat: no z faces at all; the zx / yz terms of the x and y faces below multiply all-zero metric planes
-            const bool nzl = flat || ((gk == P.dom_lo[2]) && P.neum[2][0]);
-            const bool nzh = flat || ((gk == P.dom_hi[2]) && P.neum[2][1]);
-            double JDloX = 0, JDhiX = 0, JDloY = 0, JDhiY = 0, JDloZ = 0, JDhiZ = 0, ld = 0.0;
-            if (!nxl) {
-                JDloX = +xxScale * Jx0[c] * phi[c - 1] -
-                        xyScale * Jx1[c] * (EE(0, 1, 0) - EE(0, -1, 0) + EE(-1, 1, 0) - EE(-1, -1, 0)) -
-                        zxScale * Jx2[c] * (EE(0, 0, 1) - EE(0, 0, -1) + EE(-1, 0, 1) - EE(-1, 0, -1));
-                ld = ld - xxScale * Jx0[c];
-            }
-            if (!nxh) {
-                JDhiX = +xxScale * Jx0[c + 1] * phi[c + 1] +
-                        xyScale * Jx1[c + 1] * (EE(1, 1, 0) - EE(1, -1, 0) + EE(0, 1, 0) - EE(0, -1, 0)) +
-                        zxScale * Jx2[c + 1] * (EE(1, 0, 1) - EE(1, 0, -1) + EE(0, 0, 1) - EE(0, 0, -1));
-                ld = ld - xxScale * Jx0[c + 1];
-            }
-            if (!nyl) {
-                JDloY = -xyScale * Jy0[c] * (EE(1, 0, 0) - EE(-1, 0, 0) + EE(1, -1, 0) - EE(-1, -1, 0)) +
-                        yyScale * Jy1[c] * phi[c - sj] -
-                        yzScale * Jy2[c] * (EE(0, 0, 1) - EE(0, 0, -1) + EE(0, -1, 1) - EE(0, -1, -1));
-                ld = ld - yyScale * Jy1[c];
-            }
-            if (!nyh) {
-                JDhiY = +xyScale * Jy0[c + sj] * (EE(1, 1, 0) - EE(-1, 1, 0) + EE(1, 0, 0) - EE(-1, 0, 0)) +
-                        yyScale * Jy1[c + sj] * phi[c + sj] +
-                        yzScale * Jy2[c + sj] * (EE(0, 1, 1) - EE(0, 1, -1) + EE(0, 0, 1) - EE(0, 0, -1));
-                ld = ld - yyScale * Jy1[c + sj];
-            }
-            if (!nzl) {
-                JDloZ = -zxScale * Jz0[c] * (EE(1, 0, 0) - EE(-1, 0, 0) + EE(1, 0, -1) - EE(-1, 0, -1)) -
-                        yzScale * Jz1[c] * (EE(0, 1, 0) - EE(0, -1, 0) + EE(0, 1, -1) - EE(0, -1, -1)) +
-                        zzScale * Jz2[c] * phi[c - sk];
-                ld = ld - zzScale * Jz2[c];
-            }
-            if (!nzh) {
-                JDhiZ = +zxScale * Jz0[c + sk] * (EE(1, 0, 1) - EE(-1, 0, 1) + EE(1, 0, 0) - EE(-1, 0, 0)) +
-                        yzScale * Jz1[c + sk] * (EE(0, 1, 1) - EE(0, -1, 1) + EE(0, 1, 0) - EE(0, -1, 0)) +
-                        zzScale * Jz2[c + sk] * phi[c + sk];
-                ld = ld - zzScale * Jz2[c + sk];
-            }
-            ld = ld * jinv[c];
-            const double lphi = P.beta * jinv[c] * (JDloX + JDhiX + JDloY + JDhiY + JDloZ + JDhiZ);
-            out = (rhs[c] - lphi) / (P.alpha + P.beta * ld);
+            const auto Pn = [=](int di, int dj, int dk) { return phi[c + di + sj * dj + sk * dk]; };
+            const auto En = [=](int di, int dj, int dk) { return EE(di, dj, dk); };
+            const Full19Coef C = coef_at(J, jinv, c, sj, sk, flat);
+            // flat: no z faces at all; the zx / yz terms of the x and y faces multiply all-zero metric planes
+            if (!onb) out = full19_gsrb_interior(C, S, P.alpha, P.beta, rhs[c], lapd[c], Pn, En);
+            else out = full19_gsrb_boundary(C, S, P.alpha, P.beta, rhs[c], Pn, En, FULL19_NF(xl), FULL19_NF(xh), FULL19_NF(yl),
+                                            FULL19_NF(yh), flat || FULL19_NF(zl), flat || FULL19_NF(zh));
         }
 #undef EE
         phi[c] = out;
@@ -384,7 +328,7 @@ __global__ __launch_bounds__(512) void k_gsrb_full(const Tile* __restrict__ tile
 // ------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------
-static JgFull jgfull(const LevelDev& L)
+JgFull jgfull(const LevelDev& L)
 {
     JgFull J;
     for (int d = 0; d < 3; ++d)

@@ -29,9 +29,15 @@
 // 132 B/cell.  A second register set to prefetch the next plane (which would overlap the two) does not fit in 256 VGPRs.  The
 // path therefore stays OFF by default (Tuning::fused19_min_box < 0; SOMAR_FUSED19_MIN_BOX=0 forces it for the parity tests).
 //
-// Arithmetic: GSRBITER3D / GSRBBOUNDARYITER3D's expression order as in k_full_march<2> (GSRBF.ChF:36-282, 1024-1253): same bits.
+// Arithmetic: the interior and boundary GSRB update of full19_point.inc, STANDING TWICE: this kernel keeps its own copy of the
+// two blocks (red) and of the interior block again (black, on the values after the red pass and the coefficients captured a
+// plane earlier).  With the shared text included in place its instructions were no longer the parent's (register numbers
+// from the prologue on) and the path, off by default, was not timed again; profiles/r16_full19_one_text.md.  A change to
+// full19_point.inc's parts 2 and 3 has to be made here as well; tests/test_gpu_full.py and test_gpu_amr_full.py hold this
+// kernel against k_full_march<2> and the oracle bit for bit.
 #include "common.h"
 #include "kernels.h"
+#include "stencil_point.h"
 
 namespace somar {
 
@@ -39,20 +45,11 @@ constexpr int FF_J = 8;   // region rows: 1 halo + 1 red ring + 4 output rows + 
 constexpr int FF_S = 4;   // plane slots
 constexpr int FF_I = 128;
 
-struct JgFullF { const double* c[3][3]; };
-
-__device__ __forceinline__ double2 ff_ld2(const double* __restrict__ a, long long idx, bool ok0, bool ok1, long long safe)
-{
-    const double2 v = *reinterpret_cast<const double2*>(a + ((ok0 || ok1) ? idx : safe));
-    return make_double2(ok0 ? v.x : 0.0, ok1 ? v.y : 0.0);
-}
-__device__ __forceinline__ double ff_pick(const double2& v, int s) { return s ? v.y : v.x; }
-
 template <bool ZXY>
 __global__ __launch_bounds__(64 * FF_J) void k_full_fused(const Tile* __restrict__ tiles, const PatchDesc* __restrict__ patches,
                                                           double* __restrict__ out, const double* __restrict__ phi,
                                                           const double* __restrict__ psi, const double* __restrict__ rhs,
-                                                          JgFullF J, const double* __restrict__ jinv, StencilParams P)
+                                                          JgFull J, const double* __restrict__ jinv, StencilParams P)
 {
     __shared__ __attribute__((aligned(16))) double SP[FF_S][FF_J][FF_I];  // phi, old
     __shared__ __attribute__((aligned(16))) double SE[FF_S][FF_J][FF_I];  // E, old: phi inside the box, psi in its frame
@@ -108,9 +105,9 @@ __global__ __launch_bounds__(64 * FF_J) void k_full_fused(const Tile* __restrict
         const bool fk = (kp >= -1) && (kp <= p.n[2]);
         const bool ink = (kp >= 0) && (kp < p.n[2]);
         const long long idx = base + sk * kp;
-        vp = ff_ld2(phi, idx, f0 && fk, f1 && fk, p.off);
+        vp = ld2<double>(phi, idx, f0 && fk, f1 && fk, p.off);
         const bool e0 = f0 && fk && !(in0 && ink), e1 = f1 && fk && !(in1 && ink);   // frame cells: E = psi
-        const double2 vs = ff_ld2(psi, idx, e0, e1, p.off);
+        const double2 vs = ld2<double>(psi, idx, e0, e1, p.off);
         ve = make_double2(e0 ? vs.x : vp.x, e1 ? vs.y : vp.y);
     };
     auto store_plane = [&](int kp, const double2& vp, const double2& ve) {
@@ -132,9 +129,9 @@ __global__ __launch_bounds__(64 * FF_J) void k_full_fused(const Tile* __restrict
     }
     // k-face components on the LOW face of plane k
     const bool ck0 = (k >= 0) && (k <= p.n[2]);
-    double2 Jz0c = ff_ld2(J.c[2][0], base + sk * k, c[0] && ck0, c[1] && ck0, p.off);
-    double2 Jz1c = ff_ld2(J.c[2][1], base + sk * k, c[0] && ck0, c[1] && ck0, p.off);
-    double2 Jz2c = ff_ld2(J.c[2][2], base + sk * k, c[0] && ck0, c[1] && ck0, p.off);
+    double2 Jz0c = ld2<double>(J.c[2][0], base + sk * k, c[0] && ck0, c[1] && ck0, p.off);
+    double2 Jz1c = ld2<double>(J.c[2][1], base + sk * k, c[0] && ck0, c[1] && ck0, p.off);
+    double2 Jz2c = ld2<double>(J.c[2][2], base + sk * k, c[0] && ck0, c[1] && ck0, p.off);
     // the black cell of plane k-1: its coefficients (captured one step earlier) and the pair's values after the red pass
     double b_jx0l = 0, b_jx0h = 0, b_jx1l = 0, b_jx1h = 0, b_jx2l = 0, b_jx2h = 0;
     double b_jy0l = 0, b_jy0h = 0, b_jy1l = 0, b_jy1h = 0, b_jy2l = 0, b_jy2h = 0;
@@ -151,20 +148,20 @@ __global__ __launch_bounds__(64 * FF_J) void k_full_fused(const Tile* __restrict
         load_plane(k + 1, vp, ve);
         const long long ck = base + sk * k;
         const bool a0 = c[0] && ink, a1 = c[1] && ink;
-        const double2 Jz0p = ff_ld2(J.c[2][0], ck + sk, c[0] && inkp, c[1] && inkp, p.off);
-        const double2 Jz1p = ff_ld2(J.c[2][1], ck + sk, c[0] && inkp, c[1] && inkp, p.off);
-        const double2 Jz2p = ff_ld2(J.c[2][2], ck + sk, c[0] && inkp, c[1] && inkp, p.off);
-        const double2 Rh = ff_ld2(rhs, ck, a0, a1, p.off);
-        const double2 Ji = ff_ld2(jinv, ck, a0, a1, p.off);
-        const double2 Jx0 = ff_ld2(J.c[0][0], ck, gxc0 && ink, anyc && ink, p.off);
-        const double2 Jx1 = ZXY ? make_double2(0.0, 0.0) : ff_ld2(J.c[0][1], ck, gxc0 && ink, anyc && ink, p.off);
-        const double2 Jx2 = ff_ld2(J.c[0][2], ck, gxc0 && ink, anyc && ink, p.off);
-        const double2 Jy0 = ZXY ? make_double2(0.0, 0.0) : ff_ld2(J.c[1][0], ck, a0, a1, p.off);
-        const double2 Jy1 = ff_ld2(J.c[1][1], ck, a0, a1, p.off);
-        const double2 Jy2 = ff_ld2(J.c[1][2], ck, a0, a1, p.off);
-        const double2 Jy0h = ZXY ? make_double2(0.0, 0.0) : ff_ld2(J.c[1][0], ck + sj, a0, a1, p.off);
-        const double2 Jy1h = ff_ld2(J.c[1][1], ck + sj, a0, a1, p.off);
-        const double2 Jy2h = ff_ld2(J.c[1][2], ck + sj, a0, a1, p.off);
+        const double2 Jz0p = ld2<double>(J.c[2][0], ck + sk, c[0] && inkp, c[1] && inkp, p.off);
+        const double2 Jz1p = ld2<double>(J.c[2][1], ck + sk, c[0] && inkp, c[1] && inkp, p.off);
+        const double2 Jz2p = ld2<double>(J.c[2][2], ck + sk, c[0] && inkp, c[1] && inkp, p.off);
+        const double2 Rh = ld2<double>(rhs, ck, a0, a1, p.off);
+        const double2 Ji = ld2<double>(jinv, ck, a0, a1, p.off);
+        const double2 Jx0 = ld2<double>(J.c[0][0], ck, gxc0 && ink, anyc && ink, p.off);
+        const double2 Jx1 = ZXY ? make_double2(0.0, 0.0) : ld2<double>(J.c[0][1], ck, gxc0 && ink, anyc && ink, p.off);
+        const double2 Jx2 = ld2<double>(J.c[0][2], ck, gxc0 && ink, anyc && ink, p.off);
+        const double2 Jy0 = ZXY ? make_double2(0.0, 0.0) : ld2<double>(J.c[1][0], ck, a0, a1, p.off);
+        const double2 Jy1 = ld2<double>(J.c[1][1], ck, a0, a1, p.off);
+        const double2 Jy2 = ld2<double>(J.c[1][2], ck, a0, a1, p.off);
+        const double2 Jy0h = ZXY ? make_double2(0.0, 0.0) : ld2<double>(J.c[1][0], ck + sj, a0, a1, p.off);
+        const double2 Jy1h = ld2<double>(J.c[1][1], ck + sj, a0, a1, p.off);
+        const double2 Jy2h = ld2<double>(J.c[1][2], ck + sj, a0, a1, p.off);
         const double jx0n = __shfl_down(Jx0.x, 1, 64), jx1n = __shfl_down(Jx1.x, 1, 64), jx2n = __shfl_down(Jx2.x, 1, 64);
 
         store_plane(k + 1, vp, ve);
@@ -177,30 +174,30 @@ __global__ __launch_bounds__(64 * FF_J) void k_full_fused(const Tile* __restrict
         const double jx0l = (s) ? Jx0.y : Jx0.x, jx0h = (s) ? jx0n : Jx0.y;                                                  \
         const double jx1l = (s) ? Jx1.y : Jx1.x, jx1h = (s) ? jx1n : Jx1.y;                                                  \
         const double jx2l = (s) ? Jx2.y : Jx2.x, jx2h = (s) ? jx2n : Jx2.y;                                                  \
-        const double jy0l = ff_pick(Jy0, s), jy0h = ff_pick(Jy0h, s);                                                        \
-        const double jy1l = ff_pick(Jy1, s), jy1h = ff_pick(Jy1h, s);                                                        \
-        const double jy2l = ff_pick(Jy2, s), jy2h = ff_pick(Jy2h, s);                                                        \
-        const double jz0l = ff_pick(Jz0c, s), jz0h = ff_pick(Jz0p, s);                                                       \
-        const double jz1l = ff_pick(Jz1c, s), jz1h = ff_pick(Jz1p, s);                                                       \
-        const double jz2l = ff_pick(Jz2c, s), jz2h = ff_pick(Jz2p, s);
+        const double jy0l = pick<double>(Jy0, s), jy0h = pick<double>(Jy0h, s);                                                        \
+        const double jy1l = pick<double>(Jy1, s), jy1h = pick<double>(Jy1h, s);                                                        \
+        const double jy2l = pick<double>(Jy2, s), jy2h = pick<double>(Jy2h, s);                                                        \
+        const double jz0l = pick<double>(Jz0c, s), jz0h = pick<double>(Jz0p, s);                                                       \
+        const double jz1l = pick<double>(Jz1c, s), jz1h = pick<double>(Jz1p, s);                                                       \
+        const double jz2l = pick<double>(Jz2c, s), jz2h = pick<double>(Jz2p, s);
         // ---- red(k): the two-pass kernel's colour-0 update, from the OLD values ----
         double2 U = Pc;
         if (anyc && ink && c[csel]) {
             const int s = csel;
             const int rc = ri + s;
-            const double pc = ff_pick(Pc, s);
+            const double pc = pick<double>(Pc, s);
             const int gi = p.lo[0] + li + s;
 #define Pn(di, dj, dk) SP[(dk) < 0 ? sm : ((dk) > 0 ? sp : sc)][row + (dj)][rc + (di)]
 #define En(di, dj, dk) SE[(dk) < 0 ? sm : ((dk) > 0 ? sp : sc)][row + (dj)][rc + (di)]
             FF_COEF(s, jx0l, jx0h, jx1l, jx1h, jx2l, jx2h, jy0l, jy0h, jy1l, jy1h, jy2l, jy2h, jz0l, jz0h, jz1l, jz1h, jz2l, jz2h)
-            const double ji = ff_pick(Ji, s);
-            const double rh = ff_pick(Rh, s);
+            const double ji = pick<double>(Ji, s);
+            const double rh = pick<double>(Rh, s);
             (void)pc;
             const bool onb = (gi == P.dom_lo[0]) || (gi == P.dom_hi[0]) || (gj == P.dom_lo[1]) || (gj == P.dom_hi[1]) ||
                              (gk == P.dom_lo[2]) || (gk == P.dom_hi[2]);
             double r;
             if (!onb) {
-                // GSRBITER3D (GSRBF.ChF:36-282)
+                // full19_point.inc part 2 (GSRBITER3D), a copy
                 const double pdx = En(1, 0, 0) - En(-1, 0, 0);
                 const double pdy = En(0, 1, 0) - En(0, -1, 0);
                 const double pdz = En(0, 0, 1) - En(0, 0, -1);
@@ -219,7 +216,7 @@ __global__ __launch_bounds__(64 * FF_J) void k_full_fused(const Tile* __restrict
                 const double lapd = -ji * ((jx0h + jx0l) * xxScale + (jy1h + jy1l) * yyScale + (jz2h + jz2l) * zzScale);
                 r = (rh - lphi) / (P.alpha + P.beta * lapd);
             } else {
-                // GSRBBOUNDARYITER3D (GSRBF.ChF:1024-1253)
+                // full19_point.inc part 3 (GSRBBOUNDARYITER3D), a copy
                 const bool nxl = (gi == P.dom_lo[0]) && P.neum[0][0];
                 const bool nxh = (gi == P.dom_hi[0]) && P.neum[0][1];
                 const bool nyl = (gj == P.dom_lo[1]) && P.neum[1][0];
@@ -286,7 +283,7 @@ __global__ __launch_bounds__(64 * FF_J) void k_full_fused(const Tile* __restrict
                     const int rc = ri + s;
                     const int um = (kb - 1) & (FF_S - 1), uc = kb & (FF_S - 1), up = (kb + 1) & (FF_S - 1);
 #define Un(di, dj, dk) SU[(dk) < 0 ? um : ((dk) > 0 ? up : uc)][row + (dj)][rc + (di)]
-                    // GSRBITER3D: three layers inside a box no cell touches a domain face
+                    // full19_point.inc part 2 again, a copy: three layers inside a box no cell touches a domain face
                     const double pdx = Un(1, 0, 0) - Un(-1, 0, 0);
                     const double pdy = Un(0, 1, 0) - Un(0, -1, 0);
                     const double pdz = Un(0, 0, 1) - Un(0, 0, -1);
@@ -321,8 +318,8 @@ __global__ __launch_bounds__(64 * FF_J) void k_full_fused(const Tile* __restrict
             b_jx0l = jx0l; b_jx0h = jx0h; b_jx1l = jx1l; b_jx1h = jx1h; b_jx2l = jx2l; b_jx2h = jx2h;
             b_jy0l = jy0l; b_jy0h = jy0h; b_jy1l = jy1l; b_jy1h = jy1h; b_jy2l = jy2l; b_jy2h = jy2h;
             b_jz0l = jz0l; b_jz0h = jz0h; b_jz1l = jz1l; b_jz1h = jz1h; b_jz2l = jz2l; b_jz2h = jz2h;
-            b_ji = ff_pick(Ji, s);
-            b_rh = ff_pick(Rh, s);
+            b_ji = pick<double>(Ji, s);
+            b_rh = pick<double>(Rh, s);
         }
 #undef FF_COEF
         Uprev = U;
@@ -337,15 +334,12 @@ void launch_full_fused(hipStream_t st, TileSpan tiles, const LevelDev& L, double
                        const double* psi, const double* rhs)
 {
     if (tiles.n == 0) return;
-    JgFullF J;
-    for (int d = 0; d < 3; ++d)
-        for (int c = 0; c < 3; ++c) J.c[d][c] = L.jgf[d][c];
     if (L.P.zero_xy)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_full_fused<true>), dim3(tiles.n), dim3(64, FF_J, 1), 0, st, tiles.p, L.patches, out, phi,
-                           psi, rhs, J, L.jinv, L.P);
+                           psi, rhs, jgfull(L), L.jinv, L.P);
     else
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_full_fused<false>), dim3(tiles.n), dim3(64, FF_J, 1), 0, st, tiles.p, L.patches, out, phi,
-                           psi, rhs, J, L.jinv, L.P);
+                           psi, rhs, jgfull(L), L.jinv, L.P);
 }
 
 }  // namespace somar

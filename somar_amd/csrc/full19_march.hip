@@ -11,7 +11,8 @@
 //   * psi is never copied: E = phi inside the box, psi only in the one-cell FRAME around it -- the only place where
 //     the reference's `extrap` FAB differs from phi (extrapolated out-of-domain ghosts, and the box-edge cells
 //     ExtrapolateFaceAndCopy rewrites; see solver_full.cpp: the frame-only ghost programs);
-//   * lapDiag is recomputed from the diagonal components with FILLMAPPEDLAPDIAG3D's own expression (same bits);
+//   * lapDiag is recomputed from the diagonal components with FILLMAPPEDLAPDIAG3D's own expression (the stored array's bits
+//     wherever the coefficient arrays still are what k_lapdiag read: full19_point.h);
 //   * the colour pass writes a second array (updated cells of the colour + untouched cells of the other): the
 //     same-colour diagonal neighbours a cross term reads must be PRE-pass values (the reference reads them from the
 //     snapshot `extrap`), which an in-place update cannot give a neighbouring workgroup.
@@ -19,12 +20,12 @@
 // same without rhs -> with it: ~106 B per pass, 212 per red+black sweep (algorithmic 120; the two-pass form reads every
 // coefficient line once per colour).
 //
-// Arithmetic: the expression order of k_op_full / k_gsrb_full (= MAPPEDGETFLUX + zero Neumann flux + flux *= beta +
-// MAPPEDFLUXDIVERGENCE3D + AXBYIP + SUBTRACTOP; GSRBITER3D / GSRBBOUNDARYITER3D) => bit-identical to them and to the
-// CPU oracle.  Reference: calculus/AMRElliptic/MappedAMRPoissonOpF.ChF:335-427, RelaxationMethods/GSRBF.ChF:36-282,
-// 1024-1253.
+// Arithmetic: the text of full19_point.h (operator, interior and boundary GSRB update of one cell), which k_op_full /
+// k_gsrb_full call and the N-field and fused kernels share => bit-identical to them and to the CPU oracle.
 #include "common.h"
 #include "kernels.h"
+#include "stencil_point.h"
+#include "full19_point.h"
 
 namespace somar {
 
@@ -33,23 +34,6 @@ namespace somar {
 // workgroups per CU = 12 waves, the occupancy limit, for 1.5 instead of 1.33 times the phi / psi halo traffic -- 1.4 B/cell
 // of about 106).  SOMAR_FULL_ROWS selects; the tile tables follow (Level::define).
 constexpr int FM_S = 4;    // plane slots: k-1, k, k+1 are read while k+2's slot is being written
-
-struct JgFullM { const double* c[3][3]; };  // c[faceDir][component]
-
-__device__ __forceinline__ double2 fm_ld2(const double* __restrict__ a, long long idx, bool ok0, bool ok1, long long safe)
-{
-    // branch-free predicated pair load (see resid_march.hip)
-#ifdef SOMAR_NT_LOADS
-    // streamed once per launch: keep the coefficient / right-hand-side lines out of the way of the phi halo reuse in L2
-    typedef double v2d_ __attribute__((ext_vector_type(2)));
-    const v2d_ w = __builtin_nontemporal_load(reinterpret_cast<const v2d_*>(a + ((ok0 || ok1) ? idx : safe)));
-    const double2 v = make_double2(w.x, w.y);
-#else
-    const double2 v = *reinterpret_cast<const double2*>(a + ((ok0 || ok1) ? idx : safe));
-#endif
-    return make_double2(ok0 ? v.x : 0.0, ok1 ? v.y : 0.0);
-}
-__device__ __forceinline__ double fm_pick(const double2& v, int s) { return s ? v.y : v.x; }
 
 // MODE 0: out = rhs - L[phi]   MODE 1: out = L[phi]   MODE 2: out = phi with the cells of `color` relaxed (one GSRB pass)
 // MODE 3: the colour pass on the cells of the three outer layers of each box only, in place, after k_full_fused (see there)
@@ -65,7 +49,7 @@ template <int MODE, int FM_J, bool ZXY, int CLS>
 __device__ __forceinline__ void full_march_body(double* __restrict__ SP, double* __restrict__ SE, const Tile& t,
                                                 const PatchDesc& p, double* __restrict__ out,
                                                 const double* __restrict__ phi, const double* __restrict__ psi,
-                                                const double* __restrict__ rhs, const JgFullM& J,
+                                                const double* __restrict__ rhs, const JgFull& J,
                                                 const double* __restrict__ jinv, const StencilParams& P, int color,
                                                 const double* __restrict__ phi2)
 {
@@ -104,33 +88,24 @@ __device__ __forceinline__ void full_march_body(double* __restrict__ SP, double*
     const long long sj = p.pj, sk = p.pk;
     const long long base = p.off + li + sj * lj;
 
-    const double dxi0 = 1.0 / P.dx[0], dxi1 = 1.0 / P.dx[1], dxi2 = 1.0 / P.dx[2];
-    // MAPPEDGETFLUX's scales with beta = a_ref = 1: aScale = 1.0 * dxi[a], b/cScale = 0.25 * 1.0 * dxi[b/c]
-    const double a0 = 1.0 * dxi0, a1 = 1.0 * dxi1, a2 = 1.0 * dxi2;
-    const double q0 = 0.25 * 1.0 * dxi0, q1 = 0.25 * 1.0 * dxi1, q2 = 0.25 * 1.0 * dxi2;
-    const double xxScale = 1.0 / (P.dx[0] * P.dx[0]);
-    const double yyScale = 1.0 / (P.dx[1] * P.dx[1]);
-    const double zzScale = 1.0 / (P.dx[2] * P.dx[2]);
-    const double xyScale = 0.25 / (P.dx[0] * P.dx[1]);
-    const double yzScale = 0.25 / (P.dx[1] * P.dx[2]);
-    const double zxScale = 0.25 / (P.dx[2] * P.dx[0]);
+    const Full19Scales S = full19_scales(P.dx[0], P.dx[1], P.dx[2]);
 
     // stage plane kp of phi and E into its slot (global loads first, LDS writes by the caller's schedule)
     auto load_plane = [&](int kp, double2& vp, double2& ve) {
         const bool fk = (kp >= -1) && (kp <= p.n[2]);
         const bool ink = (kp >= 0) && (kp < p.n[2]);
         const long long idx = base + sk * kp;
-        vp = fm_ld2(phi, idx, f0 && fk, f1 && fk, p.off);
+        vp = ld2<double>(phi, idx, f0 && fk, f1 && fk, p.off);
         if (MODE == 3) {
             // the pass's colour INSIDE the box comes from phi2 (the sweep's input: the pre-pass value of a cell the fused kernel
             // may already have relaxed), everything else -- the other colour, every ghost cell -- from phi
             const int cs = (p.lo[0] + li + gj + p.lo[2] + kp + color) & 1;
             const bool m0 = in0 && ink && cs == 0, m1 = in1 && ink && cs == 1;
-            const double2 vq = fm_ld2(phi2, idx, m0, m1, p.off);
+            const double2 vq = ld2<double>(phi2, idx, m0, m1, p.off);
             vp = make_double2(m0 ? vq.x : vp.x, m1 ? vq.y : vp.y);
         }
         const bool e0 = f0 && fk && !(in0 && ink), e1 = f1 && fk && !(in1 && ink);   // frame cells: E = psi
-        const double2 vs = fm_ld2(psi, idx, e0, e1, p.off);
+        const double2 vs = ld2<double>(psi, idx, e0, e1, p.off);
         ve = make_double2(e0 ? vs.x : vp.x, e1 ? vs.y : vp.y);
     };
     auto store_plane = [&](int kp, const double2& vp, const double2& ve) {
@@ -149,9 +124,9 @@ __device__ __forceinline__ void full_march_body(double* __restrict__ SP, double*
         store_plane(k, vp, ve);
     }
     // k-face components on the LOW face of plane k
-    double2 Jz0c = fm_ld2(J.c[2][0], base + sk * k, o[0], o[1], p.off);
-    double2 Jz1c = fm_ld2(J.c[2][1], base + sk * k, o[0], o[1], p.off);
-    double2 Jz2c = fm_ld2(J.c[2][2], base + sk * k, o[0], o[1], p.off);
+    double2 Jz0c = ld2<double>(J.c[2][0], base + sk * k, o[0], o[1], p.off);
+    double2 Jz1c = ld2<double>(J.c[2][1], base + sk * k, o[0], o[1], p.off);
+    double2 Jz2c = ld2<double>(J.c[2][2], base + sk * k, o[0], o[1], p.off);
 
     for (; k < kend; ++k) {
         const int gk = p.lo[2] + k;
@@ -159,21 +134,21 @@ __device__ __forceinline__ void full_march_body(double* __restrict__ SP, double*
         double2 vp, ve;
         load_plane(k + 1, vp, ve);
         const long long ck = base + sk * k;
-        const double2 Jz0p = fm_ld2(J.c[2][0], ck + sk, o[0], o[1], p.off);
-        const double2 Jz1p = fm_ld2(J.c[2][1], ck + sk, o[0], o[1], p.off);
-        const double2 Jz2p = fm_ld2(J.c[2][2], ck + sk, o[0], o[1], p.off);
+        const double2 Jz0p = ld2<double>(J.c[2][0], ck + sk, o[0], o[1], p.off);
+        const double2 Jz1p = ld2<double>(J.c[2][1], ck + sk, o[0], o[1], p.off);
+        const double2 Jz2p = ld2<double>(J.c[2][2], ck + sk, o[0], o[1], p.off);
         double2 Rh = make_double2(0.0, 0.0);
-        if (MODE != 1) Rh = fm_ld2(rhs, ck, o[0], o[1], p.off);
-        const double2 Ji = fm_ld2(jinv, ck, o[0], o[1], p.off);
-        const double2 Jx0 = fm_ld2(J.c[0][0], ck, gxo0, any, p.off);
-        const double2 Jx1 = ZXY ? make_double2(0.0, 0.0) : fm_ld2(J.c[0][1], ck, gxo0, any, p.off);
-        const double2 Jx2 = fm_ld2(J.c[0][2], ck, gxo0, any, p.off);
-        const double2 Jy0 = ZXY ? make_double2(0.0, 0.0) : fm_ld2(J.c[1][0], ck, o[0], o[1], p.off);
-        const double2 Jy1 = fm_ld2(J.c[1][1], ck, o[0], o[1], p.off);
-        const double2 Jy2 = fm_ld2(J.c[1][2], ck, o[0], o[1], p.off);
-        const double2 Jy0h = ZXY ? make_double2(0.0, 0.0) : fm_ld2(J.c[1][0], ck + sj, o[0], o[1], p.off);
-        const double2 Jy1h = fm_ld2(J.c[1][1], ck + sj, o[0], o[1], p.off);
-        const double2 Jy2h = fm_ld2(J.c[1][2], ck + sj, o[0], o[1], p.off);
+        if (MODE != 1) Rh = ld2<double>(rhs, ck, o[0], o[1], p.off);
+        const double2 Ji = ld2<double>(jinv, ck, o[0], o[1], p.off);
+        const double2 Jx0 = ld2<double>(J.c[0][0], ck, gxo0, any, p.off);
+        const double2 Jx1 = ZXY ? make_double2(0.0, 0.0) : ld2<double>(J.c[0][1], ck, gxo0, any, p.off);
+        const double2 Jx2 = ld2<double>(J.c[0][2], ck, gxo0, any, p.off);
+        const double2 Jy0 = ZXY ? make_double2(0.0, 0.0) : ld2<double>(J.c[1][0], ck, o[0], o[1], p.off);
+        const double2 Jy1 = ld2<double>(J.c[1][1], ck, o[0], o[1], p.off);
+        const double2 Jy2 = ld2<double>(J.c[1][2], ck, o[0], o[1], p.off);
+        const double2 Jy0h = ZXY ? make_double2(0.0, 0.0) : ld2<double>(J.c[1][0], ck + sj, o[0], o[1], p.off);
+        const double2 Jy1h = ld2<double>(J.c[1][1], ck + sj, o[0], o[1], p.off);
+        const double2 Jy2h = ld2<double>(J.c[1][2], ck + sj, o[0], o[1], p.off);
         const double jx0n = __shfl_down(Jx0.x, 1, 64), jx1n = __shfl_down(Jx1.x, 1, 64), jx2n = __shfl_down(Jx2.x, 1, 64);
 
         store_plane(k + 1, vp, ve);
@@ -198,124 +173,37 @@ __device__ __forceinline__ void full_march_body(double* __restrict__ SP, double*
                 // neighbours: Pn(di,dj,dk) = phi, En(di,dj,dk) = E
 #define Pn(di, dj, dk) SPx((dk) < 0 ? sm : ((dk) > 0 ? sp : sc), row + (dj), rc + (di))
 #define En(di, dj, dk) SEx((dk) < 0 ? sm : ((dk) > 0 ? sp : sc), row + (dj), rc + (di))
+#define CF(n) C.n
+#define SC(n) S.n
+#define NEU(f) FULL19_NF(f)
+#define F19_RESULT(v) res[s] = v
+                // full19_point.inc in place reads, from this scope: C and S (through CF, SC), alpha, beta, pc (operator) or rh (updates),
+                // and P, gi, gj, gk (through FULL19_NF / FULL19_ONB); FULL19_PICK reads Jx0..Jx2, jx0n..jx2n, Jy0..Jy2h, Jz0c..Jz2p, Ji
                 // coefficients on the low / high face of this cell
-                const double jx0l = s ? Jx0.y : Jx0.x, jx0h = s ? jx0n : Jx0.y;
-                const double jx1l = s ? Jx1.y : Jx1.x, jx1h = s ? jx1n : Jx1.y;
-                const double jx2l = s ? Jx2.y : Jx2.x, jx2h = s ? jx2n : Jx2.y;
-                const double jy0l = fm_pick(Jy0, s), jy0h = fm_pick(Jy0h, s);
-                const double jy1l = fm_pick(Jy1, s), jy1h = fm_pick(Jy1h, s);
-                const double jy2l = fm_pick(Jy2, s), jy2h = fm_pick(Jy2h, s);
-                const double jz0l = fm_pick(Jz0c, s), jz0h = fm_pick(Jz0p, s);
-                const double jz1l = fm_pick(Jz1c, s), jz1h = fm_pick(Jz1p, s);
-                const double jz2l = fm_pick(Jz2c, s), jz2h = fm_pick(Jz2p, s);
-                const double ji = fm_pick(Ji, s);
+                Full19Coef C;
+                FULL19_PICK(C, s);
+                const double alpha = P.alpha, beta = P.beta;
                 if (MODE < 2) {
-                    // flux19 (full19.hip) at the six faces: direction a, then b = a+1, c = a+2 (cyclic)
-                    double fxl = a0 * jx0l * (pc - Pn(-1, 0, 0)) +
-                                 q1 * jx1l * (En(0, 1, 0) - En(0, -1, 0) + En(-1, 1, 0) - En(-1, -1, 0)) +
-                                 q2 * jx2l * (En(0, 0, 1) - En(0, 0, -1) + En(-1, 0, 1) - En(-1, 0, -1));
-                    double fxh = a0 * jx0h * (Pn(1, 0, 0) - pc) +
-                                 q1 * jx1h * (En(1, 1, 0) - En(1, -1, 0) + En(0, 1, 0) - En(0, -1, 0)) +
-                                 q2 * jx2h * (En(1, 0, 1) - En(1, 0, -1) + En(0, 0, 1) - En(0, 0, -1));
-                    double fyl = a1 * jy1l * (pc - Pn(0, -1, 0)) +
-                                 q2 * jy2l * (En(0, 0, 1) - En(0, 0, -1) + En(0, -1, 1) - En(0, -1, -1)) +
-                                 q0 * jy0l * (En(1, 0, 0) - En(-1, 0, 0) + En(1, -1, 0) - En(-1, -1, 0));
-                    double fyh = a1 * jy1h * (Pn(0, 1, 0) - pc) +
-                                 q2 * jy2h * (En(0, 1, 1) - En(0, 1, -1) + En(0, 0, 1) - En(0, 0, -1)) +
-                                 q0 * jy0h * (En(1, 1, 0) - En(-1, 1, 0) + En(1, 0, 0) - En(-1, 0, 0));
-                    double fzl = a2 * jz2l * (pc - Pn(0, 0, -1)) +
-                                 q0 * jz0l * (En(1, 0, 0) - En(-1, 0, 0) + En(1, 0, -1) - En(-1, 0, -1)) +
-                                 q1 * jz1l * (En(0, 1, 0) - En(0, -1, 0) + En(0, 1, -1) - En(0, -1, -1));
-                    double fzh = a2 * jz2h * (Pn(0, 0, 1) - pc) +
-                                 q0 * jz0h * (En(1, 0, 1) - En(-1, 0, 1) + En(1, 0, 0) - En(-1, 0, 0)) +
-                                 q1 * jz1h * (En(0, 1, 1) - En(0, -1, 1) + En(0, 1, 0) - En(0, -1, 0));
-                    // EllipticConstNeumBCFluxClass: boundary faces := 0 (homogeneous)
-                    if (gi == P.dom_lo[0] && P.neum[0][0]) fxl = 0.0;
-                    if (gi == P.dom_hi[0] && P.neum[0][1]) fxh = 0.0;
-                    if (gj == P.dom_lo[1] && P.neum[1][0]) fyl = 0.0;
-                    if (gj == P.dom_hi[1] && P.neum[1][1]) fyh = 0.0;
-                    if (gk == P.dom_lo[2] && P.neum[2][0]) fzl = 0.0;
-                    if (gk == P.dom_hi[2] && P.neum[2][1]) fzh = 0.0;
-                    fxl *= P.beta; fxh *= P.beta; fyl *= P.beta; fyh *= P.beta; fzl *= P.beta; fzh *= P.beta;
-                    double l = ji * ((fxh - fxl) * dxi0 + (fyh - fyl) * dxi1 + (fzh - fzl) * dxi2);
-                    if (P.alpha != 0.0) l = P.alpha * pc + 1.0 * l;
-                    res[s] = (MODE == 0) ? (fm_pick(Rh, s) - l) : l;
+#define FULL19_PART 1
+#include "full19_point.inc"
+                    res[s] = (MODE == 0) ? (pick<double>(Rh, s) - l) : l;
                 } else {
-                    const bool onb = (gi == P.dom_lo[0]) || (gi == P.dom_hi[0]) || (gj == P.dom_lo[1]) ||
-                                     (gj == P.dom_hi[1]) || (gk == P.dom_lo[2]) || (gk == P.dom_hi[2]);
-                    const double rh = fm_pick(Rh, s);
+                    const bool onb = FULL19_ONB;
+                    const double rh = pick<double>(Rh, s);
                     if (!onb) {
-                        // GSRBITER3D (GSRBF.ChF:36-282)
-                        const double pdx = En(1, 0, 0) - En(-1, 0, 0);
-                        const double pdy = En(0, 1, 0) - En(0, -1, 0);
-                        const double pdz = En(0, 0, 1) - En(0, 0, -1);
-                        const double JDxx = jx0h * Pn(1, 0, 0) + jx0l * Pn(-1, 0, 0);
-                        const double JDxy = jx1h * (En(1, 1, 0) - En(1, -1, 0) + pdy) - jx1l * (pdy + En(-1, 1, 0) - En(-1, -1, 0));
-                        const double JDxz = jx2h * (En(1, 0, 1) - En(1, 0, -1) + pdz) - jx2l * (pdz + En(-1, 0, 1) - En(-1, 0, -1));
-                        const double JDyx = jy0h * (En(1, 1, 0) - En(-1, 1, 0) + pdx) - jy0l * (pdx + En(1, -1, 0) - En(-1, -1, 0));
-                        const double JDyy = jy1h * Pn(0, 1, 0) + jy1l * Pn(0, -1, 0);
-                        const double JDyz = jy2h * (En(0, 1, 1) - En(0, 1, -1) + pdz) - jy2l * (pdz + En(0, -1, 1) - En(0, -1, -1));
-                        const double JDzx = jz0h * (En(1, 0, 1) - En(-1, 0, 1) + pdx) - jz0l * (pdx + En(1, 0, -1) - En(-1, 0, -1));
-                        const double JDzy = jz1h * (En(0, 1, 1) - En(0, -1, 1) + pdy) - jz1l * (pdy + En(0, 1, -1) - En(0, -1, -1));
-                        const double JDzz = jz2h * Pn(0, 0, 1) + jz2l * Pn(0, 0, -1);
-                        const double lphi = P.beta * ji *
-                                            (JDxx * xxScale + JDyy * yyScale + JDzz * zzScale + (JDxy + JDyx) * xyScale +
-                                             (JDyz + JDzy) * yzScale + (JDzx + JDxz) * zxScale);
-                        // lapDiag: FILLMAPPEDLAPDIAG3D's expression (k_lapdiag), bitwise the stored array's value
-                        const double lapd = -ji * ((jx0h + jx0l) * xxScale + (jy1h + jy1l) * yyScale + (jz2h + jz2l) * zzScale);
-                        res[s] = (rh - lphi) / (P.alpha + P.beta * lapd);
+#define FULL19_PART 2
+#include "full19_point.inc"
                     } else {
-                        // GSRBBOUNDARYITER3D (GSRBF.ChF:1024-1253)
-                        const bool nxl = (gi == P.dom_lo[0]) && P.neum[0][0];
-                        const bool nxh = (gi == P.dom_hi[0]) && P.neum[0][1];
-                        const bool nyl = (gj == P.dom_lo[1]) && P.neum[1][0];
-                        const bool nyh = (gj == P.dom_hi[1]) && P.neum[1][1];
-                        const bool nzl = (gk == P.dom_lo[2]) && P.neum[2][0];
-                        const bool nzh = (gk == P.dom_hi[2]) && P.neum[2][1];
-                        double JDloX = 0, JDhiX = 0, JDloY = 0, JDhiY = 0, JDloZ = 0, JDhiZ = 0, ld = 0.0;
-                        if (!nxl) {
-                            JDloX = +xxScale * jx0l * Pn(-1, 0, 0) -
-                                    xyScale * jx1l * (En(0, 1, 0) - En(0, -1, 0) + En(-1, 1, 0) - En(-1, -1, 0)) -
-                                    zxScale * jx2l * (En(0, 0, 1) - En(0, 0, -1) + En(-1, 0, 1) - En(-1, 0, -1));
-                            ld = ld - xxScale * jx0l;
-                        }
-                        if (!nxh) {
-                            JDhiX = +xxScale * jx0h * Pn(1, 0, 0) +
-                                    xyScale * jx1h * (En(1, 1, 0) - En(1, -1, 0) + En(0, 1, 0) - En(0, -1, 0)) +
-                                    zxScale * jx2h * (En(1, 0, 1) - En(1, 0, -1) + En(0, 0, 1) - En(0, 0, -1));
-                            ld = ld - xxScale * jx0h;
-                        }
-                        if (!nyl) {
-                            JDloY = -xyScale * jy0l * (En(1, 0, 0) - En(-1, 0, 0) + En(1, -1, 0) - En(-1, -1, 0)) +
-                                    yyScale * jy1l * Pn(0, -1, 0) -
-                                    yzScale * jy2l * (En(0, 0, 1) - En(0, 0, -1) + En(0, -1, 1) - En(0, -1, -1));
-                            ld = ld - yyScale * jy1l;
-                        }
-                        if (!nyh) {
-                            JDhiY = +xyScale * jy0h * (En(1, 1, 0) - En(-1, 1, 0) + En(1, 0, 0) - En(-1, 0, 0)) +
-                                    yyScale * jy1h * Pn(0, 1, 0) +
-                                    yzScale * jy2h * (En(0, 1, 1) - En(0, 1, -1) + En(0, 0, 1) - En(0, 0, -1));
-                            ld = ld - yyScale * jy1h;
-                        }
-                        if (!nzl) {
-                            JDloZ = -zxScale * jz0l * (En(1, 0, 0) - En(-1, 0, 0) + En(1, 0, -1) - En(-1, 0, -1)) -
-                                    yzScale * jz1l * (En(0, 1, 0) - En(0, -1, 0) + En(0, 1, -1) - En(0, -1, -1)) +
-                                    zzScale * jz2l * Pn(0, 0, -1);
-                            ld = ld - zzScale * jz2l;
-                        }
-                        if (!nzh) {
-                            JDhiZ = +zxScale * jz0h * (En(1, 0, 1) - En(-1, 0, 1) + En(1, 0, 0) - En(-1, 0, 0)) +
-                                    yzScale * jz1h * (En(0, 1, 1) - En(0, -1, 1) + En(0, 1, 0) - En(0, -1, 0)) +
-                                    zzScale * jz2h * Pn(0, 0, 1);
-                            ld = ld - zzScale * jz2h;
-                        }
-                        ld = ld * ji;
-                        const double lphi = P.beta * ji * (JDloX + JDhiX + JDloY + JDhiY + JDloZ + JDhiZ);
-                        res[s] = (rh - lphi) / (P.alpha + P.beta * ld);
+#define FULL19_PART 3
+#include "full19_point.inc"
                     }
                 }
 #undef Pn
 #undef En
+#undef CF
+#undef SC
+#undef NEU
+#undef F19_RESULT
             }
             double* dst = out + base + sk * k;
             if (MODE == 3) {
@@ -341,7 +229,7 @@ __global__ __launch_bounds__(64 * FM_J, (NARROW && !ZXY && MODE == 1) ? 3 : 1) v
                                                              const PatchDesc* __restrict__ patches,
                                                              double* __restrict__ out, const double* __restrict__ phi,
                                                              const double* __restrict__ psi,
-                                                             const double* __restrict__ rhs, JgFullM J,
+                                                             const double* __restrict__ rhs, JgFull J,
                                                              const double* __restrict__ jinv, StencilParams P, int color,
                                                           const double* __restrict__ phi2)
 {
@@ -356,14 +244,6 @@ __global__ __launch_bounds__(64 * FM_J, (NARROW && !ZXY && MODE == 1) ? 3 : 1) v
     else full_march_body<MODE, FM_J, ZXY, NARROW ? 4 : 0>(SP, SE, t, p, out, phi, psi, rhs, J, jinv, P, color, phi2);
 }
 
-static JgFullM jgfullm(const LevelDev& L)
-{
-    JgFullM J;
-    for (int d = 0; d < 3; ++d)
-        for (int c = 0; c < 3; ++c) J.c[d][c] = L.jgf[d][c];
-    return J;
-}
-
 // mode 0: out = rhs - L[phi], 1: out = L[phi], 2: one GSRB colour pass.  psi needs to be right only in the one-cell frame of every box.
 template <int MODE>
 static void launch_march(hipStream_t st, TileSpan tiles, const LevelDev& L, double* out, const double* phi,
@@ -372,7 +252,7 @@ static void launch_march(hipStream_t st, TileSpan tiles, const LevelDev& L, doub
     const bool six = L.full_rows == 6, z = L.P.zero_xy != 0, nw = tiles.classes != 0;   // (6-row tables never hold narrow classes)
 #define SOMAR_FM(ROWS, Z, N)                                                                                                   \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_full_march<MODE, ROWS, Z, N>), dim3(tiles.n), dim3(64, ROWS, 1), 0, st, tiles.p, L.patches, \
-                       out, phi, psi, rhs, jgfullm(L), L.jinv, L.P, color, phi2)
+                       out, phi, psi, rhs, jgfull(L), L.jinv, L.P, color, phi2)
     if (six) { if (z) SOMAR_FM(6, true, false); else SOMAR_FM(6, false, false); }
     else if (nw) { if (z) SOMAR_FM(8, true, true); else SOMAR_FM(8, false, true); }
     else { if (z) SOMAR_FM(8, true, false); else SOMAR_FM(8, false, false); }

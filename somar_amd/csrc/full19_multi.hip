@@ -7,8 +7,8 @@
 // fields, 53 for three (computed; what was measured is in profiles/r14_multi_full19.md).
 //
 // Per field the kernel is the single-field one: the same k-march, the same four rotating plane slots of phi and of E (phi inside
-// the box, psi in its one-cell frame) staged per field, the same predicates, and full_march_body's expressions in its order =>
-// bit-identical, field by field, to full19_march.hip and hence to the CPU oracle.  Only what does not depend on the field is
+// the box, psi in its one-cell frame) staged per field, the same predicates, and the per-cell arithmetic of full19_point.h on
+// the same operands => bit-identical, field by field, to full19_march.hip BECAUSE both take that text.  Only what does not depend on the field is
 // hoisted, loaded or computed once per plane and held in registers while the fields take their turns: the thirteen coefficient
 // loads (ten with ZXY) and the shuffles of the x-face components, the carried k-face planes, Jinv, the memory and ownership
 // predicates, the colour selector, the boundary classification and the scale constants.  Every field of a launch shares one
@@ -25,6 +25,8 @@
 // keeps without scratch (the resource listing is in profiles/r14_multi_full19.md).
 #include "common.h"
 #include "kernels.h"
+#include "stencil_point.h"
+#include "full19_point.h"
 
 namespace somar {
 
@@ -33,21 +35,10 @@ namespace {
 constexpr int FN_S = 4;              // plane slots, as full19_march.hip's FM_S
 constexpr int FN_LDS_MAX = 160 * 1024;   // gfx950: what one workgroup may declare (LDS_MAX of multi_march.hip)
 
-struct JgFullN { const double* c[3][3]; };  // c[faceDir][component]
-
-// fm_ld2 of full19_march.hip: branch-free predicated pair load
-__device__ __forceinline__ double2 fn_ld2(const double* __restrict__ a, long long idx, bool ok0, bool ok1, long long safe)
-{
-#ifdef SOMAR_NT_LOADS
-    typedef double v2d_ __attribute__((ext_vector_type(2)));
-    const v2d_ w = __builtin_nontemporal_load(reinterpret_cast<const v2d_*>(a + ((ok0 || ok1) ? idx : safe)));
-    const double2 v = make_double2(w.x, w.y);
-#else
-    const double2 v = *reinterpret_cast<const double2*>(a + ((ok0 || ok1) ? idx : safe));
-#endif
-    return make_double2(ok0 ? v.x : 0.0, ok1 ? v.y : 0.0);
-}
-__device__ __forceinline__ double fn_pick(const double2& v, int s) { return s ? v.y : v.x; }
+// The kernel's own argument type, in this unnamed namespace ON PURPOSE: it gives k_full_march_nf internal linkage, the form
+// it was measured in.  With the shared JgFull of kernels.h as the argument the residual kernel ran 0.7 % slower
+// (profiles/r16_full19_one_text.md, section 3).  Filled from jgfull(L).
+struct JgFullN { const double* c[3][3]; };
 
 }  // namespace
 
@@ -95,26 +86,16 @@ __global__ __launch_bounds__(64 * FM_J) void k_full_march_nf(const Tile* __restr
     const bool any = o[0] || o[1];
     const long long sj = p.pj, sk = p.pk;
     const long long base = p.off + li + sj * lj;
-
-    const double dxi0 = 1.0 / P.dx[0], dxi1 = 1.0 / P.dx[1], dxi2 = 1.0 / P.dx[2];
-    // MAPPEDGETFLUX's scales with beta = a_ref = 1: aScale = 1.0 * dxi[a], b/cScale = 0.25 * 1.0 * dxi[b/c]
-    const double a0 = 1.0 * dxi0, a1 = 1.0 * dxi1, a2 = 1.0 * dxi2;
-    const double q0 = 0.25 * 1.0 * dxi0, q1 = 0.25 * 1.0 * dxi1, q2 = 0.25 * 1.0 * dxi2;
-    const double xxScale = 1.0 / (P.dx[0] * P.dx[0]);
-    const double yyScale = 1.0 / (P.dx[1] * P.dx[1]);
-    const double zzScale = 1.0 / (P.dx[2] * P.dx[2]);
-    const double xyScale = 0.25 / (P.dx[0] * P.dx[1]);
-    const double yzScale = 0.25 / (P.dx[1] * P.dx[2]);
-    const double zxScale = 0.25 / (P.dx[2] * P.dx[0]);
+    const Full19Scales S = full19_scales(P.dx[0], P.dx[1], P.dx[2]);
 
     // ---- per field: stage plane kp of phi and E into its slot -----------------------------------------------------------
     auto load_plane = [&](int f, int kp, double2& vp, double2& ve) {
         const bool fk = (kp >= -1) && (kp <= p.n[2]);
         const bool ink = (kp >= 0) && (kp < p.n[2]);
         const long long idx = base + sk * kp;
-        vp = fn_ld2(F.phi[f], idx, f0 && fk, f1 && fk, p.off);
+        vp = ld2<double>(F.phi[f], idx, f0 && fk, f1 && fk, p.off);
         const bool e0 = f0 && fk && !(in0 && ink), e1 = f1 && fk && !(in1 && ink);   // frame cells: E = psi
-        const double2 vs = fn_ld2(F.psi[f], idx, e0, e1, p.off);
+        const double2 vs = ld2<double>(F.psi[f], idx, e0, e1, p.off);
         ve = make_double2(e0 ? vs.x : vp.x, e1 ? vs.y : vp.y);
     };
     auto store_plane = [&](int f, int kp, const double2& vp, const double2& ve) {
@@ -134,9 +115,9 @@ __global__ __launch_bounds__(64 * FM_J) void k_full_march_nf(const Tile* __restr
         store_plane(f, k, vp, ve);
     }
     // k-face components on the LOW face of plane k (shared, carried from plane to plane)
-    double2 Jz0c = fn_ld2(J.c[2][0], base + sk * k, o[0], o[1], p.off);
-    double2 Jz1c = fn_ld2(J.c[2][1], base + sk * k, o[0], o[1], p.off);
-    double2 Jz2c = fn_ld2(J.c[2][2], base + sk * k, o[0], o[1], p.off);
+    double2 Jz0c = ld2<double>(J.c[2][0], base + sk * k, o[0], o[1], p.off);
+    double2 Jz1c = ld2<double>(J.c[2][1], base + sk * k, o[0], o[1], p.off);
+    double2 Jz2c = ld2<double>(J.c[2][2], base + sk * k, o[0], o[1], p.off);
 
     for (; k < kend; ++k) {
         const int gk = p.lo[2] + k;
@@ -146,21 +127,21 @@ __global__ __launch_bounds__(64 * FM_J) void k_full_march_nf(const Tile* __restr
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
             load_plane(f, k + 1, vp[f], ve[f]);
-            Rh[f] = fn_ld2(F.rhs[f], ck, o[0], o[1], p.off);
+            Rh[f] = ld2<double>(F.rhs[f], ck, o[0], o[1], p.off);
         }
-        const double2 Jz0p = fn_ld2(J.c[2][0], ck + sk, o[0], o[1], p.off);
-        const double2 Jz1p = fn_ld2(J.c[2][1], ck + sk, o[0], o[1], p.off);
-        const double2 Jz2p = fn_ld2(J.c[2][2], ck + sk, o[0], o[1], p.off);
-        const double2 Ji = fn_ld2(jinv, ck, o[0], o[1], p.off);
-        const double2 Jx0 = fn_ld2(J.c[0][0], ck, gxo0, any, p.off);
-        const double2 Jx1 = ZXY ? make_double2(0.0, 0.0) : fn_ld2(J.c[0][1], ck, gxo0, any, p.off);
-        const double2 Jx2 = fn_ld2(J.c[0][2], ck, gxo0, any, p.off);
-        const double2 Jy0 = ZXY ? make_double2(0.0, 0.0) : fn_ld2(J.c[1][0], ck, o[0], o[1], p.off);
-        const double2 Jy1 = fn_ld2(J.c[1][1], ck, o[0], o[1], p.off);
-        const double2 Jy2 = fn_ld2(J.c[1][2], ck, o[0], o[1], p.off);
-        const double2 Jy0h = ZXY ? make_double2(0.0, 0.0) : fn_ld2(J.c[1][0], ck + sj, o[0], o[1], p.off);
-        const double2 Jy1h = fn_ld2(J.c[1][1], ck + sj, o[0], o[1], p.off);
-        const double2 Jy2h = fn_ld2(J.c[1][2], ck + sj, o[0], o[1], p.off);
+        const double2 Jz0p = ld2<double>(J.c[2][0], ck + sk, o[0], o[1], p.off);
+        const double2 Jz1p = ld2<double>(J.c[2][1], ck + sk, o[0], o[1], p.off);
+        const double2 Jz2p = ld2<double>(J.c[2][2], ck + sk, o[0], o[1], p.off);
+        const double2 Ji = ld2<double>(jinv, ck, o[0], o[1], p.off);
+        const double2 Jx0 = ld2<double>(J.c[0][0], ck, gxo0, any, p.off);
+        const double2 Jx1 = ZXY ? make_double2(0.0, 0.0) : ld2<double>(J.c[0][1], ck, gxo0, any, p.off);
+        const double2 Jx2 = ld2<double>(J.c[0][2], ck, gxo0, any, p.off);
+        const double2 Jy0 = ZXY ? make_double2(0.0, 0.0) : ld2<double>(J.c[1][0], ck, o[0], o[1], p.off);
+        const double2 Jy1 = ld2<double>(J.c[1][1], ck, o[0], o[1], p.off);
+        const double2 Jy2 = ld2<double>(J.c[1][2], ck, o[0], o[1], p.off);
+        const double2 Jy0h = ZXY ? make_double2(0.0, 0.0) : ld2<double>(J.c[1][0], ck + sj, o[0], o[1], p.off);
+        const double2 Jy1h = ld2<double>(J.c[1][1], ck + sj, o[0], o[1], p.off);
+        const double2 Jy2h = ld2<double>(J.c[1][2], ck + sj, o[0], o[1], p.off);
         const double jx0n = __shfl_down(Jx0.x, 1, 64), jx1n = __shfl_down(Jx1.x, 1, 64), jx2n = __shfl_down(Jx2.x, 1, 64);
 
 #pragma unroll
@@ -183,124 +164,37 @@ __global__ __launch_bounds__(64 * FM_J) void k_full_march_nf(const Tile* __restr
                     // neighbours: Pn(di,dj,dk) = phi, En(di,dj,dk) = E
 #define Pn(di, dj, dk) SPx(f, (dk) < 0 ? sm : ((dk) > 0 ? sp : sc), row + (dj), rc + (di))
 #define En(di, dj, dk) SEx(f, (dk) < 0 ? sm : ((dk) > 0 ? sp : sc), row + (dj), rc + (di))
+#define CF(n) C.n
+#define SC(n) S.n
+#define NEU(f) FULL19_NF(f)
+#define F19_RESULT(v) res[s] = v
+                    // full19_point.inc in place reads, from this scope: C and S (through CF, SC), alpha, beta, pc (operator) or rh (updates),
+                    // and P, gi, gj, gk (through FULL19_NF / FULL19_ONB); FULL19_PICK reads Jx0..Jx2, jx0n..jx2n, Jy0..Jy2h, Jz0c..Jz2p, Ji
                     // coefficients on the low / high face of this cell
-                    const double jx0l = s ? Jx0.y : Jx0.x, jx0h = s ? jx0n : Jx0.y;
-                    const double jx1l = s ? Jx1.y : Jx1.x, jx1h = s ? jx1n : Jx1.y;
-                    const double jx2l = s ? Jx2.y : Jx2.x, jx2h = s ? jx2n : Jx2.y;
-                    const double jy0l = fn_pick(Jy0, s), jy0h = fn_pick(Jy0h, s);
-                    const double jy1l = fn_pick(Jy1, s), jy1h = fn_pick(Jy1h, s);
-                    const double jy2l = fn_pick(Jy2, s), jy2h = fn_pick(Jy2h, s);
-                    const double jz0l = fn_pick(Jz0c, s), jz0h = fn_pick(Jz0p, s);
-                    const double jz1l = fn_pick(Jz1c, s), jz1h = fn_pick(Jz1p, s);
-                    const double jz2l = fn_pick(Jz2c, s), jz2h = fn_pick(Jz2p, s);
-                    const double ji = fn_pick(Ji, s);
+                    Full19Coef C;
+                    FULL19_PICK(C, s);
+                    const double alpha = P.alpha, beta = P.beta;
                     if (MODE == 0) {
-                        // flux19 (full19.hip) at the six faces: direction a, then b = a+1, c = a+2 (cyclic)
-                        double fxl = a0 * jx0l * (pc - Pn(-1, 0, 0)) +
-                                     q1 * jx1l * (En(0, 1, 0) - En(0, -1, 0) + En(-1, 1, 0) - En(-1, -1, 0)) +
-                                     q2 * jx2l * (En(0, 0, 1) - En(0, 0, -1) + En(-1, 0, 1) - En(-1, 0, -1));
-                        double fxh = a0 * jx0h * (Pn(1, 0, 0) - pc) +
-                                     q1 * jx1h * (En(1, 1, 0) - En(1, -1, 0) + En(0, 1, 0) - En(0, -1, 0)) +
-                                     q2 * jx2h * (En(1, 0, 1) - En(1, 0, -1) + En(0, 0, 1) - En(0, 0, -1));
-                        double fyl = a1 * jy1l * (pc - Pn(0, -1, 0)) +
-                                     q2 * jy2l * (En(0, 0, 1) - En(0, 0, -1) + En(0, -1, 1) - En(0, -1, -1)) +
-                                     q0 * jy0l * (En(1, 0, 0) - En(-1, 0, 0) + En(1, -1, 0) - En(-1, -1, 0));
-                        double fyh = a1 * jy1h * (Pn(0, 1, 0) - pc) +
-                                     q2 * jy2h * (En(0, 1, 1) - En(0, 1, -1) + En(0, 0, 1) - En(0, 0, -1)) +
-                                     q0 * jy0h * (En(1, 1, 0) - En(-1, 1, 0) + En(1, 0, 0) - En(-1, 0, 0));
-                        double fzl = a2 * jz2l * (pc - Pn(0, 0, -1)) +
-                                     q0 * jz0l * (En(1, 0, 0) - En(-1, 0, 0) + En(1, 0, -1) - En(-1, 0, -1)) +
-                                     q1 * jz1l * (En(0, 1, 0) - En(0, -1, 0) + En(0, 1, -1) - En(0, -1, -1));
-                        double fzh = a2 * jz2h * (Pn(0, 0, 1) - pc) +
-                                     q0 * jz0h * (En(1, 0, 1) - En(-1, 0, 1) + En(1, 0, 0) - En(-1, 0, 0)) +
-                                     q1 * jz1h * (En(0, 1, 1) - En(0, -1, 1) + En(0, 1, 0) - En(0, -1, 0));
-                        // EllipticConstNeumBCFluxClass: boundary faces := 0 (homogeneous)
-                        if (gi == P.dom_lo[0] && P.neum[0][0]) fxl = 0.0;
-                        if (gi == P.dom_hi[0] && P.neum[0][1]) fxh = 0.0;
-                        if (gj == P.dom_lo[1] && P.neum[1][0]) fyl = 0.0;
-                        if (gj == P.dom_hi[1] && P.neum[1][1]) fyh = 0.0;
-                        if (gk == P.dom_lo[2] && P.neum[2][0]) fzl = 0.0;
-                        if (gk == P.dom_hi[2] && P.neum[2][1]) fzh = 0.0;
-                        fxl *= P.beta; fxh *= P.beta; fyl *= P.beta; fyh *= P.beta; fzl *= P.beta; fzh *= P.beta;
-                        double l = ji * ((fxh - fxl) * dxi0 + (fyh - fyl) * dxi1 + (fzh - fzl) * dxi2);
-                        if (P.alpha != 0.0) l = P.alpha * pc + 1.0 * l;
-                        res[s] = fn_pick(Rh[f], s) - l;
+#define FULL19_PART 1
+#include "full19_point.inc"
+                        res[s] = pick<double>(Rh[f], s) - l;
                     } else {
-                        const bool onb = (gi == P.dom_lo[0]) || (gi == P.dom_hi[0]) || (gj == P.dom_lo[1]) ||
-                                         (gj == P.dom_hi[1]) || (gk == P.dom_lo[2]) || (gk == P.dom_hi[2]);
-                        const double rh = fn_pick(Rh[f], s);
+                        const bool onb = FULL19_ONB;
+                        const double rh = pick<double>(Rh[f], s);
                         if (!onb) {
-                            // GSRBITER3D (GSRBF.ChF:36-282)
-                            const double pdx = En(1, 0, 0) - En(-1, 0, 0);
-                            const double pdy = En(0, 1, 0) - En(0, -1, 0);
-                            const double pdz = En(0, 0, 1) - En(0, 0, -1);
-                            const double JDxx = jx0h * Pn(1, 0, 0) + jx0l * Pn(-1, 0, 0);
-                            const double JDxy = jx1h * (En(1, 1, 0) - En(1, -1, 0) + pdy) - jx1l * (pdy + En(-1, 1, 0) - En(-1, -1, 0));
-                            const double JDxz = jx2h * (En(1, 0, 1) - En(1, 0, -1) + pdz) - jx2l * (pdz + En(-1, 0, 1) - En(-1, 0, -1));
-                            const double JDyx = jy0h * (En(1, 1, 0) - En(-1, 1, 0) + pdx) - jy0l * (pdx + En(1, -1, 0) - En(-1, -1, 0));
-                            const double JDyy = jy1h * Pn(0, 1, 0) + jy1l * Pn(0, -1, 0);
-                            const double JDyz = jy2h * (En(0, 1, 1) - En(0, 1, -1) + pdz) - jy2l * (pdz + En(0, -1, 1) - En(0, -1, -1));
-                            const double JDzx = jz0h * (En(1, 0, 1) - En(-1, 0, 1) + pdx) - jz0l * (pdx + En(1, 0, -1) - En(-1, 0, -1));
-                            const double JDzy = jz1h * (En(0, 1, 1) - En(0, -1, 1) + pdy) - jz1l * (pdy + En(0, 1, -1) - En(0, -1, -1));
-                            const double JDzz = jz2h * Pn(0, 0, 1) + jz2l * Pn(0, 0, -1);
-                            const double lphi = P.beta * ji *
-                                                (JDxx * xxScale + JDyy * yyScale + JDzz * zzScale + (JDxy + JDyx) * xyScale +
-                                                 (JDyz + JDzy) * yzScale + (JDzx + JDxz) * zxScale);
-                            // lapDiag: FILLMAPPEDLAPDIAG3D's expression (k_lapdiag), bitwise the stored array's value
-                            const double lapd = -ji * ((jx0h + jx0l) * xxScale + (jy1h + jy1l) * yyScale + (jz2h + jz2l) * zzScale);
-                            res[s] = (rh - lphi) / (P.alpha + P.beta * lapd);
+#define FULL19_PART 2
+#include "full19_point.inc"
                         } else {
-                            // GSRBBOUNDARYITER3D (GSRBF.ChF:1024-1253)
-                            const bool nxl = (gi == P.dom_lo[0]) && P.neum[0][0];
-                            const bool nxh = (gi == P.dom_hi[0]) && P.neum[0][1];
-                            const bool nyl = (gj == P.dom_lo[1]) && P.neum[1][0];
-                            const bool nyh = (gj == P.dom_hi[1]) && P.neum[1][1];
-                            const bool nzl = (gk == P.dom_lo[2]) && P.neum[2][0];
-                            const bool nzh = (gk == P.dom_hi[2]) && P.neum[2][1];
-                            double JDloX = 0, JDhiX = 0, JDloY = 0, JDhiY = 0, JDloZ = 0, JDhiZ = 0, ld = 0.0;
-                            if (!nxl) {
-                                JDloX = +xxScale * jx0l * Pn(-1, 0, 0) -
-                                        xyScale * jx1l * (En(0, 1, 0) - En(0, -1, 0) + En(-1, 1, 0) - En(-1, -1, 0)) -
-                                        zxScale * jx2l * (En(0, 0, 1) - En(0, 0, -1) + En(-1, 0, 1) - En(-1, 0, -1));
-                                ld = ld - xxScale * jx0l;
-                            }
-                            if (!nxh) {
-                                JDhiX = +xxScale * jx0h * Pn(1, 0, 0) +
-                                        xyScale * jx1h * (En(1, 1, 0) - En(1, -1, 0) + En(0, 1, 0) - En(0, -1, 0)) +
-                                        zxScale * jx2h * (En(1, 0, 1) - En(1, 0, -1) + En(0, 0, 1) - En(0, 0, -1));
-                                ld = ld - xxScale * jx0h;
-                            }
-                            if (!nyl) {
-                                JDloY = -xyScale * jy0l * (En(1, 0, 0) - En(-1, 0, 0) + En(1, -1, 0) - En(-1, -1, 0)) +
-                                        yyScale * jy1l * Pn(0, -1, 0) -
-                                        yzScale * jy2l * (En(0, 0, 1) - En(0, 0, -1) + En(0, -1, 1) - En(0, -1, -1));
-                                ld = ld - yyScale * jy1l;
-                            }
-                            if (!nyh) {
-                                JDhiY = +xyScale * jy0h * (En(1, 1, 0) - En(-1, 1, 0) + En(1, 0, 0) - En(-1, 0, 0)) +
-                                        yyScale * jy1h * Pn(0, 1, 0) +
-                                        yzScale * jy2h * (En(0, 1, 1) - En(0, 1, -1) + En(0, 0, 1) - En(0, 0, -1));
-                                ld = ld - yyScale * jy1h;
-                            }
-                            if (!nzl) {
-                                JDloZ = -zxScale * jz0l * (En(1, 0, 0) - En(-1, 0, 0) + En(1, 0, -1) - En(-1, 0, -1)) -
-                                        yzScale * jz1l * (En(0, 1, 0) - En(0, -1, 0) + En(0, 1, -1) - En(0, -1, -1)) +
-                                        zzScale * jz2l * Pn(0, 0, -1);
-                                ld = ld - zzScale * jz2l;
-                            }
-                            if (!nzh) {
-                                JDhiZ = +zxScale * jz0h * (En(1, 0, 1) - En(-1, 0, 1) + En(1, 0, 0) - En(-1, 0, 0)) +
-                                        yzScale * jz1h * (En(0, 1, 1) - En(0, -1, 1) + En(0, 1, 0) - En(0, -1, 0)) +
-                                        zzScale * jz2h * Pn(0, 0, 1);
-                                ld = ld - zzScale * jz2h;
-                            }
-                            ld = ld * ji;
-                            const double lphi = P.beta * ji * (JDloX + JDhiX + JDloY + JDhiY + JDloZ + JDhiZ);
-                            res[s] = (rh - lphi) / (P.alpha + P.beta * ld);
+#define FULL19_PART 3
+#include "full19_point.inc"
                         }
                     }
 #undef Pn
 #undef En
+#undef CF
+#undef SC
+#undef NEU
+#undef F19_RESULT
                 }
                 double* dst = F.out[f] + base + sk * k;
                 if (o[0] && o[1]) *reinterpret_cast<double2*>(dst) = make_double2(res[0], res[1]);
@@ -333,9 +227,10 @@ void launch_full_march_nf(hipStream_t st, TileSpan tiles, const LevelDev& L, con
     constexpr int ROWS = FullNfRows<NF>::value;
     SOMAR_CHECK(tiles.classes == 0, "internal: the N-field 19-point kernels take class-0 tiles");
     SOMAR_CHECK(mode == 0 || mode == 2, "internal: the N-field 19-point kernels are the residual and the colour pass");
+    const JgFull G = jgfull(L);
     JgFullN J;
     for (int d = 0; d < 3; ++d)
-        for (int c = 0; c < 3; ++c) J.c[d][c] = L.jgf[d][c];
+        for (int c = 0; c < 3; ++c) J.c[d][c] = G.c[d][c];
     const bool z = L.P.zero_xy != 0;
 #define SOMAR_FN(MODE, Z)                                                                                                     \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_full_march_nf<MODE, ROWS, Z, NF>), dim3(tiles.n), dim3(64, ROWS, 1), 0, st, tiles.p,   \

@@ -52,6 +52,10 @@ inline MetricPtrs<double> metric_ptrs(const LevelDev& L) { return MetricPtrs<dou
 struct FullFlux { const double* psi = nullptr; const double* J[3][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}; double dxi[3] = {0, 0, 0}; };
 
 // 19-point path (full19.hip)
+// every J g^{ab} plane of a level as a kernel argument, c[faceDir][component]; on a diagonal-metric level (no jgf) the
+// diagonal entries are its jg (what the GHOST_NEUM_FACE ops read) and the others stay null
+struct JgFull { const double* c[3][3]; };
+JgFull jgfull(const LevelDev& L);
 // redirect: a read of psi that lands INSIDE the box's valid region takes phi instead (psi is then maintained in the
 // boxes' frames only -- the frame-only programs of the marching 19-point kernels, full19_march.hip)
 void launch_ghost_ops(hipStream_t st, const LevelDev& L, const GhostOp* ops, int nops, double* phi, double* psi,

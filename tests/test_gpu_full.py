@@ -74,6 +74,13 @@ def test_full_operator_and_gsrb_bit_exact(oracle, case, kernel_path):
             gpu.residual(d, fs, fc, fr)
             for a, b in zip(download_valid(gpu, fs, g, d), valid_of(res)):
                 np.testing.assert_array_equal(a, b)
+            if d == 0:
+                # the bare operator: the marching kernel's MODE 1 on the march path, k_op_full<1> on the direct one
+                lhs = so.LevelData(g, 1)
+                op.apply_op(lhs, phi, True)
+                gpu.applyOp(0, F.F_RES, F.F_PHI)
+                for a, b in zip(download_valid(gpu, F.F_RES, g, 0), valid_of(lhs)):
+                    np.testing.assert_array_equal(a, b)
             op.relax(phi, rhs, 2)
             n_fused = gpu.fused19Sweeps()
             gpu.relax(d, fc, fr, 2)
